@@ -132,12 +132,18 @@ def _check_two_rank_line(js):
     assert abs(js["value"] - want * js["steps"] / (js["ms_per_step"] * 1e-3 * js["steps"])) / js["value"] < 1e-2
 
 
-def test_bench_self_launch_two_ranks_stub():
+def test_bench_self_launch_two_ranks_stub(tmp_path):
     """`python bench.py --gpus 2` with NO launcher must start two ranks itself (gloo, stub engine): the control flow the
-    driver's single-process command line exercises."""
-    rc, js, err = _run_bench(["--gpus", "2", "--stub", "--steps", "2", "--warmup", "1"])
+    driver's single-process command line exercises.  --dump-outputs: each rank writes its shard's waveforms of the last
+    timed step, whole, one float32 file per utterance of the global list."""
+    import numpy as np
+    rc, js, err = _run_bench(["--gpus", "2", "--stub", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)])
     assert rc == 0, err[-2000:]
     _check_two_rank_line(js)
+    assert sorted(os.listdir(tmp_path)) == [f"wav_{i:03d}.npy" for i in range(64)]
+    for i in (0, 63):
+        a = np.load(tmp_path / f"wav_{i:03d}.npy")
+        assert a.dtype == np.float32 and a.shape == (140 * 1024,)
     # config 4: mixed lengths from ONE global list -> shards carry different amounts of audio
     rc, js, err = _run_bench(["--gpus", "2", "--stub", "--steps", "1", "--warmup", "0", "--config", "4"])
     assert rc == 0, err[-2000:]
@@ -145,14 +151,19 @@ def test_bench_self_launch_two_ranks_stub():
     assert a[0] != a[1] and all(32 * 40 * 1024 / 24000 <= x <= 32 * 400 * 1024 / 24000 for x in a)
 
 
-def test_bench_eight_ranks_config4_stub():
+def test_bench_eight_ranks_config4_stub(tmp_path):
     """BASELINE config 4's real shape, rehearsed on CPU so that the first 8-GPU run is not also the first 8-rank run:
     `bench.py --gpus 8 --config 4` (self-launch, gloo, stub engine) -- 256 mixed-length utterances from ONE global list, eight
     disjoint shards of 32 (the serpentine longest-first deal of indextts/utils/dist.py), every rank reports, the shards carry
     different amounts of audio, the aggregate is their sum and the tail imbalance is in the line."""
-    rc, js, err = _run_bench(["--gpus", "8", "--stub", "--steps", "1", "--warmup", "0", "--config", "4"])
+    rc, js, err = _run_bench(["--gpus", "8", "--stub", "--steps", "1", "--warmup", "0", "--config", "4",
+                              "--dump-outputs", str(tmp_path)])
     assert rc == 0, err[-2000:]
     assert js["n_gpus"] == 8 and js["scaling"] == "weak"
+    # the job's 256 waveforms are over --dump-outputs' 64 MB: every file keeps the same share of its waveform's samples
+    dumped = sorted(os.listdir(tmp_path))
+    assert dumped == [f"wav_{i:03d}.npy" for i in range(256)]
+    assert 60 << 20 < sum(os.path.getsize(tmp_path / f) for f in dumped) <= (64 << 20) + 256 * 128
     assert sorted(r["rank"] for r in js["ranks_seen"]) == list(range(8))
     assert len({r["uuid"] for r in js["ranks_seen"]}) == 8
     rows = [set(p["rows"]) for p in sorted(js["per_rank"], key=lambda p: p["rank"])]
