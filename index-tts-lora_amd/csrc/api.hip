@@ -6,6 +6,8 @@
 
 namespace itts {
 static thread_local char g_err[512] = "";
+static thread_local const char* g_last_kernel = "";
+void set_last_kernel(const char* name) { g_last_kernel = name; }
 void set_error(const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
@@ -51,6 +53,7 @@ using namespace itts;
 
 extern "C" int itts_abi_version(void) { return ITTS_ABI_VERSION; }
 extern "C" const char* itts_last_error(void) { return g_err; }
+extern "C" const char* itts_last_kernel(void) { return g_last_kernel; }
 
 extern "C" int64_t itts_packed_bytes(int taps, int K, int N, int dtype) {
   int ks = dtype == ITTS_F32 ? 16 : 32;

@@ -162,9 +162,51 @@ __device__ __forceinline__ float gelu_new(float x) {
 }  // namespace itts
 
 // host-side helpers -------------------------------------------------------------------------------------------------
+#include <initializer_list>
 namespace itts {
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
+// itts_last_kernel(): every launch site names the form it launches; `name` must be a string of static storage duration
+void set_last_kernel(const char* name);
+
+// "base<type,p0,p1,...,tail>" built at compile time, one constant per template instantiation of a launch site
+struct KernelName {
+  char s[80];
+};
+constexpr KernelName kernel_name(const char* base, const char* type, std::initializer_list<int> params, const char* tail = "") {
+  KernelName k{};
+  int n = 0;
+  auto put = [&](char c) {
+    if (n < (int)sizeof(k.s) - 2) k.s[n++] = c;
+  };
+  for (const char* q = base; *q; ++q) put(*q);
+  put('<');
+  bool first = true;
+  for (const char* q = type; *q; ++q) put(*q), first = false;
+  for (int v : params) {
+    if (!first) put(',');
+    first = false;
+    if (v < 0) put('-');
+    unsigned u = v < 0 ? 0u - (unsigned)v : (unsigned)v;
+    char d[12] = {};
+    int m = 0;
+    do {
+      d[m++] = (char)('0' + u % 10);
+      u /= 10;
+    } while (u != 0);
+    while (m > 0) put(d[--m]);
+  }
+  if (*tail) {
+    if (!first) put(',');
+    for (const char* q = tail; *q; ++q) put(*q);
+  }
+  put('>');
+  return k;
+}
+template <typename T>
+constexpr const char* type_tag() {
+  return sizeof(T) == 4 ? "f32" : Elem<T>::DT == ITTS_BF16 ? "bf16" : "f16";
+}
 }  // namespace itts
 
 #define ITTS_REQUIRE(cond, ...)        \

@@ -677,6 +677,12 @@ using namespace itts;
 // Workgroups the MFMA form aims for: 3072 (four rounds of the 768 resident ones) at C <= 96; at C = 192 a batch element has only
 // 70 tiles per 48-channel slice, and twice the tiles per workgroup (1536 workgroups) amortise the tap-fragment set-up better:
 // 85 us against 94 for either form with 3072 (profiles/r04_act_variants.txt; C = 96: 150 / 163 / 179 us for 3072 / 1536 / 6144).
+template <typename T, int CS>
+static const char* aa_btc_name() {
+  static constexpr KernelName kn = kernel_name("aa_snake_btc", type_tag<T>(), {CS});
+  return kn.s;
+}
+
 static int aa_tiles_per_wg(int64_t tiles, int C) {
   int64_t t = tiles / (C > 96 ? 1536 : 3072);
   return (int)(t < 1 ? 1 : t > 8 ? 8 : t);
@@ -685,6 +691,7 @@ static int aa_tiles_per_wg(int64_t tiles, int C) {
 extern "C" int itts_aa_snake_fwd(const void* x, void* y, const float* alpha_log, const float* beta_log,
                                  const float* up_filter12, const float* down_filter12, int B, int T, int C, int dtype,
                                  int layout, const int32_t* valid_rows, void* stream) {
+  set_last_kernel("");
   ITTS_REQUIRE(valid_rows == nullptr || layout == 0, "itts_aa_snake_fwd: valid_rows needs the channels-last layout (0)");
   ITTS_REQUIRE(x && y && alpha_log && beta_log && up_filter12 && down_filter12, "itts_aa_snake_fwd: null pointer");
   ITTS_REQUIRE(B >= 0 && T >= 0 && C > 0, "itts_aa_snake_fwd: bad shape B=%d T=%d C=%d", B, T, C);
@@ -703,6 +710,7 @@ extern "C" int itts_aa_snake_fwd(const void* x, void* y, const float* alpha_log,
     dim3 grid((T + tt - 1) / tt, C / CS, B), block(256);
     ITTS_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "itts_aa_snake_fwd: grid too large");
 #define ITTS_AA_LAUNCH(TT_, CS_) \
+  set_last_kernel(aa_btc_name<TT_, CS_>()); \
   hipLaunchKernelGGL((aa_snake_btc_kernel<TT_, CS_>), grid, block, 0, s, (const TT_*)x, (TT_*)y, alpha_log, beta_log, f, T, C, valid_rows)
 #define ITTS_AA_BY_CS(TT_)                         \
   switch (CS) {                                    \
@@ -732,6 +740,7 @@ extern "C" int itts_aa_snake_fwd(const void* x, void* y, const float* alpha_log,
             const int nt = (T + AaMfma<3>::TT - 1) / AaMfma<3>::TT;
             const int tpw = aa_tiles_per_wg((int64_t)nt * (C / 48) * B, C);
             dim3 g3((nt + tpw - 1) / tpw, C / 48, B);
+            set_last_kernel("aa_snake_mfma<3>");
             hipLaunchKernelGGL(aa_snake_mfma_kernel<3>, g3, block, AaMfma<3>::LDS, s, (const f16_t*)x, (f16_t*)y, alpha_log, beta_log, f, T, C, valid_rows, tpw);
           } else if (C == 24 && valid_rows == nullptr && B % 2 == 0 && ITTS_AA_PAIR24) {
             // C = 24, dense batch: two batch elements share a 48-channel slice (3 full MFMA blocks instead of 2 x 1.5)
@@ -742,6 +751,7 @@ extern "C" int itts_aa_snake_fwd(const void* x, void* y, const float* alpha_log,
             const int nt = (T + AaMfma<3>::TT - 1) / AaMfma<3>::TT;
             const int tpw = aa_tiles_per_wg((int64_t)nt * (B / 2), C);
             dim3 g3((nt + tpw - 1) / tpw, 1, B / 2);
+            set_last_kernel("aa_snake_mfma<3,pair>");
             hipLaunchKernelGGL((aa_snake_mfma_kernel<3, true>), g3, block, AaMfma<3>::LDS, s, (const f16_t*)x, (f16_t*)y, alpha_log, beta_log, f, T, C, valid_rows, tpw);
           } else {
             static std::once_flag once2;
@@ -751,6 +761,7 @@ extern "C" int itts_aa_snake_fwd(const void* x, void* y, const float* alpha_log,
             const int nt = (T + AaMfma<2>::TT - 1) / AaMfma<2>::TT;
             const int tpw = aa_tiles_per_wg((int64_t)nt * ((C + 31) / 32) * B, C);
             dim3 g2((nt + tpw - 1) / tpw, (C + 31) / 32, B);
+            set_last_kernel("aa_snake_mfma<2>");
             hipLaunchKernelGGL(aa_snake_mfma_kernel<2>, g2, block, AaMfma<2>::LDS, s, (const f16_t*)x, (f16_t*)y, alpha_log, beta_log, f, T, C, valid_rows, tpw);
           }
           break;
@@ -767,12 +778,15 @@ extern "C" int itts_aa_snake_fwd(const void* x, void* y, const float* alpha_log,
     dim3 grid((T + 255) / 256, B * C), block(256);
     switch (dtype) {
       case ITTS_F32:
+        set_last_kernel("aa_snake_bct<f32>");
         hipLaunchKernelGGL(aa_snake_bct_kernel<float>, grid, block, 0, s, (const float*)x, (float*)y, alpha_log, beta_log, f, T, C);
         break;
       case ITTS_BF16:
+        set_last_kernel("aa_snake_bct<bf16>");
         hipLaunchKernelGGL(aa_snake_bct_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)x, (bf16_t*)y, alpha_log, beta_log, f, T, C);
         break;
       case ITTS_F16:
+        set_last_kernel("aa_snake_bct<f16>");
         hipLaunchKernelGGL(aa_snake_bct_kernel<f16_t>, grid, block, 0, s, (const f16_t*)x, (f16_t*)y, alpha_log, beta_log, f, T, C);
         break;
       default:

@@ -566,6 +566,8 @@ static int launch_conv(const ConvParams& p, hipStream_t s) {
     if (g > total) g = total;
   }
   dim3 grid((unsigned)g);
+  static constexpr KernelName kn = kernel_name("gemm_conv", type_tag<T>(), {WM, WN, TM, TN, CK, HALO}, PERSIST ? "persist" : "");
+  set_last_kernel(kn.s);
   hipLaunchKernelGGL((gemm_conv_kernel<T, WM, WN, TM, TN, CK, HALO>), grid, dim3(WM * WN * 64), ldsb, s, q);
   return check_launch("itts_gemm_conv");
 }
@@ -733,6 +735,8 @@ static int launch_plain(const ConvParams& p, hipStream_t s) {
   std::call_once(attr, [] {
     (void)hipFuncSetAttribute((const void*)gemm_plain_kernel<T, WM, WN, TM, TN>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   });
+  static constexpr KernelName kn = kernel_name("gemm_plain", type_tag<T>(), {WM, WN, TM, TN});
+  set_last_kernel(kn.s);
   hipLaunchKernelGGL((gemm_plain_kernel<T, WM, WN, TM, TN>), dim3((unsigned)total), dim3(WM * WN * 64), ldsb, s, q);
   return check_launch("itts_gemm_conv");
 }
@@ -876,6 +880,8 @@ static int launch_narrow(const ConvParams& p, hipStream_t s) {
   }
   int64_t grid = (int64_t)conv_num_cus() * occ_wgs;
   if (grid > tiles) grid = tiles;
+  static constexpr KernelName kn = kernel_name("conv_narrow", type_tag<T>(), {KT, NT});
+  set_last_kernel(kn.s);
   hipLaunchKernelGGL((conv_narrow_kernel<T, KT, NT>), dim3((unsigned)grid), dim3(256), ldsb, s, q);
   return check_launch("itts_gemm_conv");
 }
@@ -981,6 +987,8 @@ static int launch_narrow_taps(const ConvParams& p, hipStream_t s) {
   });
   int64_t grid = (int64_t)conv_num_cus() * per_cu;
   if (grid > tiles) grid = tiles;
+  static constexpr KernelName kn = kernel_name("conv_narrow_taps", type_tag<T>(), {KT, NT, TAPS, TM, NW});
+  set_last_kernel(kn.s);
   hipLaunchKernelGGL((conv_narrow_taps_kernel<T, KT, NT, TAPS, TM, NW>), dim3((unsigned)grid), dim3(NW * 64), ldsb, s, q);
   return check_launch("itts_gemm_conv");
 }
@@ -1170,6 +1178,8 @@ static int launch_narrow_lds(const ConvParams& p, hipStream_t s) {
   }
   int64_t grid = (int64_t)conv_num_cus() * occ_wgs;
   if (grid > tiles) grid = tiles;
+  static constexpr KernelName kn = kernel_name("conv_narrow_lds", type_tag<T>(), {CIN, TAPS, TM, NW, MAXH});
+  set_last_kernel(kn.s);
   hipLaunchKernelGGL((conv_narrow_lds_kernel<T, CIN, TAPS, TM, NW, MAXH>), dim3((unsigned)grid), dim3(NW * 64), ldsb, s, q);
   return check_launch("itts_gemm_conv");
 }
@@ -1343,6 +1353,7 @@ static int conv_params_from_args(const itts_conv_args* a, ConvParams& p, const c
 }
 
 extern "C" int itts_gemm_conv(const itts_conv_args* a, void* stream) {
+  set_last_kernel("");
   ConvParams p;
   int rc = conv_params_from_args(a, p, "itts_gemm_conv");
   if (rc != ITTS_OK) return rc;

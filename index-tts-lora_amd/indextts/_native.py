@@ -89,6 +89,7 @@ BEAM_CAND = 1024   # ITTS_BEAM_CAND: candidate slots per row in the beam step's 
 _SIGNATURES = {
     "itts_abi_version": (C.c_int, []),
     "itts_last_error": (C.c_char_p, []),
+    "itts_last_kernel": (C.c_char_p, []),
     "itts_packed_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "itts_pack_weight": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "itts_aa_snake_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
@@ -156,7 +157,7 @@ def lib():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
-        if L.itts_abi_version() != 8:
+        if L.itts_abi_version() != 9:
             raise NativeError("libindextts_hip.so ABI version mismatch")
         _lib = L
     return _lib
@@ -165,6 +166,12 @@ def lib():
 def _check(rc, what):
     if rc != 0:
         raise NativeError(f"{what} failed (code {rc}): {lib().itts_last_error().decode()}")
+
+
+def last_kernel() -> str:
+    """The kernel form (with its template parameters) that this thread's last gemm_conv / aa_snake call launched, e.g.
+    'conv_narrow_lds<f16,96,7,1,8,30>' or 'aa_snake_mfma<3,pair>'; '' if that call launched nothing."""
+    return lib().itts_last_kernel().decode()
 
 
 def dt(t: torch.dtype) -> int:

@@ -14,7 +14,8 @@ def header_symbols():
     return sorted(set(re.findall(r"\b(itts_[a-z0-9_]+)\s*\(", txt)))
 
 
-def test_library_exports_every_declared_symbol():
+def test_library_abi_and_exported_symbols():
+    """The library exports every symbol the header declares (and no diagnostic one) at the header's ABI version."""
     from indextts import _native
     if not os.path.exists(_native.LIB_PATH):
         import __graft_entry__
@@ -32,7 +33,9 @@ def test_library_exports_every_declared_symbol():
     for s in dsyms:
         assert not hasattr(lib, s), f"{s} (diagnostic build only) is exported by the product library"
     lib.itts_abi_version.restype = ctypes.c_int
-    assert lib.itts_abi_version() == 8
+    assert lib.itts_abi_version() == 9
+    hdr = open(os.path.join(ROOT, "include", "indextts_hip.h")).read()
+    assert re.search(r"#define ITTS_ABI_VERSION (\d+)", hdr).group(1) == "9"
     lib.itts_packed_bytes.restype = ctypes.c_int64
     assert lib.itts_packed_bytes(1, 1280, 3840, 1) == 1280 * 3840 * 2
     assert lib.itts_packed_bytes(7, 24, 1, 0) == 7 * 1 * 2 * 1024
@@ -44,6 +47,7 @@ def test_invalid_arguments_are_reported_not_launched():
     a = _native.ConvArgs()
     rc = L.itts_gemm_conv(ctypes.byref(a), None)
     assert rc == 1 and b"null pointer" in L.itts_last_error()
+    assert L.itts_last_kernel() == b""        # nothing was launched, so no kernel form is reported
     s = _native.SkinnyArgs()
     assert L.itts_gemm_skinny(ctypes.byref(s), None) == 1
 
