@@ -14,7 +14,9 @@ Data layout in HBM
 """
 from __future__ import annotations
 
+import itertools
 import os
+from types import SimpleNamespace
 
 import torch
 
@@ -71,6 +73,10 @@ class PagedKV:
             sp[1] = b1
             self.dirty = True
 
+    def blocks_of(self, lo, hi):
+        """Blocks that map positions [lo, hi) of a new row."""
+        return ((hi - 1) >> self.shift) - (lo >> self.shift) + 1
+
     def release(self, row):
         """The row has left: its blocks go back to the pool, its entries to the scratch block."""
         sp = self.span[row]
@@ -96,6 +102,21 @@ class PagedKV:
 
     def used_blocks(self):
         return self.blocks - 1 - len(self.free)
+
+
+def admit(kv: PagedKV, rows, items, end, max_new, check_every) -> int:
+    """Admission of fed utterances into free decode slots (GPTEngine.decode_refill), host only.  Item j = (prefix [P_j, D],
+    stop step) takes slot rows[j] with its prompt + start token at positions [end - P_j - 1, end), and its row is dealt at once
+    the blocks of its whole window [pad, end + max_new + check_every): its last token and the steps up to the poll that finds
+    it stopped.  Items are admitted in order while that window fits the block table and the free blocks; the first that does
+    not -- and every later one -- is not placed.  Returns the number of admitted items."""
+    hi = end + max_new + check_every
+    for j, (p, _) in enumerate(items):
+        pad = end - int(p.shape[0]) - 1
+        if hi - pad > kv.window or kv.blocks_of(pad, hi) > len(kv.free):
+            return j
+        kv.cover(rows[j], pad, hi)
+    return len(items)
 
 
 class GPTEngine:
@@ -199,7 +220,6 @@ class GPTEngine:
         self.force_eager = False  # measurement aid: launch every kernel eagerly
         self.share_prefix = os.environ.get("ITTS_SHARE_PREFIX", "1") != "0"   # prefill(shared_rows=C): compute the shared rows once
         self.share_kv_reads = os.environ.get("ITTS_SHARE_KV_READS", "1") != "0"   # ... and let the decode attention read them from row 0
-        self.steps_per_graph = int(os.environ.get("ITTS_STEPS_PER_GRAPH", "1"))  # decode tokens per CUDA-graph replay; measured 1 > 2 > 4 > 8 (1297 / 1319 / 1342 / 1368 us per token)
         self._sink = torch.zeros(4, dtype=torch.int32, device=dev)
         self.weight_bytes = sum(t.numel() * t.element_size() for l in self.layers for t in
                                 (l["w_qkv"], l["w_o"], l["w_fc"], l["w_pr"])) + self.w_head.numel()
@@ -555,6 +575,14 @@ class GPTEngine:
             self._shared_prefix = (B, beams)
         return self.logits[: self._B]
 
+    def prefill_beams(self, prefix_emb, pad, max_new: int, beams: int, shared_rows: int = 0):
+        """prefill() for decode_beam(): with the row table (beam_kv = "table") the prompt is computed and cached once per batch
+        element; the copy form first expands every row to `beams` identical rows, as generate() does."""
+        if self.beam_kv == "table":
+            return self.prefill(prefix_emb, pad, max_new, beams=beams, shared_rows=shared_rows)
+        return self.prefill(prefix_emb.repeat_interleave(beams, dim=0), pad.repeat_interleave(beams), max_new, shared_rows=shared_rows,
+                            paged=False)
+
     def latent(self, emb: torch.Tensor, lengths=None) -> torch.Tensor:
         """Teacher-forced pass (model.py:459-474): emb fp32 [B,S,D] (right-padded rows allowed) ->
         final_norm(ln_f(blocks(emb))) fp32 [B,S,D].  With `lengths` (host ints, real rows per element) only the real rows
@@ -633,27 +661,46 @@ class GPTEngine:
     def _fold_now(self, B):
         return self.decode_mode == "fold" and not self.lora
 
-    def _step_transformer(self, B, bump=None):
+    def _step_transformer(self, B, bump=None, gemm_only=False):
         """(bump: advance step counter / cache position inside this step's first launches; None = "a _sample call is
         waiting for it", which is what the token loop wants; the beam step kernel advances the state itself.)
         Transformer part of one cached decode step (model.py:163-193): embed token k at mel position k+1, 24 blocks,
         head.  "fold" form, 5 launches per block: QKV' (LayerNorm folded in, + K/V append) -> attention -> out-projection
         (+ residual update, T copy) -> FC' (folded, + gelu) -> FC2 (+ residual update, T copy); the loop state is advanced by
         launches that do not read the word they bump (embed_step: cache position; the first QKV': step counter).
-        "launch" form, 7 per block: split-K slabs + [residual-reduce + LayerNorm] launches (itts_ln_reduce)."""
+        "launch" form, 7 per block: split-K slabs + [residual-reduce + LayerNorm] launches (itts_ln_reduce).
+        gemm_only: ONLY the skinny GEMMs, with the step's real arguments; the loop state is left alone.  Returns (skinny-GEMM
+        launches, algorithmic bytes: weights + input rows in T, and each epilogue's output)."""
         T, D, H, KS = self.dtype, self.D, self.H, self.KSPLIT
+        es = T.itemsize
         step, pos = self.state[0:1], self.state[1:2]
         h, xn, pa = self.h[:B], self.xn, self.pa   # xn / a / f: whole buffers (packed layout is addressed from the base)
-        if bump is None:
-            bump = getattr(self, "_pending_bump", False)
-        self._pending_bump = False
+        if gemm_only:
+            bump = False
+        else:
+            if bump is None:
+                bump = getattr(self, "_pending_bump", False)
+            self._pending_bump = False
+        skip = lambda *a, **kw: None   # noqa: E731
+        k = SimpleNamespace(embed_step=skip, attn_decode=skip, ln_reduce=skip) if gemm_only else nat   # every other launch
+        tally = [0, 0]
+
+        def gemm(M, N, K, w, bias, epi, **kw):
+            nat.gemm_skinny(T, M, N, K, w, bias, epi=epi, **kw)
+            out = {nat.EPI_QKV_CACHE: es, nat.EPI_GELU_STORE: es, nat.EPI_RESID_F32: 2 * 4 + es,    # (h read and written, T copy)
+                   nat.EPI_SLAB_F32: 4 * kw.get("ksplit", 1), nat.EPI_STORE_F32: 4}[epi]
+            tally[0] += 1
+            tally[1] += (N * K + M * K) * es + M * N * out
         rs0 = self.row_step0 if self._kv_rows is None else None
         kva = self._kvargs()
+        attn_kw = dict(kv_rows=self._kv_rows, kv_step=step if self._kv_rows is not None else None,
+                       skip_rows=self.finished if self._kv_rows is None and self.skip_finished else None,
+                       kv_share=self.kv_share if self._kv_rows is None else None, **kva)
         if self._fold_now(B):
             hb = self.hb
             # mel position of token k is k + 1 (model.py:163-167); with a pending bump state[0] still holds k - 1
-            nat.embed_step(self.tokens, self.mel_emb, self.mel_pos, step, 2 if bump else 1, h, row_step0=rs0, h_packed=hb,
-                           bump=pos if bump else None)
+            k.embed_step(self.tokens, self.mel_emb, self.mel_pos, step, 2 if bump else 1, h, row_step0=rs0, h_packed=hb,
+                         bump=pos if bump else None)
             r_o, r_p = self.fold_rows
             # more than 32 rows (beam search: 32 x 3): a workgroup that covers ALL rows moves 246 KB of activations through its
             # CU's load path per 1280-deep K; 32 rows per workgroup (the row tiles dealt to grid.z, 3-4 column tiles each so that
@@ -662,57 +709,44 @@ class GPTEngine:
             if B > 32:
                 r_o, r_p = max(r_o, 32), max(r_p, 32)
             for i, l in enumerate(self.layers):
-                nat.gemm_skinny(T, B, 3 * D, D, l["wf_qkv"], l["d_qkv"], x=hb, epi=nat.EPI_QKV_CACHE, y=self.q, kcache=self.kc[i],
-                                vcache=self.vc[i], pos=pos, heads=H, smax=self._cap_s, x_packed=True, ln_c=l["c_qkv"],
-                                bump=step if (bump and i == 0) else None, rows_per_wg=r_c, **kva)
-                nat.attn_decode(self.q, self.kc[i], self.vc[i], self.a, self.pad, pos, B, H, self._cap_s, out_packed=pa,
-                                kv_rows=self._kv_rows, kv_step=step if self._kv_rows is not None else None,
-                                skip_rows=self.finished if self._kv_rows is None and self.skip_finished else None,
-                                kv_share=self.kv_share if self._kv_rows is None else None, **kva)
-                nat.gemm_skinny(T, B, D, D, l["w_o"], l["b_o"], x=self.a, epi=nat.EPI_RESID_F32, yf=h, y=hb, x_packed=pa,
-                                y_packed=True, rows_per_wg=r_o, wide_wg=self.fold_wide)
-                nat.gemm_skinny(T, B, 4 * D, D, l["wf_fc"], l["d_fc"], x=hb, epi=nat.EPI_GELU_STORE, y=self.f, x_packed=True,
-                                y_packed=pa, ln_c=l["c_fc"], rows_per_wg=r_c)
-                nat.gemm_skinny(T, B, D, 4 * D, l["w_pr"], l["b_pr"], x=self.f, epi=nat.EPI_RESID_F32, yf=h, y=hb, x_packed=pa,
-                                y_packed=True, rows_per_wg=r_p, wide_wg=self.fold_wide)
-            nat.ln_reduce(h, self.ln_f[0], self.ln_f[1], xn, w2=self.final_norm[0], b2=self.final_norm[1], y_packed=pa)
-            nat.gemm_skinny(T, B, self.V, D, self.w_head, self.b_head, x=self.xn, epi=nat.EPI_STORE_F32, yf=self.logits, x_packed=pa)
-            return
-        nat.embed_step(self.tokens, self.mel_emb, self.mel_pos, step, 2 if bump else 1, h, row_step0=rs0)
-        nat.ln_reduce(h, self.layers[0]["ln1"][0], self.layers[0]["ln1"][1], xn, state_bump=self.state[0:2] if bump else None,
-                      y_packed=pa)
-        for i, l in enumerate(self.layers):
-            last = i + 1 == self.L
-            n_o = l.get("lora_n_o", D)
-            n_p = l.get("lora_n_pr", D)
-            w_o = l.get("w_o_lora", l["w_o"])
-            w_pr = l.get("w_pr_lora", l["w_pr"])
-            nat.gemm_skinny(T, B, 3 * D, D, l["w_qkv"], l["b_qkv"], x=xn, epi=nat.EPI_QKV_CACHE, y=self.q, kcache=self.kc[i],
-                            vcache=self.vc[i], pos=pos, heads=H, smax=self._cap_s, x_packed=pa, **kva)
-            nat.attn_decode(self.q, self.kc[i], self.vc[i], self.a, self.pad, pos, B, H, self._cap_s, out_packed=pa,
-                            kv_rows=self._kv_rows, kv_step=step if self._kv_rows is not None else None,
-                            skip_rows=self.finished if self._kv_rows is None and self.skip_finished else None,
-                            kv_share=self.kv_share if self._kv_rows is None else None, **kva)
-            nxt = self.ln_f if last else self.layers[i + 1]["ln1"]
-            nxt2 = self.final_norm if last else None
-            # out-projection: split-K slabs; with a runtime adapter the GEMM also produces x A in extra columns and the
-            # reduce launch adds (x A) B^T
-            sl_o = self.slab.view(-1)[: KS * B * n_o].view(KS, B, n_o)
-            nat.gemm_skinny(T, B, n_o, D, w_o, None, x=self.a, epi=nat.EPI_SLAB_F32, yf=sl_o, ksplit=KS,
-                            x_packed=pa)
-            nat.ln_reduce(h, l["ln2"][0], l["ln2"][1], xn, slab=sl_o, nslab=KS, bias=l["b_o"], y_packed=pa,
-                          slab_stride=n_o, lora_b=l.get("lora_b_o"))
-            nat.gemm_skinny(T, B, 4 * D, D, l["w_fc"], l["b_fc"], x=xn, epi=nat.EPI_GELU_STORE, y=self.f, x_packed=pa, y_packed=pa)
-            sl_p = self.slab.view(-1)[: KS * B * n_p].view(KS, B, n_p)
-            nat.gemm_skinny(T, B, n_p, 4 * D, w_pr, None, x=self.f, epi=nat.EPI_SLAB_F32, yf=sl_p, ksplit=KS,
-                            x_packed=pa)
-            if last:
-                nat.ln_reduce(h, nxt[0], nxt[1], xn, slab=sl_p, nslab=KS, bias=l["b_pr"], w2=nxt2[0], b2=nxt2[1], y_packed=pa,
-                              slab_stride=n_p, lora_b=l.get("lora_b_pr"))
-            else:
-                nat.ln_reduce(h, nxt[0], nxt[1], xn, slab=sl_p, nslab=KS, bias=l["b_pr"], y_packed=pa, slab_stride=n_p,
-                              lora_b=l.get("lora_b_pr"))
-        nat.gemm_skinny(T, B, self.V, D, self.w_head, self.b_head, x=self.xn, epi=nat.EPI_STORE_F32, yf=self.logits, x_packed=pa)
+                gemm(B, 3 * D, D, l["wf_qkv"], l["d_qkv"], nat.EPI_QKV_CACHE, x=hb, y=self.q, kcache=self.kc[i], vcache=self.vc[i],
+                     pos=pos, heads=H, smax=self._cap_s, x_packed=True, ln_c=l["c_qkv"], bump=step if (bump and i == 0) else None,
+                     rows_per_wg=r_c, **kva)
+                k.attn_decode(self.q, self.kc[i], self.vc[i], self.a, self.pad, pos, B, H, self._cap_s, out_packed=pa, **attn_kw)
+                gemm(B, D, D, l["w_o"], l["b_o"], nat.EPI_RESID_F32, x=self.a, yf=h, y=hb, x_packed=pa, y_packed=True,
+                     rows_per_wg=r_o, wide_wg=self.fold_wide)
+                gemm(B, 4 * D, D, l["wf_fc"], l["d_fc"], nat.EPI_GELU_STORE, x=hb, y=self.f, x_packed=True, y_packed=pa,
+                     ln_c=l["c_fc"], rows_per_wg=r_c)
+                gemm(B, D, 4 * D, l["w_pr"], l["b_pr"], nat.EPI_RESID_F32, x=self.f, yf=h, y=hb, x_packed=pa, y_packed=True,
+                     rows_per_wg=r_p, wide_wg=self.fold_wide)
+            k.ln_reduce(h, self.ln_f[0], self.ln_f[1], xn, w2=self.final_norm[0], b2=self.final_norm[1], y_packed=pa)
+        else:
+            k.embed_step(self.tokens, self.mel_emb, self.mel_pos, step, 2 if bump else 1, h, row_step0=rs0)
+            k.ln_reduce(h, self.layers[0]["ln1"][0], self.layers[0]["ln1"][1], xn, state_bump=self.state[0:2] if bump else None,
+                        y_packed=pa)
+            for i, l in enumerate(self.layers):
+                last = i + 1 == self.L
+                n_o = l.get("lora_n_o", D)
+                n_p = l.get("lora_n_pr", D)
+                gemm(B, 3 * D, D, l["w_qkv"], l["b_qkv"], nat.EPI_QKV_CACHE, x=xn, y=self.q, kcache=self.kc[i], vcache=self.vc[i],
+                     pos=pos, heads=H, smax=self._cap_s, x_packed=pa, **kva)
+                k.attn_decode(self.q, self.kc[i], self.vc[i], self.a, self.pad, pos, B, H, self._cap_s, out_packed=pa, **attn_kw)
+                nxt = self.ln_f if last else self.layers[i + 1]["ln1"]
+                nxt2 = self.final_norm if last else (None, None)
+                # out-projection: split-K slabs; with a runtime adapter the GEMM also produces x A in extra columns and the
+                # reduce launch adds (x A) B^T
+                sl_o = self.slab.view(-1)[: KS * B * n_o].view(KS, B, n_o)
+                gemm(B, n_o, D, l.get("w_o_lora", l["w_o"]), None, nat.EPI_SLAB_F32, x=self.a, yf=sl_o, ksplit=KS, x_packed=pa)
+                k.ln_reduce(h, l["ln2"][0], l["ln2"][1], xn, slab=sl_o, nslab=KS, bias=l["b_o"], y_packed=pa,
+                            slab_stride=n_o, lora_b=l.get("lora_b_o"))
+                gemm(B, 4 * D, D, l["w_fc"], l["b_fc"], nat.EPI_GELU_STORE, x=xn, y=self.f, x_packed=pa, y_packed=pa)
+                sl_p = self.slab.view(-1)[: KS * B * n_p].view(KS, B, n_p)
+                gemm(B, n_p, 4 * D, l.get("w_pr_lora", l["w_pr"]), None, nat.EPI_SLAB_F32, x=self.f, yf=sl_p, ksplit=KS,
+                     x_packed=pa)
+                k.ln_reduce(h, nxt[0], nxt[1], xn, slab=sl_p, nslab=KS, bias=l["b_pr"], w2=nxt2[0], b2=nxt2[1], y_packed=pa,
+                            slab_stride=n_p, lora_b=l.get("lora_b_pr"))
+        gemm(B, self.V, D, self.w_head, self.b_head, nat.EPI_STORE_F32, x=self.xn, yf=self.logits, x_packed=pa)
+        return tuple(tally)
 
     def _poll(self):
         """One host synchronisation of the token loop: the number of finished rows."""
@@ -724,39 +758,45 @@ class GPTEngine:
 
     def gemm_launches_of_step(self, B):
         """Measurement aid (bench.py): ONLY the skinny-GEMM launches of one decode step, with the step's real arguments
-        (97 launches: 4 per block + the head).  Returns (GEMM launch count, algorithmic bytes: weights once + activations in
-        and out; "fold" mode: the residual rows the two epilogues read and write and their T copy; "launch" mode: the slabs)."""
-        T, D, H, KS = self.dtype, self.D, self.H, self.KSPLIT
-        pos = self.state[1:2]
-        h, xn, pa = self.h[:B], self.xn, self.pa
-        es = 4 if T == torch.float32 else 2
-        fold = self._fold_now(B)
-        nbytes, n = 0, 0
-        slab = self.slab.view(-1)[: KS * B * D].view(KS, B, D)
-        r_o, r_p = self.fold_rows
-        for i, l in enumerate(self.layers):
-            if fold:
-                hb = self.hb
-                nat.gemm_skinny(T, B, 3 * D, D, l["wf_qkv"], l["d_qkv"], x=hb, epi=nat.EPI_QKV_CACHE, y=self.q, kcache=self.kc[i],
-                                vcache=self.vc[i], pos=pos, heads=H, smax=self._cap_s, x_packed=True, ln_c=l["c_qkv"], **self._kvargs())
-                nat.gemm_skinny(T, B, D, D, l["w_o"], l["b_o"], x=self.a, epi=nat.EPI_RESID_F32, yf=h, y=hb, x_packed=pa,
-                                y_packed=True, rows_per_wg=r_o, wide_wg=self.fold_wide)
-                nat.gemm_skinny(T, B, 4 * D, D, l["wf_fc"], l["d_fc"], x=hb, epi=nat.EPI_GELU_STORE, y=self.f, x_packed=True,
-                                y_packed=pa, ln_c=l["c_fc"])
-                nat.gemm_skinny(T, B, D, 4 * D, l["w_pr"], l["b_pr"], x=self.f, epi=nat.EPI_RESID_F32, yf=h, y=hb, x_packed=pa,
-                                y_packed=True, rows_per_wg=r_p, wide_wg=self.fold_wide)
-                nbytes += 12 * D * D * es + B * D * es * (1 + 1 + 1 + 4) + B * es * (3 * D + 4 * D) + 2 * (2 * B * D * 4 + B * D * es)
+        (97 launches: 4 per block + the head).  Returns (GEMM launch count, algorithmic bytes); see _step_transformer."""
+        return self._step_transformer(B, gemm_only=True)
+
+    def _graph_key(self, kind, B, sp, nb=1):
+        """Key of a captured decode step: the loop kind ("token" / "beam"), its rows and beams, the sampling parameters and
+        every engine setting the captured launches read -- a setting changed after a capture must not replay the old variant."""
+        return (kind, B, nb, self.decode_mode, self.lora, tuple(self.fold_rows), self.fold_rows_consumers, self.fold_wide,
+                self.pa, self.KSPLIT, self.skip_finished, self.share_kv_reads, self.beam_kv,
+                None if self.kv is None else self.kv.bs, tuple(sorted(sp.items())))
+
+    def _graph(self, key, body):
+        """The CUDA graph of one decode step `body`, captured on first use and kept under `key` (see _graph_key)."""
+        g = self._graphs.get(key)
+        if g is None:
+            g = torch.cuda.CUDAGraph()
+            with nat.CAPTURE_LOCK, torch.cuda.graph(g):  # no other thread may allocate / synchronise during a capture
+                body()
+            self._graphs[key] = g
+        return g
+
+    def _token_loop(self, n, stop, body, key, use_graph, check_every=0, rows=0, each=None):
+        """Decode steps `body` from n tokens up to `stop`: the loop's first step (n = 1) runs eagerly and doubles as the
+        warm-up, every later one replays the graph kept under `key` (eager throughout with use_graph False or force_eager).
+        rows > 0: every check_every tokens the host polls, and the loop ends once all `rows` have finished.  each(): called
+        after every step.  Returns the new token count."""
+        graph = None
+        while n < stop:
+            if use_graph and not self.force_eager and n >= 2:
+                if graph is None:
+                    graph = self._graph(key, body)
+                graph.replay()
             else:
-                nat.gemm_skinny(T, B, 3 * D, D, l["w_qkv"], l["b_qkv"], x=xn, epi=nat.EPI_QKV_CACHE, y=self.q, kcache=self.kc[i],
-                                vcache=self.vc[i], pos=pos, heads=H, smax=self._cap_s, x_packed=pa, **self._kvargs())
-                nat.gemm_skinny(T, B, D, D, l["w_o"], None, x=self.a, epi=nat.EPI_SLAB_F32, yf=slab, ksplit=KS, x_packed=pa)
-                nat.gemm_skinny(T, B, 4 * D, D, l["w_fc"], l["b_fc"], x=xn, epi=nat.EPI_GELU_STORE, y=self.f, x_packed=pa, y_packed=pa)
-                nat.gemm_skinny(T, B, D, 4 * D, l["w_pr"], None, x=self.f, epi=nat.EPI_SLAB_F32, yf=slab, ksplit=KS, x_packed=pa)
-                nbytes += 12 * D * D * es + B * D * es * (1 + 1 + 1 + 4) + B * es * (3 * D + 4 * D) + 2 * KS * B * D * 4
-            n += 4
-        nat.gemm_skinny(T, B, self.V, D, self.w_head, self.b_head, x=self.xn, epi=nat.EPI_STORE_F32, yf=self.logits, x_packed=pa)
-        nbytes += self.V * D * es + B * D * es + B * self.V * 4
-        return n + 1, nbytes
+                body()
+            n += 1
+            if each is not None:
+                each()
+            if rows and n % check_every == 0 and self._poll() >= rows:
+                break
+        return n
 
     def decode(self, max_new: int, sp: dict, force_stop=None, use_graph=True, check_every=16, return_logits=False):
         """Run the sampling loop after prefill().  Returns codes int64 [B, n] padded with the stop token
@@ -777,21 +817,8 @@ class GPTEngine:
         logits_trace = [self.logits[:B].clone()] if return_logits else None
         sp = self._seed_to_state(sp)
         self._sample(B, sp)  # token 1 from the prefill logits
-        n = 1
-        G = 1 if return_logits else self.steps_per_graph
-        while n < max_new:
-            if use_graph and not self.force_eager and n >= 2:
-                k = G if n + G <= max_new else 1          # several tokens per replay while they fit
-                self._get_graph(B, sp, k).replay()
-            else:
-                k = 1
-                self._step_kernels(B, sp)                 # eager: first step doubles as the warm-up before capture
-            prev = n
-            n += k
-            if return_logits:
-                logits_trace.append(self.logits[:B].clone())
-            if n // check_every != prev // check_every and self._poll() >= B:
-                break
+        n = self._token_loop(1, max_new, lambda: self._step_kernels(B, sp), self._graph_key("token", B, sp), use_graph,
+                             check_every, B, each=(lambda: logits_trace.append(self.logits[:B].clone())) if return_logits else None)
         self._poll()
         codes = self.history[:B, :n].to(torch.int64)
         return (codes, torch.stack(logits_trace, 0)) if return_logits else codes
@@ -846,12 +873,19 @@ class GPTEngine:
         st.update(kst=kst, vst=vst, logits=lg_t)
         return st
 
-    def _join(self, st, sp):
+    def _join(self, st, sp, ev=None):
         """The staged rows enter the loop (between two of its steps, at the n they were staged for): keys / values into the
         slots' cache rows, the first token of every new row sampled from its prefill logits -- on buffers of its own, the
         running rows' logits stay --, and the per-row state: left padding, stop step, own clock row_step0 = n - 1 (mel
-        positions, history index and the repetition-penalty window count from the row's own first token)."""
+        positions, history index and the repetition-penalty window count from the row's own first token).  ev: _stage ran
+        on another stream and recorded it; the loop's stream waits for it and takes its buffers over."""
         k, n, dev = st["k"], st["n"], self.device
+        if ev is not None:
+            main = torch.cuda.current_stream(dev)
+            main.wait_event(ev)
+            for t in st.values():                       # allocated on the side stream, last used on this one
+                if torch.is_tensor(t):
+                    t.record_stream(main)
         self.kc[:, st["i_b"], :, st["i_p"]] = st["kst"]    # [M, L, H, 64] -> positions [pad, S+n-2] of the slots (rows | blocks)
         self.vc[:, st["i_b"], :, st["i_p"]] = st["vst"]
         tok_t = torch.zeros(k, dtype=torch.int32, device=dev)
@@ -870,6 +904,36 @@ class GPTEngine:
         self.row_step0[i_rows] = step0_t
         self.pad[i_rows] = st["pads"]
 
+    def _stage_beside(self, side, fed, rows, prefixes, stops, n):
+        """_stage on the stream `side` behind the event `fed`: (staged rows, the event that marks them ready)."""
+        with torch.cuda.stream(side):
+            side.wait_event(fed)
+            for p in prefixes:
+                p.record_stream(side)                   # allocated on the loop's stream, read on this one
+            st = self._stage(rows, prefixes, stops, n)
+            ev = torch.cuda.Event()
+            ev.record(side)
+        return st, ev
+
+    def _collect_stopped(self, owner, start, n):
+        """The refill loop's poll after n steps: {utterance id: codes ending with the stop token} of the rows that have stopped;
+        their slots become free and their blocks go back to the pool (the slot's later formal appends land in the scratch block)."""
+        self._poll()
+        fin = self.finished[: len(owner)].tolist()
+        newly = [r for r, o in enumerate(owner) if fin[r] and o is not None and o >= 0]
+        out = {}
+        if newly:
+            width = max(n - start[r] for r in newly)
+            hist = self.history[torch.tensor(newly, device=self.device), :width].cpu()
+            for j, r in enumerate(newly):
+                row = hist[j, : n - start[r]].to(torch.int64)
+                hit = (row == self.stop_mel).nonzero()
+                out[owner[r]] = row[: int(hit[0]) + 1] if hit.numel() else row
+                owner[r] = None
+                if self.kv is not None:
+                    self.kv.release(r)
+        return out
+
     def decode_refill(self, max_new: int, sp: dict, feed, force_stop=None, use_graph=True, check_every=16, positions=None,
                       staged=True):
         """Continuous batching: the sampling loop after prefill(), with every slot whose row has emitted its stop token
@@ -878,8 +942,8 @@ class GPTEngine:
         the queue is empty.  Rows are numbered in the order they entered: 0..B-1 = the prefilled batch, then the fed ones.
         max_new bounds every row's own length (a row that reaches it is stopped there).  Returns (codes, leftover): codes[id]
         int64 [n_id] ends with the stop token; leftover = items that were fed but could not be placed any more because the
-        cache positions reserved by prefill() -- or the smaller budget `positions` -- ran out (the caller starts a new loop
-        with them).
+        cache positions reserved by prefill() -- or the smaller budget `positions` -- ran out, or (paged cache) because a
+        row's window no longer fits the block table or the free blocks (admit()); the caller starts a new loop with them.
         Every check_every steps the host reads the `finished` flags (the loop's one synchronisation).  staged = True: the
         prompts of the utterances that take the freed slots are prefilled on a SECOND STREAM while the loop runs its next
         check_every steps, and join at the following poll -- the ~300 launches of that pass are enqueued and executed under
@@ -888,19 +952,19 @@ class GPTEngine:
         A row's tokens are those it would get decoded alone with the same logits (greedy: identical codes up to the usual
         reduction-order noise of a different left padding); sampled rows draw from the loop's Philox stream (row slot, loop
         step), so they differ from a stand-alone run as two seeds do."""
-        B, S = self._B, self._S
+        B, S, ce = self._B, self._S, int(check_every)
         if self._shared_prefix is not None or self._kv_rows is not None:
             raise ValueError("decode_refill(): num_beams = 1 only")
         kv = self.kv
         if kv is not None:
             # paged cache: the loop's position counter may grow for as long as the queue lasts -- a row only has to keep its own
-            # window (prompt + max_new + the steps up to the next poll) inside the block table's ring
+            # window (prompt + max_new + the steps up to the poll that finds it stopped) inside the block table's ring
             limit = (1 << 30) if positions is None else int(positions)
-            if max_new + 2 * check_every + 2 > kv.window:
+            if max_new + 2 * ce + 2 > kv.window:
                 raise ValueError("decode_refill(): max_new does not fit the block table's window")
         else:
             limit = self._cap_s if positions is None else min(self._cap_s, int(positions))
-        if S + max_new + check_every > limit:
+        if S + max_new + ce > limit:
             # the loop runs whole blocks of check_every steps before it looks at the flags again: the last rows can take
             # the loop check_every - 1 steps past max_new, and every step appends one K / V position for every slot
             raise ValueError("decode_refill(): the position budget must hold max_new + check_every positions behind the prompt "
@@ -912,115 +976,70 @@ class GPTEngine:
         sp = self._seed_to_state(sp)
         self.kv_share.zero_()                                # a refilled row 0 no longer holds the shared block where the others expect it
         owner, start = list(range(B)), [0] * B              # owner: utterance id | None (free) | -1 (reserved for staged rows)
-        next_id, codes, leftover, fed_out = B, {}, [], False
+        ids, codes, leftover, fed_out, pending = itertools.count(B), {}, [], False, None
         stats = self.refill_stats = {"steps": 0, "polls": 0, "refill_calls": 0, "rows_refilled": 0, "staged": bool(staged)}
         main = torch.cuda.current_stream(dev)
         side = torch.cuda.Stream(device=dev) if staged else None
-        pending = None                                      # (staged rows, slots, event)
-        stop_id = self.stop_mel
-        pads = list(self._pad_host[:B])                      # left padding per slot (paged cache: where a row's window starts)
         if kv is not None:
+            for b in range(B):      # the prefilled rows' whole windows, as admit() deals them (prefill(max_new + check_every) has)
+                kv.cover(b, self._pad_host[b], S + max_new + ce)
             stats["blocks"], stats["peak_blocks"] = kv.blocks - 1, kv.used_blocks()
+        step, key = (lambda: self._step_kernels(B, sp)), self._graph_key("token", B, sp)
         self._sample(B, sp)
         n = 1
         while True:
             # ---- A: rows staged during the last steps join here
             if pending is not None:
-                st, rows, ev = pending
-                main.wait_event(ev)
-                self._join(st, sp)
-                for t in st.values():                       # allocated on the side stream, last used on this one
-                    if torch.is_tensor(t):
-                        t.record_stream(main)
+                st, ev, rows = pending
+                self._join(st, sp, ev)
                 for r in rows:
-                    owner[r], start[r] = next_id, n - 1
-                    next_id += 1
+                    owner[r], start[r] = next(ids), n - 1
                 pending = None
             # ---- B: utterances for the slots that are free now
             free = [r for r in range(B) if owner[r] is None]
-            items, n_join = [], n + check_every if staged else n
+            items = []
             if free and not fed_out and n > 1:
                 items = list(feed(len(free)))
                 if len(items) > len(free):
                     raise ValueError(f"decode_refill(): feed({len(free)}) returned {len(items)} items")
-                if len(items) < len(free):
-                    fed_out = True
-                if items and limit - (S + n_join + 1) < max_new + check_every:    # steps the loop could still take
-                    leftover, items, fed_out = items, [], True
-                if items and kv is not None:
-                    # blocks for the new rows' windows: prompt + start token in front of the join position, then max_new tokens
-                    # and the steps up to the poll after the row's last one
-                    end = S + n_join - 1
-                    need = sum((end + max_new + 2 * check_every) // kv.bs - (end - int(p.shape[0]) - 1) // kv.bs + 1 for p, _ in items)
-                    if need > len(kv.free):
-                        leftover, items, fed_out = items, [], True          # (a pool sized by prefill(slots_window=...) never gets here)
+                fed_out = len(items) < len(free)
+                n_join = n + ce if staged else n
+                if limit - (S + n_join + 1) < max_new + ce:     # steps the loop could still take
+                    items, leftover = [], items
+                elif kv is not None:
+                    k = admit(kv, free, items, S + n_join - 1, max_new, ce)
+                    items, leftover = items[:k], items[k:]
+                fed_out = fed_out or bool(leftover)
             if items:
-                rows = free[: len(items)]
+                rows, prefixes = free[: len(items)], [p for p, _ in items]
                 stops = [max_new - 1 if int(v) < 0 else min(int(v), max_new - 1) for _, v in items]
-                if kv is not None:
-                    end = S + n_join - 1
-                    for r, (p, _) in zip(rows, items):
-                        pads[r] = end - (int(p.shape[0]) + 1)
-                        kv.cover(r, pads[r], end + check_every + 1)
                 stats["refill_calls"] += 1
                 stats["rows_refilled"] += len(rows)
                 if not staged:
-                    self._join(self._stage(rows, [p for p, _ in items], stops, n), sp)
+                    self._join(self._stage(rows, prefixes, stops, n), sp)
                     for r in rows:
-                        owner[r], start[r] = next_id, n - 1
-                        next_id += 1
+                        owner[r], start[r] = next(ids), n - 1
                     items = []
                 else:
                     fed = torch.cuda.Event()
                     fed.record(main)                        # the prefix embeddings are complete on the loop's stream
             if fed_out and pending is None and not items and all(o is None for o in owner):
                 break
-            # ---- C: check_every steps of the loop (paged cache: every live row's blocks reach past the last of them)
+            # ---- C: check_every steps of the loop
             if kv is not None:
-                for r in range(B):
-                    if owner[r] is not None and kv.span[r] is not None:
-                        kv.cover(r, pads[r], S + n - 1 + check_every + 1)
                 kv.flush()
                 stats["peak_blocks"] = max(stats["peak_blocks"], kv.used_blocks())
-            todo = check_every
-            while todo > 0:
-                G = self.steps_per_graph
-                if use_graph and not self.force_eager and n >= 2:
-                    kk = G if G <= todo else 1
-                    self._get_graph(B, sp, kk).replay()
-                else:
-                    kk = 1
-                    self._step_kernels(B, sp)
-                n += kk
-                todo -= kk
+            n = self._token_loop(n, n + ce, step, key, use_graph)
             # ---- D: the new rows' prompts, enqueued behind the steps on the host and run beside them on the GPU
             if items:
-                with torch.cuda.stream(side):
-                    side.wait_event(fed)
-                    for p, _ in items:
-                        p.record_stream(side)               # allocated on the loop's stream, read on this one
-                    st = self._stage(rows, [p for p, _ in items], stops, n_join)
-                    ev = torch.cuda.Event()
-                    ev.record(side)
+                st, ev = self._stage_beside(side, fed, rows, prefixes, stops, n_join)
+                pending = (st, ev, rows)
                 for r in rows:
                     owner[r] = -1
-                pending = (st, rows, ev)
             # ---- E: one host synchronisation: which rows have stopped
             stats["steps"], stats["polls"] = n, stats["polls"] + 1
-            self._poll()
-            fin = self.finished[:B].tolist()
-            newly = [r for r in range(B) if fin[r] and owner[r] is not None and owner[r] >= 0]
-            if newly:
-                width = max(n - start[r] for r in newly)
-                hist = self.history[torch.tensor(newly, device=dev), :width].cpu()
-                for j, r in enumerate(newly):
-                    row = hist[j, : n - start[r]].to(torch.int64)
-                    hit = (row == stop_id).nonzero()
-                    codes[owner[r]] = row[: int(hit[0]) + 1] if hit.numel() else row
-                    owner[r] = None
-                    if kv is not None:
-                        kv.release(r)      # its blocks go back to the pool; the slot's later (formal) appends land in the scratch block
-        return [codes[i] for i in range(next_id)], leftover
+            codes.update(self._collect_stopped(owner, start, n))
+        return [codes[i] for i in range(len(codes))], leftover
 
     # ------------------------------------------------------------------------------------------------ beam search
     def _ensure_beam(self, B: int, nb: int):
@@ -1104,24 +1123,8 @@ class GPTEngine:
     def _decode_beam_loop(self, B, nb, max_new, sp, use_graph, check_every, num_return=1):
         sp = self._seed_to_state(sp)
         self._beam_select(B, nb, sp)  # token 1 from the prefill logits
-        n = 1
-        key = ("beam", B, nb, self.beam_kv, self.decode_mode, self.lora, tuple(self.fold_rows), self.fold_rows_consumers, self.fold_wide,
-               self.pa, self.KSPLIT,
-               tuple(sorted(sp.items())))
-        while n < max_new:
-            if use_graph and not self.force_eager and n >= 2:
-                g = self._graphs.get(key)
-                if g is None:
-                    g = torch.cuda.CUDAGraph()
-                    with nat.CAPTURE_LOCK, torch.cuda.graph(g):
-                        self._step_kernels_beam(B, nb, sp)
-                    self._graphs[key] = g
-                g.replay()
-            else:
-                self._step_kernels_beam(B, nb, sp)
-            n += 1
-            if n % check_every == 0 and self._poll() >= B:
-                break
+        n = self._token_loop(1, max_new, lambda: self._step_kernels_beam(B, nb, sp), self._graph_key("beam", B * nb, sp, nb),
+                             use_graph, check_every, B)
         self._poll()
         return self._beam_finalize(B, nb, n, float(sp.get("length_penalty", 0.0)), max_new, num_return)
 
@@ -1166,20 +1169,6 @@ class GPTEngine:
         out = dict(sp)
         out["seed"] = 0
         return out
-
-    def _get_graph(self, B, sp, nsteps=1):
-        # everything the captured launches depend on besides the buffers: a knob toggled after a capture must not replay the
-        # old variant (skip_finished: whether the attention is given the finished flags)
-        key = (B, nsteps, self.skip_finished, self.decode_mode, self.lora, tuple(self.fold_rows), self.fold_wide, self.pa, self.KSPLIT,
-               self.share_kv_reads, None if self.kv is None else self.kv.bs, tuple(sorted(sp.items())))
-        g = self._graphs.get(key)
-        if g is None:
-            g = torch.cuda.CUDAGraph()
-            with nat.CAPTURE_LOCK, torch.cuda.graph(g):  # no other thread may allocate / synchronise during a capture
-                for _ in range(nsteps):
-                    self._step_kernels(B, sp)
-            self._graphs[key] = g
-        return g
 
     def step_bytes(self, B: int, ctx: int) -> int:
         """Algorithmic HBM bytes of one decode step: weights once + KV read + KV append."""

@@ -21,6 +21,17 @@ from .engine import GPTEngine
 from .perceiver import perceiver_resample
 
 
+def sampling_params(gen: dict, seed) -> dict:
+    """The decode loop's sampling parameters from generate()-style settings (do_sample, top_p, top_k, temperature,
+    repetition_penalty).  Greedy decoding ignores the distribution settings: they are normalised, so every greedy call keys
+    the same captured step."""
+    sp = dict(do_sample=bool(gen["do_sample"]), top_p=float(gen["top_p"]), top_k=int(gen["top_k"]),
+              temperature=float(gen["temperature"]), repetition_penalty=float(gen["repetition_penalty"]), seed=int(seed))
+    if not sp["do_sample"]:
+        sp["top_p"], sp["top_k"], sp["temperature"] = 1.0, 0, 1.0
+    return sp
+
+
 class UnifiedVoice:
     def __init__(self, layers=8, model_dim=512, heads=8, max_text_tokens=120, max_mel_tokens=250,
                  max_conditioning_inputs=1, mel_length_compression=1024, number_text_tokens=256, start_text_token=0,
@@ -197,13 +208,9 @@ class UnifiedVoice:
         if nrs > 1 and num_beams == 1 and not bool(hf.get("do_sample", False)):
             raise ValueError("greedy decoding returns one sequence: num_return_sequences > 1 needs do_sample=True or num_beams > 1")
         length_penalty = float(hf.pop("length_penalty", 1.0))  # HF default 1.0; infer.py passes 0.0
-        sp = dict(do_sample=bool(hf.pop("do_sample", False)), top_p=float(hf.pop("top_p", 1.0)),
-                  top_k=int(hf.pop("top_k", 50)), temperature=float(hf.pop("temperature", 1.0)),
-                  repetition_penalty=float(hf.pop("repetition_penalty", 1.0)),
-                  seed=int(torch.initial_seed() & 0x7FFFFFFFFFFFFFFF) if seed is None else int(seed))
-        if not sp["do_sample"]:
-            sp["top_p"], sp["top_k"], sp["temperature"] = 1.0, 0, 1.0
-        elif sp["top_k"] <= 0:
+        gen = {k: hf.pop(k, v) for k, v in dict(do_sample=False, top_p=1.0, top_k=50, temperature=1.0, repetition_penalty=1.0).items()}
+        sp = sampling_params(gen, torch.initial_seed() & 0x7FFFFFFFFFFFFFFF if seed is None else seed)
+        if sp["do_sample"] and sp["top_k"] <= 0:
             raise ValueError("do_sample=True needs top_k >= 1: the device sampler keeps at most 1024 candidates per row "
                              "(128 per beam) and refuses to truncate an unrestricted distribution silently")
         if hf:
@@ -217,11 +224,7 @@ class UnifiedVoice:
             if force_stop is not None or return_logits:
                 raise NotImplementedError("force_stop / return_logits are measurement aids of the num_beams=1 loop")
             sp["length_penalty"] = length_penalty
-            if self.engine.beam_kv == "table":   # prompt computed and cached once per batch element (row table)
-                self.engine.prefill(emb, pad, max_new, beams=num_beams, shared_rows=shared)
-            else:
-                self.engine.prefill(emb.repeat_interleave(num_beams, dim=0), pad.repeat_interleave(num_beams), max_new, shared_rows=shared,
-                                    paged=False)
+            self.engine.prefill_beams(emb, pad, max_new, num_beams, shared_rows=shared)
             return self.engine.decode_beam(max_new, sp, num_beams, num_return_sequences=nrs)
         if nrs > 1:
             # sampling: generate() expands every row to num_return_sequences copies before the first forward

@@ -23,7 +23,7 @@ import torch
 
 from indextts import _native as nat
 from indextts.BigVGAN.models import BigVGAN as Generator
-from indextts.gpt.model import UnifiedVoice
+from indextts.gpt.model import UnifiedVoice, sampling_params
 from indextts.utils.audio import read_audio, write_pcm16
 from indextts.utils.checkpoint import load_checkpoint
 from indextts.utils.config import Config, load_config
@@ -363,9 +363,18 @@ class IndexTTS:
         """Speaker embedding [1, 1, 512] of a prompt mel (ECAPA-TDNN): only the vocoder needs it."""
         return self._graphed("spk", lambda m: self.bigvgan.speaker_embedding(m.transpose(1, 2)), cond_mel)
 
-    def _prompt_features(self, cond_mel):
-        """(conditioning latents, speaker embedding) of a prompt mel."""
-        return self._prompt_conds(cond_mel), self._prompt_spk(cond_mel)
+    def _prompt_features(self, cond_mel, spk=True):
+        """(conditioning latents, speaker embedding) of a prompt mel, kept per prompt TENSOR: one prompt serves many batches
+        (one speaker, a stream of texts), and the same object with an unchanged version counter is the same prompt, as infer()
+        keeps them per prompt path (the cache holds a reference, so the storage cannot be recycled under it).  spk = False:
+        the speaker embedding (ECAPA, vocoder input) is not on the first token's critical path; it is computed when first
+        asked for and is None until then."""
+        bf = self._batch_feat
+        if bf is None or bf[0] is not cond_mel or bf[1] != cond_mel._version:
+            bf = self._batch_feat = [cond_mel, cond_mel._version, self._prompt_conds(cond_mel), None]
+        if spk and bf[3] is None:
+            bf[3] = self._prompt_spk(cond_mel)
+        return bf[2], bf[3]
 
     def _conds(self, cond_mel, speaker_id=None):
         """Conditioning latents of the call.  The reference passes BOTH the prompt mel and speaker_ids=[speaker_id] to
@@ -395,11 +404,7 @@ class IndexTTS:
         g = self.gpt
         emb, pad = g.prefix_rows(conds, text_tokens)
         shared = int(conds.shape[1]) if conds.shape[0] == 1 else 0   # one prompt: every row starts with the same latents
-        sp = dict(do_sample=bool(gen["do_sample"]), top_p=float(gen["top_p"]), top_k=int(gen["top_k"]),
-                  temperature=float(gen["temperature"]), repetition_penalty=float(gen["repetition_penalty"]),
-                  seed=int(extra.pop("seed", torch.initial_seed() & 0x7FFFFFFFFFFFFFFF)))
-        if not sp["do_sample"]:
-            sp["top_p"], sp["top_k"], sp["temperature"] = 1.0, 0, 1.0
+        sp = sampling_params(gen, extra.pop("seed", torch.initial_seed() & 0x7FFFFFFFFFFFFFFF))
         nb = int(gen.get("num_beams", 1))
         if nb > 1:  # beam search / beam-sample: every row becomes num_beams rows (HF generate semantics)
             sp["length_penalty"] = float(gen.get("length_penalty", 0.0))
@@ -655,22 +660,12 @@ class IndexTTS:
         if int(slots) < 1:
             raise ValueError("infer_queue: slots must be >= 1")
         self._mark(phase_events, "start")
-        bf = self._batch_feat
-        if bf is not None and bf[0] is cond_mel and bf[1] == cond_mel._version:
-            conds, spk = bf[2], bf[3]
-        else:
-            conds, spk = self._prompt_features(cond_mel)
-            self._batch_feat = [cond_mel, cond_mel._version, conds, spk]
-        if spk is None:
-            spk = self._batch_feat[3] = self._prompt_spk(cond_mel)
+        conds, spk = self._prompt_features(cond_mel)
         g, eng = self.gpt, self.gpt.engine
         N = len(text_token_rows)
         texts = [t.reshape(-1).to(torch.int32).cpu() for t in text_token_rows]
         stops = [-1] * N if force_stop is None else [int(v) for v in force_stop]
-        sp = dict(do_sample=bool(gen["do_sample"]), top_p=float(gen["top_p"]), top_k=int(gen["top_k"]),
-                  temperature=float(gen["temperature"]), repetition_penalty=float(gen["repetition_penalty"]), seed=int(seed))
-        if not sp["do_sample"]:
-            sp["top_p"], sp["top_k"], sp["temperature"] = 1.0, 0, 1.0
+        sp = sampling_params(gen, seed)
         stop_text = self.cfg.gpt.stop_text_token
 
         def prefixes(ids):
@@ -748,17 +743,7 @@ class IndexTTS:
         here is latency-bound small launches; it ends with the codes on the host, as infer.py:848-861 does."""
         gen, _ = self._gen_kwargs(generation_kwargs)
         self._mark(phase_events, "start")
-        # One prompt serves many batches (one speaker, a stream of texts): its conditioning latents and speaker embedding are
-        # kept per prompt TENSOR -- the same object with an unchanged version counter is the same prompt, as infer() keeps
-        # them per prompt path (the cache holds a reference, so the storage cannot be recycled under it).
-        bf = self._batch_feat
-        if bf is not None and bf[0] is cond_mel and bf[1] == cond_mel._version:
-            conds, spk = bf[2], bf[3]
-        else:
-            # the token loop needs the conditioning latents only; the speaker embedding (ECAPA, vocoder input) is computed
-            # when stage B asks for it (lazy_spk) -- it is not on the first token's critical path
-            conds, spk = self._prompt_conds(cond_mel), (None if lazy_spk else self._prompt_spk(cond_mel))
-            self._batch_feat = [cond_mel, cond_mel._version, conds, spk]
+        conds, spk = self._prompt_features(cond_mel, spk=not lazy_spk)   # lazy_spk: stage B asks for the speaker embedding
         L = max(int(t.numel()) for t in text_token_rows)
         stop = self.cfg.gpt.stop_text_token
         batch_h = torch.full((len(text_token_rows), L), stop, dtype=torch.int32)
@@ -768,10 +753,7 @@ class IndexTTS:
             batch_h[i, : t.numel()] = t.reshape(-1).to(torch.int32)
         g = self.gpt
         emb, pad = g.prefix_rows(conds, batch_h)   # one upload for the whole batch; the padding stays a host tensor
-        sp = dict(do_sample=bool(gen["do_sample"]), top_p=float(gen["top_p"]), top_k=int(gen["top_k"]),
-                  temperature=float(gen["temperature"]), repetition_penalty=float(gen["repetition_penalty"]), seed=int(seed))
-        if not sp["do_sample"]:
-            sp["top_p"], sp["top_k"], sp["temperature"] = 1.0, 0, 1.0
+        sp = sampling_params(gen, seed)
         self._mark(phase_events, "conditioned")
         nb = int(gen.get("num_beams", 1))
         shared = int(conds.shape[1]) if conds.shape[0] == 1 else 0   # one prompt: every row starts with the same latents
@@ -779,10 +761,7 @@ class IndexTTS:
             if force_stop is not None:
                 raise NotImplementedError("force_stop is a measurement aid of the num_beams=1 loop")
             sp["length_penalty"] = float(gen.get("length_penalty", 0.0))
-            if g.engine.beam_kv == "table":    # the prompt is computed and cached once per batch element (row table)
-                g.engine.prefill(emb, pad, max_mel_tokens, beams=nb, shared_rows=shared)
-            else:                              # generate() expands every row to num_beams copies before the first forward
-                g.engine.prefill(emb.repeat_interleave(nb, dim=0), pad.repeat_interleave(nb), max_mel_tokens, shared_rows=shared, paged=False)
+            g.engine.prefill_beams(emb, pad, max_mel_tokens, nb, shared_rows=shared)
             self._mark(phase_events, "prefilled")
             codes = g.engine.decode_beam(max_mel_tokens, sp, nb)
         else:

@@ -680,6 +680,57 @@ def test_paged_kv_long_queue_through_few_slots_in_one_loop():
                     break
 
 
+def test_decode_refill_on_a_plain_prefill_pool_hands_back_what_does_not_fit():
+    """decode_refill over the block pool plain prefill(max_new + ce + 1) deals (no slots_window): the pool only holds the
+    prefilled rows' windows, and rows stop at staggered steps.  A fed utterance is dealt its whole window when it is admitted
+    -- the blocks rows admitted earlier still need are not counted as free -- so what no longer fits comes back as leftover
+    instead of exhausting the pool mid-loop, and every utterance that ran gets the greedy codes it gets decoded alone."""
+    m = make_gpt(2, torch.float32)
+    eng = m.engine
+    rng = np.random.default_rng(7)
+    cond_mel = torch.from_numpy(synth.uniform("in.cond_mel", (1, 100, 120), -6.0, 2.0)).to(DEV)
+    conds = m.get_conditioning(cond_mel, None)
+    N, slots, max_new, ce = 16, 4, 40, 4
+    lens = sorted((int(v) for v in rng.integers(2, 15, size=N)), reverse=True)
+    texts = [torch.from_numpy(rng.integers(2, 12000, size=n)).to(torch.int32) for n in lens]
+    stops = [int(v) for v in rng.integers(3, max_new - 2, size=N)]
+    sp = dict(do_sample=False, top_p=1.0, top_k=0, temperature=1.0, repetition_penalty=10.0, seed=0)
+
+    def prefix(ids):
+        L = max(lens[i] for i in ids)
+        bh = torch.full((len(ids), L), m.stop_text_token, dtype=torch.int32)
+        for j, i in enumerate(ids):
+            bh[j, : lens[i]] = texts[i]
+        _, emb, mask = m.prepare_gpt_inputs(conds, bh.to(DEV))
+        return emb, (mask == 0).sum(1).to(torch.int32)
+
+    queue = list(range(slots, N))
+    emb, pad = prefix(list(range(slots)))
+    eng.prefill(emb, pad, max_new + ce + 1)
+    assert eng.kv is not None and not eng.kv.free
+
+    def feed(k):
+        take = [queue.pop(0) for _ in range(min(k, len(queue)))]
+        if not take:
+            return []
+        e, p = prefix(take)
+        return [(e[j, int(p[j]):], stops[i]) for j, i in enumerate(take)]
+
+    codes, leftover = eng.decode_refill(max_new, sp, feed, force_stop=stops[:slots], check_every=ce, staged=True)
+    assert len(codes) + len(leftover) + len(queue) == N and len(codes) >= slots
+    assert eng.refill_stats["peak_blocks"] <= eng.refill_stats["blocks"] and eng.kv.used_blocks() == 0
+    for i, c in enumerate(codes):
+        c = c.cpu()
+        assert int(c[-1]) == m.stop_mel_token and c.numel() == stops[i] + 1, (i, c)
+        want, lg = m.inference_speech(cond_mel, texts[i][None].to(DEV), do_sample=False, num_beams=1, repetition_penalty=10.0,
+                                      max_generate_length=max_new, force_stop=[stops[i]], return_logits=True)
+        for s_ in range(c.numel()):
+            if int(c[s_]) != int(want[0, s_]):
+                top2 = torch.topk(lg[s_, 0].cpu(), 2).values
+                assert (top2[0] - top2[1]).item() < 1e-3, (i, s_, c, want)
+                break
+
+
 @pytest.mark.parametrize("paged", [True, False])
 def test_decode_refill_idle_slot_outlives_the_position_table_and_budget_is_checked(paged):
     """Two findings of the round-3 review.  (1) A slot whose row has stopped and is not refilled keeps stepping formally until the
