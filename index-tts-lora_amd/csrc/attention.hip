@@ -13,9 +13,14 @@ constexpr int HD = 64;  // head dim
 // ---------------------------------------------------------------------------------------------------------------------
 // Decode: workgroup = (b, h), 4 waves.  Each lane owns a 16-byte slice of a key/value row (8 bf16 / 4 fp32 dims);
 // LPR = 64/E lanes cover one row, a wave-load covers RPW = 64/LPR rows (1 KiB, contiguous).  Single pass with online
-// softmax: for a chunk of CH row groups the K AND V fragments are all requested before the first use (one memory round
-// trip per chunk; a typical 100-300 token context is one chunk), every lane keeps a running (max, sum, o[E]) for the
-// rows it saw, and the partial states are merged across row groups (shuffles) and waves (LDS) at the end.
+// softmax: for a pass of NCH row groups per wave the K and then the V fragments are all requested before the first use (one
+// memory round trip per pass; a typical 100-300 token context is one pass), every lane keeps a running (max, sum, o[E])
+// for the rows it saw, and the partial states are merged across row groups (shuffles) and waves (LDS) at the end.
+// The first pass is CONTEXT-SIZED (16-bit types without a row table): NCH in {CH/4, CH/2, 3CH/4, CH} is the smallest that
+// covers the row's keys, chosen wave-uniformly once the context is known.  A chunk past the context used to be requested
+// anyway, clamped onto the last key: no HBM bytes, but a full 64-lane 16-byte request through the CU's load path, a dot
+// product and an exp each, for a term that is exactly zero -- half of all requests at a 75-216 key context.  The
+// key-to-lane assignment and every lane's order of operations are those of the full pass: the results are bit-identical.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int AD_MAXCTX = 16384;   // validation bound on cache positions per row (nothing in the kernel is sized by it)
 constexpr int AD_CH = 8;
@@ -27,6 +32,37 @@ __device__ __forceinline__ void softmax_merge(float& m, float& l, float m2, floa
   l = l * sa + l2 * sb;
   m = M;
 }
+
+// Diagnostic build only (tools/timeline_attn.py): s_memtime stamps of wave 0 of every workgroup, kept in LDS and written out
+// with ordinary vector stores at the end; 16 x u64 per workgroup (linear id = blockIdx.y * gridDim.x + blockIdx.x), see
+// include/indextts_hip_diag.h.  A stamp that stands for "this request has landed" WAITS for it (wave 0 only, and only while
+// stamps are on): read the shares, the waits forbid overlaps the product kernel has.  The product build gets neither the
+// parameter nor an instruction of this.
+#if ITTS_DIAG
+#define ITTS_AD_DIAG_PARAMS , unsigned long long* __restrict__ stamps, int full_pass
+#define ITTS_AD_DIAG_ARGS , itts::g_stamp_buf_attn, itts::g_attn_full_pass
+unsigned long long* g_stamp_buf_attn = nullptr;   // (inside namespace itts) itts_debug_set(8, 1) + itts_debug_stamps
+int g_attn_full_pass = 0;                         // itts_debug_set(7, 0 | 1)
+#else
+#define ITTS_AD_DIAG_PARAMS
+#define ITTS_AD_DIAG_ARGS
+#endif
+#if ITTS_STAMPS
+#define AD_STAMP(i) ITTS_STAMP_IF(stamps != nullptr, i)
+#define AD_STAMP_LANDED(i, cnt)                                              \
+  do {                                                                       \
+    __builtin_amdgcn_sched_barrier(0);                                       \
+    if (stamps != nullptr && threadIdx.x == 0) {                             \
+      unsigned long long t_;                                                 \
+      asm volatile("s_waitcnt vmcnt(%1)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) : "n"(cnt) : "memory"); \
+      st_[i] = t_;                                                           \
+    }                                                                        \
+    __builtin_amdgcn_sched_barrier(0);                                       \
+  } while (0)
+#else
+#define AD_STAMP(i) do { } while (0)
+#define AD_STAMP_LANDED(i, cnt) do { } while (0)
+#endif
 
 // IND: beam search -- key/value position j of logical row b lives in physical cache row kv_rows[parity][b][j] (a table
 // that itts_beam_step permutes instead of copying cache rows); parity = *kv_step & 1.
@@ -41,19 +77,26 @@ __global__ __launch_bounds__(NWV * 64) void attn_decode_kernel(const T* __restri
                                                            const int32_t* __restrict__ kv_step, int rows_total,
                                                            const int32_t* __restrict__ skip_rows,
                                                            const int32_t* __restrict__ kv_share,
-                                                           const int32_t* __restrict__ kv_tab, int bs_log2) {
+                                                           const int32_t* __restrict__ kv_tab, int bs_log2 ITTS_AD_DIAG_PARAMS) {
   typedef Elem<T> EL;
   typedef typename EL::frag frag;
   constexpr int E = EL::E;
   constexpr int LPR = HD / E;        // lanes per row: 8 (16-bit) / 16 (fp32)
 
   constexpr int RPW = 64 / LPR;      // rows per wave-load: 8 / 4
-  constexpr int CH = AD_CH * 4 / NWV;   // chunks per wave: a workgroup pass always covers 4 * RPW * AD_CH keys
+  constexpr int CH = AD_CH * 4 / NWV;   // chunks per wave of a full pass: 4 * RPW * AD_CH keys per workgroup
+  constexpr bool SIZED = !IND && sizeof(T) == 2 && CH % 4 == 0;   // context-sized first pass (see above)
   __shared__ float w_m[NWV], w_l[NWV];
   __shared__ float w_o[NWV][HD];
   const int h = blockIdx.x, b = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int part = lane % LPR, rg = lane / LPR;
+#if ITTS_STAMPS
+  __shared__ unsigned long long st_[16];
+  if (stamps != nullptr && tid < 16) st_[tid] = 0;
+  if (stamps != nullptr && tid == 0) st_[14] = __builtin_amdgcn_s_memrealtime();
+#endif
+  AD_STAMP(0);
   // Two memory round trips, not four: the query fragment and the three device scalars (left padding, cache position, the
   // row's stop flag) are requested together -- nothing here depends on a loaded value -- and the K / V requests follow as
   // soon as the scalars are back; the query is converted only after those have been issued.  (The first version read the
@@ -83,11 +126,12 @@ __global__ __launch_bounds__(NWV * 64) void attn_decode_kernel(const T* __restri
   int pos0 = pos[0];
   asm volatile("" : "+s"(pos0));              // (keeps the load here: the compiler would otherwise load it only for rows that need it)
   const int ctx = skipped ? j0 : pos0 + 1;    // keys [j0, ctx)
-  const T* kb = kc + (PAGED ? 0 : ((int64_t)b * H + h) * smax * HD) + part * E;
-  const T* vb = vc + (PAGED ? 0 : ((int64_t)b * H + h) * smax * HD) + part * E;
+  const int64_t kboff = (PAGED ? 0 : ((int64_t)b * H + h) * smax * HD) + part * E;   // this (row, head)'s keys, the lane's dims
   const int64_t sh_off = ((int64_t)h * smax + (share_w >> 8)) * HD + part * E;   // row 0, head h, position p0
   const int32_t* tab = nullptr;
   if constexpr (IND) tab = kv_rows + ((int64_t)(kv_step[0] & 1) * rows_total + b) * smax;
+
+  AD_STAMP(1);   // trip 1 is back: the context is known
 
   float qf[E];
   float m = -INFINITY, l = 0.f, o[E];
@@ -102,21 +146,35 @@ __global__ __launch_bounds__(NWV * 64) void attn_decode_kernel(const T* __restri
   // in the paged form the block id of a request is WAVE-UNIFORM -- one v_readlane out of the table register per request, no
   // per-lane lookup in front of the K / V stream.
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-  auto key_pass = [&](const int base, auto first_tag) {
+  auto key_pass = [&](const int base, auto nch_tag, auto first_tag) {
+    constexpr int NCH = decltype(nch_tag)::value;
     constexpr bool FIRST = decltype(first_tag)::value;
-    frag kf[CH], vf[CH];
-    int prow[CH];
+    frag kf[NCH], vf[NCH];
+    int prow[NCH];
+    int64_t eo[NCH];   // element offset of the lane's fragment, the same in the K and in the V cache
     // Positions past the context are CLAMPED onto its last key (same cache lines; their scores are forced to -inf below)
     // instead of being skipped: a conditional load is a branch, and a join makes the compiler drain the memory queue.
     if constexpr (IND) {
 #pragma unroll
-      for (int i = 0; i < CH; ++i) {   // the rows of this chunk's keys, all requested before the first K/V load
+      for (int i = 0; i < NCH; ++i) {   // the rows of this chunk's keys, all requested before the first K/V load
         int j = min(base + (i * NWV + wave) * RPW + rg, ctx - 1);
         prow[i] = tab[j];
       }
     }
+    int blk0[NCH];   // PAGED with shared first keys: the block of the same key in row 0's window (a per-lane lookup)
+    if constexpr (PAGED && !IND) {
+      // all of the pass's lookups are issued together, ahead of the address arithmetic: one LDS-crossbar latency for the
+      // pass instead of one in front of every request
 #pragma unroll
-    for (int i = 0; i < CH; ++i) {
+      for (int i = 0; i < NCH; ++i) {
+        const int jf = min(base + (i * NWV + wave_u) * RPW, (ctx - 1) & ~(RPW - 1));
+        const int ps = (share_w >> 8) + (min(jf + rg, ctx - 1) - j0);
+        blk0[i] = __shfl(tab0v, (ps >> bs_log2) & (ITTS_KV_TAB - 1), 64);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
       // first key of this wave-load (wave-uniform); groups past the context fall onto the group of its last key, and the rows
       // past it onto that key (same cache lines, one block)
       const int jf = min(base + (i * NWV + wave_u) * RPW, (ctx - 1) & ~(RPW - 1));
@@ -127,32 +185,39 @@ __global__ __launch_bounds__(NWV * 64) void attn_decode_kernel(const T* __restri
         const int blk = __builtin_amdgcn_readlane(tabv, (jf >> bs_log2) & (ITTS_KV_TAB - 1));
         ro = ((((int64_t)blk * H + h) << bs_log2) + (j & bsm)) * HD;
       }
-      const T* kp = kb + ro;
-      const T* vp = vb + ro;
+      eo[i] = kboff + ro;
       if constexpr (!IND) {
         const bool sh = (unsigned)(j - j0) < (unsigned)shC;   // a select, not a branch (also false for j < j0: skipped rows)
         int64_t so = sh_off + (int64_t)(j - j0) * HD;
         if constexpr (PAGED) {
-          const int ps = (share_w >> 8) + (j - j0);            // the same key in row 0's window (its block: a per-lane lookup)
-          const int blk0 = __shfl(tab0v, (ps >> bs_log2) & (ITTS_KV_TAB - 1), 64);
-          so = ((((int64_t)blk0 * H + h) << bs_log2) + (ps & bsm)) * HD + part * E;
+          const int ps = (share_w >> 8) + (j - j0);            // the same key in row 0's window
+          so = ((((int64_t)blk0[i] * H + h) << bs_log2) + (ps & bsm)) * HD + part * E;
         }
-        kp = sh ? kc + so : kp;
-        vp = sh ? vc + so : vp;
+        asm("" : "+v"(so));            // (an opaque value: the compiler would otherwise turn the select into a branch around
+                                       //  the table lookup above, a join with an LDS wait in front of every K request)
+        eo[i] = sh ? so : eo[i];
       }
-      kf[i] = ld16<frag>(kp);
-      vf[i] = ld16<frag>(vp);
+      kf[i] = ld16<frag>(kc + eo[i]);
     }
+    // All K, then all V: the memory counter retires in order and the softmax needs the maximum over ALL of the pass's scores,
+    // so with K and V interleaved the first exp waited for the last-but-one request; now the scores, their shuffles and the
+    // maximum run while V is still landing.
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) vf[i] = ld16<frag>(vc + eo[i]);
     __builtin_amdgcn_sched_barrier(0);   // every K AND V request of the pass is out before anything waits
     if constexpr (FIRST) {
 #pragma unroll
       for (int e = 0; e < E; ++e) qf[e] = EL::to_f(qv[e]) * 0.125f;
       __builtin_amdgcn_sched_barrier(0);
+      AD_STAMP(2);                        // (request order: K0 .. K[NCH-1], V0 .. V[NCH-1])
+      AD_STAMP_LANDED(3, 2 * NCH - 1);    // first K
+      AD_STAMP_LANDED(4, NCH);            // last K
     }
-    float sc[CH];
+    float sc[NCH];
     float cmax = -INFINITY;
 #pragma unroll
-    for (int i = 0; i < CH; ++i) {
+    for (int i = 0; i < NCH; ++i) {
       float d = 0.f;
 #pragma unroll
       for (int e = 0; e < E; ++e) d = fmaf(qf[e], EL::to_f(kf[i][e]), d);
@@ -162,6 +227,7 @@ __global__ __launch_bounds__(NWV * 64) void attn_decode_kernel(const T* __restri
       sc[i] = (j >= j0 && j < ctx) ? d : -INFINITY;
       cmax = fmaxf(cmax, sc[i]);
     }
+    if constexpr (FIRST) AD_STAMP_LANDED(5, 0);   // last V (the scores above ran while it was landing)
     {
       // no branch on "this lane saw a key" (the V fragments would be sunk into it and requested a round trip late): a lane
       // without keys keeps m = -inf and adds zeros
@@ -172,7 +238,7 @@ __global__ __launch_bounds__(NWV * 64) void attn_decode_kernel(const T* __restri
 #pragma unroll
       for (int e = 0; e < E; ++e) o[e] *= corr;
 #pragma unroll
-      for (int i = 0; i < CH; ++i) {
+      for (int i = 0; i < NCH; ++i) {
         float pv = __expf(sc[i] - Ms);  // -inf -> 0
         l += pv;
 #pragma unroll
@@ -182,10 +248,31 @@ __global__ __launch_bounds__(NWV * 64) void attn_decode_kernel(const T* __restri
     }
   };
   constexpr int PASS = 4 * RPW * AD_CH;
+  typedef std::integral_constant<int, CH> full_t;
   if (j0 < ctx) {
     const int b0 = j0 & ~(RPW - 1);
-    key_pass(b0, std::true_type{});
-    for (int base = b0 + PASS; base < ctx; base += PASS) key_pass(base, std::false_type{});
+    // quarter passes the row's key slots [b0, ctx) need, minus one: workgroup-uniform (pad / pos / the skip word are scalars),
+    // ONE switch; every arm is the straight line requests -> scores -> softmax, so no request waits behind a join
+    int arm = SIZED ? __builtin_amdgcn_readfirstlane(min((ctx - b0 - 1) / (PASS / 4), 3)) : 3;
+#if ITTS_DIAG
+    if (full_pass) arm = 3;   // itts_debug_set(7, 1): always the full pass (the reference form of tests/test_attn_decode_passes_gpu.py)
+#endif
+    if constexpr (SIZED) {
+      switch (arm) {
+        case 0: key_pass(b0, std::integral_constant<int, CH / 4>{}, std::true_type{}); break;
+        case 1: key_pass(b0, std::integral_constant<int, CH / 2>{}, std::true_type{}); break;
+        case 2: key_pass(b0, std::integral_constant<int, 3 * CH / 4>{}, std::true_type{}); break;
+        default:
+          key_pass(b0, full_t{}, std::true_type{});
+          for (int base = b0 + PASS; base < ctx; base += PASS) key_pass(base, full_t{}, std::false_type{});
+      }
+    } else {
+      key_pass(b0, full_t{}, std::true_type{});
+      for (int base = b0 + PASS; base < ctx; base += PASS) key_pass(base, full_t{}, std::false_type{});
+    }
+#if ITTS_STAMPS
+    if (stamps != nullptr && tid == 0) st_[13] = (unsigned long long)((arm + 1) * CH / 4);
+#endif
   }
   // merge across the row groups of the wave (lanes that share `part`)
 #pragma unroll
@@ -207,7 +294,10 @@ __global__ __launch_bounds__(NWV * 64) void attn_decode_kernel(const T* __restri
       w_l[wave] = l;
     }
   }
-  __syncthreads();
+  // LDS-only wait + raw barrier: every load of the wave has been consumed by now, and __syncthreads() would also drain vmcnt
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
   if (tid < HD && !skipped) {
     float M = w_m[0];
 #pragma unroll
@@ -221,8 +311,18 @@ __global__ __launch_bounds__(NWV * 64) void attn_decode_kernel(const T* __restri
     }
     // out_mtp > 0: packed-activation layout (the out-projection GEMM's operand), else row-major [B][H*64]
     const int64_t o = out_mtp > 0 ? pa_off<T>(b, h * HD + tid, out_mtp) : ((int64_t)b * H + h) * HD + tid;
+    AD_STAMP(6);
     out[o] = EL::from_f(L > 0.f ? acc / L : 0.f);
   }
+  AD_STAMP(7);
+#if ITTS_STAMPS
+  if (stamps != nullptr && tid == 0) {
+    st_[12] = (unsigned long long)(j0 < ctx ? ctx - (j0 & ~(RPW - 1)) : 0);   // key slots from the first group to the context's end
+    st_[15] = __builtin_amdgcn_s_memrealtime();
+  }
+  // wave 0 wrote every stamp and reads them back: LDS operations of one wave complete in order
+  if (stamps != nullptr && tid < 16) stamps[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + tid] = st_[tid];
+#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -443,7 +543,7 @@ extern "C" int itts_attn_decode(const void* q, const void* kcache, const void* v
 #define ITTS_AD(TT_, NW_, IND_, PG_)                                                                                        \
   hipLaunchKernelGGL((attn_decode_kernel<TT_, NW_, IND_, PG_>), grid, block, 0, s, (const TT_*)q, (const TT_*)kcache,      \
                      (const TT_*)vcache, (TT_*)out, pad, pos, H, smax, out_mtp, kv_rows, kv_step, B, skip_rows, kv_share, \
-                     kv_tab, bs_log2)
+                     kv_tab, bs_log2 ITTS_AD_DIAG_ARGS)
 #define ITTS_AD_T(TT_)                                                            \
   do {                                                                            \
     if (paged) { if (g_attn_waves == 8) ITTS_AD(TT_, 8, false, true); else ITTS_AD(TT_, 4, false, true); } \

@@ -682,7 +682,8 @@ extern "C" int itts_skinny_plan(int dtype, int M, int N, int K, int ksplit, int 
 
 #if ITTS_DIAG
 // ---- diagnostic build only (libindextts_hip_diag.so, include/indextts_hip_diag.h); absent from the product library
-namespace itts { extern int g_conv_cfg; extern int g_attn_waves; extern int g_conv_exp; }
+namespace itts { extern int g_conv_cfg; extern int g_attn_waves; extern int g_conv_exp; extern int g_attn_full_pass;
+                 extern unsigned long long* g_stamp_buf_attn; int g_stamp_target = 0; }
 
 extern "C" int itts_debug_set(int key, int value) {
   if (key == 1) itts::g_tune_ntb = value;
@@ -691,6 +692,8 @@ extern "C" int itts_debug_set(int key, int value) {
   else if (key == 4) itts::g_attn_waves = (value == 8) ? 8 : 4;
   else if (key == 5) itts::g_conv_exp = value;
   else if (key == 6) itts::g_skinny_exp = value;
+  else if (key == 7) itts::g_attn_full_pass = value != 0;
+  else if (key == 8) itts::g_stamp_target = value == 1;
   else return ITTS_ERR_INVALID;
   return ITTS_OK;
 }
@@ -698,7 +701,8 @@ extern "C" int itts_debug_set(int key, int value) {
 // every later itts_gemm_skinny launch writes 16 u64 per workgroup to `buf` (NULL switches it off)
 extern "C" int itts_debug_stamps(void* buf) {
 #if ITTS_STAMPS
-  itts::g_stamp_buf = (unsigned long long*)buf;
+  if (itts::g_stamp_target == 1) itts::g_stamp_buf_attn = (unsigned long long*)buf;   // itts_debug_set(8, 1): attn_decode_kernel
+  else itts::g_stamp_buf = (unsigned long long*)buf;
   return ITTS_OK;
 #else
   (void)buf;
