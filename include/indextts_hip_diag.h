@@ -12,10 +12,10 @@ extern "C" {
 #endif
 
 /* tuning overrides: key 1 = column tiles per skinny-GEMM workgroup, key 2 = waves per skinny-GEMM workgroup, key 3 =
- * plain-GEMM kernel override (0 restores the built-in heuristic), key 4 = waves per decode-attention workgroup (4 or 8),
- * key 5 = ablation BIT MASK of the tiled convolution kernel for timing experiments (results are WRONG when non-zero):
- * 1 = no weight-fragment loads, 2 = no MFMA, 4 = no LDS fragment reads, 8 = no activation prefetch after the first chunk,
- * 16 = no epilogue, key 6 = load ablations of the skinny GEMM, key 7 = decode attention: 1 forces the FULL first key pass
+ * narrow-convolution form override (2 = no narrow form: the tiled kernel, 30 = the first form everywhere, 31 = the second form
+ * in place of the third, 0 restores the built-in heuristic), key 4 = waves per decode-attention workgroup (4 or 8),
+ * key 5 = retired (it was an ablation mask of the tiled convolution kernel; ITTS_ERR_INVALID like every unknown key),
+ * key 6 = load ablations of the skinny GEMM, key 7 = decode attention: 1 forces the FULL first key pass
  * (every chunk of a pass requested whatever the row's context, the form before the context-sized pass; bit-identical output,
  * the reference of tests/test_attn_decode_passes_gpu.py), 0 restores the context-sized pass, key 8 = which kernel the next
  * itts_debug_stamps call addresses: 0 the skinny GEMM, 1 the decode attention */

@@ -9,19 +9,21 @@
 // 144 B so the 16-row fragment reads (ds_read_b128) are bank-conflict free.  Packed weight blocks go straight from
 // L2 into B-fragment registers (they are shared only by workgroups, which L2 serves), double-buffered one step ahead;
 // the next chunk's activation rows are fetched into registers while the current chunk is being multiplied.
+#include <algorithm>
+#include <map>
 #include <mutex>
+#include <type_traits>
+#include <utility>
 
 #include "common.h"
-#include <type_traits>
 
 namespace itts {
 
-#ifndef ITTS_NARROW_C96
-#define ITTS_NARROW_C96 1   // build-time A/B: the LDS-staged narrow kernel for C = 96, 3 taps (246-266 -> 198-219 us per layer at batch 32 x 35 840 rows; one row tile per wave, 8 waves: 2 or 4 row tiles per wave spill)
-#endif
 constexpr int CV_MAX_HALO = 64;                 // (taps-1)*dil must not exceed this
 
-struct ConvParams {
+// alignas(16): the size is a multiple of 16 (176 bytes), and the kernarg segment's implicit arguments follow at that offset.  At
+// 168 bytes the compiler allocates the 16-bit conv_narrow_kernel<2,1> and <2,2>, which are short of SGPRs, with one more SGPR spill.
+struct alignas(16) ConvParams {
   int B, Tin, Tout, Cin, N;
   int taps, off0, dil;
   const void* x;
@@ -40,33 +42,14 @@ struct ConvParams {
   int ksplit;      // plain GEMM only: > 1 = the batch index of a tile is a K SLICE (slabs, see itts_conv_args.ksplit)
   int MB, NB, GM;  // m-blocks per batch element, n-blocks, m-blocks per L2 group (XCD-aware tile order)
   const int32_t* valid_rows;   // [B] or null: input rows >= valid_rows[b] read as zeros, tiles wholly beyond are skipped
-  int exp;         // diagnostic build only (itts_debug_set key 5): ablation switches of the tiled kernel, 0 in the product
 #if ITTS_STAMPS
   unsigned long long* stamps;   // diagnostic build: 16 x u64 per workgroup (itts_debug_stamps_conv)
 #endif
 };
 
 #if ITTS_STAMPS
+// the kernels keep their stamps in LDS (st_), not in registers: 16 x u64 of VGPRs pushed the big tiles into scratch
 unsigned long long* g_stamp_buf_conv = nullptr;
-// stamps live in LDS, not in registers: 16 x u64 of VGPRs pushed the big tiles into scratch in the diagnostic build
-#define CSTAMP(i)                                                                                        \
-  do {                                                                                                   \
-    __builtin_amdgcn_sched_barrier(0);                                                                   \
-    if (p.stamps != nullptr && threadIdx.x == 0) {                                                       \
-      unsigned long long t_;                                                                             \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                         \
-      st_[i] = t_;                                                                                       \
-    }                                                                                                    \
-    __builtin_amdgcn_sched_barrier(0);                                                                   \
-  } while (0)
-#else
-#define CSTAMP(i) do { } while (0)
-#endif
-#if ITTS_DIAG
-int g_conv_exp = 0;
-#define ITTS_CONV_EXP(p) ((p).exp)
-#else
-#define ITTS_CONV_EXP(p) 0
 #endif
 
 // Ragged batches: valid input rows of batch element b (the rest is the convolution's zero padding)
@@ -233,6 +216,64 @@ static int conv_num_cus() {
   return n;
 }
 
+// ---- what the launchers of the five kernel forms share ---------------------------------------------------------------
+typedef void (*ConvKernel)(ConvParams);
+constexpr int CV_LDS_LIMIT = 160 * 1024 - 256;   // dynamic LDS a kernel may ask for: 160 KiB minus the diagnostic build's static stamp block
+
+// m-blocks per 32-tile L2 patch (tile_of_workgroup) of a form whose n-blocks are BN columns wide: keep the n-extent of a patch
+// within ~2 MiB of weights (one n-block touches BN/16 n-tiles x KT k-steps x 1 KiB x taps)
+static int l2_patch_gm(int BN, int KT, int taps) {
+  const int64_t wbytes = (int64_t)BN * KT * 64 * taps;
+  int gn = (int)((2 << 20) / (wbytes > 0 ? wbytes : 1));
+  gn = gn < 1 ? 1 : (gn > 8 ? 8 : gn);
+  const int gm = 32 / gn;  // 4..32 m-blocks per patch
+  return gm >= 32 ? 32 : (gm >= 16 ? 16 : (gm >= 8 ? 8 : 4));
+}
+
+// p with the grid of BM x BN output tiles filled in
+static ConvParams with_tile_grid(const ConvParams& p, int BM, int BN, int GM) {
+  ConvParams q = p;
+  q.MB = (p.Tout + BM - 1) / BM;
+  q.NB = (p.N + BN - 1) / BN;
+  q.GM = GM;
+  return q;
+}
+
+// Workgroups of `kernel` that stay resident on a CU (registers and LDS both limit them).  The first launch of a (kernel, LDS
+// size) pair raises the kernel's dynamic-LDS limit and asks the occupancy API; every later one is a table lookup -- a vocoder
+// pass makes ~100 launches.  One table under one lock: RequestPool's replica threads make their first calls concurrently.
+static int resident_workgroups(ConvKernel kernel, int threads, size_t ldsb, int lds_limit) {
+  static std::mutex mu;
+  static std::map<std::pair<uintptr_t, size_t>, int> table;
+  const std::pair<uintptr_t, size_t> key((uintptr_t)kernel, ldsb);
+  std::lock_guard<std::mutex> lock(mu);
+  const auto it = table.find(key);
+  if (it != table.end()) return it->second;
+  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit);
+  int wgs = 1;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, (const void*)kernel, threads, ldsb) != hipSuccess || wgs < 1) wgs = 1;
+  (void)hipGetLastError();   // a refusal must not stay behind as the thread's last error
+  table.emplace(key, wgs);
+  return wgs;
+}
+
+// Launches `kernel` over q's MB x NB x B tiles and names it for itts_last_kernel().  persistent: one round of resident
+// workgroups walks the tile sequence; nothing waits on another workgroup, so an over-estimate only costs a second round.
+// Otherwise one workgroup per tile, dispatched by the hardware as CUs free up.
+static int launch_tiles(ConvKernel kernel, const char* name, int threads, size_t ldsb, int lds_limit, bool persistent,
+                        const ConvParams& q, hipStream_t s) {
+  const int64_t tiles = (int64_t)q.MB * q.NB * q.B;
+  if (tiles > 0x7fffffff) {
+    set_error("itts_gemm_conv: too many tiles (%lld)", (long long)tiles);
+    return ITTS_ERR_INVALID;
+  }
+  const int per_cu = resident_workgroups(kernel, threads, ldsb, lds_limit);
+  const int64_t grid = persistent ? std::min<int64_t>((int64_t)conv_num_cus() * per_cu, tiles) : tiles;
+  set_last_kernel(name);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), ldsb, s, q);
+  return check_launch("itts_gemm_conv");
+}
+
 // CK = k-steps of channels staged per chunk (2 for convolutions, whose taps multiply the MFMA work per chunk; 4 for
 // plain GEMMs).  HALO = compile-time bound on (taps-1)*dil (0 for plain GEMMs) that sizes the staging registers.
 // Waves per SIMD the register budget is sized for: 8-wave workgroups put 2 waves on each SIMD (one wave's MFMAs run under
@@ -243,7 +284,7 @@ struct ConvOcc {
   static constexpr int WPS = (NW == 8) ? 2 : ((TM * TN <= 16 && !(WM == 4 && WN == 1)) ? 2 : 1);   // the 4x1 stacks stage 10 row fragments per thread
 };
 
-// PERSISTENT, cross-tile pipelined: the grid is one round of resident workgroups (launch_conv asks the occupancy API) and
+// PERSISTENT, cross-tile pipelined: the grid is one round of resident workgroups (launch_tiles asks the occupancy API) and
 // a workgroup walks the tile sequence with stride gridDim.x.  The activation rows of the NEXT tile's first chunk are
 // requested while the current tile's last chunk is multiplied, the weight fragments of the next TAP (CK k-steps x TN
 // column blocks) are requested at the start of the current tap -- straight across chunk and tile boundaries -- and the
@@ -275,7 +316,7 @@ __global__ __launch_bounds__(WM * WN * 64, (ConvOcc<WM, WN, TM, TN>::WPS)) void 
   if (tid < 16) st_[tid] = 0;
   if (p.stamps != nullptr && tid == 0) st_[14] = __builtin_amdgcn_s_memrealtime();
 #endif
-  CSTAMP(0);
+  ITTS_STAMP_IF(p.stamps != nullptr, 0);
   const int g = lane >> 4, r = lane & 15;
   const int wm = wave / WN, wn = wave % WN;
   const int total = p.MB * p.NB * p.B;         // tiles; tile L of the XCD-aware order is handled by workgroup L % gridDim.x
@@ -414,7 +455,7 @@ __global__ __launch_bounds__(WM * WN * 64, (ConvOcc<WM, WN, TM, TN>::WPS)) void 
   f_next = next_from(L + gridDim.x);
   fetch_b(bA);
   prefetch_a(0, cur);
-  CSTAMP(1);
+  ITTS_STAMP_IF(p.stamps != nullptr, 1);
 #if ITTS_STAMPS
   bool first_ = true;
 #endif
@@ -430,7 +471,7 @@ __global__ __launch_bounds__(WM * WN * 64, (ConvOcc<WM, WN, TM, TN>::WPS)) void 
     for (int c = 0; c < NC; ++c) {
 #if ITTS_STAMPS
       const bool stc = (c == 1 && first_);   // one steady-state chunk of the first tile, decomposed
-      if (stc) CSTAMP(6);
+      if (stc) ITTS_STAMP_IF(p.stamps != nullptr, 6);
 #endif
       // Raw barriers with an LDS-only wait: __syncthreads() would also drain vmcnt, i.e. wait for the weight fragments of the
       // next tap that were requested a moment ago (measured: 3 us per chunk in the two barriers).
@@ -438,8 +479,8 @@ __global__ __launch_bounds__(WM * WN * 64, (ConvOcc<WM, WN, TM, TN>::WPS)) void 
       commit_a();
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 #if ITTS_STAMPS
-      if (c == 0 && first_) CSTAMP(2);
-      if (stc) CSTAMP(8);
+      if (c == 0 && first_) ITTS_STAMP_IF(p.stamps != nullptr, 2);
+      if (stc) ITTS_STAMP_IF(p.stamps != nullptr, 8);
 #endif
       if (c + 1 < NC) prefetch_a(c + 1, cur);
       else if (has_next) prefetch_a(0, nxt);   // the next tile's first chunk, under this tile's last chunk + epilogue
@@ -456,9 +497,9 @@ __global__ __launch_bounds__(WM * WN * 64, (ConvOcc<WM, WN, TM, TN>::WPS)) void 
             tap_full(std::integral_constant<int, 0>{}, bB, bA, j + 1);
           }
 #if ITTS_STAMPS
-          if (stc && j == 0) CSTAMP(9);
-          if (stc && j == 2) CSTAMP(10);
-          if (stc && j == 4) CSTAMP(11);
+          if (stc && j == 0) ITTS_STAMP_IF(p.stamps != nullptr, 9);
+          if (stc && j == 2) ITTS_STAMP_IF(p.stamps != nullptr, 10);
+          if (stc && j == 4) ITTS_STAMP_IF(p.stamps != nullptr, 11);
 #endif
         }
         if (j < p.taps) {   // odd tap count: the last tap ran out of bA and fetched the next one into bB
@@ -469,7 +510,7 @@ __global__ __launch_bounds__(WM * WN * 64, (ConvOcc<WM, WN, TM, TN>::WPS)) void 
             for (int tn = 0; tn < TN; ++tn) bA[kk][tn] = bB[kk][tn];
         }
 #if ITTS_STAMPS
-        if (stc) CSTAMP(7);
+        if (stc) ITTS_STAMP_IF(p.stamps != nullptr, 7);
 #endif
       } else {
         // short last chunk (KT % CK != 0): plain order, no register ping-pong
@@ -489,11 +530,11 @@ __global__ __launch_bounds__(WM * WN * 64, (ConvOcc<WM, WN, TM, TN>::WPS)) void 
       }
     }
 #if ITTS_STAMPS
-    if (first_) CSTAMP(3);
+    if (first_) ITTS_STAMP_IF(p.stamps != nullptr, 3);
 #endif
     conv_epilogue<T, TM, TN>(p, acc, cur.b, cur.t0 + wm * TM * 16, cur.nt0, g, r);
 #if ITTS_STAMPS
-    if (first_) CSTAMP(4);
+    if (first_) ITTS_STAMP_IF(p.stamps != nullptr, 4);
     first_ = false;
 #endif
     cur = nxt;
@@ -520,56 +561,10 @@ __global__ __launch_bounds__(WM * WN * 64, (ConvOcc<WM, WN, TM, TN>::WPS)) void 
 template <typename T, int WM, int WN, int TM, int TN, int CK, int HALO, bool PERSIST = false>
 static int launch_conv(const ConvParams& p, hipStream_t s) {
   constexpr int BM = 16 * TM * WM, BN = 16 * TN * WN;
-  int HR = BM + (p.taps - 1) * p.dil;
-  size_t ldsb = (size_t)HR * (CK * 64 + 16);
-  ConvParams q = p;
-  q.MB = (p.Tout + BM - 1) / BM;
-  q.NB = (p.N + BN - 1) / BN;
-  // weight bytes one n-block touches; keep the n-extent of a 32-tile patch within ~2 MiB of weights
-  const int64_t wbytes = (int64_t)BN * p.KT * 64 * p.taps;  // BN/16 n-tiles x KT k-steps x 1 KiB x taps
-  int gn = (int)((2 << 20) / (wbytes > 0 ? wbytes : 1));
-  gn = gn < 1 ? 1 : (gn > 8 ? 8 : gn);
-  int gm = 32 / gn;  // 4..32 m-blocks per patch
-  gm = gm >= 32 ? 32 : (gm >= 16 ? 16 : (gm >= 8 ? 8 : 4));
-  q.GM = gm;
-  const int64_t total = (int64_t)q.MB * q.NB * p.B;
-  if (total > 0x7fffffff) {
-    set_error("itts_gemm_conv: too many tiles (%lld)", (long long)total);
-    return ITTS_ERR_INVALID;
-  }
-  static std::once_flag attr;   // one-shot per instantiation, safe under concurrent first calls (RequestPool threads)
-  std::call_once(attr, [] {
-    // 160 KiB minus the static block of the diagnostic build's stamps; a refusal must not stay behind as the thread's last error
-    (void)hipFuncSetAttribute((const void*)gemm_conv_kernel<T, WM, WN, TM, TN, CK, HALO>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024 - 256);
-    (void)hipGetLastError();
-  });
-  // PERSIST: one round of resident workgroups walks the tile sequence (a multiple of 8 workgroups, so that a workgroup's
-  // tiles stay on its XCD's run of the tile order); nothing waits on another workgroup, so an over-estimate only costs a
-  // second round.  Otherwise one workgroup per tile, dispatched by the hardware as CUs free up.
-  int64_t g = total;
-  if (PERSIST || (ITTS_CONV_EXP(q) & 32)) {
-    // one occupancy query per (instantiation, LDS size) and thread: a vocoder pass launches ~100 of these
-    static thread_local size_t occ_lds = ~(size_t)0;
-    static thread_local int occ_wgs = 1;
-    if (occ_lds != ldsb) {
-      int q_wgs = 1;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q_wgs, (const void*)gemm_conv_kernel<T, WM, WN, TM, TN, CK, HALO>,
-                                                       WM * WN * 64, ldsb) != hipSuccess || q_wgs < 1)
-        q_wgs = 1;
-      (void)hipGetLastError();
-      occ_lds = ldsb;
-      occ_wgs = q_wgs;
-    }
-    const int per_cu = occ_wgs;
-    g = (int64_t)conv_num_cus() * per_cu;
-    if (g > total) g = total;
-  }
-  dim3 grid((unsigned)g);
+  const size_t ldsb = (size_t)(BM + (p.taps - 1) * p.dil) * (CK * 64 + 16);   // staged rows x padded row
   static constexpr KernelName kn = kernel_name("gemm_conv", type_tag<T>(), {WM, WN, TM, TN, CK, HALO}, PERSIST ? "persist" : "");
-  set_last_kernel(kn.s);
-  hipLaunchKernelGGL((gemm_conv_kernel<T, WM, WN, TM, TN, CK, HALO>), grid, dim3(WM * WN * 64), ldsb, s, q);
-  return check_launch("itts_gemm_conv");
+  return launch_tiles(gemm_conv_kernel<T, WM, WN, TM, TN, CK, HALO>, kn.s, WM * WN * 64, ldsb, CV_LDS_LIMIT, PERSIST,
+                      with_tile_grid(p, BM, BN, l2_patch_gm(BN, p.KT, p.taps)), s);
 }
 
 // -------------------------------------------------------------------------------------------------------------------
@@ -710,35 +705,16 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_plain_kernel(ConvParams 
 template <typename T, int WM, int WN, int TM, int TN>
 static int launch_plain(const ConvParams& p, hipStream_t s) {
   constexpr int BM = 16 * TM * WM, BN = 16 * TN * WN;
-  size_t ldsb = (size_t)2 * BM * (4 * 64 + 16);
-  ConvParams q = p;
-  q.MB = (p.Tout + BM - 1) / BM;
-  q.NB = (p.N + BN - 1) / BN;
-  const int64_t wbytes = (int64_t)BN * p.KT * 64;
-  int gn = (int)((2 << 20) / (wbytes > 0 ? wbytes : 1));
-  gn = gn < 1 ? 1 : (gn > 8 ? 8 : gn);
-  int gm = 32 / gn;
-  gm = gm >= 32 ? 32 : (gm >= 16 ? 16 : (gm >= 8 ? 8 : 4));
-  q.GM = gm;
+  const size_t ldsb = (size_t)2 * BM * (4 * 64 + 16);   // two buffers of BM padded rows
+  ConvParams q = with_tile_grid(p, BM, BN, l2_patch_gm(BN, p.KT, 1));
   if (p.ksplit > 1) {            // K slices in place of batch elements; slab ks of y = the rows' partial products over slice ks
     q.B = p.ksplit;
     q.y_bstride = (int64_t)p.Tout * p.N;
     q.y_limit = (int64_t)p.Tout * p.N;
     q.y_shift = 0;
   }
-  const int64_t total = (int64_t)q.MB * q.NB * q.B;
-  if (total > 0x7fffffff) {
-    set_error("itts_gemm_conv: too many tiles (%lld)", (long long)total);
-    return ITTS_ERR_INVALID;
-  }
-  static std::once_flag attr;
-  std::call_once(attr, [] {
-    (void)hipFuncSetAttribute((const void*)gemm_plain_kernel<T, WM, WN, TM, TN>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
   static constexpr KernelName kn = kernel_name("gemm_plain", type_tag<T>(), {WM, WN, TM, TN});
-  set_last_kernel(kn.s);
-  hipLaunchKernelGGL((gemm_plain_kernel<T, WM, WN, TM, TN>), dim3((unsigned)total), dim3(WM * WN * 64), ldsb, s, q);
-  return check_launch("itts_gemm_conv");
+  return launch_tiles(gemm_plain_kernel<T, WM, WN, TM, TN>, kn.s, WM * WN * 64, ldsb, 160 * 1024, false, q, s);   // no stamp block: all 160 KiB
 }
 
 // -------------------------------------------------------------------------------------------------------------------
@@ -766,12 +742,12 @@ __global__ __launch_bounds__(256, (KT * NT <= 1 ? 4 : (KT * NT <= 4 ? 3 : 2))) v
   if (tid < 16) st_[tid] = 0;
   int ntile_ = 0;
 #endif
-  CSTAMP(0);
+  ITTS_STAMP_IF(p.stamps != nullptr, 0);
   // weights -> LDS (same block order as in memory: ((tap*NT + nt)*KT + ks) KiB)
   const int wbytes = p.taps * NT * KT * 1024;
   for (int off = tid * 16; off < wbytes; off += 256 * 16) st16(lds + off, ld16<frag>((const unsigned char*)p.wp + off));
   __syncthreads();
-  CSTAMP(1);
+  ITTS_STAMP_IF(p.stamps != nullptr, 1);
 
   const int ntiles = p.MB * p.B;
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -812,8 +788,8 @@ __global__ __launch_bounds__(256, (KT * NT <= 1 ? 4 : (KT * NT <= 4 ? 3 : 2))) v
     };
     frag a0[TM][KT], a1[TM][KT];
 #if ITTS_STAMPS
-    if (ntile_ == 0) CSTAMP(2);
-    if (ntile_ == 1) CSTAMP(6);
+    if (ntile_ == 0) ITTS_STAMP_IF(p.stamps != nullptr, 2);
+    if (ntile_ == 1) ITTS_STAMP_IF(p.stamps != nullptr, 6);
 #endif
     load_a(a0, 0);
     for (int j = 0; j < p.taps; j += 2) {
@@ -824,13 +800,13 @@ __global__ __launch_bounds__(256, (KT * NT <= 1 ? 4 : (KT * NT <= 4 ? 3 : 2))) v
     }
 #if ITTS_STAMPS
     asm volatile("" ::"v"(acc[0][0]));
-    if (ntile_ == 0) CSTAMP(3);
-    if (ntile_ == 1) CSTAMP(7);
+    if (ntile_ == 0) ITTS_STAMP_IF(p.stamps != nullptr, 3);
+    if (ntile_ == 1) ITTS_STAMP_IF(p.stamps != nullptr, 7);
 #endif
     conv_epilogue<T, TM, NT>(p, acc, b, row0, 0, g, r);
 #if ITTS_STAMPS
-    if (ntile_ == 0) CSTAMP(4);
-    if (ntile_ == 1) CSTAMP(8);
+    if (ntile_ == 0) ITTS_STAMP_IF(p.stamps != nullptr, 4);
+    if (ntile_ == 1) ITTS_STAMP_IF(p.stamps != nullptr, 8);
     ++ntile_;
 #endif
   }
@@ -849,41 +825,13 @@ __global__ __launch_bounds__(256, (KT * NT <= 1 ? 4 : (KT * NT <= 4 ? 3 : 2))) v
 #endif
 }
 
+// persistent grid = the workgroups that are actually resident (registers and LDS both limit them; the first version asked
+// for up to 6 per CU by LDS alone and ran in rounds: tools/timeline_narrow.py), each walking 256-row tiles with stride grid
 template <typename T, int KT, int NT>
 static int launch_narrow(const ConvParams& p, hipStream_t s) {
-  constexpr int BM = 256;
-  ConvParams q = p;
-  q.MB = (p.Tout + BM - 1) / BM;
-  q.NB = 1;
-  q.GM = 1;
-  const int64_t tiles = (int64_t)q.MB * p.B;
   const size_t ldsb = (size_t)p.taps * NT * KT * 1024;
-  // persistent grid: as many workgroups as stay resident (LDS- and register-bound), each walking tiles with stride grid
-  static std::once_flag attr;
-  std::call_once(attr, [] {
-    (void)hipFuncSetAttribute((const void*)conv_narrow_kernel<T, KT, NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024 - 256);   // minus the diagnostic build's static stamp block
-    (void)hipGetLastError();
-  });
-  // persistent grid = the workgroups that are actually resident (registers and LDS both limit them; the first version
-  // asked for up to 6 per CU by LDS alone and ran in rounds: tools/timeline_narrow.py)
-  static thread_local size_t occ_lds = ~(size_t)0;
-  static thread_local int occ_wgs = 1;
-  if (occ_lds != ldsb) {
-    int q_wgs = 1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q_wgs, (const void*)conv_narrow_kernel<T, KT, NT>, 256, ldsb) != hipSuccess ||
-        q_wgs < 1)
-      q_wgs = 1;
-    (void)hipGetLastError();
-    occ_lds = ldsb;
-    occ_wgs = q_wgs;
-  }
-  int64_t grid = (int64_t)conv_num_cus() * occ_wgs;
-  if (grid > tiles) grid = tiles;
   static constexpr KernelName kn = kernel_name("conv_narrow", type_tag<T>(), {KT, NT});
-  set_last_kernel(kn.s);
-  hipLaunchKernelGGL((conv_narrow_kernel<T, KT, NT>), dim3((unsigned)grid), dim3(256), ldsb, s, q);
-  return check_launch("itts_gemm_conv");
+  return launch_tiles(conv_narrow_kernel<T, KT, NT>, kn.s, 256, ldsb, CV_LDS_LIMIT, true, with_tile_grid(p, 256, 16 * NT, 1), s);
 }
 
 // Second form of the narrow kernel (round 3) for the layers that dominate the last two vocoder stages (Cin = N = 24 / 48,
@@ -965,32 +913,10 @@ void conv_narrow_taps_kernel(ConvParams p) {
 
 template <typename T, int KT, int NT, int TAPS, int TM, int NW>
 static int launch_narrow_taps(const ConvParams& p, hipStream_t s) {
-  constexpr int BM = NW * TM * 16;
-  ConvParams q = p;
-  q.MB = (p.Tout + BM - 1) / BM;
-  q.NB = 1;
-  q.GM = 1;
-  const int64_t tiles = (int64_t)q.MB * p.B;
-  const size_t ldsb = (size_t)TAPS * NT * KT * 1024;
-  static std::once_flag attr;
-  static int per_cu = 1;
-  std::call_once(attr, [] {
-    constexpr size_t ldsb = (size_t)TAPS * NT * KT * 1024;
-    (void)hipFuncSetAttribute((const void*)conv_narrow_taps_kernel<T, KT, NT, TAPS, TM, NW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024 - 256);
-    int q_wgs = 1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q_wgs, (const void*)conv_narrow_taps_kernel<T, KT, NT, TAPS, TM, NW>, NW * 64, ldsb) !=
-            hipSuccess || q_wgs < 1)
-      q_wgs = 1;
-    (void)hipGetLastError();
-    per_cu = q_wgs;
-  });
-  int64_t grid = (int64_t)conv_num_cus() * per_cu;
-  if (grid > tiles) grid = tiles;
+  constexpr size_t ldsb = (size_t)TAPS * NT * KT * 1024;
   static constexpr KernelName kn = kernel_name("conv_narrow_taps", type_tag<T>(), {KT, NT, TAPS, TM, NW});
-  set_last_kernel(kn.s);
-  hipLaunchKernelGGL((conv_narrow_taps_kernel<T, KT, NT, TAPS, TM, NW>), dim3((unsigned)grid), dim3(NW * 64), ldsb, s, q);
-  return check_launch("itts_gemm_conv");
+  return launch_tiles(conv_narrow_taps_kernel<T, KT, NT, TAPS, TM, NW>, kn.s, NW * 64, ldsb, CV_LDS_LIMIT, true,
+                      with_tile_grid(p, NW * TM * 16, 16 * NT, 1), s);
 }
 
 // Third form (round 4): the activation rows of a tile are STAGED IN LDS.  The second form requests every tap's fragments from
@@ -1152,52 +1078,40 @@ template <typename T, int CIN, int TAPS, int TM, int NW, int MAXH = CV_MAX_HALO>
 static int launch_narrow_lds(const ConvParams& p, hipStream_t s) {
   constexpr int BM = NW * TM * 16, ES = (int)sizeof(T), KS = Elem<T>::KS;
   constexpr int KT = (CIN + KS - 1) / KS, NT = (CIN + 15) / 16;
-  ConvParams q = p;
-  q.MB = (p.Tout + BM - 1) / BM;
-  q.NB = 1;
-  q.GM = 1;
-  const int64_t tiles = (int64_t)q.MB * p.B;
   constexpr size_t ldsb = (size_t)TAPS * NT * KT * 1024 + (size_t)(BM + MAXH + 1) * NarrowLds<CIN, ES>::RSB;
-  static_assert(ldsb <= 160 * 1024 - 256, "conv_narrow_lds: weights + row tile exceed the LDS");
-  static std::once_flag attr;
-  std::call_once(attr, [] {
-    (void)hipFuncSetAttribute((const void*)conv_narrow_lds_kernel<T, CIN, TAPS, TM, NW, MAXH>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024 - 256);
-    (void)hipGetLastError();
-  });
-  static thread_local size_t occ_lds = ~(size_t)0;
-  static thread_local int occ_wgs = 1;
-  if (occ_lds != ldsb) {
-    int q_wgs = 1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q_wgs, (const void*)conv_narrow_lds_kernel<T, CIN, TAPS, TM, NW, MAXH>, NW * 64, ldsb) !=
-            hipSuccess || q_wgs < 1)
-      q_wgs = 1;
-    (void)hipGetLastError();
-    occ_lds = ldsb;
-    occ_wgs = q_wgs;
-  }
-  int64_t grid = (int64_t)conv_num_cus() * occ_wgs;
-  if (grid > tiles) grid = tiles;
+  static_assert(ldsb <= CV_LDS_LIMIT, "conv_narrow_lds: weights + row tile exceed the LDS");
   static constexpr KernelName kn = kernel_name("conv_narrow_lds", type_tag<T>(), {CIN, TAPS, TM, NW, MAXH});
-  set_last_kernel(kn.s);
-  hipLaunchKernelGGL((conv_narrow_lds_kernel<T, CIN, TAPS, TM, NW, MAXH>), dim3((unsigned)grid), dim3(NW * 64), ldsb, s, q);
-  return check_launch("itts_gemm_conv");
+  return launch_tiles(conv_narrow_lds_kernel<T, CIN, TAPS, TM, NW, MAXH>, kn.s, NW * 64, ldsb, CV_LDS_LIMIT, true,
+                      with_tile_grid(p, BM, 16 * NT, 1), s);
 }
 
+// Diagnostic build: itts_debug_set(3, id) overrides the narrow-form choice for A/B measurements: 2 = no narrow form (the tiled
+// kernel), 30 = the first form everywhere, 31 = the second form in place of the third, 0 = the heuristic below.  Product
+// build: the heuristic, no mutable state (the override branches fold away).
 #if ITTS_DIAG
-int g_conv_cfg = 0;  // diagnostic build: itts_debug_set(3, id) kernel override for A/B measurements (0 = default)
+int g_conv_cfg = 0;
 #else
-constexpr int g_conv_cfg = 0;  // product build: the heuristic below, no mutable state (the override branches fold away)
+constexpr int g_conv_cfg = 0;
 #endif
 
-// (k-steps, column tiles) pairs built for the narrow kernel; everything else takes the tiled kernel
+// The third form (rows staged in LDS) has an epilogue of its own: square layers with T-typed y, no per-batch bias, no activation,
+// N / y_shift / y_limit multiples of 4
+static bool narrow_lds_eligible(const ConvParams& p) {
+  return g_conv_cfg != 30 && g_conv_cfg != 31 && p.Cin == p.N && !p.y_f32 && p.bias2 == nullptr && p.act == 0 &&
+         ((p.N | p.y_shift | p.y_limit) & 3) == 0;
+}
+
+constexpr int NOT_NARROW = -1;   // dispatch_narrow: no narrow form takes this layer, nothing was launched (otherwise an ITTS_* code)
+
+// The narrow forms keep a layer's whole packed weight tensor in LDS: C <= 64, and C = 96 at 3 / 7 taps (54 / 126 KB of weights,
+// bandwidth-shaped like the C = 48 layers), within the (k-steps, column tiles) pairs built below.  Everything else takes the
+// tiled kernel.
 template <typename T>
-static int dispatch_narrow(const ConvParams& p, hipStream_t s, bool& handled) {
-  handled = true;
+static int dispatch_narrow(const ConvParams& p, hipStream_t s) {
   const int kt = p.KT, nt = p.NT;
-  if constexpr (sizeof(T) == 2) if (g_conv_cfg != 30 && g_conv_cfg != 31 && p.Cin == p.N && (p.Cin == 24 || p.Cin == 48) && !p.y_f32 &&
-                                    p.bias2 == nullptr && p.act == 0 && ((p.N | p.y_shift | p.y_limit) & 3) == 0) {
-    // third form (rows staged in LDS); diagnostic build: cfg 31 = the second form instead, for A/B runs
+  const bool c96 = p.Cin == 96 && p.N == 96 && (p.taps == 3 || p.taps == 7);
+  if (g_conv_cfg == 2 || !((p.Cin <= 64 && p.N <= 64) || c96) || (size_t)p.taps * nt * kt * 1024 > 150 * 1024) return NOT_NARROW;
+  if constexpr (sizeof(T) == 2) if (narrow_lds_eligible(p)) {
 #define ITTS_NL_CASE(CIN_, NW3_, NW7_, NW11_)                                                                       \
     if (p.Cin == CIN_ && p.taps == 3) return launch_narrow_lds<T, CIN_, 3, 16 / NW3_, NW3_>(p, s);                  \
     if (p.Cin == CIN_ && p.taps == 7) return launch_narrow_lds<T, CIN_, 7, 16 / NW7_, NW7_>(p, s);                  \
@@ -1205,18 +1119,13 @@ static int dispatch_narrow(const ConvParams& p, hipStream_t s, bool& handled) {
     ITTS_NL_CASE(24, 4, 4, 4)       // C = 24: 256-row tiles, 4 waves x 4 row tiles; weights + rows <= 48 KB -> 3 workgroups per CU
     ITTS_NL_CASE(48, 4, 4, 8)       // C = 48: the same; 11 taps: 66 KB of weights -> one 8-wave workgroup per CU (2 row tiles per wave)
 #undef ITTS_NL_CASE
+    // C = 96: one row tile per wave, 8 waves (2 or 4 row tiles per wave spill); 3 taps 246-266 -> 198-219 us per layer at batch
+    // 32 x 35 840 rows.  7 taps with the row tile sized for the vocoder's dilations (halo <= 30 rows): 126 KB of weights + 159
+    // rows = 158 KB
+    if (p.Cin == 96 && p.taps == 3) return launch_narrow_lds<T, 96, 3, 1, 8>(p, s);
+    if (p.Cin == 96 && p.taps == 7 && 6 * p.dil <= 30) return launch_narrow_lds<T, 96, 7, 1, 8, 30>(p, s);
   }
-#if ITTS_NARROW_C96
-  // C = 96, 3 taps only (54 KB of weights; 7 taps would be 126 KB): bandwidth-shaped like the C = 48 layers
-  if constexpr (sizeof(T) == 2) if (g_conv_cfg != 30 && g_conv_cfg != 31 && p.Cin == 96 && p.N == 96 && p.taps == 3 && !p.y_f32 && p.bias2 == nullptr &&
-                                    p.act == 0 && ((p.N | p.y_shift | p.y_limit) & 3) == 0)
-    return launch_narrow_lds<T, 96, 3, 1, 8>(p, s);
-  // ... and 7 taps with the row tile sized for the vocoder's dilations (halo <= 30 rows): 126 KB of weights + 159 rows = 158 KB
-  if constexpr (sizeof(T) == 2) if (g_conv_cfg != 30 && g_conv_cfg != 31 && p.Cin == 96 && p.N == 96 && p.taps == 7 && 6 * p.dil <= 30 && !p.y_f32 &&
-                                    p.bias2 == nullptr && p.act == 0 && ((p.N | p.y_shift | p.y_limit) & 3) == 0)
-    return launch_narrow_lds<T, 96, 7, 1, 8, 30>(p, s);
-#endif
-  if (g_conv_cfg != 30) {   // (diagnostic build: cfg 30 = the first form everywhere, for A/B runs)
+  if (g_conv_cfg != 30) {
 #define ITTS_NT_CASE(KT_, NT_, TM_, NW_)                                                               \
     if (kt == KT_ && nt == NT_ && p.taps == 3) return launch_narrow_taps<T, KT_, NT_, 3, TM_, NW_>(p, s);   \
     if (kt == KT_ && nt == NT_ && p.taps == 7) return launch_narrow_taps<T, KT_, NT_, 7, TM_, NW_>(p, s);   \
@@ -1233,23 +1142,16 @@ static int dispatch_narrow(const ConvParams& p, hipStream_t s, bool& handled) {
   if (kt == 2 && nt == 2) return launch_narrow<T, 2, 2>(p, s);
   if (kt == 2 && nt == 3) return launch_narrow<T, 2, 3>(p, s);
   if (kt == 3 && nt == 3) return launch_narrow<T, 3, 3>(p, s);
-  handled = false;
-  return ITTS_OK;
+  return NOT_NARROW;
 }
 
 template <typename T>
 static int dispatch_conv(const ConvParams& p, hipStream_t s) {
   const bool plain = (p.taps == 1);  // GEMM: no halo, 4 k-steps per chunk
-  if (((p.Cin <= 64 && p.N <= 64) || (ITTS_NARROW_C96 && p.Cin == 96 && p.N == 96 && (p.taps == 3 || p.taps == 7))) && g_conv_cfg != 2 &&
-      (size_t)p.taps * p.NT * p.KT * 1024 <= 150 * 1024) {   // (C = 96, 7 taps: 126 KB)
-    bool handled;
-    int rc = dispatch_narrow<T>(p, s, handled);
-    if (handled) return rc;
-  }
+  if (const int rc = dispatch_narrow<T>(p, s); rc != NOT_NARROW) return rc;
   if (plain && p.N % 128 == 0) {
     // Measured on MI355X (bf16, M = 3008 / 7488, N = 1280..5120, K = 1280 / 5120): 128 x 128 pipelined 435-720 TFLOP/s,
     // 256 x 128 pipelined 300-625, the unpipelined 256 x 128 tile of the convolution kernel 260-540.
-    if (g_conv_cfg == 5) return launch_plain<T, 2, 4, 8, 2>(p, s);   // 256 x 128
     // (a 256 x 128 tile with both operands through LDS and four waves of 128 x 64 was built in round 3, measured slower on every
     // shape -- 300-475 against 580-670 TFLOP/s, profiles/r03_big_gemm.txt -- and removed in round 4)
     // Tile shape by rounds of the chip (all tiles of a launch take the same time, so a launch costs its number of ROUNDS over the
@@ -1267,16 +1169,6 @@ static int dispatch_conv(const ConvParams& p, hipStream_t s) {
     const int64_t rows = (int64_t)p.B * ((p.Tout + 255) / 256);
     return (rows * (p.N / 64) >= 448) ? launch_conv<T, 4, 2, 4, 2, 4, 0>(p, s) : launch_conv<T, 4, 2, 2, 2, 4, 0>(p, s);
   }
-#if ITTS_DIAG
-  if (g_conv_cfg == 10) {   // the 8-wave tiles of the first version (256-row tiles, one workgroup per CU), for A/B runs
-    if (p.N % 128 == 0) return launch_conv<T, 2, 4, 8, 2, 2, CV_MAX_HALO>(p, s);
-    if (p.N % 64 == 0) return launch_conv<T, 4, 2, 4, 2, 2, CV_MAX_HALO>(p, s);
-    if (p.N % 96 == 0) return launch_conv<T, 4, 2, 4, 3, 2, CV_MAX_HALO>(p, s);
-  }
-  if (g_conv_cfg == 15) {   // 6 waves side by side for 192 columns
-    if (p.N % 192 == 0) return launch_conv<T, 1, 6, 8, 2, 2, CV_MAX_HALO, true>(p, s);
-  }
-#endif
   // Tile choice (MI355X, fp16, batch 32; profiles/r02_conv_tiles.txt).  Two 4-wave workgroups per CU beat one 8-wave
   // workgroup everywhere: each workgroup stalls once per channel chunk on the in-order memory queue (its weight loads sit
   // behind the next chunk's activation rows), and the other workgroup's MFMAs fill that hole.
@@ -1331,11 +1223,6 @@ static int conv_params_from_args(const itts_conv_args* a, ConvParams& p, const c
   p.accumulate = a->accumulate;
   p.scale = a->scale;
   const int ks = a->dtype == ITTS_F32 ? 16 : 32;
-#if ITTS_DIAG
-  p.exp = g_conv_exp;
-#else
-  p.exp = 0;
-#endif
 #if ITTS_STAMPS
   p.stamps = g_stamp_buf_conv;
 #endif

@@ -682,7 +682,7 @@ extern "C" int itts_skinny_plan(int dtype, int M, int N, int K, int ksplit, int 
 
 #if ITTS_DIAG
 // ---- diagnostic build only (libindextts_hip_diag.so, include/indextts_hip_diag.h); absent from the product library
-namespace itts { extern int g_conv_cfg; extern int g_attn_waves; extern int g_conv_exp; extern int g_attn_full_pass;
+namespace itts { extern int g_conv_cfg; extern int g_attn_waves; extern int g_attn_full_pass;
                  extern unsigned long long* g_stamp_buf_attn; int g_stamp_target = 0; }
 
 extern "C" int itts_debug_set(int key, int value) {
@@ -690,7 +690,6 @@ extern "C" int itts_debug_set(int key, int value) {
   else if (key == 2) itts::g_tune_nw = value;
   else if (key == 3) itts::g_conv_cfg = value;
   else if (key == 4) itts::g_attn_waves = (value == 8) ? 8 : 4;
-  else if (key == 5) itts::g_conv_exp = value;
   else if (key == 6) itts::g_skinny_exp = value;
   else if (key == 7) itts::g_attn_full_pass = value != 0;
   else if (key == 8) itts::g_stamp_target = value == 1;

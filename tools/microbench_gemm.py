@@ -44,11 +44,9 @@ def bench(name, dtype, B, T, Cin, N, taps, dil, y_f32=False, resid=False, act=0)
 
 
 bf, fh = torch.bfloat16, torch.float16
-if os.environ.get("ITTS_CONV_EXP"):
-    nat.debug_set(5, int(os.environ["ITTS_CONV_EXP"]))
 if os.environ.get("ITTS_CONV_CFG"):
     nat.debug_set(3, int(os.environ["ITTS_CONV_CFG"]))
-    print("plain-GEMM tile cfg", os.environ["ITTS_CONV_CFG"])
+    print("narrow-form cfg", os.environ["ITTS_CONV_CFG"])
 bench("prefill QKV  3008x3840x1280", bf, 1, 3008, 1280, 3840, 1, 1)
 bench("prefill proj 3008x1280x1280 +res", bf, 1, 3008, 1280, 1280, 1, 1, y_f32=True, resid=True)
 bench("prefill FC   3008x5120x1280 gelu", bf, 1, 3008, 1280, 5120, 1, 1, act=1)
@@ -64,7 +62,7 @@ bench("voc C192 k7 d1 T8960 B32", fh, 32, 8960, 192, 192, 7, 1)
 bench("voc C96 k7 d1 T35840 B32", fh, 32, 35840, 96, 96, 7, 1)
 bench("voc C48 k7 d1 T71680 B32", fh, 32, 71680, 48, 48, 7, 1)
 bench("voc C24 k7 d1 T143360 B32", fh, 32, 143360, 24, 24, 7, 1)
-for d in (1, 3, 5):                           # stage 3's k = 3 layers (candidates for the LDS-staged narrow kernel, ITTS_NARROW_C96)
+for d in (1, 3, 5):                           # stage 3's k = 3 layers (LDS-staged narrow kernel)
     bench(f"voc C96 k3 d{d} T35840 B32 +res", fh, 32, 35840, 96, 96, 3, d, resid=True)
 for C, T in ((48, 71680), (24, 143360)):     # the narrow layers of the last two stages, every (taps, dilation) class, with the residual epilogue
     for k, d in ((3, 1), (3, 5), (7, 1), (7, 5), (11, 1), (11, 5)):

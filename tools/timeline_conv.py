@@ -32,8 +32,6 @@ NW = 1 << 16
 stamps = torch.zeros(NW, 16, dtype=torch.int64, device=dev)
 
 
-if os.environ.get("ITTS_CONV_EXP"):
-    nat.debug_set(5, int(os.environ["ITTS_CONV_EXP"]))
 if os.environ.get("ITTS_CONV_CFG"):
     nat.debug_set(3, int(os.environ["ITTS_CONV_CFG"]))
 
