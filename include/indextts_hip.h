@@ -48,7 +48,7 @@ extern "C" {
 #define ITTS_BF16 1
 #define ITTS_F16 2
 
-#define ITTS_ABI_VERSION 9 /* 9: itts_last_kernel (read-only: the kernel form the last itts_gemm_conv / itts_aa_snake_fwd launched); 8: prompt front-end (itts_subsample_conv, itts_mha_small, itts_glu_dwconv_ln_silu, itts_rows, itts_geglu, itts_prefix_rows) and speaker encoder (itts_im2col_reflect, itts_res2_step, itts_se_gate, itts_scale_resid, itts_col_stats, ITTS_EPI_RELU_AFFINE_*), itts_kv_share_rows, ITTS_EPI_SILU_STORE, y_row0 / y_mtp and any M with rows_per_wg in itts_gemm_skinny, itts_gemm_conv ksplit <= 64; 7: LayerNorm folded into the consuming skinny GEMM (ln_c), residual epilogue with a packed T copy, rows_per_wg / wide_wg, bump words in itts_gemm_skinny / itts_embed_step (+ clamp, packed copy); the reducer tail is gone; paged KV cache (kv_tab / kv_bs); 6: per-row clocks (row_step0) in itts_embed_step / itts_sample_args (slot refill), itts_attn_prefill_prefix / _shared, kv_share in itts_attn_decode; 5: itts_ln_reduce takes up to 6 slabs */
+#define ITTS_ABI_VERSION 9 /* 9: itts_last_kernel (read-only: the kernel form the last itts_gemm_conv / itts_aa_snake_fwd launched), itts_lora_shrink (a new symbol: no existing struct or signature changed); 8: prompt front-end (itts_subsample_conv, itts_mha_small, itts_glu_dwconv_ln_silu, itts_rows, itts_geglu, itts_prefix_rows) and speaker encoder (itts_im2col_reflect, itts_res2_step, itts_se_gate, itts_scale_resid, itts_col_stats, ITTS_EPI_RELU_AFFINE_*), itts_kv_share_rows, ITTS_EPI_SILU_STORE, y_row0 / y_mtp and any M with rows_per_wg in itts_gemm_skinny, itts_gemm_conv ksplit <= 64; 7: LayerNorm folded into the consuming skinny GEMM (ln_c), residual epilogue with a packed T copy, rows_per_wg / wide_wg, bump words in itts_gemm_skinny / itts_embed_step (+ clamp, packed copy); the reducer tail is gone; paged KV cache (kv_tab / kv_bs); 6: per-row clocks (row_step0) in itts_embed_step / itts_sample_args (slot refill), itts_attn_prefill_prefix / _shared, kv_share in itts_attn_decode; 5: itts_ln_reduce takes up to 6 slabs */
 
 int itts_abi_version(void);
 const char* itts_last_error(void);
@@ -212,6 +212,38 @@ typedef struct itts_conv_args {
 } itts_conv_args;
 int itts_gemm_conv(const itts_conv_args* a, void* stream);
 
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Per-row LoRA adapter bank (many fine-tuned voices in one batch): the shrink half.
+ *   y = x W + s_a (x A_a^T) B_a^T = [x | u] [W ; B_bank^T],   a = ids[m] the adapter of row m
+ * The consuming GEMM (itts_gemm_skinny / itts_gemm_conv) runs unchanged with K' = K + Kx over a weight that was packed from
+ * [W ; B_bank^T] (B_bank^T: every adapter's B^T, rp rows each, zero-padded); this launch writes the Kx extra operand columns:
+ *   u[m][a * rp + j] = sum_k x[m][k] A_bank[a][j][k]   (j < rp; fp32 accumulation, one rounding to T, no atomics: deterministic)
+ *   every other column of u[m][0 .. Kx) = 0;  a row with ids[m] < 0 (the base voice) is all zeros.
+ * ALL Kx columns are written on every call (the buffers are reused across batches).
+ *   x       T [M][K] row-major, or (x_packed) the packed activation layout with x_mtp row tiles (0 = ceil(M / 16))
+ *   ids     int32 [M] on the device, read by the kernel: a captured graph serves any assignment of adapters to rows
+ *   a_bank  T [n][rp][K]: adapter a's lora_A with its scaling alpha / r folded in (in fp32, before the rounding to T); rows past the
+ *           adapter's own rank are zero.  rp = 16 * ceil(r_max / 16) <= 64;  Kx = n * rp rounded up to a multiple of 32, <= 512
+ *   u       u_packed: the first block BEHIND the K / KS * u_mtp KiB of a packed operand [M][K] -- the operand's k-steps
+ *           K / KS .. (K + Kx) / KS - 1 (u_mtp row tiles, 0 = ceil(M / 16); the tiles' padding rows are written as zeros);
+ *           else row-major: element (m, j) at u + m * ldu + j (ldu in elements, a multiple of 16 bytes: u may point at column K
+ *           of a [M][K + Kx] operand).
+ * K % KS == 0; x, u and a_bank 16-byte aligned.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct itts_lora_shrink_args {
+  int dtype;
+  int M, K;
+  const void* x;
+  int x_packed, x_mtp;
+  const int32_t* ids;
+  const void* a_bank;
+  int n, rp, Kx;
+  void* u;
+  int u_packed, u_mtp;
+  int64_t ldu;
+} itts_lora_shrink_args;
+int itts_lora_shrink(const itts_lora_shrink_args* a, void* stream);
 
 /* LayerNorm over the last dim of fp32 rows; y is T (y_f32 = 0) or fp32 (y_f32 = 1).  If w2 != NULL a second LayerNorm
  * (w2,b2) is applied to the result of the first (ln_f followed by final_norm). */

@@ -54,6 +54,12 @@ class LnReduceArgs(C.Structure):
                 ("lora_r", C.c_int)]
 
 
+class LoraShrinkArgs(C.Structure):
+    _fields_ = [("dtype", C.c_int), ("M", C.c_int), ("K", C.c_int), ("x", C.c_void_p), ("x_packed", C.c_int), ("x_mtp", C.c_int),
+                ("ids", C.c_void_p), ("a_bank", C.c_void_p), ("n", C.c_int), ("rp", C.c_int), ("Kx", C.c_int), ("u", C.c_void_p),
+                ("u_packed", C.c_int), ("u_mtp", C.c_int), ("ldu", C.c_int64)]
+
+
 class ConvArgs(C.Structure):
     _fields_ = [("dtype", C.c_int), ("B", C.c_int), ("Tin", C.c_int), ("Tout", C.c_int), ("Cin", C.c_int),
                 ("N", C.c_int), ("taps", C.c_int), ("off0", C.c_int), ("dil", C.c_int), ("x", C.c_void_p),
@@ -100,6 +106,7 @@ _SIGNATURES = {
     "itts_layernorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                  C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "itts_ln_reduce": (C.c_int, [C.POINTER(LnReduceArgs), C.c_void_p]),
+    "itts_lora_shrink": (C.c_int, [C.POINTER(LoraShrinkArgs), C.c_void_p]),
     "itts_embed_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                   C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "itts_attn_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
@@ -446,6 +453,30 @@ def ln_reduce(h, w, b, out, slab=None, nslab=0, bias=None, w2=None, b2=None, sta
         a.lora_b, a.lora_r = _p(lora_b), lora_b.shape[0]
     _check(lib().itts_ln_reduce(C.byref(a), _stream()), "itts_ln_reduce")
     return out
+
+
+def lora_kx(n: int, rp: int) -> int:
+    """Operand columns a bank of n adapters of padded rank rp adds to a GEMM: n * rp rounded up to whole k-steps of either type."""
+    return (n * rp + 31) // 32 * 32
+
+
+def lora_shrink(x, ids, a_bank, u, M, K, x_packed=False, x_mtp=0, u_packed=False, u_mtp=0, ldu=0):
+    """The shrink half of the per-row LoRA adapter bank (itts_lora_shrink): u[m][ids[m] * rp + j] = x[m] . a_bank[ids[m]][j], every
+    other column of u[m][:Kx] zero.  x T [M, K] (row-major or packed), ids int32 [M] on the device (-1 = no adapter), a_bank T
+    [n, rp, K]; u: the packed operand's tail (u_packed: a tensor that starts at the first appended block) or row-major with the
+    leading dimension ldu (a view that starts at the row's first extra column)."""
+    _dev(ids, a_bank)
+    if ids.dtype != torch.int32 or ids.numel() < M:
+        raise NativeError("itts_lora_shrink: ids must be int32 [M]")
+    n, rp, Ka = a_bank.shape
+    if Ka != K or a_bank.dtype != x.dtype or u.dtype != x.dtype:
+        raise NativeError("itts_lora_shrink: a_bank must be T [n, rp, K] of the operand's type")
+    a = LoraShrinkArgs()
+    a.dtype, a.M, a.K = dt(x.dtype), int(M), int(K)
+    a.x, a.x_packed, a.x_mtp = _p(x), int(bool(x_packed)), int(x_mtp)
+    a.ids, a.a_bank, a.n, a.rp, a.Kx = _p(ids), _p(a_bank), n, rp, lora_kx(n, rp)
+    a.u, a.u_packed, a.u_mtp, a.ldu = _p(u), int(bool(u_packed)), int(u_mtp), int(ldu)
+    _check(lib().itts_lora_shrink(C.byref(a), _stream()), "itts_lora_shrink")
 
 
 def embed_step(tokens, table, pos_table, step, pos_add, h, bump=None, row_step0=None, h_packed=None):

@@ -176,6 +176,8 @@ class GPTEngine:
         self.skip_finished = True
         self._W = W          # kept (by reference) for attach_lora: the engine itself only holds packed copies
         self.lora = False
+        self.bank = None     # per-row adapter bank (attach_lora_bank): n, rp, Kx and the signature the graph key carries
+        self._ids_host = None   # adapter id per row of the batch the last prefill() cached
         self.layers = []
 
         def folded(ln, wkey, bkey):
@@ -244,6 +246,8 @@ class GPTEngine:
         def packed(w):
             return nat.pack_weight(w.to(T).contiguous())
 
+        if adapters and self.bank is not None:
+            raise ValueError("attach_lora(): an adapter bank is attached (detach_lora_bank() first): one or the other")
         self.detach_lora()   # every attach starts from the base weights: nothing of an earlier adapter set survives
         if not adapters:     # attach_lora(None) = detach
             return
@@ -287,6 +291,102 @@ class GPTEngine:
         self.lora = False
         self._graphs.clear()
 
+    # ------------------------------------------------------------------------------------------------ adapter bank
+    BANK_TARGETS = (("attn.c_attn", "w_qkv"), ("attn.c_proj", "w_o"), ("mlp.c_fc", "w_fc"), ("mlp.c_proj", "w_pr"))
+
+    def attach_lora_bank(self, bank):
+        """A bank of LoRA adapter sets, one per voice, chosen PER ROW of a batch (self.adapter_ids / prefill(adapter_ids=...); -1 =
+        the base voice).  `bank`: a list of (adapters, scaling) in the attach_lora format; every set may name any of the four
+        targets of any layer, ranks may differ (each is zero-padded to rp = 16 * ceil(r_max / 16)).
+        For a row with adapter a:  y = x W + s_a (x A_a^T) B_a^T = [x | u] [W ; B_bank^T], u = the row's Kx-wide shrink vector
+        (itts_lora_shrink: s_a x A_a^T in the slot of adapter a, zeros elsewhere), B_bank^T = every adapter's B^T stacked.  The
+        GEMMs run unchanged over K + Kx, so the LoRA term is in their accumulator before the bias, the GELU and the K/V append.
+        Per layer and target this keeps A_bank T [n, rp, K] and a packed copy of [W ; B_bank^T] (the packed layout has the
+        k-step innermost: extending K is a re-pack, i.e. a second copy of the block weights).  A target no adapter names keeps
+        its base weight and gets no shrink launch.  The decode step runs in "launch" form (the folded GEMMs take their
+        LayerNorm statistics over K on the matrix pipe; the shrink needs xn = LN(h) as an operand anyway)."""
+        if self.lora:
+            raise ValueError("attach_lora_bank(): single adapters are attached (attach_lora(None) first): one or the other")
+        if not self.pa:
+            raise ValueError("attach_lora_bank(): the bank needs the packed activation layout (ITTS_PACKED_ACT=1)")
+        bank = [(dict(ad), float(sc)) for ad, sc in bank]
+        n = len(bank)
+        if n < 1:
+            raise ValueError("attach_lora_bank(): the bank is empty")
+        known = {f"gpt.h.{i}.{name}" for i in range(self.L) for name, _ in self.BANK_TARGETS}
+        for ad, _ in bank:
+            bad = sorted(set(ad) - known)
+            if bad:
+                raise ValueError(f"attach_lora_bank(): unknown adapter targets {bad}")
+        ranks = [int(A.shape[0]) for ad, _ in bank for A, _ in ad.values()]
+        if not ranks:
+            raise ValueError("attach_lora_bank(): no adapter names a target")
+        if max(ranks) > 64:
+            raise ValueError("the adapter bank supports rank <= 64")
+        rp = (max(ranks) + 15) // 16 * 16
+        Kx = nat.lora_kx(n, rp)
+        if Kx > 512:
+            raise ValueError(f"attach_lora_bank(): {n} adapters of padded rank {rp} need {Kx} extra operand columns (limit 512)")
+        dev, T, W = self.device, self.dtype, self._W
+        self.detach_lora_bank()
+        sig = []
+        for i, l in enumerate(self.layers):
+            for name, wkey in self.BANK_TARGETS:
+                key = f"gpt.h.{i}.{name}"
+                if not any(key in ad for ad, _ in bank):
+                    continue
+                base = W[key + ".weight"].detach().to(dev, torch.float32)              # [K, N]
+                K, N = base.shape
+                a_bank = torch.zeros(n, rp, K, dtype=torch.float32, device=dev)
+                ext = torch.zeros(K + Kx, N, dtype=torch.float32, device=dev)
+                ext[:K] = base
+                for a, (ad, sc) in enumerate(bank):
+                    if key in ad:
+                        A, Bm = (t.detach().to(dev, torch.float32) for t in ad[key])
+                        r = A.shape[0]
+                        if A.shape != (r, K) or Bm.shape != (N, r):
+                            raise ValueError(f"attach_lora_bank(): {key} of adapter {a}: A must be [r, {K}] and B [{N}, r]")
+                        a_bank[a, :r] = A * sc                                           # the scaling rides on A, folded in at fp32
+                        ext[K + a * rp:K + a * rp + r] = Bm.t()
+                l["bank_a_" + wkey] = a_bank.to(T).contiguous()
+                l["bank_" + wkey] = nat.pack_weight(ext.to(T).contiguous())
+                sig.append((i, wkey))
+        self.bank = SimpleNamespace(n=n, rp=rp, Kx=Kx, sig=(n, rp, tuple(sig)))
+        self._graphs.clear()
+        if hasattr(self, "xn") and self.xn.shape[1] < self.D + Kx:
+            self._cap_b = self._cap_s = 0   # xn / a / f need room for the shrink columns: reallocate on the next prefill
+
+    def detach_lora_bank(self):
+        """Back to the base weights: drops the bank's A factors and extended weights and the graphs captured over them.  Only this
+        engine changes: a fork holds its own layer dicts."""
+        for l in self.layers:
+            for k in [k for k in l if k.startswith("bank_")]:
+                del l[k]
+        self.bank = None
+        self._ids_host = None
+        if getattr(self, "adapter_ids", None) is not None:
+            self.adapter_ids.fill_(-1)
+        self._graphs.clear()
+
+    def _row_adapters(self, adapter_ids, B):
+        """The batch's adapter ids as host ints, checked before anything is launched (None without a bank; all -1 when a bank is
+        attached and the caller names none)."""
+        if adapter_ids is None:
+            return None if self.bank is None else [-1] * B
+        if self.bank is None:
+            raise ValueError("adapter_ids were given but no adapter bank is attached (attach_lora_bank)")
+        ids = [int(v) for v in (adapter_ids.tolist() if torch.is_tensor(adapter_ids) else adapter_ids)]
+        if len(ids) != B:
+            raise ValueError(f"adapter_ids holds {len(ids)} ids for a batch of {B}")
+        if any(v < -1 or v >= self.bank.n for v in ids):
+            raise ValueError(f"adapter_ids must lie in [-1, {self.bank.n}): {ids}")
+        return ids
+
+    def _row_ids(self, ids, rows_per_element):
+        """int32 device tensor: element b's adapter id repeated over its rows (the large-M passes)."""
+        import numpy as np
+        return torch.from_numpy(np.repeat(np.asarray(ids, dtype=np.int32), np.asarray(rows_per_element, dtype=np.int64))).to(self.device)
+
     def fork(self) -> "GPTEngine":
         """A second engine over the SAME packed weights (read-only, shared tensors) with its own KV cache, scratch buffers,
         loop state, captured graphs and per-layer dicts: what a concurrent request needs (infer.RequestPool).  A fork keeps
@@ -300,6 +400,7 @@ class GPTEngine:
         e._graphs = {}
         e._beam_cap = (0, 0, 0)
         e._kv_rows = None
+        e._ids_host = None
         e._sink = torch.zeros(4, dtype=torch.int32, device=self.device)
         return e
 
@@ -312,10 +413,11 @@ class GPTEngine:
             B = max(B, self._cap_b)
             self.h = torch.zeros(B, self.D, dtype=torch.float32, device=dev)
             Bp = nat.packed_rows(B)   # the packed layout works in 16-row tiles
+            Kx = 0 if self.bank is None else self.bank.Kx   # adapter bank: the operands' shrink columns (k-steps at the end)
             self.q = torch.zeros(B, self.D, dtype=T, device=dev)
-            self.a = torch.zeros(Bp, self.D, dtype=T, device=dev)
-            self.f = torch.zeros(Bp, 4 * self.D, dtype=T, device=dev)
-            self.xn = torch.zeros(Bp, self.D, dtype=T, device=dev)
+            self.a = torch.zeros(Bp, self.D + Kx, dtype=T, device=dev)
+            self.f = torch.zeros(Bp, 4 * self.D + Kx, dtype=T, device=dev)
+            self.xn = torch.zeros(Bp, self.D + Kx, dtype=T, device=dev)
             self.hb = torch.zeros(Bp, self.D, dtype=T, device=dev)   # "fold" mode: T-typed packed copy of the residual rows
             self.slab = torch.zeros(self.KSPLIT, B, self.D + 64, dtype=torch.float32, device=dev)   # + runtime-LoRA columns
             self.logits = torch.zeros(B, self.V, dtype=torch.float32, device=dev)
@@ -323,6 +425,7 @@ class GPTEngine:
             self.finished = torch.zeros(B, dtype=torch.int32, device=dev)
             self.pad = torch.zeros(B, dtype=torch.int32, device=dev)
             self.force_stop = torch.full((B,), -1, dtype=torch.int32, device=dev)
+            self.adapter_ids = torch.full((B,), -1, dtype=torch.int32, device=dev)   # adapter of each row (bank attached), -1 = base
             self.row_step0 = torch.zeros(B, dtype=torch.int32, device=dev)   # loop step at which each row started (decode_refill)
             self.kv_share = torch.zeros(1, dtype=torch.int32, device=dev)    # (p0 << 8) | C: rows' first C keys == row 0's at p0 (itts_attn_decode)
             self.state = torch.zeros(8, dtype=torch.int32, device=dev)
@@ -397,12 +500,29 @@ class GPTEngine:
         best = min((1, 2, 3), key=lambda ks: (cost(ks), ks))
         return best if cost(best) < 0.9 * cost(rule) else rule
 
-    def _big_m_layers(self, h, attn):
+    def _big_m_layers(self, h, attn, row_ids=None):
         """The 24 blocks over packed rows h fp32 [M, D] (in place): LayerNorm -> QKV -> attn(i, qkv, att) -> out-projection ->
         LayerNorm -> FC -> FC2.  With few rows the two N = D projections run split-K into slabs and the NEXT LayerNorm launch folds
-        them into h (see _proj_ksplit); returns h with every block applied."""
+        them into h (see _proj_ksplit); returns h with every block applied.
+        With an adapter bank (row_ids int32 [M]: the adapter of every row, default -1) an adapted GEMM reads [x | u] row-major:
+        x is copied into a [M, K + Kx] operand, itts_lora_shrink writes u behind it, and the GEMM runs with Cin = K + Kx over the
+        extended weight -- one extra copy of the operand per adapted GEMM."""
         T, D, dev = self.dtype, self.D, self.device
         M = h.shape[0]
+        bank = self.bank
+        if bank is not None:
+            if row_ids is None:
+                row_ids = torch.full((M,), -1, dtype=torch.int32, device=dev)
+            xc = {D: torch.empty(M, D + bank.Kx, dtype=T, device=dev), 4 * D: torch.empty(M, 4 * D + bank.Kx, dtype=T, device=dev)}
+
+        def operand(l, wkey, x, K):
+            """(packed weight, operand, Cin) of one GEMM of the block"""
+            if bank is None or "bank_" + wkey not in l:
+                return l.get(wkey + "_merged", l[wkey]), x, K
+            c = xc[K]
+            c[:, :K].copy_(x)
+            nat.lora_shrink(x, row_ids, l["bank_a_" + wkey], c[:, K:], M, K, ldu=K + bank.Kx)
+            return l["bank_" + wkey], c, K + bank.Kx
         xn = torch.empty(M, D, dtype=T, device=dev)
         qkv = torch.empty(M, 3 * D, dtype=T, device=dev)
         att = torch.empty(M, D, dtype=T, device=dev)
@@ -415,26 +535,29 @@ class GPTEngine:
                 nat.layernorm(h, l["ln1"][0], l["ln1"][1], xn)
             else:
                 nat.ln_reduce(h, l["ln1"][0], l["ln1"][1], xn, slab=slab, nslab=ks, bias=pending)
-            nat.gemm_conv(T, 1, M, M, D, 3 * D, l["w_qkv"], xn, qkv, bias=l["b_qkv"])
+            w, x, K = operand(l, "w_qkv", xn, D)
+            nat.gemm_conv(T, 1, M, M, K, 3 * D, w, x, qkv, bias=l["b_qkv"])
             attn(i, qkv, att)
-            w_o, w_pr = l.get("w_o_merged", l["w_o"]), l.get("w_pr_merged", l["w_pr"])
+            w, x, K = operand(l, "w_o", att, D)
             if ks > 1:
-                nat.gemm_conv(T, 1, M, M, D, D, w_o, att, slab, y_f32=True, ksplit=ks)
+                nat.gemm_conv(T, 1, M, M, K, D, w, x, slab, y_f32=True, ksplit=ks)
                 nat.ln_reduce(h, l["ln2"][0], l["ln2"][1], xn, slab=slab, nslab=ks, bias=l["b_o"])
             else:
-                nat.gemm_conv(T, 1, M, M, D, D, w_o, att, h, bias=l["b_o"], y_f32=True, resid=h)
+                nat.gemm_conv(T, 1, M, M, K, D, w, x, h, bias=l["b_o"], y_f32=True, resid=h)
                 nat.layernorm(h, l["ln2"][0], l["ln2"][1], xn)
-            nat.gemm_conv(T, 1, M, M, D, 4 * D, l["w_fc"], xn, ff, bias=l["b_fc"], act=1)
+            w, x, K = operand(l, "w_fc", xn, D)
+            nat.gemm_conv(T, 1, M, M, K, 4 * D, w, x, ff, bias=l["b_fc"], act=1)
+            w, x, K = operand(l, "w_pr", ff, 4 * D)
             if ks > 1:
-                nat.gemm_conv(T, 1, M, M, 4 * D, D, w_pr, ff, slab, y_f32=True, ksplit=ks)
+                nat.gemm_conv(T, 1, M, M, K, D, w, x, slab, y_f32=True, ksplit=ks)
                 pending = l["b_pr"]
             else:
-                nat.gemm_conv(T, 1, M, M, 4 * D, D, w_pr, ff, h, bias=l["b_pr"], y_f32=True, resid=h)
+                nat.gemm_conv(T, 1, M, M, K, D, w, x, h, bias=l["b_pr"], y_f32=True, resid=h)
         if pending is not None:              # the last block's FC2 slabs: fold them in (the LayerNorm output is not used)
             nat.ln_reduce(h, self.ln_f[0], self.ln_f[1], xn, slab=slab, nslab=ks, bias=pending)
         return h
 
-    def _blocks_full(self, h, B, S, pad, use_cache, row_off=None, cache_shift=None):
+    def _blocks_full(self, h, B, S, pad, use_cache, row_off=None, cache_shift=None, row_ids=None):
         """All transformer blocks over h fp32 [M, D] (in place).  Padded form: M = B*S rows, pad int32 [B] (left padding)
         or None.  Packed form (row_off int32 [B+1] on device): only real rows exist, batch element b owns rows
         [row_off[b], row_off[b+1]), S is the longest element, cache row = cache_shift[b] + local row."""
@@ -447,7 +570,7 @@ class GPTEngine:
                 nat.attn_prefill(qkv, att, kc, vc, pad, B, S, H, self._cap_s)
             else:
                 nat.attn_prefill_packed(qkv, att, kc, vc, row_off, cache_shift, B, S, H, self._cap_s, **kva)
-        return self._big_m_layers(h, attn)
+        return self._big_m_layers(h, attn, row_ids)
 
     def _head(self, h_rows, B):
         """ln_f -> final_norm -> mel_head on fp32 rows."""
@@ -496,7 +619,7 @@ class GPTEngine:
         return h[last_rows].contiguous()
 
     def prefill(self, prefix_emb: torch.Tensor, pad: torch.Tensor, max_new: int, beams: int = 1, shared_rows: int = 0, paged=None,
-                slots_window: int = 0):
+                slots_window: int = 0, adapter_ids=None):
         """prefix_emb fp32 [B,P,D] (left-padded with zeros), pad int [B].  Runs prefix + start token (mel position 0,
         model.py:152-162), fills the KV cache rows [pad_b, P] of every element, leaves logits of the last position in
         self.logits.  The left-padding rows are never computed: the real rows are packed (one gather), the GEMMs run over
@@ -512,10 +635,16 @@ class GPTEngine:
         paged (default: the engine's setting for beams == 1, never with beams > 1): the cache is a block pool behind a block
         table (class PagedKV).  Every row gets the blocks for its own window [pad_b, S + max_new]; a caller that goes on with
         decode_beam() over expanded rows passes paged=False (beam search addresses whole contiguous rows).  slots_window > 0
-        (decode_refill's pool): size the pool for B rows of up to that many live positions each instead of this batch's."""
+        (decode_refill's pool): size the pool for B rows of up to that many live positions each instead of this batch's.
+        adapter_ids (host ints, one per element; needs attach_lora_bank): the adapter every row speaks with, -1 = the base voice;
+        None with a bank attached = all base.  The ids reach the device as self.adapter_ids, which the decode step's shrink
+        launches read: they are data, a captured step serves every assignment."""
         B, P, D = prefix_emb.shape
         S = P + 1
         beams = int(beams)
+        ids = self._row_adapters(adapter_ids, B)
+        if ids is not None and beams > 1:
+            raise NotImplementedError("beam search with an adapter bank is not built")
         if beams > 1 and self.beam_kv != "table":
             raise ValueError("prefill(beams>1) needs the KV row table (beam_kv='table')")
         pad_h = [int(v) for v in torch.as_tensor(pad).tolist()]
@@ -542,7 +671,11 @@ class GPTEngine:
         self._pad_host = pad_h             # latent_mel_rows() finds the prompt's K/V in the cache through it
         self.pad[:B] = torch.tensor(pad_h, dtype=torch.int32).to(dev)
         self.kv_share.zero_()
-        if shared_rows and B > 1 and self.share_prefix:
+        self._ids_host = ids
+        if ids is not None:
+            self.adapter_ids[:B] = torch.tensor(ids, dtype=torch.int32).to(dev)
+        # (with a bank the conditioning rows' hidden states depend on the row's adapter: nothing is shared)
+        if shared_rows and B > 1 and self.share_prefix and ids is None:
             # every element starts with the same `shared_rows` rows (the caller's promise: one prompt's conditioning latents)
             self._head(self._prefill_shared(emb, pad_h, S, int(shared_rows)), B)
             if beams == 1 and int(shared_rows) <= 255 and self.share_kv_reads:
@@ -557,7 +690,8 @@ class GPTEngine:
             meta = torch.tensor(off + [b_off - 1 for b_off in off[1:]], dtype=torch.int32).to(dev)   # row_off | last rows
             row_off, last_rows = meta[: B + 1], meta[B + 1:].long()
             h = emb.view(B * S, D)[idx.to(dev)]
-            h = self._blocks_full(h, B, S, None, True, row_off=row_off, cache_shift=self.pad[:B])
+            h = self._blocks_full(h, B, S, None, True, row_off=row_off, cache_shift=self.pad[:B],
+                                  row_ids=None if ids is None else self._row_ids(ids, lens))
             self._head(h[last_rows].contiguous(), B)
         self.state.zero_()                 # step, cache position, finished rows, arrival counter, seed (lo, hi)
         self.state[1] = S - 1
@@ -583,18 +717,19 @@ class GPTEngine:
         return self.prefill(prefix_emb.repeat_interleave(beams, dim=0), pad.repeat_interleave(beams), max_new, shared_rows=shared_rows,
                             paged=False)
 
-    def latent(self, emb: torch.Tensor, lengths=None) -> torch.Tensor:
+    def latent(self, emb: torch.Tensor, lengths=None, adapter_ids=None) -> torch.Tensor:
         """Teacher-forced pass (model.py:459-474): emb fp32 [B,S,D] (right-padded rows allowed) ->
         final_norm(ln_f(blocks(emb))) fp32 [B,S,D].  With `lengths` (host ints, real rows per element) only the real rows
-        are computed (packed); the padding rows of the result are zero."""
+        are computed (packed); the padding rows of the result are zero.  adapter_ids: as in prefill()."""
         B, S, D = emb.shape
+        ids = self._row_adapters(adapter_ids, B)
         if self._cap_b == 0:
             self._ensure(1, 64)
         dev = self.device
         src = emb.to(dev, torch.float32).contiguous().view(B * S, D)
         if lengths is None:
             h = src.clone()
-            self._blocks_full(h, B, S, None, False)
+            self._blocks_full(h, B, S, None, False, row_ids=None if ids is None else self._row_ids(ids, [S] * B))
             out = torch.empty_like(h)
             nat.layernorm(h, self.ln_f[0], self.ln_f[1], out, self.final_norm[0], self.final_norm[1])
             return out.view(B, S, D)
@@ -605,14 +740,14 @@ class GPTEngine:
         idx = torch.cat([torch.arange(b * S, b * S + lens[b]) for b in range(B)]).to(dev)
         row_off = torch.tensor(off, dtype=torch.int32).to(dev)
         h = src[idx]
-        self._blocks_full(h, B, max(lens), None, False, row_off=row_off)
+        self._blocks_full(h, B, max(lens), None, False, row_off=row_off, row_ids=None if ids is None else self._row_ids(ids, lens))
         packed = torch.empty_like(h)
         nat.layernorm(h, self.ln_f[0], self.ln_f[1], packed, self.final_norm[0], self.final_norm[1])
         out = torch.zeros(B * S, D, dtype=torch.float32, device=dev)
         out[idx] = packed
         return out.view(B, S, D)
 
-    def latent_mel_rows(self, mel_emb: torch.Tensor, m_lens, cache_rows=None) -> torch.Tensor:
+    def latent_mel_rows(self, mel_emb: torch.Tensor, m_lens, cache_rows=None, adapter_ids=None) -> torch.Tensor:
         """The teacher-forced pass (model.py:459-474, :548-597) over the MEL rows only, for the batch whose prompt the last
         prefill() cached.  In cond | text | mel the causal mask lets no prompt position see a mel position, so the prompt's
         keys and values in every layer are exactly what prefill() computed for the decode loop -- same kernels, same inputs,
@@ -623,10 +758,14 @@ class GPTEngine:
         (tests/test_engines_gpu.py::test_latent_pass_reuses_the_cached_prompt).
         mel_emb fp32 [sum(m_lens), D]: the mel segments' embeddings, elements in prefill order; cache_rows: the cache row that
         holds element b's prompt (default b; b * num_beams after a beam prefill that copied rows).
+        adapter_ids: the ids prefill() was given (the default): the cached prompt K / V were computed under them, other ids are refused.
         Returns final_norm(ln_f(hidden)) fp32 [sum(m_lens), D]."""
         import numpy as np
         T, D, H, dev = self.dtype, self.D, self.H, self.device
         B, P = len(m_lens), self._S - 1
+        ids = self._ids_host if adapter_ids is None else self._row_adapters(adapter_ids, B)
+        if ids is not None and (self._ids_host is None or list(ids) != list(self._ids_host[:B]) or len(self._ids_host) != B):
+            raise ValueError("latent_mel_rows(): the cached prompt was prefilled under other adapter ids")
         cache_rows = list(range(B)) if cache_rows is None else [int(r) for r in cache_rows]
         if len(cache_rows) != B or max(cache_rows) >= len(self._pad_host):
             raise ValueError("latent_mel_rows(): the batch differs from the one prefill() cached")
@@ -643,7 +782,8 @@ class GPTEngine:
         kva = self._kvargs()
         # the prompt's keys / values straight from the decode cache (itts_attn_prefill_prefix), the mel rows' from qkv
         h = self._big_m_layers(h, lambda i, qkv, att: nat.attn_prefill_prefix(
-            qkv, att, self.kc[i], self.vc[i], row_off, pre_len, pre_row, pre_pos0, B, max(m), H, self._cap_s, **kva))
+            qkv, att, self.kc[i], self.vc[i], row_off, pre_len, pre_row, pre_pos0, B, max(m), H, self._cap_s, **kva),
+            None if ids is None else self._row_ids(ids, m))
         out = torch.empty_like(h)
         nat.layernorm(h, self.ln_f[0], self.ln_f[1], out, self.final_norm[0], self.final_norm[1])
         return out
@@ -659,7 +799,7 @@ class GPTEngine:
         self._pending_bump = True
 
     def _fold_now(self, B):
-        return self.decode_mode == "fold" and not self.lora
+        return self.decode_mode == "fold" and not self.lora and self.bank is None
 
     def _step_transformer(self, B, bump=None, gemm_only=False):
         """(bump: advance step counter / cache position inside this step's first launches; None = "a _sample call is
@@ -682,7 +822,7 @@ class GPTEngine:
                 bump = getattr(self, "_pending_bump", False)
             self._pending_bump = False
         skip = lambda *a, **kw: None   # noqa: E731
-        k = SimpleNamespace(embed_step=skip, attn_decode=skip, ln_reduce=skip) if gemm_only else nat   # every other launch
+        k = SimpleNamespace(embed_step=skip, attn_decode=skip, ln_reduce=skip, lora_shrink=skip) if gemm_only else nat   # every other launch
         tally = [0, 0]
 
         def gemm(M, N, K, w, bias, epi, **kw):
@@ -724,11 +864,23 @@ class GPTEngine:
             k.embed_step(self.tokens, self.mel_emb, self.mel_pos, step, 2 if bump else 1, h, row_step0=rs0)
             k.ln_reduce(h, self.layers[0]["ln1"][0], self.layers[0]["ln1"][1], xn, state_bump=self.state[0:2] if bump else None,
                         y_packed=pa)
+            bank = self.bank
+            Bp = nat.packed_rows(B)
+
+            def adapted(l, wkey, x, K):
+                """(packed weight, K) of one GEMM of the block.  Adapter bank: the rows' shrink vectors u = s_a x A_a^T go behind the
+                operand's K / KS k-steps (the packed layout has the k-step outermost: the producers keep writing the front) and
+                the GEMM runs over K + Kx with [W ; B_bank^T]."""
+                if bank is None or "bank_" + wkey not in l:
+                    return l.get(wkey + "_lora", l[wkey]), K
+                k.lora_shrink(x, self.adapter_ids, l["bank_a_" + wkey], x.view(-1)[K * Bp:], B, K, x_packed=True, u_packed=True)
+                return l["bank_" + wkey], K + bank.Kx
             for i, l in enumerate(self.layers):
                 last = i + 1 == self.L
                 n_o = l.get("lora_n_o", D)
                 n_p = l.get("lora_n_pr", D)
-                gemm(B, 3 * D, D, l["w_qkv"], l["b_qkv"], nat.EPI_QKV_CACHE, x=xn, y=self.q, kcache=self.kc[i], vcache=self.vc[i],
+                w, K = adapted(l, "w_qkv", xn, D)
+                gemm(B, 3 * D, K, w, l["b_qkv"], nat.EPI_QKV_CACHE, x=xn, y=self.q, kcache=self.kc[i], vcache=self.vc[i],
                      pos=pos, heads=H, smax=self._cap_s, x_packed=pa, **kva)
                 k.attn_decode(self.q, self.kc[i], self.vc[i], self.a, self.pad, pos, B, H, self._cap_s, out_packed=pa, **attn_kw)
                 nxt = self.ln_f if last else self.layers[i + 1]["ln1"]
@@ -736,13 +888,15 @@ class GPTEngine:
                 # out-projection: split-K slabs; with a runtime adapter the GEMM also produces x A in extra columns and the
                 # reduce launch adds (x A) B^T
                 sl_o = self.slab.view(-1)[: KS * B * n_o].view(KS, B, n_o)
-                gemm(B, n_o, D, l.get("w_o_lora", l["w_o"]), None, nat.EPI_SLAB_F32, x=self.a, yf=sl_o, ksplit=KS, x_packed=pa)
+                w, K = adapted(l, "w_o", self.a, D)
+                gemm(B, n_o, K, w, None, nat.EPI_SLAB_F32, x=self.a, yf=sl_o, ksplit=KS, x_packed=pa)
                 k.ln_reduce(h, l["ln2"][0], l["ln2"][1], xn, slab=sl_o, nslab=KS, bias=l["b_o"], y_packed=pa,
                             slab_stride=n_o, lora_b=l.get("lora_b_o"))
-                gemm(B, 4 * D, D, l["w_fc"], l["b_fc"], nat.EPI_GELU_STORE, x=xn, y=self.f, x_packed=pa, y_packed=pa)
+                w, K = adapted(l, "w_fc", xn, D)
+                gemm(B, 4 * D, K, w, l["b_fc"], nat.EPI_GELU_STORE, x=xn, y=self.f, x_packed=pa, y_packed=pa)
                 sl_p = self.slab.view(-1)[: KS * B * n_p].view(KS, B, n_p)
-                gemm(B, n_p, 4 * D, l.get("w_pr_lora", l["w_pr"]), None, nat.EPI_SLAB_F32, x=self.f, yf=sl_p, ksplit=KS,
-                     x_packed=pa)
+                w, K = adapted(l, "w_pr", self.f, 4 * D)
+                gemm(B, n_p, K, w, None, nat.EPI_SLAB_F32, x=self.f, yf=sl_p, ksplit=KS, x_packed=pa)
                 k.ln_reduce(h, nxt[0], nxt[1], xn, slab=sl_p, nslab=KS, bias=l["b_pr"], w2=nxt2[0], b2=nxt2[1], y_packed=pa,
                             slab_stride=n_p, lora_b=l.get("lora_b_pr"))
         gemm(B, self.V, D, self.w_head, self.b_head, nat.EPI_STORE_F32, x=self.xn, yf=self.logits, x_packed=pa)
@@ -764,9 +918,11 @@ class GPTEngine:
     def _graph_key(self, kind, B, sp, nb=1):
         """Key of a captured decode step: the loop kind ("token" / "beam"), its rows and beams, the sampling parameters and
         every engine setting the captured launches read -- a setting changed after a capture must not replay the old variant."""
-        return (kind, B, nb, self.decode_mode, self.lora, tuple(self.fold_rows), self.fold_rows_consumers, self.fold_wide,
-                self.pa, self.KSPLIT, self.skip_finished, self.share_kv_reads, self.beam_kv,
-                None if self.kv is None else self.kv.bs, tuple(sorted(sp.items())))
+        key = (kind, B, nb, self.decode_mode, self.lora, tuple(self.fold_rows), self.fold_rows_consumers, self.fold_wide,
+               self.pa, self.KSPLIT, self.skip_finished, self.share_kv_reads, self.beam_kv,
+               None if self.kv is None else self.kv.bs, tuple(sorted(sp.items())))
+        # an adapter bank: its shape and targets (what the captured launches were built from) -- never the rows' ids, which are data
+        return key if self.bank is None else key + (("bank",) + self.bank.sig,)
 
     def _graph(self, key, body):
         """The CUDA graph of one decode step `body`, captured on first use and kept under `key` (see _graph_key)."""
@@ -952,6 +1108,8 @@ class GPTEngine:
         A row's tokens are those it would get decoded alone with the same logits (greedy: identical codes up to the usual
         reduction-order noise of a different left padding); sampled rows draw from the loop's Philox stream (row slot, loop
         step), so they differ from a stand-alone run as two seeds do."""
+        if self.bank is not None:
+            raise NotImplementedError("decode_refill(): slot refill with an adapter bank is not built")
         B, S, ce = self._B, self._S, int(check_every)
         if self._shared_prefix is not None or self._kv_rows is not None:
             raise ValueError("decode_refill(): num_beams = 1 only")
@@ -1086,6 +1244,8 @@ class GPTEngine:
         num_return_sequences best hypotheses of every element, best first (row = b * num_return_sequences + rank),
         right-padded with the stop token."""
         nb = int(num_beams)
+        if self.bank is not None:
+            raise NotImplementedError("decode_beam(): beam search with an adapter bank is not built")
         if not 1 <= int(num_return_sequences) <= nb:
             raise ValueError("num_return_sequences has to be in [1, num_beams]")   # generate() raises the same
         R = self._B

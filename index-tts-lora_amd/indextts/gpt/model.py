@@ -189,13 +189,19 @@ class UnifiedVoice:
     # ---- generation -------------------------------------------------------------------------------------------
     def inference_speech(self, speech_conditioning_mel, text_inputs, cond_mel_lengths=None, input_tokens=None,
                          num_return_sequences=1, max_generate_length=None, typical_sampling=False, typical_mass=.9,
-                         speaker_ids=None, force_stop=None, seed=None, return_logits=False, **hf):
+                         speaker_ids=None, force_stop=None, seed=None, return_logits=False, adapter_ids=None, **hf):
         """model.py:669-720.  Accepted generate() keywords: do_sample, top_p, top_k, temperature, repetition_penalty,
         num_beams, length_penalty.  Returns codes [B * num_return_sequences, n] (stop-token padded), like
         `output[:, trunc_index:]`: with beams the num_return_sequences best hypotheses of each element, best first; with
-        sampling that many independent draws per element."""
+        sampling that many independent draws per element.
+        adapter_ids (host ints, one per batch element; needs attach_lora_bank): the LoRA adapter -- the voice -- each element
+        speaks with, -1 = the base model; expanded with num_return_sequences like the rows themselves."""
         if self.engine is None:
             raise RuntimeError("call post_init_gpt2_config() first")
+        if adapter_ids is not None:     # checked here, before the conditioner launches anything
+            adapter_ids = self.engine._row_adapters(adapter_ids, int(text_inputs.shape[0]))
+        if int(hf.get("num_beams", 1)) > 1 and (adapter_ids is not None or self.engine.bank is not None):
+            raise NotImplementedError("beam search with an adapter bank is not built (num_beams = 1)")
         if input_tokens is not None:
             raise NotImplementedError("input_tokens (continuing a given code prefix) is off the infer.py path")
         num_beams = int(hf.pop("num_beams", 1))
@@ -232,7 +238,9 @@ class UnifiedVoice:
             emb, pad = emb.repeat_interleave(nrs, dim=0), pad.repeat_interleave(nrs)
             if force_stop is not None:
                 force_stop = [v for v in force_stop for _ in range(nrs)]
-        self.engine.prefill(emb, pad, max_new, shared_rows=shared)
+            if adapter_ids is not None:
+                adapter_ids = [v for v in adapter_ids for _ in range(nrs)]
+        self.engine.prefill(emb, pad, max_new, shared_rows=shared, adapter_ids=adapter_ids)
         out = self.engine.decode(max_new, sp, force_stop=force_stop, return_logits=return_logits)
         return out
 
@@ -242,6 +250,20 @@ class UnifiedVoice:
         if self.engine is None:
             raise RuntimeError("call post_init_gpt2_config() first")
         self.engine.attach_lora(adapters, scaling)
+        return self
+
+    def attach_lora_bank(self, bank):
+        """A bank of LoRA adapter sets -- one per fine-tuned voice -- chosen per batch element with adapter_ids: a list of
+        (adapters, scaling) in the attach_lora format (see GPTEngine.attach_lora_bank).  Exclusive with attach_lora."""
+        if self.engine is None:
+            raise RuntimeError("call post_init_gpt2_config() first")
+        self.engine.attach_lora_bank(bank)
+        return self
+
+    def detach_lora_bank(self):
+        if self.engine is None:
+            raise RuntimeError("call post_init_gpt2_config() first")
+        self.engine.detach_lora_bank()
         return self
 
     def replica(self) -> "UnifiedVoice":
@@ -255,12 +277,15 @@ class UnifiedVoice:
     # ---- teacher-forced latent pass -----------------------------------------------------------------------------
     def forward(self, speech_conditioning_latent, text_inputs, text_lengths, mel_codes, wav_lengths,
                 cond_mel_lengths=None, types=None, text_first=True, raw_mels=None, return_attentions=False,
-                return_latent=False, clip_inputs=False, speaker_ids=None, conds=None):
-        """model.py:548-597 with return_latent=True (the only mode infer.py uses): -> latent [B, T, D] fp32."""
+                return_latent=False, clip_inputs=False, speaker_ids=None, conds=None, adapter_ids=None):
+        """model.py:548-597 with return_latent=True (the only mode infer.py uses): -> latent [B, T, D] fp32.
+        adapter_ids: as in inference_speech."""
         if not return_latent:
             raise NotImplementedError("training losses are out of scope; call with return_latent=True")
         eng = self.engine
         dev = self.device
+        if adapter_ids is not None:
+            adapter_ids = eng._row_adapters(adapter_ids, int(text_inputs.shape[0]))
         if conds is None:
             conds = self.get_conditioning(speech_conditioning_latent, cond_mel_lengths, speaker_ids)
         text_inputs = text_inputs.to(dev).long()
@@ -283,7 +308,7 @@ class UnifiedVoice:
         if c.shape[0] == 1 and B > 1:
             c = c.expand(B, -1, -1)
         emb = torch.cat([c, te, me], dim=1)
-        enc = eng.latent(emb)[:, c.shape[1]:]
+        enc = eng.latent(emb, adapter_ids=adapter_ids)[:, c.shape[1]:]
         mel_part = enc[:, -mi.shape[1]:]
         return mel_part[:, :-2]
 

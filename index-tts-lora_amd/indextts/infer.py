@@ -402,6 +402,8 @@ class IndexTTS:
     def _generate(self, conds, text_tokens, gen, max_mel_tokens, **extra):
         """gpt.inference_speech with precomputed conditioning latents (same values as recomputing them per call)."""
         g = self.gpt
+        if g.engine.bank is not None:   # infer / infer_fast, the REST service's calls: no way to name a voice per request yet
+            raise NotImplementedError("infer / infer_fast with an adapter bank is not built: use infer_batch(adapter_ids=...)")
         emb, pad = g.prefix_rows(conds, text_tokens)
         shared = int(conds.shape[1]) if conds.shape[0] == 1 else 0   # one prompt: every row starts with the same latents
         sp = sampling_params(gen, extra.pop("seed", torch.initial_seed() & 0x7FFFFFFFFFFFFFFF))
@@ -413,14 +415,16 @@ class IndexTTS:
         g.engine.prefill(emb, pad, max_mel_tokens, shared_rows=shared)
         return g.engine.decode(max_mel_tokens, sp, force_stop=extra.pop("force_stop", None))
 
-    def _latents(self, conds, text_rows: List[torch.Tensor], code_rows: List[torch.Tensor], reuse_prefix=False, cache_rows=None):
+    def _latents(self, conds, text_rows: List[torch.Tensor], code_rows: List[torch.Tensor], reuse_prefix=False, cache_rows=None,
+                 adapter_ids=None):
         """Teacher-forced pass for several utterances at once (right-padded; causal attention makes padding inert).
         Each row reproduces gpt(cond, text, [L], codes, code_len*1024, return_latent=True) of infer.py:864-874.
         The [cond | text | mel] embedding batch is assembled with two gathers from index arrays built on the host (one
         upload) instead of a dozen small launches per utterance.
         reuse_prefix: the rows are, in order, the batch the engine's LAST prefill() cached (same conds, same texts) and nothing
         has touched its KV cache since -- then only the mel rows are recomputed and the prompt's keys / values come from the
-        cache (GPTEngine.latent_mel_rows: same bits, ~40 % fewer GEMM rows)."""
+        cache (GPTEngine.latent_mel_rows: same bits, ~40 % fewer GEMM rows).
+        adapter_ids: the rows' adapters of an attached bank (with reuse_prefix: the ids the cached prompt was prefilled under)."""
         g, eng, dev = self.gpt, self.gpt.engine, self.device
         if reuse_prefix and self.reuse_prompt_kv:
             cl = [int(c.numel()) for c in code_rows]
@@ -434,7 +438,8 @@ class IndexTTS:
             ids[pos == 0] = g.start_mel_token
             ids[(pos > 0) & (pos <= np.repeat(cln, m))] = flat
             idx = torch.from_numpy(np.stack([ids, pos])).to(dev)
-            enc = eng.latent_mel_rows(eng.mel_emb[idx[0]] + eng.mel_pos[idx[1]], [c + 2 for c in cl], cache_rows)
+            enc = eng.latent_mel_rows(eng.mel_emb[idx[0]] + eng.mel_pos[idx[1]], [c + 2 for c in cl], cache_rows,
+                                      adapter_ids=adapter_ids)
             return [enc[int(offs[i]): int(offs[i]) + cl[i]] for i in range(len(cl))]
 
         def flat_host(rows):
@@ -466,7 +471,7 @@ class IndexTTS:
         batch[:, :nc] = conds[0].to(dev, torch.float32)
         batch[idx[0, :n_t], idx[1, :n_t]] = eng.text_emb[idx[2, :n_t]] + eng.text_pos[idx[3, :n_t]]
         batch[idx[0, n_t:], idx[1, n_t:]] = eng.mel_emb[idx[2, n_t:]] + eng.mel_pos[idx[3, n_t:]]
-        enc = eng.latent(batch, lengths=[s0 + n + 2 for s0, n in spans])   # real rows only (cond | text | mel incl. start/stop)
+        enc = eng.latent(batch, lengths=[s0 + n + 2 for s0, n in spans], adapter_ids=adapter_ids)   # real rows only (cond | text | mel incl. start/stop)
         return [enc[i, s0: s0 + n] for i, (s0, n) in enumerate(spans)]
 
     def _finish(self, wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, sampling_rate=24000):
@@ -628,14 +633,16 @@ class IndexTTS:
         return self._finish(wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time)
 
     def infer_batch(self, cond_mel: torch.Tensor, text_token_rows: List[torch.Tensor], max_mel_tokens=600, force_stop=None,
-                    seed=1234, return_codes=False, phase_events: dict | None = None, **generation_kwargs):
+                    seed=1234, return_codes=False, phase_events: dict | None = None, adapter_ids=None, **generation_kwargs):
         """Utterance-batch data path used by bench.py / the multi-GPU sharder (not in the reference API): one shared
         prompt, N independent texts decoded as ONE left-padded batch, one batched latent pass, and one vocoder call per
         group of equal-length utterances (batching unequal lengths would change the tail of the shorter waveforms).
         Returns a list of fp32 waveforms already scaled to the int16 range, like infer.py:892.
-        phase_events, if given, receives torch.cuda.Event marks at the phase boundaries."""
+        phase_events, if given, receives torch.cuda.Event marks at the phase boundaries.
+        adapter_ids (host ints, one per utterance; needs gpt.attach_lora_bank): the voice -- LoRA adapter of the bank, -1 = base
+        model -- each utterance is spoken with, in the token loop and in the latent pass."""
         st = self._batch_tokens(cond_mel, text_token_rows, max_mel_tokens, force_stop, seed, phase_events, lazy_spk=True,
-                                **generation_kwargs)
+                                adapter_ids=adapter_ids, **generation_kwargs)
         outs = self._batch_waveforms(st, phase_events, reuse_prefix=True)   # serial: the KV cache still holds this batch's prompt
         return (outs, st["rows"]) if return_codes else outs
 
@@ -655,6 +662,8 @@ class IndexTTS:
         gen, _ = self._gen_kwargs(generation_kwargs)
         if int(gen.get("num_beams", 1)) != 1:
             raise NotImplementedError("infer_queue: num_beams = 1 only (beam rows cannot be refilled one at a time)")
+        if self.gpt.engine.bank is not None:
+            raise NotImplementedError("infer_queue: slot refill with an adapter bank is not built (use infer_batch)")
         if not text_token_rows:
             return ([], []) if return_codes else []
         if int(slots) < 1:
@@ -738,10 +747,14 @@ class IndexTTS:
             phase_events[name] = e
 
     def _batch_tokens(self, cond_mel, text_token_rows, max_mel_tokens=600, force_stop=None, seed=1234, phase_events=None,
-                      lazy_spk=False, **generation_kwargs):
+                      lazy_spk=False, adapter_ids=None, **generation_kwargs):
         """Stage A of infer_batch: prompt conditioning -> prefill -> sampling loop -> silence squeeze (host).  Everything
         here is latency-bound small launches; it ends with the codes on the host, as infer.py:848-861 does."""
         gen, _ = self._gen_kwargs(generation_kwargs)
+        if adapter_ids is not None:     # checked before anything is launched
+            adapter_ids = self.gpt.engine._row_adapters(adapter_ids, len(text_token_rows))
+            if int(gen.get("num_beams", 1)) > 1:
+                raise NotImplementedError("beam search with an adapter bank is not built (num_beams = 1)")
         self._mark(phase_events, "start")
         conds, spk = self._prompt_features(cond_mel, spk=not lazy_spk)   # lazy_spk: stage B asks for the speaker embedding
         L = max(int(t.numel()) for t in text_token_rows)
@@ -765,7 +778,7 @@ class IndexTTS:
             self._mark(phase_events, "prefilled")
             codes = g.engine.decode_beam(max_mel_tokens, sp, nb)
         else:
-            g.engine.prefill(emb, pad, max_mel_tokens, shared_rows=shared)
+            g.engine.prefill(emb, pad, max_mel_tokens, shared_rows=shared, adapter_ids=adapter_ids)
             self._mark(phase_events, "prefilled")
             codes = g.engine.decode(max_mel_tokens, sp, force_stop=force_stop)
         self._mark(phase_events, "decoded")
@@ -776,7 +789,7 @@ class IndexTTS:
         # expanded the rows (beam_kv = "copy")
         crows = [b * nb for b in range(len(rows))] if nb > 1 and g.engine.beam_kv != "table" else None
         return dict(conds=conds, spk=spk, rows=rows, texts=[t.reshape(-1) for t in text_token_rows], cache_rows=crows,
-                    cond_mel=cond_mel)
+                    cond_mel=cond_mel, adapter_ids=adapter_ids)
 
     def _batch_waveforms(self, st, phase_events=None, reuse_prefix=False):
         """Stage B of infer_batch: batched teacher-forced latent pass + vocoder (large MFMA-bound launches, no host sync).
@@ -788,7 +801,8 @@ class IndexTTS:
             bf = self._batch_feat
             if bf is not None and bf[0] is st["cond_mel"] and bf[2] is conds:
                 bf[3] = spk
-        lat = self._latents(conds, st["texts"], st["rows"], reuse_prefix=reuse_prefix, cache_rows=st.get("cache_rows"))
+        lat = self._latents(conds, st["texts"], st["rows"], reuse_prefix=reuse_prefix, cache_rows=st.get("cache_rows"),
+                            adapter_ids=st.get("adapter_ids"))
         self._mark(phase_events, "latents")
         outs = self._vocode_ragged(lat, spk)
         self._mark(phase_events, "vocoded")
