@@ -89,7 +89,7 @@ def gelu_new(x):
     return 0.5 * x * (1.0 + torch.tanh(0.7978845608028654 * (x + 0.044715 * x ** 3)))
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("M,N,K", [(1, 1280, 1280), (7, 3840, 1280), (16, 1280, 5120), (32, 5120, 1280), (19, 8194, 1280),
                                    (32, 1280, 5120), (45, 64, 96)])
 def test_gemm_skinny_plain(nat, dtype, M, N, K):
@@ -117,7 +117,7 @@ def test_gemm_skinny_plain(nat, dtype, M, N, K):
     assert (hres - (h0 + x.float() @ w.float())).abs().max().item() < 2e-4 * max(1.0, ref.abs().max().item())
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("M,KSP", [(1, 4), (13, 3), (32, 3), (32, 4)])
 def test_ln_reduce_and_splitk_slabs(nat, dtype, M, KSP):
     """out-proj with split-K slabs, then residual-reduce + LayerNorm (+ second LayerNorm), as in one decode block."""
@@ -156,7 +156,7 @@ def test_ln_reduce_and_splitk_slabs(nat, dtype, M, KSP):
     assert (out.float() - ref2).abs().max().item() < (6e-5 if dtype == torch.float32 else 4e-2)
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
 def test_gemm_skinny_qkv_cache(nat, dtype):
     M, D, H, smax = 5, 1280, 20, 40
     x = rnd(M, D, seed=30).to(dtype)
@@ -372,7 +372,7 @@ def test_attn_decode_reads_the_shared_first_keys_from_row_zero(nat, dtype):
     assert torch.equal(o3[1:5], outs[0][1:5])
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("smax,pos", [(200, 150), (900, 777), (64, 0)])
 def test_attn_decode(nat, dtype, smax, pos):
     B, H = 5, 20
@@ -392,7 +392,7 @@ def test_attn_decode(nat, dtype, smax, pos):
     assert (out.float() - ref).abs().max().item() < tol
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("S", [47, 130])
 def test_attn_prefill(nat, dtype, S):
     B, H, smax = 3, 20, 160

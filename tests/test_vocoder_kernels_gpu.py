@@ -35,12 +35,12 @@ import pytest
 import torch
 
 import weights
+from fp64_check import check, excess, must_fail, ulp  # noqa: F401  (shared with test_decode_kernels_gpu.py)
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 F16, BF16 = torch.float16, torch.bfloat16
-PREC = {F16: (11, -14), BF16: (8, -126)}   # significand bits, smallest normal exponent
 PINNED = set()                            # forms the edge matrix below has pinned to fp64 (read by the coverage test)
 
 
@@ -63,38 +63,6 @@ def fir():
 def rnd(*shape, seed=0, scale=1.0):
     g = torch.Generator().manual_seed(seed)
     return (torch.randn(*shape, generator=g, dtype=torch.float64) * scale).to(DEV)
-
-
-def ulp(v, dtype):
-    """Spacing of the storage type's grid at |v| (subnormal spacing below the smallest normal), float64."""
-    p, emin = PREC[dtype]
-    _, e = torch.frexp(v)
-    e = torch.where(v == 0, torch.full_like(e, emin), torch.clamp(e - 1, min=emin))
-    return torch.ldexp(torch.ones_like(v), e - (p - 1))
-
-
-def excess(y, ref, bound, valid=None):
-    """(worst err / bound, message parts) over the elements selected by `valid` (bool, broadcastable) or all."""
-    err = (y.double() - ref).abs()
-    r = torch.where(torch.isfinite(err), err / bound, torch.full_like(err, math.inf))
-    if valid is not None:
-        r = torch.where(valid, r, torch.zeros_like(r))
-    i = int(torch.argmax(r))
-    idx = tuple(int(v) for v in np.unravel_index(i, tuple(r.shape)))
-    return r.flatten()[i].item(), (idx, y.double().flatten()[i].item(), ref.flatten()[i].item(),
-                                   err.flatten()[i].item(), bound.flatten()[i].item())
-
-
-def check(what, y, ref, bound, valid=None):
-    ratio, (idx, got, want, err, b) = excess(y, ref, bound, valid)
-    assert ratio <= 1.0, (f"{what}: worst element {idx}: got {got!r} want {want!r} err {err:.3e} > bound {b:.3e} "
-                          f"({ratio:.2f}x)")
-    return ratio
-
-
-def must_fail(what, control, y, ref, bound, valid=None):
-    ratio, (idx, _, _, err, b) = excess(y, ref, bound, valid)
-    assert ratio > 1.0, f"{what}: negative control '{control}' passed (worst {ratio:.2f}x of the bound at {idx}): the bound cannot discriminate"
 
 
 def form(nat, expect=None, pin=True):
