@@ -63,23 +63,13 @@ extern "C" int64_t itts_packed_bytes(int taps, int K, int N, int dtype) {
 
 extern "C" int itts_pack_weight(const void* w, void* packed, int taps, int K, int N, int dtype, void* stream) {
   ITTS_REQUIRE(w && packed && taps > 0 && K > 0 && N > 0, "itts_pack_weight: bad arguments");
-  int ks = dtype == ITTS_F32 ? 16 : 32;
-  int NT = (N + 15) / 16, KT = (K + ks - 1) / ks;
-  int64_t total = (int64_t)taps * NT * KT * 64;
-  dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case ITTS_F32:
-      hipLaunchKernelGGL(pack_weight_kernel<float>, grid, block, 0, s, (const float*)w, (float*)packed, taps, K, N, NT, KT);
-      break;
-    case ITTS_BF16:
-      hipLaunchKernelGGL(pack_weight_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)w, (bf16_t*)packed, taps, K, N, NT, KT);
-      break;
-    case ITTS_F16:
-      hipLaunchKernelGGL(pack_weight_kernel<f16_t>, grid, block, 0, s, (const f16_t*)w, (f16_t*)packed, taps, K, N, NT, KT);
-      break;
-    default:
-      ITTS_REQUIRE(false, "itts_pack_weight: unknown dtype %d", dtype);
-  }
-  return check_launch("itts_pack_weight");
+  return by_dtype(dtype, "itts_pack_weight", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    constexpr int ks = Elem<T>::KS;
+    int NT = (N + 15) / 16, KT = (K + ks - 1) / ks;
+    int64_t total = (int64_t)taps * NT * KT * 64;
+    dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    hipLaunchKernelGGL(pack_weight_kernel<T>, grid, block, 0, (hipStream_t)stream, (const T*)w, (T*)packed, taps, K, N, NT, KT);
+    return check_launch("itts_pack_weight");
+  });
 }

@@ -533,39 +533,24 @@ extern "C" int itts_attn_decode(const void* q, const void* kcache, const void* v
   const bool paged = kv_tab != nullptr;
   ITTS_REQUIRE(B > 0 && H > 0 && (paged || (smax > 0 && smax <= AD_MAXCTX)), "itts_attn_decode: bad shape B=%d H=%d smax=%d (max %d)", B, H,
                smax, AD_MAXCTX);
-  ITTS_REQUIRE(!paged || ((kv_bs == 16 || kv_bs == 32 || kv_bs == 64) && kv_rows == nullptr),
+  const int bs_log2 = kv_block_log2(paged, kv_bs);
+  ITTS_REQUIRE(bs_log2 >= 0 && (!paged || kv_rows == nullptr),
                "itts_attn_decode: a paged cache needs kv_bs in {16, 32, 64} and no beam row table");
-  const int bs_log2 = kv_bs == 64 ? 6 : kv_bs == 32 ? 5 : 4;
   ITTS_REQUIRE((kv_rows == nullptr) == (kv_step == nullptr), "itts_attn_decode: pass both or neither of kv_rows / kv_step");
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(H, B), block(g_attn_waves * 64);
   const bool ind = kv_rows != nullptr;
-#define ITTS_AD(TT_, NW_, IND_, PG_)                                                                                        \
-  hipLaunchKernelGGL((attn_decode_kernel<TT_, NW_, IND_, PG_>), grid, block, 0, s, (const TT_*)q, (const TT_*)kcache,      \
-                     (const TT_*)vcache, (TT_*)out, pad, pos, H, smax, out_mtp, kv_rows, kv_step, B, skip_rows, kv_share, \
-                     kv_tab, bs_log2 ITTS_AD_DIAG_ARGS)
-#define ITTS_AD_T(TT_)                                                            \
-  do {                                                                            \
-    if (paged) { if (g_attn_waves == 8) ITTS_AD(TT_, 8, false, true); else ITTS_AD(TT_, 4, false, true); } \
-    else if (g_attn_waves == 8) { if (ind) ITTS_AD(TT_, 8, true, false); else ITTS_AD(TT_, 8, false, false); } \
-    else { if (ind) ITTS_AD(TT_, 4, true, false); else ITTS_AD(TT_, 4, false, false); }          \
-  } while (0)
-  switch (dtype) {
-    case ITTS_F32:
-      ITTS_AD_T(float);
-      break;
-    case ITTS_BF16:
-      ITTS_AD_T(bf16_t);
-      break;
-    case ITTS_F16:
-      ITTS_AD_T(f16_t);
-      break;
-    default:
-      ITTS_REQUIRE(false, "itts_attn_decode: unknown dtype %d", dtype);
-  }
-#undef ITTS_AD_T
+  return by_dtype(dtype, "itts_attn_decode", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+#define ITTS_AD(NW_, IND_, PG_)                                                                                                   \
+  hipLaunchKernelGGL((attn_decode_kernel<T, NW_, IND_, PG_>), grid, block, 0, s, (const T*)q, (const T*)kcache, (const T*)vcache, \
+                     (T*)out, pad, pos, H, smax, out_mtp, kv_rows, kv_step, B, skip_rows, kv_share, kv_tab, bs_log2 ITTS_AD_DIAG_ARGS)
+    if (paged) { if (g_attn_waves == 8) ITTS_AD(8, false, true); else ITTS_AD(4, false, true); }
+    else if (g_attn_waves == 8) { if (ind) ITTS_AD(8, true, false); else ITTS_AD(8, false, false); }
+    else { if (ind) ITTS_AD(4, true, false); else ITTS_AD(4, false, false); }
 #undef ITTS_AD
-  return check_launch("itts_attn_decode");
+    return check_launch("itts_attn_decode");
+  });
 }
 
 static int attn_prefill_impl(const void* qkv, void* out, void* kcache, void* vcache, const int32_t* pad, int B, int S, int H,
@@ -575,31 +560,21 @@ static int attn_prefill_impl(const void* qkv, void* out, void* kcache, void* vca
                              void* wkc = nullptr, void* wvc = nullptr, const int32_t* w_row = nullptr,
                              const int32_t* w_pos0 = nullptr, const int32_t* kv_tab = nullptr, int kv_bs = 0) {
   ITTS_REQUIRE(qkv && out, "itts_attn_prefill: null pointer");
-  ITTS_REQUIRE(kv_tab == nullptr || kv_bs == 16 || kv_bs == 32 || kv_bs == 64, "itts_attn_prefill: kv_bs must be 16, 32 or 64");
-  const int bs_log2 = kv_bs == 64 ? 6 : kv_bs == 32 ? 5 : 4;
+  const int bs_log2 = kv_block_log2(kv_tab != nullptr, kv_bs);
+  ITTS_REQUIRE(bs_log2 >= 0, "itts_attn_prefill: kv_bs must be 16, 32 or 64");
   if (kv_tab != nullptr && kcache != nullptr) smax = S > smax ? S : smax;   // (no per-row capacity in the paged form)
   ITTS_REQUIRE((kcache == nullptr) == (vcache == nullptr), "itts_attn_prefill: pass both caches or neither");
   ITTS_REQUIRE(B > 0 && S > 0 && H > 0 && (!kcache || S <= smax), "itts_attn_prefill: bad shape B=%d S=%d H=%d smax=%d", B, S, H, smax);
   ITTS_REQUIRE(B <= 65535 && H <= 65535, "itts_attn_prefill: grid too large");
   dim3 grid((S + 63) / 64, H, B), block(256);
   hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case ITTS_F32:
-      hipLaunchKernelGGL(attn_prefill_kernel<float>, grid, block, 0, s, (const float*)qkv, (float*)out, (float*)kcache, (float*)vcache, pad, S, H, smax, row_off, cache_shift,
-                         (const float*)pkc, (const float*)pvc, pre_len, pre_row, pre_pos0, pre_qkv, (float*)wkc, (float*)wvc, w_row, w_pos0, kv_tab, bs_log2);
-      break;
-    case ITTS_BF16:
-      hipLaunchKernelGGL(attn_prefill_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)qkv, (bf16_t*)out, (bf16_t*)kcache, (bf16_t*)vcache, pad, S, H, smax, row_off, cache_shift,
-                         (const bf16_t*)pkc, (const bf16_t*)pvc, pre_len, pre_row, pre_pos0, pre_qkv, (bf16_t*)wkc, (bf16_t*)wvc, w_row, w_pos0, kv_tab, bs_log2);
-      break;
-    case ITTS_F16:
-      hipLaunchKernelGGL(attn_prefill_kernel<f16_t>, grid, block, 0, s, (const f16_t*)qkv, (f16_t*)out, (f16_t*)kcache, (f16_t*)vcache, pad, S, H, smax, row_off, cache_shift,
-                         (const f16_t*)pkc, (const f16_t*)pvc, pre_len, pre_row, pre_pos0, pre_qkv, (f16_t*)wkc, (f16_t*)wvc, w_row, w_pos0, kv_tab, bs_log2);
-      break;
-    default:
-      ITTS_REQUIRE(false, "itts_attn_prefill: unknown dtype %d", dtype);
-  }
-  return check_launch("itts_attn_prefill");
+  return by_dtype(dtype, "itts_attn_prefill", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(attn_prefill_kernel<T>, grid, block, 0, s, (const T*)qkv, (T*)out, (T*)kcache, (T*)vcache, pad, S, H, smax, row_off,
+                       cache_shift, (const T*)pkc, (const T*)pvc, pre_len, pre_row, pre_pos0, pre_qkv, (T*)wkc, (T*)wvc, w_row, w_pos0,
+                       kv_tab, bs_log2);
+    return check_launch("itts_attn_prefill");
+  });
 }
 
 extern "C" int itts_attn_prefill(const void* qkv, void* out, void* kcache, void* vcache, const int32_t* pad, int B, int S,
@@ -663,13 +638,16 @@ __global__ __launch_bounds__(256) void kv_share_rows_kernel(char* __restrict__ k
 extern "C" int itts_kv_share_rows(void* kcache, void* vcache, int layers, int64_t layer_stride, int B, int H, int C, int p0,
                                   const int32_t* pad, int smax, const int32_t* kv_tab, int kv_bs, int dtype, void* stream) {
   ITTS_REQUIRE(kcache && vcache && pad && layers > 0 && B >= 1 && H > 0 && C > 0 && p0 >= 0, "itts_kv_share_rows: bad arguments");
-  ITTS_REQUIRE(kv_tab != nullptr ? (kv_bs == 16 || kv_bs == 32 || kv_bs == 64) : smax >= p0 + C,
+  const int bs_log2 = kv_block_log2(kv_tab != nullptr, kv_bs);
+  ITTS_REQUIRE(bs_log2 >= 0 && (kv_tab != nullptr || smax >= p0 + C),
                "itts_kv_share_rows: paged cache: kv_bs must be 16, 32 or 64; contiguous cache: smax covers the block");
   ITTS_REQUIRE(layers <= 65535 && B <= 65536, "itts_kv_share_rows: too many layers / rows");
-  if (B == 1) return ITTS_OK;
-  const int es = dtype == ITTS_F32 ? 4 : 2;
-  const int total = H * C * 2 * (64 * es / 16);
-  hipLaunchKernelGGL(itts::kv_share_rows_kernel, dim3((total + 255) / 256, B - 1, layers), dim3(256), 0, (hipStream_t)stream, (char*)kcache,
-                     (char*)vcache, layer_stride * es, H, C, p0, pad, smax, kv_tab, kv_bs == 64 ? 6 : kv_bs == 32 ? 5 : 4, es, total);
-  return itts::check_launch("itts_kv_share_rows");
+  if (B == 1) return ITTS_OK;   // (nothing to copy: like the M == 0 returns elsewhere, in front of the dtype dispatch)
+  return by_dtype(dtype, "itts_kv_share_rows", [&](auto tag) {   // one kernel moves 16-byte chunks: only the element size matters
+    const int es = (int)sizeof(typename decltype(tag)::type);
+    const int total = H * C * 2 * (64 * es / 16);
+    hipLaunchKernelGGL(itts::kv_share_rows_kernel, dim3((total + 255) / 256, B - 1, layers), dim3(256), 0, (hipStream_t)stream,
+                       (char*)kcache, (char*)vcache, layer_stride * es, H, C, p0, pad, smax, kv_tab, bs_log2, es, total);
+    return check_launch("itts_kv_share_rows");
+  });
 }

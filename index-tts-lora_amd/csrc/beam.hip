@@ -573,21 +573,10 @@ extern "C" int itts_beam_reorder_kv(void* kcache, void* vcache, const int32_t* s
   dim3 grid(heads, B, layers * 2), block(256);
   ITTS_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "itts_beam_reorder_kv: grid too large");
   hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case ITTS_F32:
-      hipLaunchKernelGGL(beam_reorder_kv_kernel<float>, grid, block, 0, s, (float*)kcache, (float*)vcache, src, state, B, num_beams,
-                         heads, smax, layer_stride);
-      break;
-    case ITTS_BF16:
-      hipLaunchKernelGGL(beam_reorder_kv_kernel<bf16_t>, grid, block, 0, s, (bf16_t*)kcache, (bf16_t*)vcache, src, state, B,
-                         num_beams, heads, smax, layer_stride);
-      break;
-    case ITTS_F16:
-      hipLaunchKernelGGL(beam_reorder_kv_kernel<f16_t>, grid, block, 0, s, (f16_t*)kcache, (f16_t*)vcache, src, state, B, num_beams,
-                         heads, smax, layer_stride);
-      break;
-    default:
-      ITTS_REQUIRE(false, "itts_beam_reorder_kv: unknown dtype %d", dtype);
-  }
-  return check_launch("itts_beam_reorder_kv");
+  return by_dtype(dtype, "itts_beam_reorder_kv", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(beam_reorder_kv_kernel<T>, grid, block, 0, s, (T*)kcache, (T*)vcache, src, state, B, num_beams, heads, smax,
+                       layer_stride);
+    return check_launch("itts_beam_reorder_kv");
+  });
 }

@@ -207,6 +207,41 @@ template <typename T>
 constexpr const char* type_tag() {
   return sizeof(T) == 4 ? "f32" : Elem<T>::DT == ITTS_BF16 ? "bf16" : "f16";
 }
+
+// dtype dispatch, stated once:  by_dtype(dtype, "itts_name", [&](auto tag) { using T = typename decltype(tag)::type; ... })
+// runs the body (which returns an ITTS_* status) with the element type of `dtype`; any other value is an error that names
+// the entry point `who`.  Checks that come after the dtype check in an entry point go inside the body, so their order holds.
+template <typename T>
+struct TypeTag {
+  typedef T type;
+};
+template <typename F>
+int by_dtype(int dtype, const char* who, F&& body) {
+  switch (dtype) {
+    case ITTS_F32: return body(TypeTag<float>{});
+    case ITTS_BF16: return body(TypeTag<bf16_t>{});
+    case ITTS_F16: return body(TypeTag<f16_t>{});
+  }
+  set_error("%s: unknown dtype %d", who, dtype);
+  return ITTS_ERR_INVALID;
+}
+// the 16-bit-only sibling (the front-end kernels): no fp32 instantiation exists, fp32 is refused
+template <typename F>
+int by_dtype16(int dtype, const char* who, F&& body) {
+  switch (dtype) {
+    case ITTS_BF16: return body(TypeTag<bf16_t>{});
+    case ITTS_F16: return body(TypeTag<f16_t>{});
+    case ITTS_F32: set_error("%s: built for bf16 / f16", who); return ITTS_ERR_INVALID;
+  }
+  set_error("%s: unknown dtype %d", who, dtype);
+  return ITTS_ERR_INVALID;
+}
+
+// Paged KV pool: positions per block (16, 32 or 64) -> their log2, -1 for any other size.  A contiguous cache (paged ==
+// false) has no blocks: every kv_bs passes and the value goes unused.
+inline int kv_block_log2(bool paged, int kv_bs) {
+  return kv_bs == 64 ? 6 : kv_bs == 32 ? 5 : (kv_bs == 16 || !paged) ? 4 : -1;
+}
 }  // namespace itts
 
 #define ITTS_REQUIRE(cond, ...)        \

@@ -583,29 +583,22 @@ static int launch_ln_reduce(const itts_ln_reduce_args& a, hipStream_t s) {
   }
   dim3 grid(M), block(wide ? D / 4 : 64);
   const bool two = w2 != nullptr;
-#define ITTS_LNR(NS, L2)                                                                                                   \
+#define ITTS_LNR_L2(NS, L2)                                                                                                \
   do {                                                                                                                     \
     if (wide) hipLaunchKernelGGL((ln_reduce_wide_kernel<T, NS, L2>), grid, block, 0, s, h, slab, bias, w, b, w2, b2, y, M, D, bump, y_pa, sstride, lora_b, lora_r); \
     else hipLaunchKernelGGL((ln_reduce_kernel<T, NV, NS, L2>), grid, block, 0, s, h, slab, bias, w, b, w2, b2, y, M, D, bump);     \
   } while (0)
-  if (nslab == 0) {
-    if (two) ITTS_LNR(0, true); else ITTS_LNR(0, false);
-  } else if (nslab == 6) {
-    if (two) ITTS_LNR(6, true); else ITTS_LNR(6, false);
-  } else if (nslab == 5) {
-    if (two) ITTS_LNR(5, true); else ITTS_LNR(5, false);
-  } else if (nslab == 4) {
-    if (two) ITTS_LNR(4, true); else ITTS_LNR(4, false);
-  } else if (nslab == 3) {
-    if (two) ITTS_LNR(3, true); else ITTS_LNR(3, false);
-  } else if (nslab == 2) {
-    if (two) ITTS_LNR(2, true); else ITTS_LNR(2, false);
-  } else if (nslab == 1) {
-    if (two) ITTS_LNR(1, true); else ITTS_LNR(1, false);
-  } else {
-    set_error("itts_ln_reduce: nslab must be 0..6 (got %d)", nslab);
-    return ITTS_ERR_INVALID;
+#define ITTS_LNR(NS)                                                  \
+  case NS:                                                            \
+    if (two) ITTS_LNR_L2(NS, true); else ITTS_LNR_L2(NS, false);      \
+    break
+  switch (nslab) {
+    ITTS_LNR(0); ITTS_LNR(1); ITTS_LNR(2); ITTS_LNR(3); ITTS_LNR(4); ITTS_LNR(5); ITTS_LNR(6);
+    default:
+      set_error("itts_ln_reduce: nslab must be 0..6 (got %d)", nslab);
+      return ITTS_ERR_INVALID;
   }
+#undef ITTS_LNR_L2
 #undef ITTS_LNR
   return check_launch("itts_ln_reduce");
 }
@@ -683,6 +676,12 @@ static const char* aa_btc_name() {
   return kn.s;
 }
 
+template <typename T>
+static const char* aa_bct_name() {
+  static constexpr KernelName kn = kernel_name("aa_snake_bct", type_tag<T>(), {});
+  return kn.s;
+}
+
 static int aa_tiles_per_wg(int64_t tiles, int C) {
   int64_t t = tiles / (C > 96 ? 1536 : 3072);
   return (int)(t < 1 ? 1 : t > 8 ? 8 : t);
@@ -709,25 +708,10 @@ extern "C" int itts_aa_snake_fwd(const void* x, void* y, const float* alpha_log,
     const int tt = CS == 64 ? AaTile<64>::TT : CS == 48 ? AaTile<48>::TT : CS == 32 ? AaTile<32>::TT : AaTile<24>::TT;
     dim3 grid((T + tt - 1) / tt, C / CS, B), block(256);
     ITTS_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "itts_aa_snake_fwd: grid too large");
-#define ITTS_AA_LAUNCH(TT_, CS_) \
-  set_last_kernel(aa_btc_name<TT_, CS_>()); \
-  hipLaunchKernelGGL((aa_snake_btc_kernel<TT_, CS_>), grid, block, 0, s, (const TT_*)x, (TT_*)y, alpha_log, beta_log, f, T, C, valid_rows)
-#define ITTS_AA_BY_CS(TT_)                         \
-  switch (CS) {                                    \
-    case 64: ITTS_AA_LAUNCH(TT_, 64); break;       \
-    case 48: ITTS_AA_LAUNCH(TT_, 48); break;       \
-    case 32: ITTS_AA_LAUNCH(TT_, 32); break;       \
-    default: ITTS_AA_LAUNCH(TT_, 24); break;       \
-  }
-    switch (dtype) {
-      case ITTS_F32:
-        ITTS_AA_BY_CS(float);
-        break;
-      case ITTS_BF16:
-        ITTS_AA_BY_CS(bf16_t);
-        break;
-      case ITTS_F16:
-        if (ITTS_AA_F16_MFMA && C <= ITTS_AA_MFMA_MAXC && (int64_t)B * T >= 32768) {
+    return by_dtype(dtype, "itts_aa_snake_fwd", [&](auto tag) {
+      using TT = typename decltype(tag)::type;
+      if constexpr (ITTS_AA_F16_MFMA && Elem<TT>::DT == ITTS_F16) {
+        if (C <= ITTS_AA_MFMA_MAXC && (int64_t)B * T >= 32768) {
           // Both FIRs on the matrix cores: 48-channel slices where the channel count allows, one 32-channel slice for C = 24.
           // Measured (batch 32, MI355X, us per launch, MFMA form | VALU form): C = 96: 163 | 207, C = 48: 151 | 193, C = 24: 166 |
           // 191; C = 192: 97 | 96 (85 with twice the tiles per workgroup: round 4), C = 384: 56 | 46, C = 768: 37 | 27 (few rows per batch
@@ -764,36 +748,31 @@ extern "C" int itts_aa_snake_fwd(const void* x, void* y, const float* alpha_log,
             set_last_kernel("aa_snake_mfma<2>");
             hipLaunchKernelGGL(aa_snake_mfma_kernel<2>, g2, block, AaMfma<2>::LDS, s, (const f16_t*)x, (f16_t*)y, alpha_log, beta_log, f, T, C, valid_rows, tpw);
           }
-          break;
+          return check_launch("itts_aa_snake_fwd");
         }
-        ITTS_AA_BY_CS(f16_t);
-        break;
-      default:
-        ITTS_REQUIRE(false, "itts_aa_snake_fwd: unknown dtype %d", dtype);
-    }
-#undef ITTS_AA_BY_CS
+      }
+#define ITTS_AA_LAUNCH(CS_)                \
+  set_last_kernel(aa_btc_name<TT, CS_>()); \
+  hipLaunchKernelGGL((aa_snake_btc_kernel<TT, CS_>), grid, block, 0, s, (const TT*)x, (TT*)y, alpha_log, beta_log, f, T, C, valid_rows)
+      switch (CS) {
+        case 64: ITTS_AA_LAUNCH(64); break;
+        case 48: ITTS_AA_LAUNCH(48); break;
+        case 32: ITTS_AA_LAUNCH(32); break;
+        default: ITTS_AA_LAUNCH(24); break;
+      }
 #undef ITTS_AA_LAUNCH
+      return check_launch("itts_aa_snake_fwd");
+    });
   } else {
     ITTS_REQUIRE((int64_t)B * C <= 65535, "itts_aa_snake_fwd: B*C too large for layout 1");
     dim3 grid((T + 255) / 256, B * C), block(256);
-    switch (dtype) {
-      case ITTS_F32:
-        set_last_kernel("aa_snake_bct<f32>");
-        hipLaunchKernelGGL(aa_snake_bct_kernel<float>, grid, block, 0, s, (const float*)x, (float*)y, alpha_log, beta_log, f, T, C);
-        break;
-      case ITTS_BF16:
-        set_last_kernel("aa_snake_bct<bf16>");
-        hipLaunchKernelGGL(aa_snake_bct_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)x, (bf16_t*)y, alpha_log, beta_log, f, T, C);
-        break;
-      case ITTS_F16:
-        set_last_kernel("aa_snake_bct<f16>");
-        hipLaunchKernelGGL(aa_snake_bct_kernel<f16_t>, grid, block, 0, s, (const f16_t*)x, (f16_t*)y, alpha_log, beta_log, f, T, C);
-        break;
-      default:
-        ITTS_REQUIRE(false, "itts_aa_snake_fwd: unknown dtype %d", dtype);
-    }
+    return by_dtype(dtype, "itts_aa_snake_fwd", [&](auto tag) {
+      using TT = typename decltype(tag)::type;
+      set_last_kernel(aa_bct_name<TT>());
+      hipLaunchKernelGGL(aa_snake_bct_kernel<TT>, grid, block, 0, s, (const TT*)x, (TT*)y, alpha_log, beta_log, f, T, C);
+      return check_launch("itts_aa_snake_fwd");
+    });
   }
-  return check_launch("itts_aa_snake_fwd");
 }
 
 extern "C" int itts_layernorm(const float* h, const float* w, const float* b, const float* w2, const float* b2, void* y,
@@ -803,20 +782,11 @@ extern "C" int itts_layernorm(const float* h, const float* w, const float* b, co
   if (M == 0) return ITTS_OK;
   dim3 grid((M + 3) / 4), block(256);
   hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case ITTS_F32:
-      hipLaunchKernelGGL(layernorm_kernel<float>, grid, block, 0, s, h, w, b, w2, b2, y, y_f32, M, D);
-      break;
-    case ITTS_BF16:
-      hipLaunchKernelGGL(layernorm_kernel<bf16_t>, grid, block, 0, s, h, w, b, w2, b2, y, y_f32, M, D);
-      break;
-    case ITTS_F16:
-      hipLaunchKernelGGL(layernorm_kernel<f16_t>, grid, block, 0, s, h, w, b, w2, b2, y, y_f32, M, D);
-      break;
-    default:
-      ITTS_REQUIRE(false, "itts_layernorm: unknown dtype %d", dtype);
-  }
-  return check_launch("itts_layernorm");
+  return by_dtype(dtype, "itts_layernorm", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(layernorm_kernel<T>, grid, block, 0, s, h, w, b, w2, b2, y, y_f32, M, D);
+    return check_launch("itts_layernorm");
+  });
 }
 
 extern "C" int itts_ln_reduce(const itts_ln_reduce_args* a, void* stream) {
@@ -833,15 +803,10 @@ extern "C" int itts_ln_reduce(const itts_ln_reduce_args* a, void* stream) {
                  "itts_ln_reduce: LoRA needs 1 <= r <= 64, slabs, and slab_stride >= D + r");
   if (a->M == 0) return ITTS_OK;
   hipStream_t s = (hipStream_t)stream;
-  switch (a->dtype) {
-    case ITTS_F32:
-      return launch_ln_reduce<float, 5>(*a, s);
-    case ITTS_BF16:
-      return launch_ln_reduce<bf16_t, 5>(*a, s);
-    case ITTS_F16:
-      return launch_ln_reduce<f16_t, 5>(*a, s);
-  }
-  ITTS_REQUIRE(false, "itts_ln_reduce: unknown dtype %d", a->dtype);
+  return by_dtype(a->dtype, "itts_ln_reduce", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch_ln_reduce<T, 5>(*a, s);
+  });
 }
 
 extern "C" int itts_embed_step(const int32_t* tokens, const float* table, const float* pos_table, const int32_t* step,
@@ -852,23 +817,12 @@ extern "C" int itts_embed_step(const int32_t* tokens, const float* table, const 
   if (h_packed != nullptr) ITTS_REQUIRE(D % (dtype == ITTS_F32 ? 16 : 32) == 0, "itts_embed_step: a packed copy needs D %% k-step == 0");
   hipStream_t s = (hipStream_t)stream;
   const int mtp = (B + 15) / 16;
-  switch (dtype) {
-    case ITTS_F32:
-      hipLaunchKernelGGL(embed_step_kernel<float>, dim3(B), dim3(256), 0, s, tokens, table, pos_table, step, pos_add, h, D, bump,
-                         row_step0, pos_rows, (float*)h_packed, mtp);
-      break;
-    case ITTS_BF16:
-      hipLaunchKernelGGL(embed_step_kernel<bf16_t>, dim3(B), dim3(256), 0, s, tokens, table, pos_table, step, pos_add, h, D, bump,
-                         row_step0, pos_rows, (bf16_t*)h_packed, mtp);
-      break;
-    case ITTS_F16:
-      hipLaunchKernelGGL(embed_step_kernel<f16_t>, dim3(B), dim3(256), 0, s, tokens, table, pos_table, step, pos_add, h, D, bump,
-                         row_step0, pos_rows, (f16_t*)h_packed, mtp);
-      break;
-    default:
-      ITTS_REQUIRE(false, "itts_embed_step: unknown dtype %d", dtype);
-  }
-  return check_launch("itts_embed_step");
+  return by_dtype(dtype, "itts_embed_step", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(embed_step_kernel<T>, dim3(B), dim3(256), 0, s, tokens, table, pos_table, step, pos_add, h, D, bump, row_step0,
+                       pos_rows, (T*)h_packed, mtp);
+    return check_launch("itts_embed_step");
+  });
 }
 
 extern "C" int itts_tanh_pcm(const void* x, float* wav, int16_t* pcm, int64_t n, int dtype, int apply_tanh, void* stream) {
@@ -878,19 +832,10 @@ extern "C" int itts_tanh_pcm(const void* x, float* wav, int16_t* pcm, int64_t n,
   if (blocks > 4096) blocks = 4096;
   dim3 grid((unsigned)blocks), block(256);
   hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case ITTS_F32:
-      hipLaunchKernelGGL(tanh_pcm_kernel<float>, grid, block, 0, s, (const float*)x, wav, pcm, n, apply_tanh);
-      break;
-    case ITTS_BF16:
-      hipLaunchKernelGGL(tanh_pcm_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)x, wav, pcm, n, apply_tanh);
-      break;
-    case ITTS_F16:
-      hipLaunchKernelGGL(tanh_pcm_kernel<f16_t>, grid, block, 0, s, (const f16_t*)x, wav, pcm, n, apply_tanh);
-      break;
-    default:
-      ITTS_REQUIRE(false, "itts_tanh_pcm: unknown dtype %d", dtype);
-  }
-  return check_launch("itts_tanh_pcm");
+  return by_dtype(dtype, "itts_tanh_pcm", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(tanh_pcm_kernel<T>, grid, block, 0, s, (const T*)x, wav, pcm, n, apply_tanh);
+    return check_launch("itts_tanh_pcm");
+  });
 }
 

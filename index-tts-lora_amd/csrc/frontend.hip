@@ -787,77 +787,65 @@ using namespace itts;
 extern "C" int itts_subsample_conv(const float* mel, const float* w, const float* b, void* y, int T, int F, int C, int dtype,
                                    void* stream) {
   ITTS_REQUIRE(mel && w && b && y && T >= 3 && F >= 3 && C > 0, "itts_subsample_conv: bad arguments");
-  ITTS_REQUIRE(dtype == ITTS_BF16 || dtype == ITTS_F16, "itts_subsample_conv: the front-end kernels are built for bf16 / f16");
-  const int T2 = (T - 3) / 2 + 1, F2 = (F - 3) / 2 + 1;
-  hipStream_t s = (hipStream_t)stream;
-  // staged form: every wave's run of cpw channels x F2 outputs is a whole number of 16-byte vectors and the row fits 64 KiB of LDS
-  const int cpw = (C + 7) / 8;
-  const bool staged = C % 8 == 0 && (cpw * F2) % 8 == 0 && (size_t)C * F2 * 2 <= 64 * 1024;
-  const size_t lds = staged ? (size_t)C * F2 * 2 : 0;
-  if (dtype == ITTS_BF16) {
-    if (staged) hipLaunchKernelGGL((subsample_conv_kernel<bf16_t, true>), dim3(T2), dim3(512), lds, s, mel, w, b, (bf16_t*)y, F, C, F2);
-    else hipLaunchKernelGGL((subsample_conv_kernel<bf16_t, false>), dim3(T2), dim3(512), 0, s, mel, w, b, (bf16_t*)y, F, C, F2);
-  } else {
-    if (staged) hipLaunchKernelGGL((subsample_conv_kernel<f16_t, true>), dim3(T2), dim3(512), lds, s, mel, w, b, (f16_t*)y, F, C, F2);
-    else hipLaunchKernelGGL((subsample_conv_kernel<f16_t, false>), dim3(T2), dim3(512), 0, s, mel, w, b, (f16_t*)y, F, C, F2);
-  }
-  return check_launch("itts_subsample_conv");
+  return by_dtype16(dtype, "itts_subsample_conv", [&](auto tag) {
+    using TT = typename decltype(tag)::type;
+    const int T2 = (T - 3) / 2 + 1, F2 = (F - 3) / 2 + 1;
+    hipStream_t s = (hipStream_t)stream;
+    // staged form: every wave's run of cpw channels x F2 outputs is a whole number of 16-byte vectors and the row fits 64 KiB of LDS
+    const int cpw = (C + 7) / 8;
+    const bool staged = C % 8 == 0 && (cpw * F2) % 8 == 0 && (size_t)C * F2 * 2 <= 64 * 1024;
+    const size_t lds = staged ? (size_t)C * F2 * 2 : 0;
+    if (staged) hipLaunchKernelGGL((subsample_conv_kernel<TT, true>), dim3(T2), dim3(512), lds, s, mel, w, b, (TT*)y, F, C, F2);
+    else hipLaunchKernelGGL((subsample_conv_kernel<TT, false>), dim3(T2), dim3(512), 0, s, mel, w, b, (TT*)y, F, C, F2);
+    return check_launch("itts_subsample_conv");
+  });
 }
 
 extern "C" int itts_mha_small(const itts_mha_args* a, void* stream) {
   ITTS_REQUIRE(a && a->q && a->k && a->v && a->out, "itts_mha_small: null args");
-  ITTS_REQUIRE(a->dtype == ITTS_BF16 || a->dtype == ITTS_F16, "itts_mha_small: built for bf16 / f16");
-  ITTS_REQUIRE(a->Tq > 0 && a->Tk > 0 && a->H > 0 && a->H <= 65535, "itts_mha_small: bad shape Tq=%d Tk=%d H=%d", a->Tq, a->Tk, a->H);
-  ITTS_REQUIRE(a->q_stride % 8 == 0 && a->k_stride % 8 == 0 && a->v_stride % 8 == 0 && a->q_stride >= a->H * 64 &&
-                   a->k_stride >= a->H * 64 && a->v_stride >= a->H * 64,
-               "itts_mha_small: row strides must be multiples of 8 elements and cover H * 64");
-  ITTS_REQUIRE(a->out_mtp * 16 >= a->Tq, "itts_mha_small: out_mtp = %d row tiles do not cover Tq = %d", a->out_mtp, a->Tq);
-  const bool rel = a->pos != nullptr;
-  if (rel) ITTS_REQUIRE(a->bias_u && a->bias_v, "itts_mha_small: the relative-position form needs bias_u and bias_v");
-  MhaParams p;
-  p.Tq = a->Tq; p.Tk = a->Tk; p.H = a->H;
-  p.q = a->q; p.k = a->k; p.v = a->v;
-  p.qs = a->q_stride; p.ks = a->k_stride; p.vs = a->v_stride;
-  p.pos = a->pos; p.bu = a->bias_u; p.bv = a->bias_v;
-  p.scale = a->scale;
-  p.out = a->out; p.out_mtp = a->out_mtp;
-  const dim3 grid((a->Tq + 15) / 16, a->H), block(256);
-  hipStream_t s = (hipStream_t)stream;
-#define ITTS_MHA(T_, R_) hipLaunchKernelGGL((mha_small_kernel<T_, R_>), grid, block, 0, s, p)
-  if (a->dtype == ITTS_BF16) {
-    if (rel) ITTS_MHA(bf16_t, true);
-    else ITTS_MHA(bf16_t, false);
-  } else {
-    if (rel) ITTS_MHA(f16_t, true);
-    else ITTS_MHA(f16_t, false);
-  }
-#undef ITTS_MHA
-  return check_launch("itts_mha_small");
+  return by_dtype16(a->dtype, "itts_mha_small", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    ITTS_REQUIRE(a->Tq > 0 && a->Tk > 0 && a->H > 0 && a->H <= 65535, "itts_mha_small: bad shape Tq=%d Tk=%d H=%d", a->Tq, a->Tk, a->H);
+    ITTS_REQUIRE(a->q_stride % 8 == 0 && a->k_stride % 8 == 0 && a->v_stride % 8 == 0 && a->q_stride >= a->H * 64 &&
+                     a->k_stride >= a->H * 64 && a->v_stride >= a->H * 64,
+                 "itts_mha_small: row strides must be multiples of 8 elements and cover H * 64");
+    ITTS_REQUIRE(a->out_mtp * 16 >= a->Tq, "itts_mha_small: out_mtp = %d row tiles do not cover Tq = %d", a->out_mtp, a->Tq);
+    const bool rel = a->pos != nullptr;
+    if (rel) ITTS_REQUIRE(a->bias_u && a->bias_v, "itts_mha_small: the relative-position form needs bias_u and bias_v");
+    MhaParams p;
+    p.Tq = a->Tq; p.Tk = a->Tk; p.H = a->H;
+    p.q = a->q; p.k = a->k; p.v = a->v;
+    p.qs = a->q_stride; p.ks = a->k_stride; p.vs = a->v_stride;
+    p.pos = a->pos; p.bu = a->bias_u; p.bv = a->bias_v;
+    p.scale = a->scale;
+    p.out = a->out; p.out_mtp = a->out_mtp;
+    const dim3 grid((a->Tq + 15) / 16, a->H), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    if (rel) hipLaunchKernelGGL((mha_small_kernel<T, true>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((mha_small_kernel<T, false>), grid, block, 0, s, p);
+    return check_launch("itts_mha_small");
+  });
 }
 
 extern "C" int itts_glu_dwconv_ln_silu(const void* x, const float* w, const float* b, const float* ln_w, const float* ln_b, void* y,
                                        int T, int C, int taps, int y_mtp, float eps, int dtype, void* stream) {
   ITTS_REQUIRE(x && w && b && ln_w && ln_b && y && T > 0, "itts_glu_dwconv_ln_silu: bad arguments");
-  ITTS_REQUIRE(dtype == ITTS_BF16 || dtype == ITTS_F16, "itts_glu_dwconv_ln_silu: built for bf16 / f16");
-  ITTS_REQUIRE(C % 128 == 0 && C <= 2048, "itts_glu_dwconv_ln_silu: C = %d must be a multiple of 128, at most 2048", C);
-  ITTS_REQUIRE(taps == 15 || taps == 7 || taps == 31, "itts_glu_dwconv_ln_silu: taps = %d (7, 15 and 31 are built)", taps);
-  ITTS_REQUIRE(y_mtp * 16 >= T, "itts_glu_dwconv_ln_silu: y_mtp = %d row tiles do not cover T = %d", y_mtp, T);
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(T), block(C / 2);
-  if (eps <= 0.f) eps = 1e-5f;
-#define ITTS_DW(T_, K_)                                                                                                      \
-  hipLaunchKernelGGL((glu_dwconv_ln_silu_kernel<T_, K_>), grid, block, 0, s, (const T_*)x, w, b, ln_w, ln_b, (T_*)y, T, C, y_mtp, eps)
-  if (dtype == ITTS_BF16) {
-    if (taps == 15) ITTS_DW(bf16_t, 15);
-    else if (taps == 7) ITTS_DW(bf16_t, 7);
-    else ITTS_DW(bf16_t, 31);
-  } else {
-    if (taps == 15) ITTS_DW(f16_t, 15);
-    else if (taps == 7) ITTS_DW(f16_t, 7);
-    else ITTS_DW(f16_t, 31);
-  }
+  return by_dtype16(dtype, "itts_glu_dwconv_ln_silu", [&](auto tag) {
+    using TT = typename decltype(tag)::type;
+    ITTS_REQUIRE(C % 128 == 0 && C <= 2048, "itts_glu_dwconv_ln_silu: C = %d must be a multiple of 128, at most 2048", C);
+    ITTS_REQUIRE(taps == 15 || taps == 7 || taps == 31, "itts_glu_dwconv_ln_silu: taps = %d (7, 15 and 31 are built)", taps);
+    ITTS_REQUIRE(y_mtp * 16 >= T, "itts_glu_dwconv_ln_silu: y_mtp = %d row tiles do not cover T = %d", y_mtp, T);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(T), block(C / 2);
+    if (eps <= 0.f) eps = 1e-5f;
+#define ITTS_DW(K_) \
+  hipLaunchKernelGGL((glu_dwconv_ln_silu_kernel<TT, K_>), grid, block, 0, s, (const TT*)x, w, b, ln_w, ln_b, (TT*)y, T, C, y_mtp, eps)
+    if (taps == 15) ITTS_DW(15);
+    else if (taps == 7) ITTS_DW(7);
+    else ITTS_DW(31);
 #undef ITTS_DW
-  return check_launch("itts_glu_dwconv_ln_silu");
+    return check_launch("itts_glu_dwconv_ln_silu");
+  });
 }
 
 extern "C" int itts_rows(const itts_rows_args* a, void* stream) {
@@ -878,22 +866,27 @@ extern "C" int itts_rows(const itts_rows_args* a, void* stream) {
   p.norm = a->norm; p.w = a->w; p.b = a->b; p.eps = a->eps > 0.f ? a->eps : 1e-5f;
   p.y = a->y; p.yp = a->y_packed; p.y_row0 = a->y_row0; p.y_mtp = mtp;
   hipStream_t s = (hipStream_t)stream;
-  if (a->dtype == ITTS_BF16) hipLaunchKernelGGL(rows_kernel<bf16_t>, dim3(a->M), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(rows_kernel<f16_t>, dim3(a->M), dim3(256), 0, s, p);
-  return check_launch("itts_rows");
+  if (a->y_packed == nullptr) {   // only the packed copy is of type T: without one dtype is not read, and either instantiation stores no T
+    hipLaunchKernelGGL(rows_kernel<f16_t>, dim3(a->M), dim3(256), 0, s, p);
+    return check_launch("itts_rows");
+  }
+  return by_dtype16(a->dtype, "itts_rows", [&](auto tag) {
+    hipLaunchKernelGGL(rows_kernel<typename decltype(tag)::type>, dim3(a->M), dim3(256), 0, s, p);
+    return check_launch("itts_rows");
+  });
 }
 
 extern "C" int itts_geglu(const void* h, void* y, int M, int Kp, int y_mtp, int dtype, void* stream) {
   ITTS_REQUIRE(h && y && M > 0 && Kp > 0 && Kp % 32 == 0, "itts_geglu: bad arguments (Kp %% 32 == 0)");
-  ITTS_REQUIRE(dtype == ITTS_BF16 || dtype == ITTS_F16, "itts_geglu: built for bf16 / f16");
-  const int mtp = y_mtp > 0 ? y_mtp : (M + 15) / 16;
-  ITTS_REQUIRE(mtp * 16 >= M, "itts_geglu: y_mtp does not cover M");
-  const int64_t n = (int64_t)M * (Kp / 4);
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  if (dtype == ITTS_BF16) hipLaunchKernelGGL(geglu_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)h, (bf16_t*)y, M, Kp, mtp);
-  else hipLaunchKernelGGL(geglu_kernel<f16_t>, grid, block, 0, s, (const f16_t*)h, (f16_t*)y, M, Kp, mtp);
-  return check_launch("itts_geglu");
+  return by_dtype16(dtype, "itts_geglu", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    const int mtp = y_mtp > 0 ? y_mtp : (M + 15) / 16;
+    ITTS_REQUIRE(mtp * 16 >= M, "itts_geglu: y_mtp does not cover M");
+    const int64_t n = (int64_t)M * (Kp / 4);
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    hipLaunchKernelGGL(geglu_kernel<T>, grid, block, 0, (hipStream_t)stream, (const T*)h, (T*)y, M, Kp, mtp);
+    return check_launch("itts_geglu");
+  });
 }
 
 extern "C" int itts_prefix_rows(const int64_t* text, const float* conds, int conds_rows, const float* text_emb, const float* text_pos,
@@ -909,67 +902,62 @@ extern "C" int itts_prefix_rows(const int64_t* text, const float* conds, int con
   return check_launch("itts_prefix_rows");
 }
 
-#define ITTS_FE_DTYPE(who) ITTS_REQUIRE(dtype == ITTS_BF16 || dtype == ITTS_F16, who ": built for bf16 / f16")
-
 extern "C" int itts_im2col_reflect(const float* x, void* y, int T, int F, int taps, int dil, int Kp, int y_mtp, int dtype, void* stream) {
   ITTS_REQUIRE(x && y && T > 0 && F > 0 && taps > 0 && taps % 2 == 1 && dil > 0, "itts_im2col_reflect: bad arguments");
-  ITTS_FE_DTYPE("itts_im2col_reflect");
-  ITTS_REQUIRE(Kp % 32 == 0 && Kp >= taps * F && y_mtp * 16 >= T, "itts_im2col_reflect: Kp %% 32 == 0, Kp >= taps * F, y_mtp covers T");
-  ITTS_REQUIRE((taps - 1) / 2 * dil < T, "itts_im2col_reflect: the reflect padding needs more than %d frames", (taps - 1) / 2 * dil);
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == ITTS_BF16) hipLaunchKernelGGL(im2col_reflect_kernel<bf16_t>, dim3(T), dim3(256), 0, s, x, (bf16_t*)y, T, F, taps, dil, Kp, y_mtp);
-  else hipLaunchKernelGGL(im2col_reflect_kernel<f16_t>, dim3(T), dim3(256), 0, s, x, (f16_t*)y, T, F, taps, dil, Kp, y_mtp);
-  return check_launch("itts_im2col_reflect");
+  return by_dtype16(dtype, "itts_im2col_reflect", [&](auto tag) {
+    using TT = typename decltype(tag)::type;
+    ITTS_REQUIRE(Kp % 32 == 0 && Kp >= taps * F && y_mtp * 16 >= T, "itts_im2col_reflect: Kp %% 32 == 0, Kp >= taps * F, y_mtp covers T");
+    ITTS_REQUIRE((taps - 1) / 2 * dil < T, "itts_im2col_reflect: the reflect padding needs more than %d frames", (taps - 1) / 2 * dil);
+    hipLaunchKernelGGL(im2col_reflect_kernel<TT>, dim3(T), dim3(256), 0, (hipStream_t)stream, x, (TT*)y, T, F, taps, dil, Kp, y_mtp);
+    return check_launch("itts_im2col_reflect");
+  });
 }
 
 extern "C" int itts_res2_step(const void* y1, void* cat, const void* wp, const float* bias, const float* scale, const float* shift, int T,
                               int mtp, int chunk, int dil, int first, int dtype, void* stream) {
   ITTS_REQUIRE(y1 && cat && wp && bias && scale && shift && T > 0 && chunk >= 1 && dil > 0, "itts_res2_step: bad arguments");
-  ITTS_FE_DTYPE("itts_res2_step");
-  ITTS_REQUIRE(mtp * 16 >= T && dil < T, "itts_res2_step: mtp covers T, dilation < T");
-  Res2Params p;
-  p.y1 = y1; p.cat = cat; p.wp = wp; p.bias = bias; p.scale = scale; p.shift = shift;
-  p.T = T; p.mtp = mtp; p.s = chunk; p.dil = dil; p.first = first != 0;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == ITTS_BF16) hipLaunchKernelGGL(res2_step_kernel<bf16_t>, dim3((T + 15) / 16), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(res2_step_kernel<f16_t>, dim3((T + 15) / 16), dim3(256), 0, s, p);
-  return check_launch("itts_res2_step");
+  return by_dtype16(dtype, "itts_res2_step", [&](auto tag) {
+    ITTS_REQUIRE(mtp * 16 >= T && dil < T, "itts_res2_step: mtp covers T, dilation < T");
+    Res2Params p;
+    p.y1 = y1; p.cat = cat; p.wp = wp; p.bias = bias; p.scale = scale; p.shift = shift;
+    p.T = T; p.mtp = mtp; p.s = chunk; p.dil = dil; p.first = first != 0;
+    hipLaunchKernelGGL(res2_step_kernel<typename decltype(tag)::type>, dim3((T + 15) / 16), dim3(256), 0, (hipStream_t)stream, p);
+    return check_launch("itts_res2_step");
+  });
 }
 
 extern "C" int itts_se_gate(const void* y, const void* w1, const float* b1, const void* w2, const float* b2, float* gate, int T, int C,
                             int H, int mtp, int dtype, void* stream) {
   ITTS_REQUIRE(y && w1 && b1 && w2 && b2 && gate && T > 0, "itts_se_gate: bad arguments");
-  ITTS_FE_DTYPE("itts_se_gate");
-  ITTS_REQUIRE(C % 64 == 0 && C <= 1024 && H % 16 == 0 && H <= 512 && mtp * 16 >= T, "itts_se_gate: C %% 64, C <= 1024, H %% 16, H <= 512");
-  const size_t lds = (size_t)(C + H) * 4;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == ITTS_BF16)
-    hipLaunchKernelGGL(se_gate_kernel<bf16_t>, dim3(1), dim3(1024), lds, s, (const bf16_t*)y, (const bf16_t*)w1, b1, (const bf16_t*)w2, b2, gate, T, C, H, mtp);
-  else
-    hipLaunchKernelGGL(se_gate_kernel<f16_t>, dim3(1), dim3(1024), lds, s, (const f16_t*)y, (const f16_t*)w1, b1, (const f16_t*)w2, b2, gate, T, C, H, mtp);
-  return check_launch("itts_se_gate");
+  return by_dtype16(dtype, "itts_se_gate", [&](auto tag) {
+    using TT = typename decltype(tag)::type;
+    ITTS_REQUIRE(C % 64 == 0 && C <= 1024 && H % 16 == 0 && H <= 512 && mtp * 16 >= T, "itts_se_gate: C %% 64, C <= 1024, H %% 16, H <= 512");
+    const size_t lds = (size_t)(C + H) * 4;
+    hipLaunchKernelGGL(se_gate_kernel<TT>, dim3(1), dim3(1024), lds, (hipStream_t)stream, (const TT*)y, (const TT*)w1, b1, (const TT*)w2, b2,
+                       gate, T, C, H, mtp);
+    return check_launch("itts_se_gate");
+  });
 }
 
 extern "C" int itts_scale_resid(const void* y, const void* res, const float* gate, void* out, int T, int C, int mtp, int dtype, void* stream) {
   ITTS_REQUIRE(y && res && gate && out && T > 0 && C % 32 == 0 && mtp * 16 >= T, "itts_scale_resid: bad arguments");
-  ITTS_FE_DTYPE("itts_scale_resid");
-  const int nchunks = C / 32 * mtp * 64;
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((nchunks + 255) / 256), block(256);
-  if (dtype == ITTS_BF16) hipLaunchKernelGGL(scale_resid_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)y, (const bf16_t*)res, gate, (bf16_t*)out, nchunks, mtp);
-  else hipLaunchKernelGGL(scale_resid_kernel<f16_t>, grid, block, 0, s, (const f16_t*)y, (const f16_t*)res, gate, (f16_t*)out, nchunks, mtp);
-  return check_launch("itts_scale_resid");
+  return by_dtype16(dtype, "itts_scale_resid", [&](auto tag) {
+    using TT = typename decltype(tag)::type;
+    const int nchunks = C / 32 * mtp * 64;
+    const dim3 grid((nchunks + 255) / 256), block(256);
+    hipLaunchKernelGGL(scale_resid_kernel<TT>, grid, block, 0, (hipStream_t)stream, (const TT*)y, (const TT*)res, gate, (TT*)out, nchunks, mtp);
+    return check_launch("itts_scale_resid");
+  });
 }
 
 extern "C" int itts_col_stats(const void* x, const void* logit, const float* scale, const float* shift, void* out, int T, int C, int mtp,
                               int dtype, void* stream) {
   ITTS_REQUIRE(x && out && T > 0 && C % 64 == 0 && mtp * 16 >= T, "itts_col_stats: bad arguments (C %% 64 == 0)");
   ITTS_REQUIRE((scale == nullptr) == (shift == nullptr), "itts_col_stats: scale and shift come together");
-  ITTS_FE_DTYPE("itts_col_stats");
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == ITTS_BF16)
-    hipLaunchKernelGGL(col_stats_kernel<bf16_t>, dim3(C / 64), dim3(1024), 0, s, (const bf16_t*)x, (const bf16_t*)logit, scale, shift, (bf16_t*)out, T, C, mtp);
-  else
-    hipLaunchKernelGGL(col_stats_kernel<f16_t>, dim3(C / 64), dim3(1024), 0, s, (const f16_t*)x, (const f16_t*)logit, scale, shift, (f16_t*)out, T, C, mtp);
-  return check_launch("itts_col_stats");
+  return by_dtype16(dtype, "itts_col_stats", [&](auto tag) {
+    using TT = typename decltype(tag)::type;
+    hipLaunchKernelGGL(col_stats_kernel<TT>, dim3(C / 64), dim3(1024), 0, (hipStream_t)stream, (const TT*)x, (const TT*)logit, scale, shift,
+                       (TT*)out, T, C, mtp);
+    return check_launch("itts_col_stats");
+  });
 }

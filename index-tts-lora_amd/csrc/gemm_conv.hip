@@ -1245,14 +1245,5 @@ extern "C" int itts_gemm_conv(const itts_conv_args* a, void* stream) {
   int rc = conv_params_from_args(a, p, "itts_gemm_conv");
   if (rc != ITTS_OK) return rc;
   if (a->B == 0 || a->Tout == 0) return ITTS_OK;
-  hipStream_t s = (hipStream_t)stream;
-  switch (a->dtype) {
-    case ITTS_F32:
-      return dispatch_conv<float>(p, s);
-    case ITTS_BF16:
-      return dispatch_conv<bf16_t>(p, s);
-    case ITTS_F16:
-      return dispatch_conv<f16_t>(p, s);
-  }
-  ITTS_REQUIRE(false, "itts_gemm_conv: unknown dtype %d", a->dtype);
+  return by_dtype(a->dtype, "itts_gemm_conv", [&](auto tag) { return dispatch_conv<typename decltype(tag)::type>(p, (hipStream_t)stream); });
 }

@@ -477,6 +477,8 @@ int g_skinny_exp = 0;               // itts_debug_set(6, bits): load ablations o
 template <typename T>
 static SkinnyPlan plan_skinny(int N, int K, int ksplit, int MTall, int rows_per_wg, bool wide, bool fold) {
   constexpr int KS = Elem<T>::KS;
+  fold = fold && sizeof(T) == 2;   // fp32 has no folded form: the launcher refuses it
+  wide = wide && !fold;            // a folded launch never takes 16 waves
   SkinnyPlan q;
   int MT = MTall;
   if (rows_per_wg > 0 && rows_per_wg / 16 < MTall) MT = rows_per_wg / 16;
@@ -518,60 +520,64 @@ static SkinnyPlan plan_skinny(int N, int K, int ksplit, int MTall, int rows_per_
   return q;
 }
 
+// The row-tile rule (the launcher and itts_skinny_plan): of `m` rows still to do, one launch takes *rows of them and covers them
+// with the returned number of 16-row tiles, the MTall of plan_skinny.  fp32: 16 rows, one tile.  16-bit: up to 96 rows as 1 / 2 /
+// 4 / 6 tiles in every workgroup; more than 96 rows go 96 at a time or, with rows_per_wg > 0, all in one launch (plan_skinny deals
+// the tiles to grid.z).
+static int skinny_row_tiles(int dtype, int m, int rows_per_wg, int* rows) {
+  const int cap = dtype == ITTS_F32 ? 16 : (rows_per_wg > 0 && m > 96) ? m : 96;
+  const int r = *rows = m < cap ? m : cap;
+  return r <= 16 ? 1 : r <= 32 ? 2 : r <= 64 ? 4 : r <= 96 ? 6 : (r + 15) / 16;
+}
+
+static int skinny_no_form(const SkinnyPlan& q, bool fold) {
+  set_error("itts_gemm_skinny: no form <%d,%d,%d,%d,%d> is built", q.MT, q.SPWc, q.ntb, (int)fold, q.NW);
+  return ITTS_ERR_INVALID;
+}
+
+// Looks the planned (SPWc, ntb, 8 | 16 waves) up among the instantiations that exist for this (T, MT, FOLD): the same list as
+// plan_skinny's register-budget rules.  A plan outside it launches nothing.
 template <typename T, int MT, bool FOLD>
-static void launch_skinny_mt(const SkinnyParams& p, const SkinnyPlan& q, hipStream_t s) {
+static int launch_skinny_mt(const SkinnyParams& p, const SkinnyPlan& q, hipStream_t s) {
   dim3 grid(q.gx, q.gy, q.gz), block(q.NW * 64);
-#define ITTS_SK(SPW_, NTB_, MAXW_) hipLaunchKernelGGL((gemm_skinny_kernel<T, MT, SPW_, NTB_, FOLD, MAXW_>), grid, block, q.lds, s, p)
-  if constexpr (MT == 1 && !FOLD) {
-    if (q.NW == 16) {
-      ITTS_SK(10, 1, 16);
-      return;
-    }
+  const int maxw = q.NW == 16 ? 16 : 8;
+#define ITTS_SK(SPW_, NTB_, MAXW_)                                                                         \
+  if (q.SPWc == SPW_ && q.ntb == NTB_ && maxw == MAXW_) {                                                  \
+    hipLaunchKernelGGL((gemm_skinny_kernel<T, MT, SPW_, NTB_, FOLD, MAXW_>), grid, block, q.lds, s, p);    \
+    return check_launch("itts_gemm_skinny");                                                               \
   }
-  if (q.SPWc == 5) {
-    if (q.ntb == 1) ITTS_SK(5, 1, 8);
-    else if (q.ntb == 2) ITTS_SK(5, 2, 8);
-    else if (q.ntb == 3) {
-      if constexpr (FOLD && MT > 2) ITTS_SK(5, 2, 8);   // (the plan never asks for 3 tiles there: register budget)
-      else ITTS_SK(5, 3, 8);
-    } else {
-      if constexpr (FOLD && MT <= 2) ITTS_SK(5, 4, 8);
-      else ITTS_SK(5, 1, 8);                            // (never planned)
-    }
-  } else {
-    if (q.ntb == 1) ITTS_SK(10, 1, 8);
-    else {
-      if constexpr (MT <= 2) ITTS_SK(10, 2, 8);
-      else ITTS_SK(10, 1, 8);
-    }
-  }
+  ITTS_SK(5, 1, 8)
+  ITTS_SK(5, 2, 8)
+  if constexpr (!(FOLD && MT > 2)) ITTS_SK(5, 3, 8)    // the statistics accumulators take 8 registers per row tile
+  if constexpr (FOLD && MT <= 2) ITTS_SK(5, 4, 8)
+  ITTS_SK(10, 1, 8)
+  if constexpr (MT <= 2) ITTS_SK(10, 2, 8)
+  if constexpr (MT == 1 && !FOLD) ITTS_SK(10, 1, 16)
 #undef ITTS_SK
+  return skinny_no_form(q, FOLD);
 }
 
 template <typename T>
-static int launch_skinny(const SkinnyParams& p, int rows_per_wg, bool wide, hipStream_t s) {
+static int launch_skinny(const SkinnyParams& p, const SkinnyPlan& q, hipStream_t s) {
   const bool fold = p.cvec != nullptr;
-  const int MTall = p.M <= 16 ? 1 : p.M <= 32 ? 2 : p.M <= 64 ? 4 : p.M <= 96 ? 6 : (p.M + 15) / 16;   // > 96: rows dealt to grid.z
-  const SkinnyPlan q = plan_skinny<T>(p.N, p.K, p.ksplit, MTall, rows_per_wg, wide && !fold, fold);
   if constexpr (sizeof(T) == 4) {
     if (fold) {
       set_error("itts_gemm_skinny: the LayerNorm-folded form is built for bf16 / f16");
       return ITTS_ERR_INVALID;
     }
-    launch_skinny_mt<T, 1, false>(p, q, s);
+    if (q.MT == 1) return launch_skinny_mt<T, 1, false>(p, q, s);
   } else {
-#define ITTS_MT(MT_)                                          \
-  do {                                                        \
-    if (fold) launch_skinny_mt<T, MT_, true>(p, q, s);        \
-    else launch_skinny_mt<T, MT_, false>(p, q, s);            \
-  } while (0)
-    if (q.MT == 1) ITTS_MT(1);
-    else if (q.MT == 2) ITTS_MT(2);
-    else if (q.MT == 4) ITTS_MT(4);
-    else ITTS_MT(6);
+    switch (q.MT) {
+#define ITTS_MT(MT_) \
+  case MT_: return fold ? launch_skinny_mt<T, MT_, true>(p, q, s) : launch_skinny_mt<T, MT_, false>(p, q, s)
+      ITTS_MT(1);
+      ITTS_MT(2);
+      ITTS_MT(4);
+      ITTS_MT(6);
 #undef ITTS_MT
+    }
   }
-  return check_launch("itts_gemm_skinny");
+  return skinny_no_form(q, fold);
 }
 
 }  // namespace itts
@@ -587,9 +593,11 @@ extern "C" int itts_gemm_skinny(const itts_skinny_args* a, void* stream) {
   const int ksplit = a->ksplit > 0 ? a->ksplit : 1;
   ITTS_REQUIRE(ksplit <= a->K / ks && ksplit <= 64, "itts_gemm_skinny: ksplit=%d too large", ksplit);
   ITTS_REQUIRE(ksplit == 1 || a->epi == ITTS_EPI_SLAB_F32, "itts_gemm_skinny: ksplit > 1 requires the slab epilogue");
+  // (the block size is checked where the table is used: the QKV epilogue)
+  const int kv_bs_log2 = kv_block_log2(a->epi == ITTS_EPI_QKV_CACHE && a->kv_tab != nullptr, a->kv_bs);
   if (a->epi == ITTS_EPI_QKV_CACHE)
     ITTS_REQUIRE(a->y && a->kcache && a->vcache && a->pos && a->N % 3 == 0 && a->N / 3 == a->heads * 64 &&
-                     (a->kv_tab != nullptr ? (a->kv_bs == 16 || a->kv_bs == 32 || a->kv_bs == 64) : a->smax > 0),
+                     (a->kv_tab != nullptr ? kv_bs_log2 >= 0 : a->smax > 0),
                  "itts_gemm_skinny: bad QKV epilogue arguments (paged cache: kv_bs must be 16, 32 or 64)");
   else if (a->epi == ITTS_EPI_RESID_F32 || a->epi == ITTS_EPI_STORE_F32 || a->epi == ITTS_EPI_SLAB_F32)
     ITTS_REQUIRE(a->yf, "itts_gemm_skinny: yf is null");
@@ -617,13 +625,12 @@ extern "C" int itts_gemm_skinny(const itts_skinny_args* a, void* stream) {
                "itts_gemm_skinny: y_row0 / y_mtp place the rows of a PACKED y inside a taller operand (y_row0 %% 16 == 0)");
   ITTS_REQUIRE(a->x_mtp == 0 || (a->x_packed && a->x_mtp * 16 >= a->M), "itts_gemm_skinny: x_mtp is for a packed x of at least M rows");
   if (a->M == 0) return ITTS_OK;
-  // one launch covers 96 rows per workgroup; with rows_per_wg > 0 the row tiles are dealt to grid.z and any M runs as one launch
-  const int rows_per = (a->dtype == ITTS_F32) ? 16 : (a->rows_per_wg > 0 ? (a->M > 96 ? a->M : 96) : 96);
   ITTS_REQUIRE(a->M <= 96 || a->rows_per_wg == 0 || (a->M + 15) / 16 / (a->rows_per_wg / 16) < 65535, "itts_gemm_skinny: too many rows");
   hipStream_t s = (hipStream_t)stream;
-  for (int r0 = 0; r0 < a->M; r0 += rows_per) {
+  for (int r0 = 0, rows = 0; r0 < a->M; r0 += rows) {
+    const int MTall = skinny_row_tiles(a->dtype, a->M - r0, a->rows_per_wg, &rows);
     SkinnyParams p;
-    p.M = a->M - r0 < rows_per ? a->M - r0 : rows_per;
+    p.M = rows;
     p.N = a->N;
     p.K = a->K;
     p.wp = a->wp;
@@ -646,7 +653,7 @@ extern "C" int itts_gemm_skinny(const itts_skinny_args* a, void* stream) {
     p.kcache = a->kcache ? (char*)a->kcache + (paged ? 0 : (size_t)r0 * crow) : nullptr;
     p.vcache = a->vcache ? (char*)a->vcache + (paged ? 0 : (size_t)r0 * crow) : nullptr;
     p.kv_tab = a->kv_tab;
-    p.kv_bs_log2 = a->kv_bs == 64 ? 6 : a->kv_bs == 32 ? 5 : 4;
+    p.kv_bs_log2 = kv_bs_log2;
     p.pos = a->pos;
     p.heads = a->heads;
     p.smax = a->smax;
@@ -661,11 +668,10 @@ extern "C" int itts_gemm_skinny(const itts_skinny_args* a, void* stream) {
 #if ITTS_DIAG
     p.exp = g_skinny_exp;
 #endif
-    int rc;
-    if (a->dtype == ITTS_F32) rc = launch_skinny<float>(p, a->rows_per_wg, a->wide_wg != 0, s);
-    else if (a->dtype == ITTS_BF16) rc = launch_skinny<bf16_t>(p, a->rows_per_wg, a->wide_wg != 0, s);
-    else if (a->dtype == ITTS_F16) rc = launch_skinny<f16_t>(p, a->rows_per_wg, a->wide_wg != 0, s);
-    else ITTS_REQUIRE(false, "itts_gemm_skinny: unknown dtype %d", a->dtype);
+    const int rc = by_dtype(a->dtype, "itts_gemm_skinny", [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      return launch_skinny<T>(p, plan_skinny<T>(p.N, p.K, p.ksplit, MTall, a->rows_per_wg, a->wide_wg != 0, p.cvec != nullptr), s);
+    });
     if (rc != ITTS_OK) return rc;
   }
   return ITTS_OK;
@@ -673,11 +679,13 @@ extern "C" int itts_gemm_skinny(const itts_skinny_args* a, void* stream) {
 
 extern "C" int itts_skinny_plan(int dtype, int M, int N, int K, int ksplit, int rows_per_wg, int wide_wg, int fold, int* out8) {
   ITTS_REQUIRE(out8 && N > 0 && K > 0 && ksplit > 0 && M > 0, "itts_skinny_plan: bad arguments");
-  const int MT = dtype == ITTS_F32 ? 1 : M <= 16 ? 1 : M <= 32 ? 2 : M <= 64 ? 4 : (M <= 96 || rows_per_wg == 0) ? 6 : (M + 15) / 16;
-  const SkinnyPlan q = dtype == ITTS_F32 ? plan_skinny<float>(N, K, ksplit, 1, 0, false, false)
-                                         : plan_skinny<bf16_t>(N, K, ksplit, MT, rows_per_wg, wide_wg != 0 && !fold, fold != 0);
-  out8[0] = q.gx; out8[1] = q.gy; out8[2] = q.NW; out8[3] = q.ntb; out8[4] = q.spw; out8[5] = (int)q.lds; out8[6] = q.gz; out8[7] = q.MT;
-  return ITTS_OK;
+  int rows;
+  const int MTall = skinny_row_tiles(dtype, M, rows_per_wg, &rows);   // (of the first launch, when the rows take several)
+  return by_dtype(dtype, "itts_skinny_plan", [&](auto tag) {
+    const SkinnyPlan q = plan_skinny<typename decltype(tag)::type>(N, K, ksplit, MTall, rows_per_wg, wide_wg != 0, fold != 0);
+    out8[0] = q.gx; out8[1] = q.gy; out8[2] = q.NW; out8[3] = q.ntb; out8[4] = q.spw; out8[5] = (int)q.lds; out8[6] = q.gz; out8[7] = q.MT;
+    return ITTS_OK;
+  });
 }
 
 #if ITTS_DIAG

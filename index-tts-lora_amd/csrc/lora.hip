@@ -134,39 +134,38 @@ using namespace itts;
 
 extern "C" int itts_lora_shrink(const itts_lora_shrink_args* a, void* stream) {
   ITTS_REQUIRE(a && a->x && a->ids && a->a_bank && a->u, "itts_lora_shrink: null args");
-  ITTS_REQUIRE(a->dtype == ITTS_F32 || a->dtype == ITTS_BF16 || a->dtype == ITTS_F16, "itts_lora_shrink: unknown dtype %d", a->dtype);
-  const int ks = a->dtype == ITTS_F32 ? 16 : 32, e = a->dtype == ITTS_F32 ? 4 : 8;
-  ITTS_REQUIRE(a->M >= 0 && a->K > 0 && a->K % ks == 0, "itts_lora_shrink: bad shape M=%d K=%d (K %% %d != 0)", a->M, a->K, ks);
-  ITTS_REQUIRE(a->n >= 1 && a->rp >= 16 && a->rp <= 64 && a->rp % 16 == 0,
-               "itts_lora_shrink: n=%d adapters of padded rank rp=%d (1 <= n, rank <= 64, rp %% 16 == 0)", a->n, a->rp);
-  ITTS_REQUIRE(a->Kx <= 512 && a->Kx == ((int64_t)a->n * a->rp + 31) / 32 * 32,
-               "itts_lora_shrink: Kx=%d must be n * rp rounded up to a multiple of 32, and <= 512", a->Kx);
-  const int mtp = (a->M + 15) / 16;
-  const int x_mtp = a->x_mtp > 0 ? a->x_mtp : mtp, u_mtp = a->u_mtp > 0 ? a->u_mtp : mtp;
-  ITTS_REQUIRE((a->x_packed || a->x_mtp == 0) && x_mtp * 16 >= a->M, "itts_lora_shrink: x_mtp is for a packed x of at least M rows");
-  ITTS_REQUIRE((a->u_packed || a->u_mtp == 0) && u_mtp * 16 >= a->M, "itts_lora_shrink: u_mtp is for a packed u of at least M rows");
-  ITTS_REQUIRE(a->u_packed || (a->ldu >= a->Kx && a->ldu % e == 0), "itts_lora_shrink: a row-major u needs ldu >= Kx, ldu %% %d == 0", e);
-  ITTS_REQUIRE(((uintptr_t)a->x & 15) == 0 && ((uintptr_t)a->u & 15) == 0 && ((uintptr_t)a->a_bank & 15) == 0,
-               "itts_lora_shrink: x, u and a_bank must be 16-byte aligned");
-  if (a->M == 0) return ITTS_OK;
-  LoraShrinkParams p;
-  p.x = a->x;
-  p.ids = a->ids;
-  p.a_bank = a->a_bank;
-  p.u = a->u;
-  p.ldu = a->ldu;
-  p.M = a->M;
-  p.K = a->K;
-  p.n = a->n;
-  p.rp = a->rp;
-  p.Kx = a->Kx;
-  p.x_packed = a->x_packed ? 1 : 0;
-  p.x_mtp = x_mtp;
-  p.u_packed = a->u_packed ? 1 : 0;
-  p.u_mtp = u_mtp;
-  const int rows = p.u_packed ? u_mtp * 16 : a->M;   // the packed tail's padding rows are written too (zeros)
-  hipStream_t s = (hipStream_t)stream;
-  if (a->dtype == ITTS_F32) return launch_lora_shrink<float>(p, rows, s);
-  if (a->dtype == ITTS_BF16) return launch_lora_shrink<bf16_t>(p, rows, s);
-  return launch_lora_shrink<f16_t>(p, rows, s);
+  return by_dtype(a->dtype, "itts_lora_shrink", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    constexpr int ks = Elem<T>::KS, e = Elem<T>::E;
+    ITTS_REQUIRE(a->M >= 0 && a->K > 0 && a->K % ks == 0, "itts_lora_shrink: bad shape M=%d K=%d (K %% %d != 0)", a->M, a->K, ks);
+    ITTS_REQUIRE(a->n >= 1 && a->rp >= 16 && a->rp <= 64 && a->rp % 16 == 0,
+                 "itts_lora_shrink: n=%d adapters of padded rank rp=%d (1 <= n, rank <= 64, rp %% 16 == 0)", a->n, a->rp);
+    ITTS_REQUIRE(a->Kx <= 512 && a->Kx == ((int64_t)a->n * a->rp + 31) / 32 * 32,
+                 "itts_lora_shrink: Kx=%d must be n * rp rounded up to a multiple of 32, and <= 512", a->Kx);
+    const int mtp = (a->M + 15) / 16;
+    const int x_mtp = a->x_mtp > 0 ? a->x_mtp : mtp, u_mtp = a->u_mtp > 0 ? a->u_mtp : mtp;
+    ITTS_REQUIRE((a->x_packed || a->x_mtp == 0) && x_mtp * 16 >= a->M, "itts_lora_shrink: x_mtp is for a packed x of at least M rows");
+    ITTS_REQUIRE((a->u_packed || a->u_mtp == 0) && u_mtp * 16 >= a->M, "itts_lora_shrink: u_mtp is for a packed u of at least M rows");
+    ITTS_REQUIRE(a->u_packed || (a->ldu >= a->Kx && a->ldu % e == 0), "itts_lora_shrink: a row-major u needs ldu >= Kx, ldu %% %d == 0", e);
+    ITTS_REQUIRE(((uintptr_t)a->x & 15) == 0 && ((uintptr_t)a->u & 15) == 0 && ((uintptr_t)a->a_bank & 15) == 0,
+                 "itts_lora_shrink: x, u and a_bank must be 16-byte aligned");
+    if (a->M == 0) return ITTS_OK;
+    LoraShrinkParams p;
+    p.x = a->x;
+    p.ids = a->ids;
+    p.a_bank = a->a_bank;
+    p.u = a->u;
+    p.ldu = a->ldu;
+    p.M = a->M;
+    p.K = a->K;
+    p.n = a->n;
+    p.rp = a->rp;
+    p.Kx = a->Kx;
+    p.x_packed = a->x_packed ? 1 : 0;
+    p.x_mtp = x_mtp;
+    p.u_packed = a->u_packed ? 1 : 0;
+    p.u_mtp = u_mtp;
+    const int rows = p.u_packed ? u_mtp * 16 : a->M;   // the packed tail's padding rows are written too (zeros)
+    return launch_lora_shrink<T>(p, rows, (hipStream_t)stream);
+  });
 }

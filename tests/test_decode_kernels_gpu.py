@@ -69,6 +69,7 @@ import pytest
 import torch
 
 from fp64_check import check, must_fail, ulp
+from skinny_forms import GEMM_SHAPES, REACHABLE, form_key
 
 pytestmark = pytest.mark.gpu
 
@@ -116,35 +117,6 @@ def bad(what, control, y, ref, bound, valid=None):
 
 
 # ------------------------------------------------------------------------------------------------- skinny GEMM
-def form_key(nat, dtype, M, N, K, ksplit=1, rows_per_wg=0, wide=False, fold=False):
-    """(MT, SPW, NTB, FOLD, MAXW) of the gemm_skinny_kernel instantiation a launch of this shape runs."""
-    p = nat.skinny_plan(dtype, M, N, K, ksplit, rows_per_wg, wide, fold)
-    return (p["row_tiles_per_wg"], 5 if p["ksteps_per_wave"] <= 5 else 10, p["tiles_per_wg"], bool(fold), 16 if p["waves"] == 16 else 8)
-
-
-# Every instantiation launch_skinny_mt can be asked for, by plan_skinny's rules:
-#   SPW 5:  NTB 1, 2, 3 -- 3 not with FOLD and MT > 2 (the statistics accumulators: demoted to 2) --, and NTB 4 only with FOLD and MT <= 2;
-#   SPW 10: NTB 1, and NTB 2 only with MT <= 2 (4-6 row tiles with 10-step chunks: accumulators + weight fragments);
-#   16 waves: MT 1, not folded, always <10, 1, 16>.
-# Never planned (arms of launch_skinny_mt that exist only as fall-backs of its if-chain):
-#   <5, 2> standing in for NTB 3 with FOLD and MT > 2  -- plan_skinny caps ntb at 2 there before the launch;
-#   <5, 1> standing in for NTB 4 without FOLD or with MT > 2 -- ntb_max is 4 only for FOLD, MT <= 2, SPW 5;
-#   <10, 1> standing in for NTB 2 with MT > 2 -- plan_skinny sets ntb = 1 for MT > 2 with 10-step chunks;
-#   a 16-wave folded form -- the entry point clears `wide` for a folded launch;
-#   MT 3 / 5 -- 33-64 rows run MT 4 with tiles that may be empty, 65-96 rows MT 6.
-REACHABLE = set()
-for _mt in (1, 2, 4, 6):
-    for _fold in (False, True):
-        for _ntb in (1, 2, 3, 4):
-            if (_ntb == 3 and _fold and _mt > 2) or (_ntb == 4 and not (_fold and _mt <= 2)):
-                continue
-            REACHABLE.add((_mt, 5, _ntb, _fold, 8))
-        REACHABLE.add((_mt, 10, 1, _fold, 8))
-        if _mt <= 2:
-            REACHABLE.add((_mt, 10, 2, _fold, 8))
-REACHABLE.add((1, 10, 1, False, 16))
-
-
 def gelu_new(x):
     return 0.5 * x * (1.0 + torch.tanh(0.7978845608028654 * (x + 0.044715 * x ** 3)))
 
@@ -466,6 +438,7 @@ GEMM_CASES = [
     (96, 8196, 320, (6, 5, 2, True, 8), P(fold=True)),                    # 513 column tiles: the grid rule asks for 3, FOLD with MT > 2 runs 2
     (95, 64, 5248, (6, 10, 1, True, 8), P(fold=True, epi="gelu")),
 ]
+assert {(c[1], c[2], c[4].get("ksplit", 1)) for c in GEMM_CASES} == set(GEMM_SHAPES)   # the CPU planner sweep starts from these
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=tname)
