@@ -48,7 +48,7 @@ extern "C" {
 #define ITTS_BF16 1
 #define ITTS_F16 2
 
-#define ITTS_ABI_VERSION 9 /* 9: itts_last_kernel (read-only: the kernel form the last itts_gemm_conv / itts_aa_snake_fwd launched), itts_lora_shrink (a new symbol: no existing struct or signature changed); 8: prompt front-end (itts_subsample_conv, itts_mha_small, itts_glu_dwconv_ln_silu, itts_rows, itts_geglu, itts_prefix_rows) and speaker encoder (itts_im2col_reflect, itts_res2_step, itts_se_gate, itts_scale_resid, itts_col_stats, ITTS_EPI_RELU_AFFINE_*), itts_kv_share_rows, ITTS_EPI_SILU_STORE, y_row0 / y_mtp and any M with rows_per_wg in itts_gemm_skinny, itts_gemm_conv ksplit <= 64; 7: LayerNorm folded into the consuming skinny GEMM (ln_c), residual epilogue with a packed T copy, rows_per_wg / wide_wg, bump words in itts_gemm_skinny / itts_embed_step (+ clamp, packed copy); the reducer tail is gone; paged KV cache (kv_tab / kv_bs); 6: per-row clocks (row_step0) in itts_embed_step / itts_sample_args (slot refill), itts_attn_prefill_prefix / _shared, kv_share in itts_attn_decode; 5: itts_ln_reduce takes up to 6 slabs */
+#define ITTS_ABI_VERSION 9 /* 9: itts_last_kernel (read-only: the kernel form the last itts_gemm_conv / itts_aa_snake_fwd launched), itts_lora_shrink (a new symbol: no existing struct or signature changed), and the entry points of indextts_hip_rows.h; 8: prompt front-end (itts_subsample_conv, itts_mha_small, itts_glu_dwconv_ln_silu, itts_rows, itts_geglu, itts_prefix_rows) and speaker encoder (itts_im2col_reflect, itts_res2_step, itts_se_gate, itts_scale_resid, itts_col_stats, ITTS_EPI_RELU_AFFINE_*), itts_kv_share_rows, ITTS_EPI_SILU_STORE, y_row0 / y_mtp and any M with rows_per_wg in itts_gemm_skinny, itts_gemm_conv ksplit <= 64; 7: LayerNorm folded into the consuming skinny GEMM (ln_c), residual epilogue with a packed T copy, rows_per_wg / wide_wg, bump words in itts_gemm_skinny / itts_embed_step (+ clamp, packed copy); the reducer tail is gone; paged KV cache (kv_tab / kv_bs); 6: per-row clocks (row_step0) in itts_embed_step / itts_sample_args (slot refill), itts_attn_prefill_prefix / _shared, kv_share in itts_attn_decode; 5: itts_ln_reduce takes up to 6 slabs */
 
 int itts_abi_version(void);
 const char* itts_last_error(void);
@@ -378,6 +378,34 @@ typedef struct itts_sample_args {
                         force_stop[b] is compared with; the Philox counter stays (b, state[0]). */
 } itts_sample_args;
 int itts_sample(const itts_sample_args* a, void* stream);
+
+/* The same step with PER-ROW sampling settings: a device table of one record per row replaces the scalar parameters, so a
+ * row of a batch -- or a slot of a refilled loop -- keeps its own request's settings and one captured launch serves every
+ * assignment (the records are data, like the adapter ids of itts_lora_shrink).  Row b is processed exactly as itts_sample
+ * processes a row under the scalars of rows[b]; greedy and sampling rows may share a launch.
+ * Record: 32 bytes, 16-byte aligned (a workgroup fetches its row's record as two 16-byte words):
+ *   byte  0  float    rep_penalty
+ *         4  float    temperature
+ *         8  float    top_p
+ *        12  int32    top_k
+ *        16  uint64   seed       Philox key = seed + the 64-bit value in state[4..5]
+ *        24  uint32   stream     Philox counter = (stream, k_b, 0, 0) with the row's OWN step k_b = state[0] - row_step0[b]:
+ *                                what a request draws depends on its seed, stream and step, not on its slot or on when it
+ *                                entered.  stream = b without row_step0 is itts_sample's counter.
+ *        28  int32    do_sample  0 = argmax (temperature, top_k, top_p unused)
+ * The library cannot see the records at launch time.  The caller validates them before the upload (sampling rows: 1 <= top_k
+ * <= 1024, 0 < top_p <= 1, temperature > 0; every row: rep_penalty > 0); the kernel itself only stays memory-safe for any
+ * record: a sampling row's top_k is clamped into [1, min(V, 1024)], a temperature or penalty that is not > 0 is taken as 1,
+ * the emitted token is clamped into [0, V).  Every other field of the arguments is as in itts_sample_args. */
+typedef struct itts_sample_row {
+  float rep_penalty, temperature, top_p;
+  int32_t top_k;
+  uint64_t seed;
+  uint32_t stream;
+  int32_t do_sample;
+} itts_sample_row;
+/* The argument struct and the prototype are in indextts_hip_rows.h (see there why), which this header pulls in: */
+#include "indextts_hip_rows.h"
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Beam search / beam-sample step (num_beams > 1) -- replaces, for the generate() call at indextts/gpt/model.py:710-715,

@@ -3,6 +3,7 @@
 // repetition penalty -> temperature -> top-k -> top-p -> softmax -> draw | argmax, plus the EOS/pad bookkeeping of
 // GenerationMixin (finished rows keep emitting pad = stop token).  One workgroup per batch row.
 #include "common.h"
+#include <cstddef>
 
 namespace itts {
 
@@ -27,10 +28,53 @@ struct SampleParams {
   float* dbg_scores;
   int advance;
   const int32_t* row_step0;
+  const itts_sample_row* rows;   // itts_sample_rows: one record per row instead of the scalars above
 #if ITTS_STAMPS
   unsigned long long* stamps;
 #endif
 };
+
+// The sampling settings of one workgroup's row, in scalar registers either way: the launch arguments (itts_sample) or the row's
+// 32-byte record (itts_sample_rows; two 16-byte loads issued with the first round trip, every lane reads the same words).  A
+// record is device data nobody checked at launch time: what indexes or sizes memory is clamped here.
+struct RowSettings {
+  float rep_penalty, temperature, top_p;
+  int top_k, do_sample;
+  uint32_t seed_lo, seed_hi, c0, c1;   // Philox key (before state[4..5] is added) and counter words 0 / 1
+};
+
+template <bool ROWS>
+__device__ __forceinline__ RowSettings row_settings(const SampleParams& p, int b, int kg, int k) {
+  RowSettings r;
+  if constexpr (ROWS) {
+    const u32x4* rec = reinterpret_cast<const u32x4*>(p.rows + b);
+    const u32x4 lo = rec[0], hi = rec[1];
+    auto word = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+    r.rep_penalty = __uint_as_float(word(lo[0]));
+    r.temperature = __uint_as_float(word(lo[1]));
+    r.top_p = __uint_as_float(word(lo[2]));
+    r.top_k = (int)word(lo[3]);
+    r.seed_lo = word(hi[0]);
+    r.seed_hi = word(hi[1]);
+    r.c0 = word(hi[2]);
+    r.do_sample = word(hi[3]) != 0u;
+    r.c1 = (uint32_t)k;                                      // the row's own step: a request draws the same numbers in any slot
+    if (!(r.rep_penalty > 0.f)) r.rep_penalty = 1.0f;
+    if (!(r.temperature > 0.f)) r.temperature = 1.0f;
+    r.top_k = max(1, min(r.top_k, min(p.V, SM_MAXC)));
+  } else {
+    r.rep_penalty = p.rep_penalty;
+    r.temperature = p.temperature;
+    r.top_p = p.top_p;
+    r.top_k = p.top_k;
+    r.do_sample = p.do_sample;
+    r.seed_lo = p.seed_lo;
+    r.seed_hi = p.seed_hi;
+    r.c0 = (uint32_t)b;
+    r.c1 = (uint32_t)kg;
+  }
+  return r;
+}
 
 __device__ __forceinline__ uint32_t fkey(float f) {
   uint32_t u = __float_as_uint(f);
@@ -54,6 +98,7 @@ __device__ __forceinline__ uint32_t philox_first(uint32_t c0, uint32_t c1, uint3
   return c0;
 }
 
+template <bool ROWS>
 __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
   __shared__ float sv[SM_MAXV];
   __shared__ uint32_t flag[SM_MAXV / 32];
@@ -72,6 +117,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
   const int k = kg - (p.row_step0 != nullptr ? p.row_step0[b] : 0);           // the ROW's step (a refilled slot starts at 0)
   const int V = p.V;
   const float* lg = p.logits + (int64_t)b * p.ldl;
+  const RowSettings rs = row_settings<ROWS>(p, b, kg, k);
 #if ITTS_STAMPS
   unsigned long long st_[16];
 #pragma unroll
@@ -104,7 +150,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
   }
   __syncthreads();
   SSTAMP(1);
-  if (p.rep_penalty != 1.0f) {
+  if (rs.rep_penalty != 1.0f) {
     const int nh = min(k, p.hist_cap);
     for (int i = tid; i < p.n_extra + nh; i += 256) {
       const int id = i < p.n_extra ? p.extra_ids[i] : p.history[(int64_t)b * p.hist_cap + (i - p.n_extra)];
@@ -112,13 +158,13 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
         const uint32_t bit = 1u << (id & 31);
         if (!(atomicOr(&flag[id >> 5], bit) & bit)) {
           const float v = sv[id];
-          sv[id] = v < 0.f ? v * p.rep_penalty : v / p.rep_penalty;
+          sv[id] = v < 0.f ? v * rs.rep_penalty : v / rs.rep_penalty;
         }
       }
     }
     __syncthreads();
   }
-  const float inv_t = (p.do_sample && p.temperature != 1.0f) ? 1.0f / p.temperature : 1.0f;
+  const float inv_t = (rs.do_sample && rs.temperature != 1.0f) ? 1.0f / rs.temperature : 1.0f;
 #pragma unroll
   for (int i = 0; i < SM_MAXV / 256; ++i) {   // processed scores back into registers (independent LDS reads)
     int idx = tid + i * 256;
@@ -129,7 +175,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
     for (int i = 0; i < SM_MAXV / 256; ++i) {
       int idx = tid + i * 256;
       if (idx < V) {
-        lv[i] = lv[i] / p.temperature;
+        lv[i] = lv[i] / rs.temperature;
         sv[idx] = lv[i];
       }
     }
@@ -137,7 +183,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
   __syncthreads();
   SSTAMP(2);
 
-  if (!p.do_sample) {
+  if (!rs.do_sample) {
     // ---- greedy: argmax, lowest id on ties
     float bv = -INFINITY;
     int bi = 0x7fffffff;
@@ -164,7 +210,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
       for (int i = tid; i < V; i += 256) p.dbg_scores[(int64_t)b * V + i] = sv[i];
     __syncthreads();
   } else {
-    int kk = p.top_k > 0 ? min(p.top_k, V) : min(V, SM_MAXC);
+    int kk = rs.top_k > 0 ? min(rs.top_k, V) : min(V, SM_MAXC);
     if (kk > SM_MAXC) kk = SM_MAXC;
     uint32_t keys[SM_MAXV / 256];
     uint32_t kmax = 0u;
@@ -269,15 +315,15 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
     for (int i = tid; i < n2; i += 256) cs[i] = expf(ss[i] - ss[0]);
     if (tid == 64) {
       // key = launch argument + the 64-bit seed held in state[4..5] (lets a captured launch serve every seed)
-      const uint64_t key = (((uint64_t)p.seed_hi << 32) | p.seed_lo) + (((uint64_t)(uint32_t)p.state[5] << 32) | (uint32_t)p.state[4]);
-      uint32_t x = philox_first((uint32_t)b, (uint32_t)kg, 0u, 0u, (uint32_t)key, (uint32_t)(key >> 32));
+      const uint64_t key = (((uint64_t)rs.seed_hi << 32) | rs.seed_lo) + (((uint64_t)(uint32_t)p.state[5] << 32) | (uint32_t)p.state[4]);
+      uint32_t x = philox_first(rs.c0, rs.c1, 0u, 0u, (uint32_t)key, (uint32_t)(key >> 32));
       rv[0] = (float)(x >> 8) * (1.0f / 16777216.0f);
     }
     __syncthreads();
     if (wave == 0) {
       const int n = __builtin_amdgcn_readfirstlane(n2);
       const float u = rv[0];
-      const float lim = 1.0f - p.top_p;
+      const float lim = 1.0f - rs.top_p;
       if (n <= 64) {
         // the order-sensitive fp32 running sums of the reference, with the numerators in registers (lane i holds
         // candidate i) and v_readlane instead of one dependent LDS read per term; every lane computes the same scalars
@@ -287,7 +333,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
         float total = 0.f;
         for (int i = n - 1; i >= 0; --i) total += term(i);
         int keep = n;
-        if (p.top_p < 1.0f) {
+        if (rs.top_p < 1.0f) {
           // HF TopPLogitsWarper: ascending cumulative probability <= 1 - top_p is removed, at least one token kept
           float cum = 0.f;
           for (int i = n - 1; i >= 1; --i) {
@@ -310,7 +356,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
         float total = 0.f;
         for (int i = n - 1; i >= 0; --i) total += cs[i];
         int keep = n;
-        if (p.top_p < 1.0f) {
+        if (rs.top_p < 1.0f) {
           float cum = 0.f;
           for (int i = n - 1; i >= 1; --i) {
             cum += cs[i] / total;
@@ -340,7 +386,9 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
   SSTAMP(6);
   // ---- bookkeeping
   if (tid == 0) {
-    int tok = forced ? p.stop_token : sh_tok;
+    int sel = sh_tok;
+    if constexpr (ROWS) sel = max(0, min(sel, V - 1));   // (a record's NaN settings must not become an index of the next step)
+    int tok = forced ? p.stop_token : sel;
     p.tokens[b] = tok;
     if (k < p.hist_cap) p.history[(int64_t)b * p.hist_cap + k] = tok;
     if (tok == p.stop_token && p.finished[b] == 0) {
@@ -373,15 +421,12 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
 
 using namespace itts;
 
-extern "C" int itts_sample(const itts_sample_args* a, void* stream) {
-  ITTS_REQUIRE(a && a->logits && a->tokens && a->history && a->finished && a->state, "itts_sample: null pointer");
-  ITTS_REQUIRE(a->B > 0 && a->V > 0 && a->V <= SM_MAXV && a->ldl >= a->V, "itts_sample: bad shape B=%d V=%d (max %d)", a->B, a->V, SM_MAXV);
-  ITTS_REQUIRE(a->rep_penalty > 0.f && a->temperature > 0.f, "itts_sample: rep_penalty/temperature must be positive");
-  ITTS_REQUIRE(a->top_k <= SM_MAXC, "itts_sample: top_k=%d exceeds %d", a->top_k, SM_MAXC);
-  // the candidate store holds SM_MAXC entries: sampling from the whole vocabulary (top-k disabled) would be truncated to
-  // the 1024 best logits, silently -- refuse it instead (every caller on the infer.py path passes k = 30 or 50)
-  ITTS_REQUIRE(!a->do_sample || a->top_k > 0, "itts_sample: do_sample needs 1 <= top_k <= %d (top_k=%d)", SM_MAXC, a->top_k);
-  SampleParams p;
+// What both argument structs share (same field names), checked and copied once.
+template <class Args>
+static int common_params(const Args* a, const char* who, SampleParams& p) {
+  ITTS_REQUIRE(a && a->logits && a->tokens && a->history && a->finished && a->state, "%s: null pointer", who);
+  ITTS_REQUIRE(a->B > 0 && a->V > 0 && a->V <= SM_MAXV && a->ldl >= a->V, "%s: bad shape B=%d V=%d (max %d)", who, a->B, a->V, SM_MAXV);
+  p = SampleParams{};
   p.logits = a->logits;
   p.B = a->B;
   p.V = a->V;
@@ -394,13 +439,6 @@ extern "C" int itts_sample(const itts_sample_args* a, void* stream) {
   p.extra_ids = a->extra_ids;
   p.n_extra = a->extra_ids ? a->n_extra : 0;
   p.force_stop = a->force_stop;
-  p.rep_penalty = a->rep_penalty;
-  p.temperature = a->temperature;
-  p.top_p = a->top_p;
-  p.top_k = a->top_k;
-  p.do_sample = a->do_sample;
-  p.seed_lo = (uint32_t)(a->seed & 0xFFFFFFFFull);
-  p.seed_hi = (uint32_t)(a->seed >> 32);
   p.stop_token = a->stop_token;
   p.dbg_scores = a->dbg_scores;
   p.advance = a->no_advance ? 0 : 1;
@@ -408,6 +446,39 @@ extern "C" int itts_sample(const itts_sample_args* a, void* stream) {
 #if ITTS_STAMPS
   p.stamps = itts::g_stamp_buf_sample;
 #endif
-  hipLaunchKernelGGL(sample_kernel, dim3(a->B), dim3(256), 0, (hipStream_t)stream, p);
+  return ITTS_OK;
+}
+
+extern "C" int itts_sample(const itts_sample_args* a, void* stream) {
+  SampleParams p;
+  if (int rc = common_params(a, "itts_sample", p)) return rc;
+  ITTS_REQUIRE(a->rep_penalty > 0.f && a->temperature > 0.f, "itts_sample: rep_penalty/temperature must be positive");
+  ITTS_REQUIRE(a->top_k <= SM_MAXC, "itts_sample: top_k=%d exceeds %d", a->top_k, SM_MAXC);
+  // the candidate store holds SM_MAXC entries: sampling from the whole vocabulary (top-k disabled) would be truncated to
+  // the 1024 best logits, silently -- refuse it instead (every caller on the infer.py path passes k = 30 or 50)
+  ITTS_REQUIRE(!a->do_sample || a->top_k > 0, "itts_sample: do_sample needs 1 <= top_k <= %d (top_k=%d)", SM_MAXC, a->top_k);
+  p.rep_penalty = a->rep_penalty;
+  p.temperature = a->temperature;
+  p.top_p = a->top_p;
+  p.top_k = a->top_k;
+  p.do_sample = a->do_sample;
+  p.seed_lo = (uint32_t)(a->seed & 0xFFFFFFFFull);
+  p.seed_hi = (uint32_t)(a->seed >> 32);
+  hipLaunchKernelGGL(sample_kernel<false>, dim3(a->B), dim3(256), 0, (hipStream_t)stream, p);
   return check_launch("itts_sample");
+}
+
+static_assert(sizeof(itts_sample_row) == 32 && offsetof(itts_sample_row, seed) == 16 && offsetof(itts_sample_row, do_sample) == 28,
+              "itts_sample_row is read as two 16-byte words");
+
+extern "C" int itts_sample_rows(const itts_sample_rows_args* a, void* stream) {
+  SampleParams p;
+  if (int rc = common_params(a, "itts_sample_rows", p)) return rc;
+  // the records are device data: their VALUES are the caller's to check before the upload (the kernel clamps what could
+  // index memory); only the table's address can be looked at here
+  ITTS_REQUIRE(a->rows != nullptr && (reinterpret_cast<uintptr_t>(a->rows) & 15) == 0,
+               "itts_sample_rows: rows must be a 16-byte aligned table of B records");
+  p.rows = a->rows;
+  hipLaunchKernelGGL(sample_kernel<true>, dim3(a->B), dim3(256), 0, (hipStream_t)stream, p);
+  return check_launch("itts_sample_rows");
 }

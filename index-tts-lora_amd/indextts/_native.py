@@ -78,6 +78,19 @@ class SampleArgs(C.Structure):
                 ("no_advance", C.c_int), ("row_step0", C.c_void_p)]
 
 
+class SampleRow(C.Structure):
+    """itts_sample_row: one row's sampling settings, 32 bytes (include/indextts_hip.h)."""
+    _fields_ = [("rep_penalty", C.c_float), ("temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_int32),
+                ("seed", C.c_uint64), ("stream", C.c_uint32), ("do_sample", C.c_int32)]
+
+
+class SampleRowsArgs(C.Structure):
+    _fields_ = [("logits", C.c_void_p), ("B", C.c_int), ("V", C.c_int), ("ldl", C.c_int), ("tokens", C.c_void_p),
+                ("history", C.c_void_p), ("hist_cap", C.c_int), ("finished", C.c_void_p), ("state", C.c_void_p),
+                ("extra_ids", C.c_void_p), ("n_extra", C.c_int), ("force_stop", C.c_void_p), ("rows", C.c_void_p),
+                ("stop_token", C.c_int), ("dbg_scores", C.c_void_p), ("no_advance", C.c_int), ("row_step0", C.c_void_p)]
+
+
 class BeamArgs(C.Structure):
     _fields_ = [("logits", C.c_void_p), ("B", C.c_int), ("num_beams", C.c_int), ("V", C.c_int), ("ldl", C.c_int),
                 ("tokens", C.c_void_p), ("src", C.c_void_p), ("beam_scores", C.c_void_p), ("hist", C.c_void_p),
@@ -147,7 +160,13 @@ _SIGNATURES = {
                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
 
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+# include/indextts_hip_rows.h: the entry points whose per-row settings are a device table
+_ROW_SIGNATURES = {
+    "itts_sample_rows": (C.c_int, [C.POINTER(SampleRowsArgs), C.c_void_p]),
+}
+
+EXPORTED_SYMBOLS = tuple(_SIGNATURES)          # what include/indextts_hip.h declares itself
+ROW_SYMBOLS = tuple(_ROW_SIGNATURES)           # what include/indextts_hip_rows.h declares
 _lib = None
 
 
@@ -160,7 +179,7 @@ def lib():
             raise NativeError(f"{path} not found: build it with `make -C index-tts-lora_amd/csrc` "
                               f"(or python -c 'import __graft_entry__ as g; g.build()'). There is no fallback path.")
         L = C.CDLL(path)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in {**_SIGNATURES, **_ROW_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -555,6 +574,72 @@ def sample(logits, tokens, history, finished, state, extra_ids, force_stop, rep_
     a.no_advance = int(bool(no_advance))
     a.row_step0 = _p(row_step0)
     _check(lib().itts_sample(C.byref(a), _stream()), "itts_sample")
+
+
+SAMPLE_ROW_BYTES = 32
+SAMPLE_MAX_TOP_K = 1024     # the sampler's candidate store
+_ROW_KEYS = ("do_sample", "temperature", "top_k", "top_p", "repetition_penalty", "seed", "stream")
+
+
+def check_sample_row(d: dict, what="sampling") -> dict:
+    """One row's settings, complete (keys: do_sample, temperature, top_k, top_p, repetition_penalty, seed, stream), checked as
+    itts_sample checks its scalars -- ValueError before anything reaches the device.  Returns the normalised dict."""
+    unknown = sorted(set(d) - set(_ROW_KEYS))
+    missing = sorted(set(_ROW_KEYS) - set(d))
+    if unknown or missing:
+        raise ValueError(f"{what}: unknown keys {unknown}, missing keys {missing} (a row holds {list(_ROW_KEYS)})")
+    r = dict(do_sample=bool(d["do_sample"]), temperature=float(d["temperature"]), top_k=int(d["top_k"]), top_p=float(d["top_p"]),
+             repetition_penalty=float(d["repetition_penalty"]), seed=int(d["seed"]) & 0xFFFFFFFFFFFFFFFF,
+             stream=int(d["stream"]))
+    if not r["repetition_penalty"] > 0.0:
+        raise ValueError(f"{what}: repetition_penalty must be positive (got {r['repetition_penalty']})")
+    if not 0 <= r["stream"] < (1 << 32):
+        raise ValueError(f"{what}: stream must fit 32 bits (got {r['stream']})")
+    if r["do_sample"]:
+        if not 1 <= r["top_k"] <= SAMPLE_MAX_TOP_K:
+            raise ValueError(f"{what}: do_sample needs 1 <= top_k <= {SAMPLE_MAX_TOP_K} (got {r['top_k']}): the device sampler keeps "
+                             f"at most {SAMPLE_MAX_TOP_K} candidates per row and refuses to truncate a distribution silently")
+        if not 0.0 < r["top_p"] <= 1.0:
+            raise ValueError(f"{what}: top_p must lie in (0, 1] (got {r['top_p']})")
+        if not r["temperature"] > 0.0:
+            raise ValueError(f"{what}: temperature must be positive (got {r['temperature']})")
+    else:   # greedy ignores the distribution settings: normalised, as sampling_params does for the scalar form
+        r["temperature"], r["top_k"], r["top_p"] = 1.0, 1, 1.0
+    return r
+
+
+def pack_sample_rows(rows):
+    """Checked rows (check_sample_row) -> numpy uint8 [len(rows), 32]: the records itts_sample_rows reads (itts_sample_row)."""
+    import numpy as np
+    recs = (SampleRow * max(len(rows), 1))()
+    for rec, d in zip(recs, rows):
+        r = check_sample_row(d)
+        rec.rep_penalty, rec.temperature, rec.top_p, rec.top_k = r["repetition_penalty"], r["temperature"], r["top_p"], r["top_k"]
+        rec.seed, rec.stream, rec.do_sample = r["seed"], r["stream"], int(r["do_sample"])
+    return np.frombuffer(bytes(recs), dtype=np.uint8).reshape(-1, SAMPLE_ROW_BYTES)[: len(rows)].copy()
+
+
+def sample_rows(logits, tokens, history, finished, state, extra_ids, force_stop, rows, stop_token, dbg_scores=None,
+                no_advance=False, row_step0=None):
+    """itts_sample with per-row settings: rows is a uint8 device tensor [>= B, 32] of packed records (pack_sample_rows: the
+    values are checked on the host before the upload, the kernel only guards memory) -- or a list of row dicts, which is
+    checked, packed and uploaded here (tests; a captured loop keeps a persistent table)."""
+    B, V = logits.shape
+    if not torch.is_tensor(rows):
+        if len(rows) != B:
+            raise ValueError(f"itts_sample_rows: {len(rows)} rows of settings for {B} rows of logits")
+        rows = torch.from_numpy(pack_sample_rows(rows)).to(logits.device)
+    _dev(rows)
+    if rows.dtype != torch.uint8 or rows.numel() < B * SAMPLE_ROW_BYTES:
+        raise NativeError("itts_sample_rows: rows must be a uint8 device tensor of B 32-byte records")
+    a = SampleRowsArgs()
+    a.logits, a.B, a.V, a.ldl = _p(logits), B, V, logits.stride(0)
+    a.tokens, a.history, a.hist_cap = _p(tokens), _p(history), history.shape[1]
+    a.finished, a.state = _p(finished), _p(state)
+    a.extra_ids, a.n_extra = _p(extra_ids), 0 if extra_ids is None else extra_ids.numel()
+    a.force_stop, a.rows, a.stop_token = _p(force_stop), _p(rows), int(stop_token)
+    a.dbg_scores, a.no_advance, a.row_step0 = _p(dbg_scores), int(bool(no_advance)), _p(row_step0)
+    _check(lib().itts_sample_rows(C.byref(a), _stream()), "itts_sample_rows")
 
 
 def beam_step(logits, num_beams, tokens, src, beam_scores, hist, hyp_score, hyp_len, hyp_tok, n_hyp, worst, done, state,

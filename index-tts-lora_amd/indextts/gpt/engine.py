@@ -104,6 +104,35 @@ class PagedKV:
         return self.blocks - 1 - len(self.free)
 
 
+PER_ROW = {"per_row": True}   # what a loop's `sp` becomes once its rows' settings live in the device table (RowSampling): the
+#                               captured step's key carries this marker, never the values
+
+
+class RowSampling:
+    """Per-row sampling settings of one engine: the device table itts_sample_rows reads (uint8 [rows][32], one itts_sample_row
+    per decode slot), a host mirror and a dirty flag -- flushed with one copy between graph replays, like PagedKV's block
+    table.  The records are data: one captured step serves every assignment of settings to rows."""
+
+    def __init__(self, rows, device):
+        import numpy as np
+        self.rows = rows
+        self.tab = torch.zeros(rows, nat.SAMPLE_ROW_BYTES, dtype=torch.uint8, device=device)
+        self.tab_h = np.zeros((rows, nat.SAMPLE_ROW_BYTES), dtype=np.uint8)
+        self.dirty = True
+
+    def set(self, rows, settings):
+        """Slot rows[j] <- settings[j] (dicts that passed nat.check_sample_row)."""
+        if len(rows):
+            self.tab_h[list(rows)] = nat.pack_sample_rows(settings)
+            self.dirty = True
+
+    def flush(self):
+        """Host mirror -> device table, on the current stream (ordered between the loop's graph replays)."""
+        if self.dirty:
+            self.tab.copy_(torch.from_numpy(self.tab_h))
+            self.dirty = False
+
+
 def admit(kv: PagedKV, rows, items, end, max_new, check_every) -> int:
     """Admission of fed utterances into free decode slots (GPTEngine.decode_refill), host only.  Item j = (prefix [P_j, D],
     stop step) takes slot rows[j] with its prompt + start token at positions [end - P_j - 1, end), and its row is dealt at once
@@ -401,6 +430,7 @@ class GPTEngine:
         e._beam_cap = (0, 0, 0)
         e._kv_rows = None
         e._ids_host = None
+        e.row_sampling = None           # (allocated with the fork's own row buffers)
         e._sink = torch.zeros(4, dtype=torch.int32, device=self.device)
         return e
 
@@ -427,6 +457,7 @@ class GPTEngine:
             self.force_stop = torch.full((B,), -1, dtype=torch.int32, device=dev)
             self.adapter_ids = torch.full((B,), -1, dtype=torch.int32, device=dev)   # adapter of each row (bank attached), -1 = base
             self.row_step0 = torch.zeros(B, dtype=torch.int32, device=dev)   # loop step at which each row started (decode_refill)
+            self.row_sampling = RowSampling(B, dev)                          # each row's own sampling settings (sp given as a list)
             self.kv_share = torch.zeros(1, dtype=torch.int32, device=dev)    # (p0 << 8) | C: rows' first C keys == row 0's at p0 (itts_attn_decode)
             self.state = torch.zeros(8, dtype=torch.int32, device=dev)
             self.history = torch.zeros(B, 2048, dtype=torch.int32, device=dev)
@@ -792,7 +823,13 @@ class GPTEngine:
     def _sample(self, B, sp, dbg=None):
         """Token selection for all rows.  The loop state (step counter, cache position) is NOT advanced here: the next
         transformer step does it in its first LayerNorm launch (a launch that reads neither word), which takes a
-        device-wide fence and a returning atomic per row out of the sampling kernel."""
+        device-wide fence and a returning atomic per row out of the sampling kernel.  sp is PER_ROW: every row under its own
+        record of the device table (itts_sample_rows)."""
+        if sp is PER_ROW:
+            nat.sample_rows(self.logits[:B], self.tokens, self.history, self.finished, self.state, self.extra_ids, self.force_stop,
+                            self.row_sampling.tab, self.stop_mel, dbg, no_advance=True, row_step0=self.row_step0)
+            self._pending_bump = True
+            return
         nat.sample(self.logits[:B], self.tokens, self.history, self.finished, self.state, self.extra_ids, self.force_stop,
                    sp["repetition_penalty"], sp["temperature"], sp["top_k"], sp["top_p"], sp["do_sample"], sp["seed"],
                    self.stop_mel, dbg, no_advance=True, row_step0=self.row_step0)
@@ -954,10 +991,30 @@ class GPTEngine:
                 break
         return n
 
-    def decode(self, max_new: int, sp: dict, force_stop=None, use_graph=True, check_every=16, return_logits=False):
+    @staticmethod
+    def check_row_settings(rows, B, what="sp"):
+        """A list of per-row sampling dicts (keys do_sample, temperature, top_k, top_p, repetition_penalty, seed, stream), checked
+        on the host as the scalar form checks its arguments: ValueError before anything is launched."""
+        if len(rows) != B:
+            raise ValueError(f"{what} holds {len(rows)} rows of sampling settings for a batch of {B}")
+        return [nat.check_sample_row(d, f"{what}[{b}]") for b, d in enumerate(rows)]
+
+    def _rows_to_table(self, rows):
+        """The loop runs under per-row settings: slot b <- rows[b] (checked), seeds in the records (state[4..5] = 0)."""
+        self.state[4:6] = 0
+        self.row_sampling.set(range(len(rows)), rows)
+        self.row_sampling.flush()
+        return PER_ROW
+
+    def decode(self, max_new: int, sp, force_stop=None, use_graph=True, check_every=16, return_logits=False):
         """Run the sampling loop after prefill().  Returns codes int64 [B, n] padded with the stop token
-        (HF generate semantics: rows that emitted EOS keep emitting pad = EOS)."""
+        (HF generate semantics: rows that emitted EOS keep emitting pad = EOS).
+        sp: one dict for the whole batch, or a list of B dicts (check_row_settings) -- every row under its own settings, seed and
+        draw stream (itts_sample_rows); the captured step is the same for every such list."""
         B = self._B
+        per_row = isinstance(sp, (list, tuple))
+        if per_row:
+            sp = self.check_row_settings(sp, B)
         if self._shared_prefix is not None:
             raise ValueError("decode(): prefill(beams=n) cached the prompt once per batch element; only decode_beam() can follow it")
         if self.kv is None and self._S + max_new + 1 > self._cap_s:
@@ -971,7 +1028,7 @@ class GPTEngine:
         else:
             self.force_stop[:B] = torch.as_tensor(force_stop, dtype=torch.int32).to(self.device)
         logits_trace = [self.logits[:B].clone()] if return_logits else None
-        sp = self._seed_to_state(sp)
+        sp = self._rows_to_table(sp) if per_row else self._seed_to_state(sp)
         self._sample(B, sp)  # token 1 from the prefill logits
         n = self._token_loop(1, max_new, lambda: self._step_kernels(B, sp), self._graph_key("token", B, sp), use_graph,
                              check_every, B, each=(lambda: logits_trace.append(self.logits[:B].clone())) if return_logits else None)
@@ -1006,7 +1063,7 @@ class GPTEngine:
             slot, posi = self.kv.phys(slot, posi)          # has dealt the new rows their blocks already)
         meta = torch.from_numpy(np.concatenate([slot, posi, off, off[1:] - 1, np.asarray(rows), np.asarray(pads),
                                                 np.asarray(stops)]).astype(np.int64)).to(dev)     # one upload
-        st = {"k": k, "n": n, "i_b": meta[:M], "i_p": meta[M:2 * M],
+        st = {"k": k, "n": n, "rows_h": list(rows), "i_b": meta[:M], "i_p": meta[M:2 * M],
               "i_rows": meta[2 * M + 2 * k + 1:2 * M + 3 * k + 1],
               "pads": meta[2 * M + 3 * k + 1:2 * M + 4 * k + 1].to(torch.int32), "stops": meta[2 * M + 4 * k + 1:].to(torch.int32)}
         row_off = meta[2 * M:2 * M + k + 1].to(torch.int32)
@@ -1029,12 +1086,13 @@ class GPTEngine:
         st.update(kst=kst, vst=vst, logits=lg_t)
         return st
 
-    def _join(self, st, sp, ev=None):
+    def _join(self, st, sp, ev=None, row_sp=None):
         """The staged rows enter the loop (between two of its steps, at the n they were staged for): keys / values into the
         slots' cache rows, the first token of every new row sampled from its prefill logits -- on buffers of its own, the
         running rows' logits stay --, and the per-row state: left padding, stop step, own clock row_step0 = n - 1 (mel
         positions, history index and the repetition-penalty window count from the row's own first token).  ev: _stage ran
-        on another stream and recorded it; the loop's stream waits for it and takes its buffers over."""
+        on another stream and recorded it; the loop's stream waits for it and takes its buffers over.  row_sp (sp is PER_ROW): the
+        new rows' own settings -- their first tokens are drawn under them and their slots' records written here, with row_step0."""
         k, n, dev = st["k"], st["n"], self.device
         if ev is not None:
             main = torch.cuda.current_stream(dev)
@@ -1049,9 +1107,16 @@ class GPTEngine:
         fin_t = torch.zeros(k, dtype=torch.int32, device=dev)
         step0_t = torch.full((k,), n - 1, dtype=torch.int32, device=dev)
         self.state[2:3] -= k                               # these slots were counted as finished
-        nat.sample(st["logits"], tok_t, hist_t, fin_t, self.state, self.extra_ids, st["stops"], sp["repetition_penalty"],
-                   sp["temperature"], sp["top_k"], sp["top_p"], sp["do_sample"], sp["seed"], self.stop_mel, None, no_advance=True,
-                   row_step0=step0_t)
+        if sp is PER_ROW:
+            self.row_sampling.set(st["rows_h"], row_sp)
+            self.row_sampling.flush()
+            nat.sample_rows(st["logits"], tok_t, hist_t, fin_t, self.state, self.extra_ids, st["stops"],
+                            self.row_sampling.tab[torch.tensor(st["rows_h"], device=dev)].contiguous(), self.stop_mel, None,
+                            no_advance=True, row_step0=step0_t)
+        else:
+            nat.sample(st["logits"], tok_t, hist_t, fin_t, self.state, self.extra_ids, st["stops"], sp["repetition_penalty"],
+                       sp["temperature"], sp["top_k"], sp["top_p"], sp["do_sample"], sp["seed"], self.stop_mel, None,
+                       no_advance=True, row_step0=step0_t)
         i_rows = st["i_rows"]
         self.tokens[i_rows] = tok_t
         self.history[i_rows, 0] = tok_t
@@ -1070,6 +1135,14 @@ class GPTEngine:
             ev = torch.cuda.Event()
             ev.record(side)
         return st, ev
+
+    @staticmethod
+    def _fed_settings(item, sp_default):
+        """The checked sampling settings of a fed item of a per-row loop: its own third element, else the loop's default."""
+        own = item[2] if len(item) > 2 else None
+        if own is None and sp_default is None:
+            raise ValueError("decode_refill(): a fed item brings no sampling settings and no sp_default was given")
+        return sp_default if own is None else nat.check_sample_row(own, "a fed item's settings")
 
     def _collect_stopped(self, owner, start, n):
         """The refill loop's poll after n steps: {utterance id: codes ending with the stop token} of the rows that have stopped;
@@ -1090,8 +1163,8 @@ class GPTEngine:
                     self.kv.release(r)
         return out
 
-    def decode_refill(self, max_new: int, sp: dict, feed, force_stop=None, use_graph=True, check_every=16, positions=None,
-                      staged=True):
+    def decode_refill(self, max_new: int, sp, feed, force_stop=None, use_graph=True, check_every=16, positions=None,
+                      staged=True, sp_default=None):
         """Continuous batching: the sampling loop after prefill(), with every slot whose row has emitted its stop token
         refilled from a queue (the mitigation for mixed output lengths).  num_beams = 1 only.
         feed(k) -> up to k items (prefix_emb fp32 [P, D] = cond | text without padding, stop step or -1); fewer than k means
@@ -1107,7 +1180,18 @@ class GPTEngine:
         join at once, the loop waits.
         A row's tokens are those it would get decoded alone with the same logits (greedy: identical codes up to the usual
         reduction-order noise of a different left padding); sampled rows draw from the loop's Philox stream (row slot, loop
-        step), so they differ from a stand-alone run as two seeds do."""
+        step), so they differ from a stand-alone run as two seeds do.
+        sp as a list of B dicts (check_row_settings): every row under its own settings.  A fed item may then carry its own dict as
+        a third element, (prefix, stop step, settings); one that brings none gets sp_default.  The settings are written into the
+        slot's record at the poll where the row enters; the row draws from (its seed, its stream, its own step), wherever and
+        whenever it entered."""
+        per_row = isinstance(sp, (list, tuple))
+        if per_row:
+            sp = self.check_row_settings(sp, self._B)
+            if sp_default is not None:
+                sp_default = nat.check_sample_row(sp_default, "sp_default")
+        elif sp_default is not None:
+            raise ValueError("decode_refill(): sp_default belongs to per-row settings (sp given as a list)")
         if self.bank is not None:
             raise NotImplementedError("decode_refill(): slot refill with an adapter bank is not built")
         B, S, ce = self._B, self._S, int(check_every)
@@ -1131,10 +1215,10 @@ class GPTEngine:
         fs = [-1] * B if force_stop is None else [int(v) for v in force_stop]
         fs = [max_new - 1 if v < 0 else min(v, max_new - 1) for v in fs]
         self.force_stop[:B] = torch.tensor(fs, dtype=torch.int32).to(dev)
-        sp = self._seed_to_state(sp)
+        sp = self._rows_to_table(sp) if per_row else self._seed_to_state(sp)
         self.kv_share.zero_()                                # a refilled row 0 no longer holds the shared block where the others expect it
         owner, start = list(range(B)), [0] * B              # owner: utterance id | None (free) | -1 (reserved for staged rows)
-        ids, codes, leftover, fed_out, pending = itertools.count(B), {}, [], False, None
+        ids, codes, leftover, fed_out, pending, row_sp = itertools.count(B), {}, [], False, None, None
         stats = self.refill_stats = {"steps": 0, "polls": 0, "refill_calls": 0, "rows_refilled": 0, "staged": bool(staged)}
         main = torch.cuda.current_stream(dev)
         side = torch.cuda.Stream(device=dev) if staged else None
@@ -1148,8 +1232,8 @@ class GPTEngine:
         while True:
             # ---- A: rows staged during the last steps join here
             if pending is not None:
-                st, ev, rows = pending
-                self._join(st, sp, ev)
+                st, ev, rows, row_sp = pending
+                self._join(st, sp, ev, row_sp)
                 for r in rows:
                     owner[r], start[r] = next(ids), n - 1
                 pending = None
@@ -1160,6 +1244,12 @@ class GPTEngine:
                 items = list(feed(len(free)))
                 if len(items) > len(free):
                     raise ValueError(f"decode_refill(): feed({len(free)}) returned {len(items)} items")
+                if per_row:      # (prefix, stop step[, settings]) -> the old pairs + the rows' checked settings
+                    fed_items, fed_sp = items, [self._fed_settings(it, sp_default) for it in items]
+                    items = [tuple(it)[:2] for it in items]
+                elif any(len(it) > 2 for it in items):
+                    raise ValueError("decode_refill(): a fed item carries sampling settings but the loop runs under one dict "
+                                     "(pass sp as a list)")
                 fed_out = len(items) < len(free)
                 n_join = n + ce if staged else n
                 if limit - (S + n_join + 1) < max_new + ce:     # steps the loop could still take
@@ -1167,14 +1257,17 @@ class GPTEngine:
                 elif kv is not None:
                     k = admit(kv, free, items, S + n_join - 1, max_new, ce)
                     items, leftover = items[:k], items[k:]
+                if per_row and leftover:
+                    leftover = fed_items[len(fed_items) - len(leftover):]   # as they were fed, settings included
                 fed_out = fed_out or bool(leftover)
             if items:
                 rows, prefixes = free[: len(items)], [p for p, _ in items]
+                row_sp = fed_sp[: len(items)] if per_row else None
                 stops = [max_new - 1 if int(v) < 0 else min(int(v), max_new - 1) for _, v in items]
                 stats["refill_calls"] += 1
                 stats["rows_refilled"] += len(rows)
                 if not staged:
-                    self._join(self._stage(rows, prefixes, stops, n), sp)
+                    self._join(self._stage(rows, prefixes, stops, n), sp, row_sp=row_sp)
                     for r in rows:
                         owner[r], start[r] = next(ids), n - 1
                     items = []
@@ -1187,11 +1280,13 @@ class GPTEngine:
             if kv is not None:
                 kv.flush()
                 stats["peak_blocks"] = max(stats["peak_blocks"], kv.used_blocks())
+            if per_row:
+                self.row_sampling.flush()
             n = self._token_loop(n, n + ce, step, key, use_graph)
             # ---- D: the new rows' prompts, enqueued behind the steps on the host and run beside them on the GPU
             if items:
                 st, ev = self._stage_beside(side, fed, rows, prefixes, stops, n_join)
-                pending = (st, ev, rows)
+                pending = (st, ev, rows, row_sp)
                 for r in rows:
                     owner[r] = -1
             # ---- E: one host synchronisation: which rows have stopped
@@ -1246,6 +1341,8 @@ class GPTEngine:
         nb = int(num_beams)
         if self.bank is not None:
             raise NotImplementedError("decode_beam(): beam search with an adapter bank is not built")
+        if isinstance(sp, (list, tuple)):
+            raise NotImplementedError("decode_beam(): beam search with per-row sampling settings is not built")
         if not 1 <= int(num_return_sequences) <= nb:
             raise ValueError("num_return_sequences has to be in [1, num_beams]")   # generate() raises the same
         R = self._B

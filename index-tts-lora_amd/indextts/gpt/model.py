@@ -32,6 +32,34 @@ def sampling_params(gen: dict, seed) -> dict:
     return sp
 
 
+ROW_SAMPLING_KEYS = ("do_sample", "temperature", "top_k", "top_p", "repetition_penalty", "seed", "stream")
+
+
+def row_sampling_params(sampling, n: int, gen: dict, seed) -> list:
+    """Per-utterance sampling settings for a batch or a queue of n utterances: entry i is a dict of any of do_sample,
+    temperature, top_k, top_p, repetition_penalty, seed (and stream); what it leaves out comes from the call's own settings
+    `gen` and `seed`.  The draw stream defaults to 0 for an entry with its own seed -- such a request draws the same numbers
+    wherever it is placed -- and to the utterance's index otherwise (the call's seed is shared: the rows must not draw alike).
+    Host only: everything is checked here (ValueError), before anything touches the device.  Returns n complete dicts, what
+    GPTEngine.decode / decode_refill take as a list."""
+    if sampling is None or isinstance(sampling, dict) or len(sampling) != n:
+        raise ValueError(f"sampling must be a list of {n} dicts, one per utterance"
+                         + ("" if sampling is None or isinstance(sampling, dict) else f" (got {len(sampling)})"))
+    out = []
+    for i, e in enumerate(sampling):
+        e = {} if e is None else dict(e)
+        unknown = sorted(set(e) - set(ROW_SAMPLING_KEYS))
+        if unknown:
+            raise ValueError(f"sampling[{i}]: unknown keys {unknown} (known: {list(ROW_SAMPLING_KEYS)})")
+        d = {k: e.get(k, gen[k]) for k in ("do_sample", "temperature", "top_k", "top_p", "repetition_penalty")}
+        d["seed"] = e.get("seed", seed)
+        d["stream"] = e.get("stream", 0 if "seed" in e else i)
+        if d["top_k"] is None:
+            d["top_k"] = 0
+        out.append(nat.check_sample_row(d, f"sampling[{i}]"))
+    return out
+
+
 class UnifiedVoice:
     def __init__(self, layers=8, model_dim=512, heads=8, max_text_tokens=120, max_mel_tokens=250,
                  max_conditioning_inputs=1, mel_length_compression=1024, number_text_tokens=256, start_text_token=0,
@@ -189,19 +217,26 @@ class UnifiedVoice:
     # ---- generation -------------------------------------------------------------------------------------------
     def inference_speech(self, speech_conditioning_mel, text_inputs, cond_mel_lengths=None, input_tokens=None,
                          num_return_sequences=1, max_generate_length=None, typical_sampling=False, typical_mass=.9,
-                         speaker_ids=None, force_stop=None, seed=None, return_logits=False, adapter_ids=None, **hf):
+                         speaker_ids=None, force_stop=None, seed=None, return_logits=False, adapter_ids=None, sampling=None,
+                         **hf):
         """model.py:669-720.  Accepted generate() keywords: do_sample, top_p, top_k, temperature, repetition_penalty,
         num_beams, length_penalty.  Returns codes [B * num_return_sequences, n] (stop-token padded), like
         `output[:, trunc_index:]`: with beams the num_return_sequences best hypotheses of each element, best first; with
         sampling that many independent draws per element.
         adapter_ids (host ints, one per batch element; needs attach_lora_bank): the LoRA adapter -- the voice -- each element
-        speaks with, -1 = the base model; expanded with num_return_sequences like the rows themselves."""
+        speaks with, -1 = the base model; expanded with num_return_sequences like the rows themselves.
+        sampling (a list of dicts, one per batch element: row_sampling_params): each element under its own sampling settings and
+        seed; what an entry leaves out comes from this call's keywords.  num_beams = 1 and num_return_sequences = 1 only."""
         if self.engine is None:
             raise RuntimeError("call post_init_gpt2_config() first")
         if adapter_ids is not None:     # checked here, before the conditioner launches anything
             adapter_ids = self.engine._row_adapters(adapter_ids, int(text_inputs.shape[0]))
         if int(hf.get("num_beams", 1)) > 1 and (adapter_ids is not None or self.engine.bank is not None):
             raise NotImplementedError("beam search with an adapter bank is not built (num_beams = 1)")
+        if sampling is not None and int(hf.get("num_beams", 1)) > 1:
+            raise NotImplementedError("beam search with per-row sampling settings is not built (num_beams = 1)")
+        if sampling is not None and int(num_return_sequences) != 1:
+            raise NotImplementedError("num_return_sequences > 1 with per-row sampling settings is not built")
         if input_tokens is not None:
             raise NotImplementedError("input_tokens (continuing a given code prefix) is off the infer.py path")
         num_beams = int(hf.pop("num_beams", 1))
@@ -216,7 +251,9 @@ class UnifiedVoice:
         length_penalty = float(hf.pop("length_penalty", 1.0))  # HF default 1.0; infer.py passes 0.0
         gen = {k: hf.pop(k, v) for k, v in dict(do_sample=False, top_p=1.0, top_k=50, temperature=1.0, repetition_penalty=1.0).items()}
         sp = sampling_params(gen, torch.initial_seed() & 0x7FFFFFFFFFFFFFFF if seed is None else seed)
-        if sp["do_sample"] and sp["top_k"] <= 0:
+        if sampling is not None:        # checked here, before the conditioner launches anything
+            sampling = row_sampling_params(sampling, int(text_inputs.shape[0]), gen, sp["seed"])
+        elif sp["do_sample"] and sp["top_k"] <= 0:
             raise ValueError("do_sample=True needs top_k >= 1: the device sampler keeps at most 1024 candidates per row "
                              "(128 per beam) and refuses to truncate an unrestricted distribution silently")
         if hf:
@@ -241,7 +278,7 @@ class UnifiedVoice:
             if adapter_ids is not None:
                 adapter_ids = [v for v in adapter_ids for _ in range(nrs)]
         self.engine.prefill(emb, pad, max_new, shared_rows=shared, adapter_ids=adapter_ids)
-        out = self.engine.decode(max_new, sp, force_stop=force_stop, return_logits=return_logits)
+        out = self.engine.decode(max_new, sp if sampling is None else sampling, force_stop=force_stop, return_logits=return_logits)
         return out
 
     def attach_lora(self, adapters: dict | None, scaling: float = 1.0):

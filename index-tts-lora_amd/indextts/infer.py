@@ -23,7 +23,7 @@ import torch
 
 from indextts import _native as nat
 from indextts.BigVGAN.models import BigVGAN as Generator
-from indextts.gpt.model import UnifiedVoice, sampling_params
+from indextts.gpt.model import UnifiedVoice, row_sampling_params, sampling_params
 from indextts.utils.audio import read_audio, write_pcm16
 from indextts.utils.checkpoint import load_checkpoint
 from indextts.utils.config import Config, load_config
@@ -633,22 +633,26 @@ class IndexTTS:
         return self._finish(wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time)
 
     def infer_batch(self, cond_mel: torch.Tensor, text_token_rows: List[torch.Tensor], max_mel_tokens=600, force_stop=None,
-                    seed=1234, return_codes=False, phase_events: dict | None = None, adapter_ids=None, **generation_kwargs):
+                    seed=1234, return_codes=False, phase_events: dict | None = None, adapter_ids=None, sampling=None,
+                    **generation_kwargs):
         """Utterance-batch data path used by bench.py / the multi-GPU sharder (not in the reference API): one shared
         prompt, N independent texts decoded as ONE left-padded batch, one batched latent pass, and one vocoder call per
         group of equal-length utterances (batching unequal lengths would change the tail of the shorter waveforms).
         Returns a list of fp32 waveforms already scaled to the int16 range, like infer.py:892.
         phase_events, if given, receives torch.cuda.Event marks at the phase boundaries.
         adapter_ids (host ints, one per utterance; needs gpt.attach_lora_bank): the voice -- LoRA adapter of the bank, -1 = base
-        model -- each utterance is spoken with, in the token loop and in the latent pass."""
+        model -- each utterance is spoken with, in the token loop and in the latent pass.
+        sampling (a list of dicts, one per utterance, in the order of text_token_rows): each utterance under its own request's
+        settings -- any of do_sample, temperature, top_k, top_p, repetition_penalty, seed; what an entry leaves out comes from
+        generation_kwargs and seed (gpt.model.row_sampling_params).  num_beams = 1 only."""
         st = self._batch_tokens(cond_mel, text_token_rows, max_mel_tokens, force_stop, seed, phase_events, lazy_spk=True,
-                                adapter_ids=adapter_ids, **generation_kwargs)
+                                adapter_ids=adapter_ids, sampling=sampling, **generation_kwargs)
         outs = self._batch_waveforms(st, phase_events, reuse_prefix=True)   # serial: the KV cache still holds this batch's prompt
         return (outs, st["rows"]) if return_codes else outs
 
     def infer_queue(self, cond_mel: torch.Tensor, text_token_rows: List[torch.Tensor], slots=32, max_mel_tokens=600,
                     force_stop=None, seed=1234, return_codes=False, cache_positions=4096, check_every=16, staged=True,
-                    phase_events: dict | None = None, **generation_kwargs):
+                    phase_events: dict | None = None, sampling=None, **generation_kwargs):
         """Continuous batching (not in the reference API; SURVEY.md section 8e's mitigation for mixed output lengths): any
         number of utterances of one prompt through `slots` decode slots.  The longest texts start; whenever a row emits its
         stop token its codes are taken and its slot is refilled with the next utterance (GPTEngine.decode_refill: the new
@@ -658,10 +662,13 @@ class IndexTTS:
         num_beams = 1 only.  cache_positions bounds the KV cache (one loop runs at most that many steps past its prompt; the
         queue continues in a fresh loop after that); check_every / staged: how often the loop looks for finished rows and whether
         a refill's prefill runs on a second stream under the loop's next steps (GPTEngine.decode_refill).  Returns the waveforms
-        in the order of text_token_rows, as infer_batch."""
+        in the order of text_token_rows, as infer_batch.  sampling: as in infer_batch -- an utterance keeps its own settings, seed
+        and draw stream in whichever slot, and at whichever step, it enters."""
         gen, _ = self._gen_kwargs(generation_kwargs)
         if int(gen.get("num_beams", 1)) != 1:
             raise NotImplementedError("infer_queue: num_beams = 1 only (beam rows cannot be refilled one at a time)")
+        if sampling is not None:        # checked before anything is launched
+            sampling = row_sampling_params(sampling, len(text_token_rows), gen, seed)
         if self.gpt.engine.bank is not None:
             raise NotImplementedError("infer_queue: slot refill with an adapter bank is not built (use infer_batch)")
         if not text_token_rows:
@@ -712,9 +719,12 @@ class IndexTTS:
                 e, p = prefixes(take)
                 p = p.tolist()
                 entered.extend(take)
+                if sampling is not None:
+                    return [(e[j, p[j]:], stops[i], sampling[i]) for j, i in enumerate(take)]
                 return [(e[j, p[j]:], stops[i]) for j, i in enumerate(take)]
 
-            codes, leftover = eng.decode_refill(max_mel_tokens, sp, feed, force_stop=[stops[i] for i in first],
+            codes, leftover = eng.decode_refill(max_mel_tokens, sp if sampling is None else [sampling[i] for i in first], feed,
+                                                force_stop=[stops[i] for i in first],
                                                 positions=None if eng.kv is not None else
                                                 max(int(cache_positions), eng._S + max_mel_tokens + int(check_every) + 1),
                                                 check_every=int(check_every), staged=bool(staged))
@@ -747,7 +757,7 @@ class IndexTTS:
             phase_events[name] = e
 
     def _batch_tokens(self, cond_mel, text_token_rows, max_mel_tokens=600, force_stop=None, seed=1234, phase_events=None,
-                      lazy_spk=False, adapter_ids=None, **generation_kwargs):
+                      lazy_spk=False, adapter_ids=None, sampling=None, **generation_kwargs):
         """Stage A of infer_batch: prompt conditioning -> prefill -> sampling loop -> silence squeeze (host).  Everything
         here is latency-bound small launches; it ends with the codes on the host, as infer.py:848-861 does."""
         gen, _ = self._gen_kwargs(generation_kwargs)
@@ -755,6 +765,10 @@ class IndexTTS:
             adapter_ids = self.gpt.engine._row_adapters(adapter_ids, len(text_token_rows))
             if int(gen.get("num_beams", 1)) > 1:
                 raise NotImplementedError("beam search with an adapter bank is not built (num_beams = 1)")
+        if sampling is not None:        # checked before anything is launched
+            if int(gen.get("num_beams", 1)) > 1:
+                raise NotImplementedError("beam search with per-row sampling settings is not built (num_beams = 1)")
+            sampling = row_sampling_params(sampling, len(text_token_rows), gen, seed)
         self._mark(phase_events, "start")
         conds, spk = self._prompt_features(cond_mel, spk=not lazy_spk)   # lazy_spk: stage B asks for the speaker embedding
         L = max(int(t.numel()) for t in text_token_rows)
@@ -780,7 +794,7 @@ class IndexTTS:
         else:
             g.engine.prefill(emb, pad, max_mel_tokens, shared_rows=shared, adapter_ids=adapter_ids)
             self._mark(phase_events, "prefilled")
-            codes = g.engine.decode(max_mel_tokens, sp, force_stop=force_stop)
+            codes = g.engine.decode(max_mel_tokens, sp if sampling is None else sampling, force_stop=force_stop)
         self._mark(phase_events, "decoded")
         codes_np, lens_h = self._squeeze_silence_host(codes)   # infer.py:848-861 on the host copy: one device-to-host transfer in all
         codes_h = torch.from_numpy(codes_np)
