@@ -477,14 +477,15 @@ int itts_tanh_pcm(const void* x, float* wav, int16_t* pcm, int64_t n, int dtype,
  * residual stream, every GEMM operand in the packed activation layout.  The host side is indextts/gpt/conditioner.py.
  * ------------------------------------------------------------------------------------------------------------------ */
 /* y (T [T2][C * F2], T2 = (T-3)/2+1, F2 = (F-3)/2+1) = relu(Conv2d(1, C, 3, stride 2)(mel [T][F])) laid out as the operand of
- * the Linear(C * F2 -> d) that follows: element (t, c * F2 + f).  w [C][9], b [C] fp32. */
+ * the Linear(C * F2 -> d) that follows: element (t, c * F2 + f).  w [C][9], b [C] fp32.  Exactly the T2 * C * F2 elements of y are
+ * written. */
 int itts_subsample_conv(const float* mel, const float* w, const float* b, void* y, int T, int F, int C, int dtype, void* stream);
 
 /* Multi-head attention over a short sequence, head dim 64:  out[i] = softmax_j( scale * ((q_i + u) . k_j + (q_i + v) . p_j) ) v_j
  * for i < Tq, j < Tk.  q / k / v: T rows with the given strides (elements, multiples of 8), head h at columns [64 h, 64 h + 64).
  * pos (T [H][Tk][64], the layer's projected position table) with bias_u / bias_v (fp32 [H * 64]) = the Conformer's relative-
  * position attention WITHOUT rel_shift; pos = NULL: plain attention (the term and the biases are absent).  out: T in the packed
- * activation layout of a [Tq][H * 64] operand with out_mtp row tiles. */
+ * activation layout of a [Tq][H * 64] operand with out_mtp row tiles; rows >= Tq of the tiles are not written. */
 typedef struct itts_mha_args {
   int dtype;
   int Tq, Tk, H;
@@ -503,7 +504,7 @@ int itts_mha_small(const itts_mha_args* a, void* stream);
 
 /* The Conformer convolution module between its pointwise convolutions: x (T [T][2 C], value | gate) -> GLU -> depthwise
  * Conv1d(taps, zero "same" padding; w fp32 [C][taps], b [C]) -> LayerNorm(ln_w, ln_b, eps) -> SiLU -> y (T, packed layout of
- * [T][C] with y_mtp row tiles).  C % 128 == 0, C <= 2048; taps 7 / 15 / 31. */
+ * [T][C] with y_mtp row tiles; rows >= T of the tiles are not written).  C % 128 == 0, C <= 2048; taps 7 / 15 / 31. */
 int itts_glu_dwconv_ln_silu(const void* x, const float* w, const float* b, const float* ln_w, const float* ln_b, void* y, int T,
                             int C, int taps, int y_mtp, float eps, int dtype, void* stream);
 
@@ -511,7 +512,7 @@ int itts_glu_dwconv_ln_silu(const void* x, const float* w, const float* b, const
  *   v = (x ? x[m] : 0) + (bias ? bias : 0) + slab[0][m] + ... + slab[nslab-1][m]       (fixed order; slab fp32 [nslab][M][D])
  *   norm 1: v = LayerNorm(v; w, b, eps)     norm 2: v = v / max(|v|_2, 1e-12) * sqrt(D) * w     norm 0: as is
  *   y (fp32 [M][D], may alias x, or NULL) = v;   y_packed (T, or NULL): rows [y_row0, y_row0 + M) of a packed operand of y_mtp
- *   row tiles (0 = ceil(M / 16)).  */
+ *   row tiles (0 = ceil(M / 16)); no other row of that operand is written.  */
 typedef struct itts_rows_args {
   int dtype, M, D;
   const float* x;
@@ -528,7 +529,8 @@ typedef struct itts_rows_args {
 } itts_rows_args;
 int itts_rows(const itts_rows_args* a, void* stream);
 
-/* y (T, packed layout of [M][Kp], y_mtp row tiles, 0 = ceil(M / 16)) = gelu(h[:, Kp:]) * h[:, :Kp]  (erf gelu; h T [M][2 Kp]). */
+/* y (T, packed layout of [M][Kp], y_mtp row tiles, 0 = ceil(M / 16)) = gelu(h[:, Kp:]) * h[:, :Kp]  (erf gelu; h T [M][2 Kp]).
+ * Rows >= M of the tiles are not written. */
 int itts_geglu(const void* h, void* y, int M, int Kp, int y_mtp, int dtype, void* stream);
 
 /* The GPT prompt rows of UnifiedVoice.prepare_gpt_inputs (indextts/gpt/model.py:606-667): per batch row b the ids of text [B][L]
@@ -547,21 +549,26 @@ int itts_prefix_rows(const int64_t* text, const float* conds, int conds_rows, co
  * [frames][channels] of `mtp` row tiles; bf16 / f16 only.  The host side is indextts/BigVGAN/speaker_engine.py.
  * ------------------------------------------------------------------------------------------------------------------ */
 /* y (packed [T][Kp]) column j * F + f = x[reflect(t + (j - (taps-1)/2) * dil)][f] (x fp32 [T][F]), zeros from taps * F on: a k-tap
- * convolution with reflect "same" padding (nnet/CNN.py:430-488) becomes a plain GEMM over this operand. */
+ * convolution with reflect "same" padding (nnet/CNN.py:430-488) becomes a plain GEMM over this operand.  Rows >= T of the y_mtp
+ * tiles are not written. */
 int itts_im2col_reflect(const float* x, void* y, int T, int F, int taps, int dil, int Kp, int y_mtp, int dtype, void* stream);
 /* One step of a Res2Net block (scale 8, 64-channel chunks): cat[:, 64 c : 64 c + 64] = BN(relu(conv_k3_dil(y1 chunk c [+ cat chunk
  * c - 1 unless first]) + bias)), reflect padding; first also copies chunk 0 (cat[:, :64] = y1[:, :64]).  wp = itts_pack_weight of the
- * [3 * 64][64] matrix (row = tap * 64 + input channel); bias / scale / shift fp32 [64]. */
+ * [3 * 64][64] matrix (row = tap * 64 + input channel); bias / scale / shift fp32 [64].  Rows >= T of y1 and cat (the padding rows of
+ * the last tile) are neither read nor written, and no other column of cat is touched. */
 int itts_res2_step(const void* y1, void* cat, const void* wp, const float* bias, const float* scale, const float* shift, int T, int mtp,
                    int chunk, int dil, int first, int dtype, void* stream);
-/* gate (fp32 [C]) = sigmoid(w2 relu(w1 mean_t(y) + b1) + b2): the squeeze-and-excitation gate; w1 T [H][C], w2 T [C][H] row-major. */
+/* gate (fp32 [C]) = sigmoid(w2 relu(w1 mean_t(y) + b1) + b2): the squeeze-and-excitation gate; w1 T [H][C], w2 T [C][H] row-major.
+ * The mean runs over rows < T: the padding rows of y may hold anything. */
 int itts_se_gate(const void* y, const void* w1, const float* b1, const void* w2, const float* b2, float* gate, int T, int C, int H,
                  int mtp, int dtype, void* stream);
-/* out = gate[c] * y + res over packed [T][C] operands of one geometry (out may be a k-step run of a wider operand). */
+/* out = gate[c] * y + res over packed [T][C] operands of one geometry (out may be a k-step run of a wider operand).  Whole row tiles
+ * are mapped: the padding rows of out are written too, from the padding rows of y and res. */
 int itts_scale_resid(const void* y, const void* res, const float* gate, void* out, int T, int C, int mtp, int dtype, void* stream);
 /* Per-channel statistics over time of packed x [T][C]: weights w_t = softmax_t(logit[t][c]) (logit T row-major [T][C]) or 1 / T
  * (logit NULL); m = sum w x, s = sqrt(max(sum w (x - m)^2, 1e-12)); out (T [2 C]) = [m | s] * scale + shift (fp32 [2 C], or NULL):
- * the global-context statistics and the attentive statistics pooling + BatchNorm (ECAPA_TDNN.py:543-581). */
+ * the global-context statistics and the attentive statistics pooling + BatchNorm (ECAPA_TDNN.py:543-581).  The sums run over
+ * rows < T: the padding rows of x may hold anything. */
 int itts_col_stats(const void* x, const void* logit, const float* scale, const float* shift, void* out, int T, int C, int mtp, int dtype,
                    void* stream);
 

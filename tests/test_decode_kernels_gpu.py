@@ -68,7 +68,7 @@ import numpy as np
 import pytest
 import torch
 
-from fp64_check import check, must_fail, ulp
+from fp64_check import bad, check, fold_rows, must_fail, note, ok, tname, ulp, walk_start, walk_step  # noqa: F401
 from skinny_forms import GEMM_SHAPES, REACHABLE, form_key
 
 pytestmark = pytest.mark.gpu
@@ -100,39 +100,12 @@ def i32(v):
     return torch.tensor(np.asarray(v), dtype=torch.int32, device=DEV)
 
 
-def tname(dtype):
-    return "f16" if dtype == F16 else "bf16"
-
-
-def note(kind, what, ratio):
-    print(f"fp64 | {kind} | {what} | {ratio:.3f}")
-
-
-def ok(what, y, ref, bound, valid=None):
-    note("case", what, check(what, y, ref, bound, valid))
-
-
-def bad(what, control, y, ref, bound, valid=None):
-    note("control", f"{what}: {control}", must_fail(what, control, y, ref, bound, valid))
-
-
 # ------------------------------------------------------------------------------------------------- skinny GEMM
 def gelu_new(x):
     return 0.5 * x * (1.0 + torch.tanh(0.7978845608028654 * (x + 0.044715 * x ** 3)))
 
 
 ACT = {"store": (lambda v: v, None), "gelu": (gelu_new, 1.13), "silu": (lambda v: v * torch.sigmoid(v), 1.10)}
-
-
-def fold_rows(M, K, seed):
-    """Raw residual rows for the folded form: sigma 1, and by row index mod 4 a common offset of 0, 8 and 64 sigma and a row with
-    one outlier feature (GPT-2 residual streams have both)."""
-    h = rnd(M, K, seed=seed)
-    r = torch.arange(M, device=DEV)
-    h[r % 4 == 1] += 8.0
-    h[r % 4 == 2] += 64.0
-    h[r % 4 == 3, 7] = 60.0
-    return h
 
 
 def gemm_pre(x, w, bias, fold=None, kstat=None):
@@ -167,7 +140,7 @@ def run_gemm(nat, dtype, M, N, K, key, epi="store", ksplit=1, rpw=0, wide=False,
             PINNED.add((dtype, form_key(nat, dtype, M - 96 * ((M - 1) // 96), N, K, ksplit, rpw, wide, fold)))
     what = f"gemm {tname(dtype)} {k} M={M} N={N} K={K} {epi}" + (f" ksplit={ksplit}" if ksplit > 1 else "") + \
         (f" rows_per_wg={rpw}" if rpw else "") + (" packed-y" if ypk else "") + (f" paged{bs}" if bs else "")
-    x = (fold_rows(M, K, seed) if fold else rnd(M, K, seed=seed)).to(dtype)
+    x = (fold_rows(M, K, seed, DEV) if fold else rnd(M, K, seed=seed)).to(dtype)
     w = (rnd(K, N, seed=seed + 1) / math.sqrt(K)).to(dtype)
     bias = rnd(N, seed=seed + 2).float()
     bias[-1] = 0.75
@@ -665,26 +638,10 @@ def prefill_ref(q, k, v, qpos, lo, drop=None, causal_shift=0):
     Tmax = T.max(-1, keepdim=True).values
     delta = 2.0 ** -21 * (T + Tmax) + 2.0 ** -19                   # relative distance of the kernel's fp32 P_j from the float64 P_j
     vd = v.double().transpose(0, 1)                               # [H][J][64]
-    m = torch.full((H, Q, 1), -math.inf, dtype=torch.float64, device=DEV)
-    l = torch.zeros(H, Q, 1, dtype=torch.float64, device=DEV)
-    O, Ab, Em, Ed = (torch.zeros(H, Q, 64, dtype=torch.float64, device=DEV) for _ in range(4))
-    dbar = torch.zeros_like(l)
+    state = walk_start(H, Q, DEV)
     for jt in range(0, J, 64):
-        st, dt = s[:, :, jt:jt + 64], delta[:, :, jt:jt + 64]
-        mn = torch.maximum(m, st.max(-1, keepdim=True).values)
-        ms = torch.where(torch.isinf(mn), torch.zeros_like(mn), mn)
-        corr = torch.where(torch.isinf(m), torch.zeros_like(m), torch.exp(m - ms))
-        P = torch.exp(st - ms)
-        Pr = P.to(dtype).double()
-        near = (0.5 * ulp(P, dtype) - (P - Pr).abs()) <= dt * P
-        vt = vd[:, jt:jt + 64]
-        O = O * corr + Pr @ vt
-        Ab = Ab * corr + Pr @ vt.abs()
-        Em = Em * corr + torch.where(near & (P > 0), ulp(P, dtype), torch.zeros_like(P)) @ vt.abs()
-        Ed = Ed * corr + (P * dt) @ vt.abs()
-        dbar = dbar * corr + (P * dt).sum(-1, keepdim=True)
-        l = l * corr + P.sum(-1, keepdim=True)
-        m = mn
+        state, _ = walk_step(state, s[:, :, jt:jt + 64], delta[:, :, jt:jt + 64], vd[:, jt:jt + 64], dtype, sum_rounded=False)
+    _, l, O, Ab, Em, Ed, dbar, _ = state
     inv = torch.where(l > 0, 1.0 / torch.clamp(l, min=1e-300), torch.zeros_like(l))
     out = lambda t: (t * inv).transpose(0, 1).reshape(Q, H * 64)  # noqa: E731
     ref, A = out(O), out(Ab)

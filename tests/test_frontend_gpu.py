@@ -235,7 +235,8 @@ def _prefix_ref(t, c, text_emb, text_pos, start, stop):
     tok[:, 0] = start
     rows = torch.arange(B, device=t.device)[:, None].expand(B, L)
     tok[rows[valid], (rank + 1)[valid]] = t[valid]
-    te = text_emb[tok] + text_pos[: L + 2][None]
+    # ids past the token table and positions past the position table are clamped, as the kernel clamps them
+    te = text_emb[tok.clamp(0, text_emb.shape[0] - 1)] + text_pos[torch.arange(L + 2, device=t.device).clamp(max=text_pos.shape[0] - 1)][None]
     if c.shape[0] == 1 and B > 1:
         c = c.expand(B, -1, -1)
     row = torch.cat([c, te], dim=1)
@@ -264,6 +265,32 @@ def test_prefix_rows_matches_torch(B, L, C, D, shared):
     te, tp = rnd(V, D, seed=32), rnd(L + 2, D, seed=33)
     emb, mask, pad = nat.prefix_rows(t, conds, te, tp, start, stop)
     remb, rmask, rpad = _prefix_ref(t, conds, te, tp, start, stop)
+    assert torch.equal(mask, rmask) and torch.equal(pad, rpad)
+    assert torch.equal(emb, remb)
+
+
+@pytest.mark.parametrize("B,L,C,D,n_pos", [(2, 256, 3, 8, 0), (2, 257, 3, 8, 0), (1, 2046, 0, 4, 0), (4, 40, 2, 16, 0), (3, 40, 2, 16, 17)])
+def test_prefix_rows_edges(B, L, C, D, n_pos):
+    """The scan-pass edge (L = 256: one pass of 256 ids, 257: a second pass with one id), the longest text (L = 2046, B = 1, D = 4:
+    no id stripped, so all eight scan passes carry a non-zero base, n = 2046, pad = 0 and the stop id lands in the last slot of the
+    compacted list), a row whose ids are all stripped (start / stop ids only; row 0 where B > 1), a row where none is, an id >= n_tok
+    (clamped to the last table row) and a position table shorter than L + 2 (clamped to its last row; n_pos = 0 here means L + 2
+    rows).  Bit-exact like the test above."""
+    from indextts import _native as nat
+    g = torch.Generator().manual_seed(B * 1000 + L)
+    start, stop, V = 0, 1, 300
+    t = torch.randint(2, V, (B, L), generator=g)
+    if B > 1:
+        t[0] = torch.where(torch.arange(L) % 2 == 0, start, stop)   # every id stripped: pad = L
+        t[1, 5] = V + 1000                                          # none stripped, one id past the table
+    if B > 2:
+        t[2, L // 2:] = stop
+    t = t.to(DEV)
+    conds = rnd(1, C, D, seed=34)
+    te, tp = rnd(V, D, seed=35), rnd(n_pos or L + 2, D, seed=36)
+    emb, mask, pad = nat.prefix_rows(t, conds, te, tp, start, stop)
+    remb, rmask, rpad = _prefix_ref(t, conds, te, tp, start, stop)
+    assert pad[0].item() == (L if B > 1 else 0) and (B == 1 or pad[1].item() == 0)
     assert torch.equal(mask, rmask) and torch.equal(pad, rpad)
     assert torch.equal(emb, remb)
 
