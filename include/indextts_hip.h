@@ -173,6 +173,10 @@ int itts_gemm_skinny(const itts_skinny_args* a, void* stream);
 /* launch geometry itts_gemm_skinny would use: out8 = {grid.x, grid.y, waves per workgroup, column tiles per workgroup,
  * k-steps per wave, dynamic LDS bytes, grid.z, row tiles per workgroup} (host-only, launches nothing) */
 int itts_skinny_plan(int dtype, int M, int N, int K, int ksplit, int rows_per_wg, int wide_wg, int fold, int* out8);
+/* The same GEMM over FP8 (E4M3) weights with one fp32 scale per output column -- itts_gemm_skinny_w8, its packed weight layout,
+ * packer and planner -- is declared in indextts_hip_w8.h (new symbols: no struct or signature above changed), which this header
+ * pulls in: */
+#include "indextts_hip_w8.h"
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Tiled MFMA GEMM / 1-D convolution, channels-last.

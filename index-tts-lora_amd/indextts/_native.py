@@ -35,6 +35,16 @@ class SkinnyArgs(C.Structure):
                 ("post_scale", C.c_void_p), ("post_shift", C.c_void_p)]
 
 
+class SkinnyW8Args(C.Structure):
+    """itts_skinny_w8_args (include/indextts_hip_w8.h)."""
+    _fields_ = [("dtype", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("wp", C.c_void_p), ("w_scale", C.c_void_p),
+                ("bias", C.c_void_p), ("x", C.c_void_p), ("epi", C.c_int), ("y", C.c_void_p), ("yf", C.c_void_p),
+                ("kcache", C.c_void_p), ("vcache", C.c_void_p), ("pos", C.c_void_p), ("heads", C.c_int), ("smax", C.c_int),
+                ("ksplit", C.c_int), ("ln_c", C.c_void_p), ("ln_eps", C.c_float), ("bump", C.c_void_p), ("rows_per_wg", C.c_int),
+                ("kv_tab", C.c_void_p), ("kv_bs", C.c_int), ("x_packed", C.c_int), ("y_packed", C.c_int), ("y_row0", C.c_int),
+                ("y_mtp", C.c_int), ("x_mtp", C.c_int)]
+
+
 class MhaArgs(C.Structure):
     _fields_ = [("dtype", C.c_int), ("Tq", C.c_int), ("Tk", C.c_int), ("H", C.c_int), ("q", C.c_void_p), ("k", C.c_void_p),
                 ("v", C.c_void_p), ("q_stride", C.c_int64), ("k_stride", C.c_int64), ("v_stride", C.c_int64), ("pos", C.c_void_p),
@@ -165,8 +175,17 @@ _ROW_SIGNATURES = {
     "itts_sample_rows": (C.c_int, [C.POINTER(SampleRowsArgs), C.c_void_p]),
 }
 
+# include/indextts_hip_w8.h: the FP8 (E4M3) weight-only forms of the skinny GEMM
+_W8_SIGNATURES = {
+    "itts_packed_bytes_w8": (C.c_int64, [C.c_int, C.c_int]),
+    "itts_pack_weight_w8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "itts_gemm_skinny_w8": (C.c_int, [C.POINTER(SkinnyW8Args), C.c_void_p]),
+    "itts_skinny_plan_w8": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+}
+
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)          # what include/indextts_hip.h declares itself
 ROW_SYMBOLS = tuple(_ROW_SIGNATURES)           # what include/indextts_hip_rows.h declares
+W8_SYMBOLS = tuple(_W8_SIGNATURES)             # what include/indextts_hip_w8.h declares
 _lib = None
 
 
@@ -179,7 +198,7 @@ def lib():
             raise NativeError(f"{path} not found: build it with `make -C index-tts-lora_amd/csrc` "
                               f"(or python -c 'import __graft_entry__ as g; g.build()'). There is no fallback path.")
         L = C.CDLL(path)
-        for name, (res, args) in {**_SIGNATURES, **_ROW_SIGNATURES}.items():
+        for name, (res, args) in {**_SIGNATURES, **_ROW_SIGNATURES, **_W8_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -300,6 +319,45 @@ def gemm_skinny(dtype, M, N, K, wp, bias=None, x=None, epi=EPI_STORE, y=None, yf
     if post is not None:
         a.post_scale, a.post_shift = _p(post[0]), _p(post[1])
     _check(lib().itts_gemm_skinny(C.byref(a), _stream()), "itts_gemm_skinny")
+
+
+def pack_weight_w8(codes: torch.Tensor) -> torch.Tensor:
+    """codes uint8 [K, N] (device; E4M3 codes of utils/quant.quantize_e4m3_cols) -> the packed FP8 weight image
+    (include/indextts_hip_w8.h: 1-KiB blocks of 16 columns x 64 k)."""
+    codes = codes.contiguous()
+    _dev(codes)
+    if codes.dtype != torch.uint8 or codes.dim() != 2:
+        raise NativeError("itts_pack_weight_w8: codes must be uint8 [K, N]")
+    K, N = codes.shape
+    out = torch.empty(lib().itts_packed_bytes_w8(K, N), dtype=torch.uint8, device=codes.device)
+    _check(lib().itts_pack_weight_w8(_p(codes), _p(out), K, N, _stream()), "itts_pack_weight_w8")
+    return out
+
+
+def gemm_skinny_w8(dtype, M, N, K, wp, w_scale, bias=None, x=None, epi=EPI_STORE, y=None, yf=None, kcache=None, vcache=None,
+                   pos=None, heads=0, smax=0, ksplit=1, x_packed=False, y_packed=False, ln_c=None, ln_eps=1e-5, bump=None,
+                   rows_per_wg=0, kv_tab=None, kv_bs=0, y_row0=0, y_mtp=0, x_mtp=0):
+    """gemm_skinny over FP8 weights: wp = pack_weight_w8(codes), w_scale fp32 [N]; the accumulator is scaled per column in front
+    of the epilogue.  dtype: the activation type (bf16 / f16).  ln_c = w_scale * column sums of the decoded codes (folded form)."""
+    a = SkinnyW8Args()
+    a.dtype, a.M, a.N, a.K = dt(dtype), M, N, K
+    a.wp, a.w_scale, a.bias, a.x = _p(wp), _p(w_scale), _p(bias), _p(x)
+    a.epi, a.y, a.yf = epi, _p(y), _p(yf)
+    a.kcache, a.vcache, a.pos, a.heads, a.smax, a.ksplit = _p(kcache), _p(vcache), _p(pos), heads, smax, ksplit
+    a.x_packed, a.y_packed = int(bool(x_packed)), int(bool(y_packed))
+    a.ln_c, a.ln_eps, a.bump = _p(ln_c), float(ln_eps), _p(bump)
+    a.rows_per_wg = int(rows_per_wg)
+    a.kv_tab, a.kv_bs = _p(kv_tab), int(kv_bs)
+    a.y_row0, a.y_mtp, a.x_mtp = int(y_row0), int(y_mtp), int(x_mtp)
+    _check(lib().itts_gemm_skinny_w8(C.byref(a), _stream()), "itts_gemm_skinny_w8")
+
+
+def skinny_plan_w8(dtype, M, N, K, rows_per_wg=0, fold=False) -> dict:
+    """Launch geometry itts_gemm_skinny_w8 would use (host-only); ksteps_per_wave counts 64-k weight blocks."""
+    out = (C.c_int * 8)()
+    _check(lib().itts_skinny_plan_w8(dt(dtype), M, N, K, int(rows_per_wg), int(bool(fold)), out), "itts_skinny_plan_w8")
+    return dict(grid=(out[0], out[1], out[6]), waves=out[2], tiles_per_wg=out[3], ksteps_per_wave=out[4], lds=out[5],
+                row_tiles_per_wg=out[7])
 
 
 def subsample_conv(mel, w, b, y):

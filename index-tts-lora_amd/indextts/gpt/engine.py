@@ -21,6 +21,7 @@ from types import SimpleNamespace
 import torch
 
 from .. import _native as nat
+from ..utils import quant
 
 
 KV_TAB = 64   # ITTS_KV_TAB: ring entries of a row's block table
@@ -150,8 +151,13 @@ def admit(kv: PagedKV, rows, items, end, max_new, check_every) -> int:
 
 class GPTEngine:
     def __init__(self, W: dict, layers: int, model_dim: int, heads: int, dtype=torch.bfloat16, device="cuda",
-                 start_mel_token=8192, stop_mel_token=8193):
+                 start_mel_token=8192, stop_mel_token=8193, weight_dtype=None):
         assert model_dim == heads * 64, "kernels are specialised for head_dim 64"
+        if weight_dtype not in (None, "fp8"):
+            raise ValueError(f"weight_dtype must be None or 'fp8' (got {weight_dtype!r})")
+        # "fp8": the decode step streams E4M3 weights with one fp32 scale per output column (itts_gemm_skinny_w8; utils/quant.py);
+        # activations, accumulation, KV cache and statistics stay `dtype`.  DESIGN.md section 4.10.
+        self.weight_dtype = weight_dtype
         self.L, self.D, self.H = layers, model_dim, heads
         self.dtype, self.device = dtype, torch.device(device)
         self.start_mel, self.stop_mel = start_mel_token, stop_mel_token
@@ -178,6 +184,12 @@ class GPTEngine:
             raise ValueError("ITTS_DECODE_MODE must be 'fold' or 'launch'")
         if dtype == torch.float32:
             self.decode_mode = "launch"
+        if weight_dtype == "fp8":
+            if dtype == torch.float32:
+                raise ValueError("weight_dtype='fp8' needs 16-bit activations (dtype bf16 or f16): the FP8 GEMM converts to them")
+            if self.decode_mode != "fold":
+                raise ValueError("weight_dtype='fp8' needs the 'fold' decode step (ITTS_DECODE_MODE=launch runs split-K GEMMs, "
+                                 "which the FP8 forms do not have)")
         # launch geometry of the two GEMMs that run without split-K in "fold" mode (rows per workgroup, 16-wave workgroups)
         self.fold_rows = [int(v) for v in os.environ.get("ITTS_FOLD_ROWS", "16,16").split(",")]   # out-projection, FC2
         self.fold_rows_consumers = int(os.environ.get("ITTS_FOLD_ROWS_C", "32"))   # QKV' / FC' rows per workgroup when a step has > 32 rows
@@ -218,24 +230,53 @@ class GPTEngine:
             c = Wr.to(torch.float64).sum(0).to(torch.float32).contiguous()
             d = (bt @ Wm + W[bkey].detach().to(dev, torch.float64)).to(torch.float32).contiguous()
             return nat.pack_weight(Wr.contiguous()), c, d
+
+        def w8(w_kn):
+            """fp64 [K, N] -> (packed E4M3 image, fp32 scales [N], the dequantised matrix fp64): what the decode step streams, and
+            the values every other pass of this engine must see."""
+            codes, scale = quant.quantize_e4m3_cols(w_kn)
+            return nat.pack_weight_w8(codes), scale.contiguous(), quant.dequantize(codes, scale)
+
+        def folded_w8(l, tag, ln, wkey, bkey):
+            """The folded form over FP8 weights: gamma . W is what is quantised; c = scale . (column sums of the decoded codes), in
+            float64, so a constant row still cancels; d = beta W + b from the unquantised W (an fp32 vector, like every bias).
+            The big-M passes get the SAME weight values: LayerNorm without affine (ones, zeros), then x @ T(dequantised gamma . W)
+            + d -- the identity above with rstd (h - mean) formed by the LayerNorm launch."""
+            Wm = W[wkey].detach().to(dev, torch.float64)
+            g, bt = l[ln][0].to(torch.float64), l[ln][1].to(torch.float64)
+            l["wf_" + tag], l["s_" + tag], deq = w8(g[:, None] * Wm)
+            l["c_" + tag] = deq.sum(0).to(torch.float32).contiguous()
+            l["d_" + tag] = (bt @ Wm + W[bkey].detach().to(dev, torch.float64)).to(torch.float32).contiguous()
+            l[ln] = (torch.ones_like(l[ln][0]), torch.zeros_like(l[ln][1]))
+            l["w_" + tag], l["b_" + tag] = packed(deq), l["d_" + tag]
         for i in range(layers):
             p = f"gpt.h.{i}."
             d = dict(
                 ln1=(f32(p + "ln_1.weight"), f32(p + "ln_1.bias")),
                 ln2=(f32(p + "ln_2.weight"), f32(p + "ln_2.bias")),
-                w_qkv=packed(W[p + "attn.c_attn.weight"]), b_qkv=f32(p + "attn.c_attn.bias"),
-                w_o=packed(W[p + "attn.c_proj.weight"]), b_o=f32(p + "attn.c_proj.bias"),
-                w_fc=packed(W[p + "mlp.c_fc.weight"]), b_fc=f32(p + "mlp.c_fc.bias"),
-                w_pr=packed(W[p + "mlp.c_proj.weight"]), b_pr=f32(p + "mlp.c_proj.bias"),
+                b_qkv=f32(p + "attn.c_attn.bias"), b_o=f32(p + "attn.c_proj.bias"),
+                b_fc=f32(p + "mlp.c_fc.bias"), b_pr=f32(p + "mlp.c_proj.bias"),
             )
-            if self.decode_mode == "fold":
+            if weight_dtype != "fp8":   # (an FP8 engine packs 16-bit copies of the DEQUANTISED weights below: each weight once)
+                d.update(w_qkv=packed(W[p + "attn.c_attn.weight"]), w_o=packed(W[p + "attn.c_proj.weight"]),
+                         w_fc=packed(W[p + "mlp.c_fc.weight"]), w_pr=packed(W[p + "mlp.c_proj.weight"]))
+            if weight_dtype == "fp8":
+                folded_w8(d, "qkv", "ln1", p + "attn.c_attn.weight", p + "attn.c_attn.bias")
+                folded_w8(d, "fc", "ln2", p + "mlp.c_fc.weight", p + "mlp.c_fc.bias")
+                for tag, wkey in (("o", p + "attn.c_proj.weight"), ("pr", p + "mlp.c_proj.weight")):
+                    d["w8_" + tag], d["s_" + tag], deq = w8(W[wkey].detach().to(dev, torch.float64))
+                    d["w_" + tag] = packed(deq)       # the prefill / latent passes: 16-bit copies of the dequantised values
+            elif self.decode_mode == "fold":
                 d["wf_qkv"], d["c_qkv"], d["d_qkv"] = folded(d["ln1"], p + "attn.c_attn.weight", p + "attn.c_attn.bias")
                 d["wf_fc"], d["c_fc"], d["d_fc"] = folded(d["ln2"], p + "mlp.c_fc.weight", p + "mlp.c_fc.bias")
             self.layers.append(d)
         self.ln_f = (f32("gpt.ln_f.weight"), f32("gpt.ln_f.bias"))
         self.final_norm = (f32("final_norm.weight"), f32("final_norm.bias"))
         self.V = W["mel_head.weight"].shape[0]
-        self.w_head = packed(W["mel_head.weight"].t())
+        if weight_dtype == "fp8":   # every use of the head is a skinny GEMM: no 16-bit copy
+            self.w_head, self.s_head, _ = w8(W["mel_head.weight"].detach().to(dev, torch.float64).t())
+        else:
+            self.w_head, self.s_head = packed(W["mel_head.weight"].t()), None
         self.b_head = f32("mel_head.bias")
         self.mel_emb = f32("mel_embedding.weight")
         self.mel_pos = f32("mel_pos_embedding.emb.weight")
@@ -252,8 +293,9 @@ class GPTEngine:
         self.share_prefix = os.environ.get("ITTS_SHARE_PREFIX", "1") != "0"   # prefill(shared_rows=C): compute the shared rows once
         self.share_kv_reads = os.environ.get("ITTS_SHARE_KV_READS", "1") != "0"   # ... and let the decode attention read them from row 0
         self._sink = torch.zeros(4, dtype=torch.int32, device=dev)
-        self.weight_bytes = sum(t.numel() * t.element_size() for l in self.layers for t in
-                                (l["w_qkv"], l["w_o"], l["w_fc"], l["w_pr"])) + self.w_head.numel()
+        # the packed weights one decode step streams (FP8: one byte per weight; the scales, like the biases, are not counted)
+        step_w = ("wf_qkv", "w8_o", "wf_fc", "w8_pr") if weight_dtype == "fp8" else ("w_qkv", "w_o", "w_fc", "w_pr")
+        self.weight_bytes = sum(l[k].numel() * l[k].element_size() for l in self.layers for k in step_w) + self.w_head.numel()
 
     # ------------------------------------------------------------------------------------------------ runtime LoRA
     def attach_lora(self, adapters: dict, scaling: float):
@@ -268,6 +310,9 @@ class GPTEngine:
             packed copies here (their GEMMs have no reduce stage to carry the correction)."""
         dev, T, D = self.device, self.dtype, self.D
         W = self._W
+        if adapters and self.weight_dtype is not None:
+            raise ValueError("attach_lora(): LoRA on an FP8 base is not built (weight_dtype='fp8'): the adapters' extra columns and "
+                             "merged copies are 16-bit operands")
 
         def f32(k):
             return W[k].detach().to(dev, torch.float32)
@@ -334,6 +379,9 @@ class GPTEngine:
         k-step innermost: extending K is a re-pack, i.e. a second copy of the block weights).  A target no adapter names keeps
         its base weight and gets no shrink launch.  The decode step runs in "launch" form (the folded GEMMs take their
         LayerNorm statistics over K on the matrix pipe; the shrink needs xn = LN(h) as an operand anyway)."""
+        if self.weight_dtype is not None:
+            raise ValueError("attach_lora_bank(): LoRA on an FP8 base is not built (weight_dtype='fp8'): the bank's K-extended "
+                             "weight mixes base rows and adapter rows in one packed operand")
         if self.lora:
             raise ValueError("attach_lora_bank(): single adapters are attached (attach_lora(None) first): one or the other")
         if not self.pa:
@@ -606,8 +654,15 @@ class GPTEngine:
     def _head(self, h_rows, B):
         """ln_f -> final_norm -> mel_head on fp32 rows."""
         nat.ln_reduce(h_rows, self.ln_f[0], self.ln_f[1], self.xn, w2=self.final_norm[0], b2=self.final_norm[1], y_packed=self.pa)
-        nat.gemm_skinny(self.dtype, B, self.V, self.D, self.w_head, self.b_head, x=self.xn, epi=nat.EPI_STORE_F32,
-                        yf=self.logits, x_packed=self.pa)
+        self._head_gemm(B, self.xn, self.logits)
+
+    def _head_gemm(self, M, xn, logits):
+        """mel_head over M normalised rows (fp32 logits); FP8 weights when the engine has them."""
+        kw = dict(x=xn, epi=nat.EPI_STORE_F32, yf=logits, x_packed=self.pa)
+        if self.s_head is None:
+            nat.gemm_skinny(self.dtype, M, self.V, self.D, self.w_head, self.b_head, **kw)
+        else:
+            nat.gemm_skinny_w8(self.dtype, M, self.V, self.D, self.w_head, self.s_head, self.b_head, **kw)
 
     def _prefill_shared(self, emb, pad_h, S, C):
         """The packed prefill pass for a batch whose elements all begin with the SAME C rows (one prompt's conditioning
@@ -862,12 +917,18 @@ class GPTEngine:
         k = SimpleNamespace(embed_step=skip, attn_decode=skip, ln_reduce=skip, lora_shrink=skip) if gemm_only else nat   # every other launch
         tally = [0, 0]
 
-        def gemm(M, N, K, w, bias, epi, **kw):
-            nat.gemm_skinny(T, M, N, K, w, bias, epi=epi, **kw)
+        def gemm(M, N, K, w, bias, epi, scale=None, **kw):
+            """scale (fp32 [N]): w is a packed E4M3 image (weight_dtype "fp8"), one byte per weight."""
+            if scale is None:
+                nat.gemm_skinny(T, M, N, K, w, bias, epi=epi, **kw)
+            else:
+                kw.pop("wide_wg", None)     # (the FP8 forms have no 16-wave workgroups)
+                nat.gemm_skinny_w8(T, M, N, K, w, scale, bias, epi=epi, **kw)
             out = {nat.EPI_QKV_CACHE: es, nat.EPI_GELU_STORE: es, nat.EPI_RESID_F32: 2 * 4 + es,    # (h read and written, T copy)
                    nat.EPI_SLAB_F32: 4 * kw.get("ksplit", 1), nat.EPI_STORE_F32: 4}[epi]
             tally[0] += 1
-            tally[1] += (N * K + M * K) * es + M * N * out
+            tally[1] += N * K * (es if scale is None else 1) + M * K * es + M * N * out
+        w8 = self.weight_dtype == "fp8"
         rs0 = self.row_step0 if self._kv_rows is None else None
         kva = self._kvargs()
         attn_kw = dict(kv_rows=self._kv_rows, kv_step=step if self._kv_rows is not None else None,
@@ -888,14 +949,14 @@ class GPTEngine:
             for i, l in enumerate(self.layers):
                 gemm(B, 3 * D, D, l["wf_qkv"], l["d_qkv"], nat.EPI_QKV_CACHE, x=hb, y=self.q, kcache=self.kc[i], vcache=self.vc[i],
                      pos=pos, heads=H, smax=self._cap_s, x_packed=True, ln_c=l["c_qkv"], bump=step if (bump and i == 0) else None,
-                     rows_per_wg=r_c, **kva)
+                     rows_per_wg=r_c, scale=l.get("s_qkv"), **kva)
                 k.attn_decode(self.q, self.kc[i], self.vc[i], self.a, self.pad, pos, B, H, self._cap_s, out_packed=pa, **attn_kw)
-                gemm(B, D, D, l["w_o"], l["b_o"], nat.EPI_RESID_F32, x=self.a, yf=h, y=hb, x_packed=pa, y_packed=True,
-                     rows_per_wg=r_o, wide_wg=self.fold_wide)
+                gemm(B, D, D, l["w8_o" if w8 else "w_o"], l["b_o"], nat.EPI_RESID_F32, x=self.a, yf=h, y=hb, x_packed=pa, y_packed=True,
+                     rows_per_wg=r_o, wide_wg=self.fold_wide, scale=l.get("s_o"))
                 gemm(B, 4 * D, D, l["wf_fc"], l["d_fc"], nat.EPI_GELU_STORE, x=hb, y=self.f, x_packed=True, y_packed=pa,
-                     ln_c=l["c_fc"], rows_per_wg=r_c)
-                gemm(B, D, 4 * D, l["w_pr"], l["b_pr"], nat.EPI_RESID_F32, x=self.f, yf=h, y=hb, x_packed=pa, y_packed=True,
-                     rows_per_wg=r_p, wide_wg=self.fold_wide)
+                     ln_c=l["c_fc"], rows_per_wg=r_c, scale=l.get("s_fc"))
+                gemm(B, D, 4 * D, l["w8_pr" if w8 else "w_pr"], l["b_pr"], nat.EPI_RESID_F32, x=self.f, yf=h, y=hb, x_packed=pa,
+                     y_packed=True, rows_per_wg=r_p, wide_wg=self.fold_wide, scale=l.get("s_pr"))
             k.ln_reduce(h, self.ln_f[0], self.ln_f[1], xn, w2=self.final_norm[0], b2=self.final_norm[1], y_packed=pa)
         else:
             k.embed_step(self.tokens, self.mel_emb, self.mel_pos, step, 2 if bump else 1, h, row_step0=rs0)
@@ -936,7 +997,7 @@ class GPTEngine:
                 gemm(B, n_p, K, w, None, nat.EPI_SLAB_F32, x=self.f, yf=sl_p, ksplit=KS, x_packed=pa)
                 k.ln_reduce(h, nxt[0], nxt[1], xn, slab=sl_p, nslab=KS, bias=l["b_pr"], w2=nxt2[0], b2=nxt2[1], y_packed=pa,
                             slab_stride=n_p, lora_b=l.get("lora_b_pr"))
-        gemm(B, self.V, D, self.w_head, self.b_head, nat.EPI_STORE_F32, x=self.xn, yf=self.logits, x_packed=pa)
+        gemm(B, self.V, D, self.w_head, self.b_head, nat.EPI_STORE_F32, x=self.xn, yf=self.logits, x_packed=pa, scale=self.s_head)
         return tuple(tally)
 
     def _poll(self):
@@ -957,7 +1018,7 @@ class GPTEngine:
         every engine setting the captured launches read -- a setting changed after a capture must not replay the old variant."""
         key = (kind, B, nb, self.decode_mode, self.lora, tuple(self.fold_rows), self.fold_rows_consumers, self.fold_wide,
                self.pa, self.KSPLIT, self.skip_finished, self.share_kv_reads, self.beam_kv,
-               None if self.kv is None else self.kv.bs, tuple(sorted(sp.items())))
+               None if self.kv is None else self.kv.bs, tuple(sorted(sp.items())), ("weights", self.weight_dtype))
         # an adapter bank: its shape and targets (what the captured launches were built from) -- never the rows' ids, which are data
         return key if self.bank is None else key + (("bank",) + self.bank.sig,)
 
@@ -1082,7 +1143,7 @@ class GPTEngine:
         lg_t = torch.empty(k, self.V, dtype=torch.float32, device=dev)
         nat.ln_reduce(h[last].contiguous(), self.ln_f[0], self.ln_f[1], xn_t, w2=self.final_norm[0], b2=self.final_norm[1],
                       y_packed=self.pa)
-        nat.gemm_skinny(T, k, self.V, D, self.w_head, self.b_head, x=xn_t, epi=nat.EPI_STORE_F32, yf=lg_t, x_packed=self.pa)
+        self._head_gemm(k, xn_t, lg_t)
         st.update(kst=kst, vst=vst, logits=lg_t)
         return st
 

@@ -40,13 +40,24 @@ def set_seed(seed):
 
 
 def _resolve_dtype(name):
+    """The activation type of a precision name ("fp8": E4M3 weights under bf16 activations, see _resolve_gpt_precision)."""
     if name in ("bf16", "bfloat16"):
         return torch.bfloat16
     if name in ("fp16", "float16"):
         return torch.float16
     if name == "fp8":
-        return torch.bfloat16  # no fp8 weights path; served in bf16
+        return torch.bfloat16
     return torch.float32
+
+
+def _resolve_gpt_precision(gpt_p, quantization=None):
+    """The `gpt` entry of a precision config -> (activation dtype, weight dtype: "fp8" | None, fell_back).  "fp8" is served: E4M3
+    decode-step weights under bf16 activations.  The bitsandbytes formats (int8 / int4 / quantization.enabled) are not claimed: they
+    fall back to bf16 weights, and fell_back says so."""
+    quant = quantization or {}
+    if quant.get("enabled", False) or gpt_p in ("int8", "int4"):
+        return torch.bfloat16, None, True
+    return _resolve_dtype(gpt_p), ("fp8" if gpt_p == "fp8" else None), False
 
 
 class IndexTTS:
@@ -75,16 +86,15 @@ class IndexTTS:
             elif "inference" in self.cfg:
                 precision_config, source = self.cfg["inference"], "config.yaml [inference]"
         self.use_quantization = self.load_in_8bit = self.load_in_4bit = False
+        self.gpt_weight_dtype = None     # "fp8": E4M3 decode-step weights (precision_config gpt: "fp8")
         if precision_config and isinstance(precision_config, dict):
             gpt_p = precision_config.get("gpt", "bf16")
-            quant = precision_config.get("quantization", {}) or {}
-            if quant.get("enabled", False) or gpt_p in ("int8", "int4"):
+            self.gpt_dtype, self.gpt_weight_dtype, fell_back = _resolve_gpt_precision(gpt_p, precision_config.get("quantization", {}))
+            if fell_back:
                 print(">> [warning] bitsandbytes quantisation is not available in this build; using BF16 weights")
-                self.gpt_dtype = torch.bfloat16
-            else:
-                self.gpt_dtype = _resolve_dtype(gpt_p)
             self.vocoder_dtype = _resolve_dtype(precision_config.get("vocoder", "bf16"))
-            print(f">> [config] mixed precision ({source}): GPT={self.gpt_dtype} vocoder={self.vocoder_dtype}")
+            gpt_s = "bf16 activations / e4m3 weights" if self.gpt_weight_dtype == "fp8" else str(self.gpt_dtype)
+            print(f">> [config] mixed precision ({source}): GPT={gpt_s} vocoder={self.vocoder_dtype}")
         elif self.is_fp16:
             self.gpt_dtype, self.vocoder_dtype = torch.bfloat16, torch.float32
             print(">> [config] BF16 GPT / FP32 vocoder (legacy is_fp16)")
@@ -116,7 +126,8 @@ class IndexTTS:
         else:
             self.gpt.load_state_dict(_weights["gpt"])
         self.gpt = self.gpt.to(self.device).to(self.gpt_dtype).eval()
-        self.gpt.post_init_gpt2_config(use_deepspeed=False, kv_cache=True, half=self.gpt_dtype != torch.float32)
+        self.gpt.post_init_gpt2_config(use_deepspeed=False, kv_cache=True, half=self.gpt_dtype != torch.float32,
+                                       weight_dtype=self.gpt_weight_dtype)
         print(f">> [system] GPT loaded ({self.gpt_dtype})")
 
         self.bigvgan = Generator(self.cfg.bigvgan, use_cuda_kernel=True)
@@ -177,7 +188,8 @@ class IndexTTS:
         new_gpt = UnifiedVoice(**self.cfg.gpt)
         info = load_checkpoint(new_gpt, model_path)
         new_gpt = new_gpt.to(self.device).to(self.gpt_dtype).eval()
-        new_gpt.post_init_gpt2_config(use_deepspeed=False, kv_cache=True, half=self.gpt_dtype != torch.float32)
+        new_gpt.post_init_gpt2_config(use_deepspeed=False, kv_cache=True, half=self.gpt_dtype != torch.float32,
+                                       weight_dtype=self.gpt_weight_dtype)
         del self.gpt
         self.torch_empty_cache()
         self.gpt = new_gpt

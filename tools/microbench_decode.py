@@ -2,7 +2,8 @@
 """Slot time of each decode-step kernel inside a replayed CUDA graph (MI355X; writes gpurun_out/microbench.txt).
 
 Each experiment captures `reps` launches cycling through 24 layers' worth of distinct weights (so the weight stream is
-real HBM traffic, not L2 hits), replays the graph a few times and reports microseconds per launch."""
+real HBM traffic, not L2 hits), replays the graph a few times and reports microseconds per launch.
+  --w8: only the FP8-weight comparison (w8_report: the "fold" step's five GEMMs and a 24-layer engine, FP8 against bf16)."""
 import os
 import sys
 import time
@@ -49,6 +50,82 @@ def timed_graph(fn, reps_in_graph, replays=20):
 def rand_w(K, N):
     return nat.pack_weight((torch.randn(K, N, device=dev) * 0.02).to(T))
 
+
+def w8_report():
+    """--w8: the five decode-step GEMMs of the "fold" step at 32 rows, FP8 (E4M3) weights against bf16 from the same process, and
+    the microseconds per token of a 24-layer engine both ways (logged like every other experiment of this file).  Same method as
+    the rest of this file: warm, 24 layers' worth of distinct weights per shape, 4 passes per captured graph, 20 replays."""
+    from indextts.utils import quant
+    import weights as synth_weights
+    from indextts.gpt.engine import GPTEngine
+    log(f"==== w8 microbench {time.strftime('%H:%M:%S')} B={B} (us per launch, graph replay; bf16 | fp8 weights)")
+    log(f"library: {os.path.basename(os.environ['ITTS_HIP_LIB'])}")
+    R, V = 4, 8194
+    hb = torch.randn(nat.packed_rows(B) * D, device=dev).to(T)
+    fb = torch.randn(nat.packed_rows(B) * 4 * D, device=dev).to(T)
+    ab = torch.randn(nat.packed_rows(B) * D, device=dev).to(T)
+    hres = torch.randn(B, D, device=dev)
+    q, lg = torch.zeros(B, D, device=dev, dtype=T), torch.zeros(B, V, device=dev)
+    smax = 320
+    kc = torch.zeros(L, B, H, smax, 64, device=dev, dtype=T)
+    vc = torch.zeros(L, B, H, smax, 64, device=dev, dtype=T)
+    pos = torch.full((1,), 150, dtype=torch.int32, device=dev)
+    c3, c4 = torch.zeros(3 * D, device=dev), torch.zeros(4 * D, device=dev)     # ln_c of the folded forms
+
+    def pair(K, N):
+        w = torch.randn(K, N, device=dev) * 0.02
+        codes, scale = quant.quantize_e4m3_cols(w)
+        return nat.pack_weight(w.to(T)), nat.pack_weight_w8(codes), scale.contiguous()
+    shapes = {
+        "QKV' 1280x3840 fold + KV append": (D, 3 * D, lambda i: dict(x=hb, x_packed=True, epi=nat.EPI_QKV_CACHE, y=q, kcache=kc[i], vcache=vc[i],
+                                                                     pos=pos, heads=H, smax=smax, ln_c=c3)),
+        "out-proj 1280x1280 resid": (D, D, lambda i: dict(x=ab, x_packed=True, epi=nat.EPI_RESID_F32, yf=hres, y=hb, y_packed=True, rows_per_wg=16)),
+        "FC' 1280x5120 fold + gelu": (D, 4 * D, lambda i: dict(x=hb, x_packed=True, epi=nat.EPI_GELU_STORE, y=fb, y_packed=True,
+                                                               ln_c=c4)),
+        "FC2 5120x1280 resid": (4 * D, D, lambda i: dict(x=fb, x_packed=True, epi=nat.EPI_RESID_F32, yf=hres, y=hb, y_packed=True, rows_per_wg=16)),
+        "mel_head 1280x8194": (D, V, lambda i: dict(x=hb, x_packed=True, epi=nat.EPI_STORE_F32, yf=lg)),
+    }
+    for name, (K, N, kwf) in shapes.items():
+        ws = [pair(K, N) for _ in range(L)]
+        bias = torch.zeros(N, device=dev)
+        kws = [kwf(i) for i in range(L)]
+
+        def run16():
+            for _ in range(R):
+                for i in range(L):
+                    nat.gemm_skinny(T, B, N, K, ws[i][0], bias, **kws[i])
+
+        def run8():
+            for _ in range(R):
+                for i in range(L):
+                    nat.gemm_skinny_w8(T, B, N, K, ws[i][1], ws[i][2], bias, **kws[i])
+        u16, u8 = timed_graph(run16, R * L), timed_graph(run8, R * L)
+        log(f"{name:34s} bf16 {u16:6.2f} us ({K * N * 2 / u16 / 1e6:5.2f} TB/s) | fp8 {u8:6.2f} us ({K * N / u8 / 1e6:5.2f} TB/s)")
+        del ws
+    Wsd = {k: v.float() for k, v in synth_weights.gpt_state_dict(L, with_conditioner=False).items()}
+    emb = torch.randn(B, 60, D) * 0.5
+    pad = torch.zeros(B, dtype=torch.int32)
+    sp = dict(do_sample=True, top_p=0.8, top_k=30, temperature=1.0, repetition_penalty=10.0, seed=1)
+    steps = 120
+    for wd in (None, "fp8"):
+        eng = GPTEngine(Wsd, L, D, H, dtype=T, device=dev, weight_dtype=wd)
+        best = float("inf")
+        for rep in range(3):      # the first run captures the graph and is not counted
+            eng.prefill(emb, pad, steps + 2)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eng.decode(steps, sp, force_stop=[steps - 1] * B, check_every=steps)
+            torch.cuda.synchronize()
+            dt = (time.perf_counter() - t0) / (steps - 1) * 1e6
+            best = min(best, dt) if rep > 0 else best
+        log(f"engine 24 layers, {B} rows, weights {wd or 'bf16'}: {best:7.1f} us / token ({eng.weight_bytes / 1e6:.0f} MB streamed per token)")
+        del eng
+        torch.cuda.empty_cache()
+
+
+if "--w8" in sys.argv[1:]:
+    w8_report()
+    sys.exit(0)
 
 log(f"==== microbench {time.strftime('%H:%M:%S')} B={B}")
 tokens = torch.zeros(B, dtype=torch.int32, device=dev)
