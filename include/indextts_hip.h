@@ -209,7 +209,9 @@ typedef struct itts_conv_args {
   const int32_t* valid_rows;
   /* split-K of a plain GEMM (taps = 1, B = 1, N % 128 == 0; 0 / 1 = off, <= 64): the K range is cut into ksplit slices that run as
    * separate tiles of ONE launch, and y (fp32, y_f32 = 1) receives the slabs [ksplit][Tout][N] -- slice ks holds the rows' partial
-   * products over its K range; no bias / bias2 / resid / accumulate / act (itts_ln_reduce sums the slabs in order, adds the bias
+   * products over its K range: with KT = Cin / KS k-steps (KS = 32 columns, 16 at fp32; Cin % KS == 0, ksplit <= KT, Tin == Tout,
+   * off0 = 0, no valid_rows) slice ks covers k-steps [(ks * KT) / ksplit, ((ks + 1) * KT) / ksplit), and y_bstride / y_shift /
+   * y_limit are not read (slab ks starts at y + ks * Tout * N); no bias / bias2 / resid / accumulate / act (itts_ln_reduce sums the slabs in order, adds the bias
    * and the residual and applies the LayerNorm that follows; itts_rows sums any number of them).  For GEMMs with few output tiles (the prefill's N = 1280 projections:
    * 160 tiles of 128 x 128 for 512 workgroup slots). */
   int ksplit;
