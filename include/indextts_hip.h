@@ -177,6 +177,7 @@ int itts_skinny_plan(int dtype, int M, int N, int K, int ksplit, int rows_per_wg
  * packer and planner -- is declared in indextts_hip_w8.h (new symbols: no struct or signature above changed), which this header
  * pulls in: */
 #include "indextts_hip_w8.h"
+#include "indextts_hip_kv8.h"
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Tiled MFMA GEMM / 1-D convolution, channels-last.

@@ -183,9 +183,18 @@ _W8_SIGNATURES = {
     "itts_skinny_plan_w8": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
 }
 
+# include/indextts_hip_kv8.h: the FP8 (E4M3) KV cache of the paged sampling loop
+_KV8_SIGNATURES = {
+    "itts_attn_decode_kv8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                       C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "itts_kv8_store": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                 C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+}
+
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)          # what include/indextts_hip.h declares itself
 ROW_SYMBOLS = tuple(_ROW_SIGNATURES)           # what include/indextts_hip_rows.h declares
 W8_SYMBOLS = tuple(_W8_SIGNATURES)             # what include/indextts_hip_w8.h declares
+KV8_SYMBOLS = tuple(_KV8_SIGNATURES)           # what include/indextts_hip_kv8.h declares
 _lib = None
 
 
@@ -198,7 +207,7 @@ def lib():
             raise NativeError(f"{path} not found: build it with `make -C index-tts-lora_amd/csrc` "
                               f"(or python -c 'import __graft_entry__ as g; g.build()'). There is no fallback path.")
         L = C.CDLL(path)
-        for name, (res, args) in {**_SIGNATURES, **_ROW_SIGNATURES, **_W8_SIGNATURES}.items():
+        for name, (res, args) in {**_SIGNATURES, **_ROW_SIGNATURES, **_W8_SIGNATURES, **_KV8_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -575,6 +584,21 @@ def attn_decode(q, kcache, vcache, out, pad, pos, B, H, smax, out_packed=False, 
                                   int(bool(out_packed)), _p(kv_rows), _p(kv_step), _p(skip_rows), _p(kv_share), _p(kv_tab), int(kv_bs),
                                   _stream()),
            "itts_attn_decode")
+
+
+def attn_decode_kv8(qkv, kcache, vcache, out, pad, pos, kv_scale, B, H, out_packed=False, skip_rows=None, kv_tab=None, kv_bs=0):
+    """The decode step's attention over an FP8 paged cache, with the append of the step's own key / value
+    (include/indextts_hip_kv8.h).  qkv T [B][3 * H * 64]; kcache / vcache uint8 pools of one layer; kv_scale fp32 [2][H]."""
+    _check(lib().itts_attn_decode_kv8(_p(qkv), _p(kcache), _p(vcache), _p(out), _p(pad), _p(pos), _p(kv_scale), B, H, dt(qkv.dtype),
+                                      int(bool(out_packed)), _p(skip_rows), _p(kv_tab), int(kv_bs), _stream()), "itts_attn_decode_kv8")
+
+
+def kv8_store(qkv, kcache, vcache, kv_scale, B, S, H, pad=None, row_off=None, cache_shift=None, kv_tab=None, kv_bs=0):
+    """The prefill's k / v thirds of qkv T [rows][3 * H * 64] -> E4M3 codes in the paged pool of one layer
+    (include/indextts_hip_kv8.h): rows [B][S] with pad, or packed rows with row_off / cache_shift."""
+    _dev(qkv, kcache, vcache, kv_scale)
+    _check(lib().itts_kv8_store(_p(qkv), _p(kcache), _p(vcache), _p(kv_scale), _p(pad), _p(row_off), _p(cache_shift), B, S, H,
+                                dt(qkv.dtype), _p(kv_tab), int(kv_bs), _stream()), "itts_kv8_store")
 
 
 def attn_prefill(qkv, out, kcache, vcache, pad, B, S, H, smax):

@@ -151,8 +151,14 @@ def admit(kv: PagedKV, rows, items, end, max_new, check_every) -> int:
 
 class GPTEngine:
     def __init__(self, W: dict, layers: int, model_dim: int, heads: int, dtype=torch.bfloat16, device="cuda",
-                 start_mel_token=8192, stop_mel_token=8193, weight_dtype=None):
+                 start_mel_token=8192, stop_mel_token=8193, weight_dtype=None, kv_dtype=None):
         assert model_dim == heads * 64, "kernels are specialised for head_dim 64"
+        if kv_dtype not in (None, "fp8"):
+            raise ValueError(f"kv_dtype must be None or 'fp8' (got {kv_dtype!r})")
+        # "fp8": the paged KV cache holds one E4M3 byte per element with one power-of-two fp32 scale per (layer, K | V, head)
+        # (self.kv_scale); the decode step's attention appends and reads it (itts_attn_decode_kv8), the prefill writes it through
+        # itts_kv8_store.  Composes with weight_dtype.  DESIGN.md section 4.11.
+        self.kv_dtype = kv_dtype
         if weight_dtype not in (None, "fp8"):
             raise ValueError(f"weight_dtype must be None or 'fp8' (got {weight_dtype!r})")
         # "fp8": the decode step streams E4M3 weights with one fp32 scale per output column (itts_gemm_skinny_w8; utils/quant.py);
@@ -190,6 +196,11 @@ class GPTEngine:
             if self.decode_mode != "fold":
                 raise ValueError("weight_dtype='fp8' needs the 'fold' decode step (ITTS_DECODE_MODE=launch runs split-K GEMMs, "
                                  "which the FP8 forms do not have)")
+        if kv_dtype == "fp8":
+            if dtype == torch.float32:
+                raise ValueError("kv_dtype='fp8' needs 16-bit activations (dtype bf16 or f16): the FP8 KV kernels are built for them")
+            if self.decode_mode != "fold":
+                raise ValueError("kv_dtype='fp8' needs the 'fold' decode step (ITTS_DECODE_MODE=launch is not built for the FP8 KV cache)")
         # launch geometry of the two GEMMs that run without split-K in "fold" mode (rows per workgroup, 16-wave workgroups)
         self.fold_rows = [int(v) for v in os.environ.get("ITTS_FOLD_ROWS", "16,16").split(",")]   # out-projection, FC2
         self.fold_rows_consumers = int(os.environ.get("ITTS_FOLD_ROWS_C", "32"))   # QKV' / FC' rows per workgroup when a step has > 32 rows
@@ -205,6 +216,12 @@ class GPTEngine:
         # that takes its slot -- the loop runs for as long as the queue lasts inside a fixed pool.  ITTS_PAGED_KV=0: contiguous
         # [rows][H][smax][64] strips (what beam search uses: its per-position row table addresses whole rows).
         self.paged = os.environ.get("ITTS_PAGED_KV", "1") == "1"
+        if kv_dtype == "fp8" and not self.paged:
+            raise NotImplementedError("the FP8 KV cache (kv_dtype='fp8') is built for the paged cache only (ITTS_PAGED_KV=0 asks for "
+                                      "the contiguous one)")
+        # one scale per (layer, K | V, head), device data the kernels read: never part of a graph key.  1.0 until set_kv_scales /
+        # calibrate_kv_scales.
+        self.kv_scale = torch.ones(layers, 2, heads, dtype=torch.float32, device=self.device) if kv_dtype == "fp8" else None
         self.kv = None            # PagedKV of the batch in flight (None: contiguous cache)
         self.beam_kv = os.environ.get("ITTS_BEAM_KV", "table")
         self._kv_rows = None   # the table of the beam decode in progress (None outside decode_beam)
@@ -310,6 +327,9 @@ class GPTEngine:
             packed copies here (their GEMMs have no reduce stage to carry the correction)."""
         dev, T, D = self.device, self.dtype, self.D
         W = self._W
+        if adapters and self.kv_dtype is not None:
+            raise NotImplementedError("attach_lora(): LoRA with the FP8 KV cache (kv_dtype='fp8') is not built: adapters run the "
+                                      "7-launch decode step, whose QKV epilogue appends 16-bit keys")
         if adapters and self.weight_dtype is not None:
             raise ValueError("attach_lora(): LoRA on an FP8 base is not built (weight_dtype='fp8'): the adapters' extra columns and "
                              "merged copies are 16-bit operands")
@@ -379,6 +399,9 @@ class GPTEngine:
         k-step innermost: extending K is a re-pack, i.e. a second copy of the block weights).  A target no adapter names keeps
         its base weight and gets no shrink launch.  The decode step runs in "launch" form (the folded GEMMs take their
         LayerNorm statistics over K on the matrix pipe; the shrink needs xn = LN(h) as an operand anyway)."""
+        if self.kv_dtype is not None:
+            raise NotImplementedError("attach_lora_bank(): LoRA with the FP8 KV cache (kv_dtype='fp8') is not built: the bank runs "
+                                      "the 7-launch decode step, whose QKV epilogue appends 16-bit keys")
         if self.weight_dtype is not None:
             raise ValueError("attach_lora_bank(): LoRA on an FP8 base is not built (weight_dtype='fp8'): the bank's K-extended "
                              "weight mixes base rows and adapter rows in one packed operand")
@@ -479,6 +502,8 @@ class GPTEngine:
         e._kv_rows = None
         e._ids_host = None
         e.row_sampling = None           # (allocated with the fork's own row buffers)
+        if self.kv_scale is not None:
+            e.kv_scale = self.kv_scale.clone()   # the scales belong to the engine's cache, not to the shared weights
         e._sink = torch.zeros(4, dtype=torch.int32, device=self.device)
         return e
 
@@ -493,6 +518,8 @@ class GPTEngine:
             Bp = nat.packed_rows(B)   # the packed layout works in 16-row tiles
             Kx = 0 if self.bank is None else self.bank.Kx   # adapter bank: the operands' shrink columns (k-steps at the end)
             self.q = torch.zeros(B, self.D, dtype=T, device=dev)
+            if self.kv_dtype is not None:   # FP8 KV cache: the step's q | k | v rows, row-major (the attention launch appends k / v)
+                self.qkv = torch.zeros(B, 3 * self.D, dtype=T, device=dev)
             self.a = torch.zeros(Bp, self.D + Kx, dtype=T, device=dev)
             self.f = torch.zeros(Bp, 4 * self.D + Kx, dtype=T, device=dev)
             self.xn = torch.zeros(Bp, self.D + Kx, dtype=T, device=dev)
@@ -518,7 +545,8 @@ class GPTEngine:
             if kv is None or kv.rows < self._cap_b or kv.blocks < blocks or kv.bs != bs:
                 kv = None
                 self.kv = self._kv_pool = None          # release the old pool before the new one is allocated
-                kv = self._kv_pool = PagedKV(self.L, self.H, self._cap_b, max(blocks, 2), bs, T, dev)
+                kv = self._kv_pool = PagedKV(self.L, self.H, self._cap_b, max(blocks, 2), bs,
+                                             torch.uint8 if self.kv_dtype is not None else T, dev)
                 self._graphs.clear()
             else:
                 kv.reset()
@@ -545,8 +573,58 @@ class GPTEngine:
         """Keyword arguments that tell a kernel where position j of a cache row lives."""
         return dict(kv_tab=self.kv.tab, kv_bs=self.kv.bs) if self.kv is not None else {}
 
+    def export_kv(self, rows: int, S: int):
+        """(K, V) [L, rows, H, S, 64] of cache positions [0, S) as VALUES: dense_kv() for a 16-bit cache; for the FP8 cache the
+        decoded codes times their head's scale, fp32 (exact: an E4M3 value times a power of two)."""
+        k, v = self.dense_kv(rows, S)
+        if self.kv_dtype is None:
+            return k, v
+        sc = self.kv_scale[:, :, None, :, None, None]            # [L, 2, 1, H, 1, 1]
+        return (quant.dequantize_kv(k, sc[:, 0]).to(torch.float32), quant.dequantize_kv(v, sc[:, 1]).to(torch.float32))
+
+    # ------------------------------------------------------------------------------------------------ FP8 KV scales
+    def set_kv_scales(self, scales):
+        """scales [L][2][H] (K | V): positive powers of two, anything else is refused (the kernels and the host quantiser agree
+        bit for bit because multiplying by the inverse is exact).  Device data: no captured step is invalidated."""
+        if self.kv_dtype is None:
+            raise ValueError("set_kv_scales(): the engine has no FP8 KV cache (kv_dtype='fp8')")
+        t = torch.as_tensor(scales).detach().to("cpu", torch.float32)
+        if tuple(t.shape) != (self.L, 2, self.H):
+            raise ValueError(f"set_kv_scales(): expected shape [{self.L}, 2, {self.H}], got {list(t.shape)}")
+        if not bool(quant.is_pow2(t).all()):
+            raise ValueError("set_kv_scales(): every scale must be a positive power of two")
+        self.kv_scale.copy_(t.to(self.device))
+
+    def calibrate_kv_scales(self, prefix_emb: torch.Tensor, pad, headroom: float = 2.0):
+        """Scales from one prompt batch: runs the ordinary un-shared prefill's layer loop over prefix_emb fp32 [B, P, D] (+ the start
+        token), takes per layer and head the maximum of |k| and of |v| over the rows' real positions (torch on the layer's qkv
+        buffer: off the hot path, one host sync) and writes quant.kv_scales_from_amax of those maxima.  Nothing is cached."""
+        if self.kv_dtype is None:
+            raise ValueError("calibrate_kv_scales(): the engine has no FP8 KV cache (kv_dtype='fp8')")
+        B, P, D = prefix_emb.shape
+        S, H, dev = P + 1, self.H, self.device
+        pad_h = [int(v) for v in torch.as_tensor(pad).tolist()]
+        if self._cap_b == 0:
+            self._ensure(1, 64, paged=True, blocks=2)
+        start = self.mel_emb[self.start_mel] + self.mel_pos[0]
+        emb = torch.cat([prefix_emb.to(dev, torch.float32), start.expand(B, 1, D)], dim=1).contiguous()
+        off = [0]
+        for p in pad_h:
+            off.append(off[-1] + S - p)
+        idx = torch.cat([torch.arange(b * S + pad_h[b], (b + 1) * S) for b in range(B)])
+        row_off = torch.tensor(off, dtype=torch.int32).to(dev)
+        amax = torch.zeros(self.L, 2, H, dtype=torch.float32, device=dev)
+
+        def attn(i, qkv, att):
+            amax[i] = qkv.view(-1, 3, H, 64)[:, 1:].abs().amax(dim=(0, 3)).to(torch.float32)
+            nat.attn_prefill_packed(qkv, att, None, None, row_off, None, B, S, H, 0)
+        self._big_m_layers(emb.view(B * S, D)[idx.to(dev)], attn)
+        self.kv_scale.copy_(quant.kv_scales_from_amax(amax.cpu(), headroom).to(dev))
+        return self.kv_scale
+
     def dense_kv(self, rows: int, S: int):
-        """(K, V) T [L, rows, H, S, 64] of cache positions [0, S): a dense copy whatever the cache layout (tests, tools)."""
+        """(K, V) [L, rows, H, S, 64] of cache positions [0, S), in the cache's element type (T; uint8 codes for the FP8 cache, see
+        export_kv): a dense copy whatever the cache layout (tests, tools)."""
         if self.kv is None:
             return self.kc[:, :rows, :, :S].clone(), self.vc[:, :rows, :, :S].clone()
         import numpy as np
@@ -645,10 +723,14 @@ class GPTEngine:
 
         def attn(i, qkv, att):
             kc, vc = (self.kc[i], self.vc[i]) if use_cache else (None, None)
+            if use_cache and self.kv_dtype is not None:
+                # FP8 cache: the attention runs without a cache (a form it has), one small launch quantises the layer's k / v
+                nat.kv8_store(qkv, kc, vc, self.kv_scale[i], B, S, H, pad=pad, row_off=row_off, cache_shift=cache_shift, **kva)
+                kc = vc = None
             if row_off is None:
                 nat.attn_prefill(qkv, att, kc, vc, pad, B, S, H, self._cap_s)
             else:
-                nat.attn_prefill_packed(qkv, att, kc, vc, row_off, cache_shift, B, S, H, self._cap_s, **kva)
+                nat.attn_prefill_packed(qkv, att, kc, vc, row_off, cache_shift, B, S, H, self._cap_s, **({} if kc is None else kva))
         return self._big_m_layers(h, attn, row_ids)
 
     def _head(self, h_rows, B):
@@ -729,6 +811,11 @@ class GPTEngine:
         S = P + 1
         beams = int(beams)
         ids = self._row_adapters(adapter_ids, B)
+        if self.kv_dtype is not None:
+            if beams > 1:
+                raise NotImplementedError("beam search over the FP8 KV cache (kv_dtype='fp8') is not built")
+            if paged is not None and not paged:
+                raise NotImplementedError("the FP8 KV cache (kv_dtype='fp8') is built for the paged cache only (paged=False)")
         if ids is not None and beams > 1:
             raise NotImplementedError("beam search with an adapter bank is not built")
         if beams > 1 and self.beam_kv != "table":
@@ -740,6 +827,9 @@ class GPTEngine:
             bs = 16 if window <= (KV_TAB - 2) * 16 else 32 if window <= (KV_TAB - 2) * 32 else 64
             if window > (KV_TAB - 2) * 64:
                 use_pages = False      # a window no block table of 64 entries covers: contiguous rows
+                if self.kv_dtype is not None:
+                    raise NotImplementedError(f"the FP8 KV cache (kv_dtype='fp8') is built for the paged cache only: a window of "
+                                              f"{window} positions does not fit the block table ({(KV_TAB - 2) * 64})")
         if use_pages:
             span = lambda lo, hi: ((hi - 1) // bs) - (lo // bs) + 1   # noqa: E731  blocks that cover positions [lo, hi)
             need = sum(span(p, S + max_new + 1) for p in pad_h)
@@ -761,7 +851,8 @@ class GPTEngine:
         if ids is not None:
             self.adapter_ids[:B] = torch.tensor(ids, dtype=torch.int32).to(dev)
         # (with a bank the conditioning rows' hidden states depend on the row's adapter: nothing is shared)
-        if shared_rows and B > 1 and self.share_prefix and ids is None:
+        # (FP8 KV cache: the shared-prefix path is off in this version -- the un-shared prefill runs and kv_share stays 0)
+        if shared_rows and B > 1 and self.share_prefix and ids is None and self.kv_dtype is None:
             # every element starts with the same `shared_rows` rows (the caller's promise: one prompt's conditioning latents)
             self._head(self._prefill_shared(emb, pad_h, S, int(shared_rows)), B)
             if beams == 1 and int(shared_rows) <= 255 and self.share_kv_reads:
@@ -798,6 +889,8 @@ class GPTEngine:
     def prefill_beams(self, prefix_emb, pad, max_new: int, beams: int, shared_rows: int = 0):
         """prefill() for decode_beam(): with the row table (beam_kv = "table") the prompt is computed and cached once per batch
         element; the copy form first expands every row to `beams` identical rows, as generate() does."""
+        if self.kv_dtype is not None:
+            raise NotImplementedError("beam search over the FP8 KV cache (kv_dtype='fp8') is not built")
         if self.beam_kv == "table":
             return self.prefill(prefix_emb, pad, max_new, beams=beams, shared_rows=shared_rows)
         return self.prefill(prefix_emb.repeat_interleave(beams, dim=0), pad.repeat_interleave(beams), max_new, shared_rows=shared_rows,
@@ -847,6 +940,9 @@ class GPTEngine:
         adapter_ids: the ids prefill() was given (the default): the cached prompt K / V were computed under them, other ids are refused.
         Returns final_norm(ln_f(hidden)) fp32 [sum(m_lens), D]."""
         import numpy as np
+        if self.kv_dtype is not None:
+            raise NotImplementedError("latent_mel_rows(): the prompt-KV reuse reads the cache as T; over the FP8 KV cache "
+                                      "(kv_dtype='fp8') run latent() on the whole sequence")
         T, D, H, dev = self.dtype, self.D, self.H, self.device
         B, P = len(m_lens), self._S - 1
         ids = self._ids_host if adapter_ids is None else self._row_adapters(adapter_ids, B)
@@ -914,7 +1010,7 @@ class GPTEngine:
                 bump = getattr(self, "_pending_bump", False)
             self._pending_bump = False
         skip = lambda *a, **kw: None   # noqa: E731
-        k = SimpleNamespace(embed_step=skip, attn_decode=skip, ln_reduce=skip, lora_shrink=skip) if gemm_only else nat   # every other launch
+        k = SimpleNamespace(embed_step=skip, attn_decode=skip, attn_decode_kv8=skip, ln_reduce=skip, lora_shrink=skip) if gemm_only else nat   # every other launch
         tally = [0, 0]
 
         def gemm(M, N, K, w, bias, epi, scale=None, **kw):
@@ -924,7 +1020,7 @@ class GPTEngine:
             else:
                 kw.pop("wide_wg", None)     # (the FP8 forms have no 16-wave workgroups)
                 nat.gemm_skinny_w8(T, M, N, K, w, scale, bias, epi=epi, **kw)
-            out = {nat.EPI_QKV_CACHE: es, nat.EPI_GELU_STORE: es, nat.EPI_RESID_F32: 2 * 4 + es,    # (h read and written, T copy)
+            out = {nat.EPI_QKV_CACHE: es, nat.EPI_STORE: es, nat.EPI_GELU_STORE: es, nat.EPI_RESID_F32: 2 * 4 + es,    # (h read and written, T copy)
                    nat.EPI_SLAB_F32: 4 * kw.get("ksplit", 1), nat.EPI_STORE_F32: 4}[epi]
             tally[0] += 1
             tally[1] += N * K * (es if scale is None else 1) + M * K * es + M * N * out
@@ -946,7 +1042,22 @@ class GPTEngine:
             r_c = self.fold_rows_consumers if B > 32 else 0
             if B > 32:
                 r_o, r_p = max(r_o, 32), max(r_p, 32)
+            kv8 = self.kv_dtype is not None
             for i, l in enumerate(self.layers):
+                if kv8:
+                    # FP8 KV cache: the existing row-major STORE epilogue writes q | k | v, and the attention launch quantises and
+                    # appends the new key itself (still 5 launches per block); `bump` travels as before (it is not tied to an epilogue)
+                    gemm(B, 3 * D, D, l["wf_qkv"], l["d_qkv"], nat.EPI_STORE, x=hb, y=self.qkv, x_packed=True, ln_c=l["c_qkv"],
+                         bump=step if (bump and i == 0) else None, rows_per_wg=r_c, scale=l.get("s_qkv"))
+                    k.attn_decode_kv8(self.qkv, self.kc[i], self.vc[i], self.a, self.pad, pos, self.kv_scale[i], B, H, out_packed=pa,
+                                      skip_rows=attn_kw["skip_rows"], **kva)
+                    gemm(B, D, D, l["w8_o" if w8 else "w_o"], l["b_o"], nat.EPI_RESID_F32, x=self.a, yf=h, y=hb, x_packed=pa,
+                         y_packed=True, rows_per_wg=r_o, wide_wg=self.fold_wide, scale=l.get("s_o"))
+                    gemm(B, 4 * D, D, l["wf_fc"], l["d_fc"], nat.EPI_GELU_STORE, x=hb, y=self.f, x_packed=True, y_packed=pa,
+                         ln_c=l["c_fc"], rows_per_wg=r_c, scale=l.get("s_fc"))
+                    gemm(B, D, 4 * D, l["w8_pr" if w8 else "w_pr"], l["b_pr"], nat.EPI_RESID_F32, x=self.f, yf=h, y=hb, x_packed=pa,
+                         y_packed=True, rows_per_wg=r_p, wide_wg=self.fold_wide, scale=l.get("s_pr"))
+                    continue
                 gemm(B, 3 * D, D, l["wf_qkv"], l["d_qkv"], nat.EPI_QKV_CACHE, x=hb, y=self.q, kcache=self.kc[i], vcache=self.vc[i],
                      pos=pos, heads=H, smax=self._cap_s, x_packed=True, ln_c=l["c_qkv"], bump=step if (bump and i == 0) else None,
                      rows_per_wg=r_c, scale=l.get("s_qkv"), **kva)
@@ -1018,7 +1129,8 @@ class GPTEngine:
         every engine setting the captured launches read -- a setting changed after a capture must not replay the old variant."""
         key = (kind, B, nb, self.decode_mode, self.lora, tuple(self.fold_rows), self.fold_rows_consumers, self.fold_wide,
                self.pa, self.KSPLIT, self.skip_finished, self.share_kv_reads, self.beam_kv,
-               None if self.kv is None else self.kv.bs, tuple(sorted(sp.items())), ("weights", self.weight_dtype))
+               None if self.kv is None else self.kv.bs, tuple(sorted(sp.items())), ("weights", self.weight_dtype),
+               ("kv", self.kv_dtype))
         # an adapter bank: its shape and targets (what the captured launches were built from) -- never the rows' ids, which are data
         return key if self.bank is None else key + (("bank",) + self.bank.sig,)
 
@@ -1129,12 +1241,18 @@ class GPTEngine:
               "pads": meta[2 * M + 3 * k + 1:2 * M + 4 * k + 1].to(torch.int32), "stops": meta[2 * M + 4 * k + 1:].to(torch.int32)}
         row_off = meta[2 * M:2 * M + k + 1].to(torch.int32)
         last = meta[2 * M + k + 1:2 * M + 2 * k + 1]
-        kst = torch.empty(M, self.L, H, 64, dtype=T, device=dev)
-        vst = torch.empty(M, self.L, H, 64, dtype=T, device=dev)
+        Tkv = T if self.kv_dtype is None else torch.uint8
+        kst = torch.empty(M, self.L, H, 64, dtype=Tkv, device=dev)
+        vst = torch.empty(M, self.L, H, 64, dtype=Tkv, device=dev)
         Smax = max(lens)
 
         def attn(i, qkv, att):     # keys / values are kept aside (they enter the cache when the rows join), plain causal attention
             q4 = qkv.view(M, 3, H, 64)
+            if self.kv_dtype is not None:   # FP8 cache: the host quantiser, bit-equal to itts_kv8_store by construction
+                kst[:, i] = quant.quantize_kv_e4m3(q4[:, 1], self.kv_scale[i, 0][None, :, None])
+                vst[:, i] = quant.quantize_kv_e4m3(q4[:, 2], self.kv_scale[i, 1][None, :, None])
+                nat.attn_prefill_packed(qkv, att, None, None, row_off, None, k, Smax, H, self._cap_s)
+                return
             kst[:, i] = q4[:, 1]
             vst[:, i] = q4[:, 2]
             nat.attn_prefill_packed(qkv, att, None, None, row_off, None, k, Smax, H, self._cap_s)
@@ -1400,6 +1518,8 @@ class GPTEngine:
         num_return_sequences best hypotheses of every element, best first (row = b * num_return_sequences + rank),
         right-padded with the stop token."""
         nb = int(num_beams)
+        if self.kv_dtype is not None:
+            raise NotImplementedError("decode_beam(): beam search over the FP8 KV cache (kv_dtype='fp8') is not built")
         if self.bank is not None:
             raise NotImplementedError("decode_beam(): beam search with an adapter bank is not built")
         if isinstance(sp, (list, tuple)):
@@ -1490,6 +1610,6 @@ class GPTEngine:
 
     def step_bytes(self, B: int, ctx: int) -> int:
         """Algorithmic HBM bytes of one decode step: weights once + KV read + KV append."""
-        es = 4 if self.dtype == torch.float32 else 2
+        es = 1 if self.kv_dtype is not None else 4 if self.dtype == torch.float32 else 2   # bytes per cached element
         kv = self.L * 2 * self.D * es
         return self.weight_bytes + B * ctx * kv + B * kv

@@ -123,9 +123,10 @@ class UnifiedVoice:
     def eval(self):
         return self
 
-    def post_init_gpt2_config(self, use_deepspeed=False, kv_cache=False, half=False, weight_dtype=None):
+    def post_init_gpt2_config(self, use_deepspeed=False, kv_cache=False, half=False, weight_dtype=None, kv_dtype=None):
         """Reference: builds GPT2InferenceModel (model.py:395-432).  Here: packs the weights into the HIP engine.
-        weight_dtype "fp8": the decode step streams E4M3 weights (GPTEngine); None: weights in the activation type."""
+        weight_dtype "fp8": the decode step streams E4M3 weights (GPTEngine); None: weights in the activation type.
+        kv_dtype "fp8": the sampling loop's KV cache holds E4M3 codes (GPTEngine); None: the activation type."""
         if self.device.type != "cuda":
             raise RuntimeError("UnifiedVoice runs on the HIP kernels only: move it to a cuda device (no CPU fallback)")
         need = ["gpt.ln_f.weight", "mel_head.weight", "mel_embedding.weight", "text_embedding.weight"]
@@ -133,7 +134,8 @@ class UnifiedVoice:
         if missing:
             raise RuntimeError(f"checkpoint is missing {missing}")
         self.engine = GPTEngine(self._sd, self.layers, self.model_dim, self.heads, dtype=self.dtype, device=self.device,
-                                start_mel_token=self.start_mel_token, stop_mel_token=self.stop_mel_token, weight_dtype=weight_dtype)
+                                start_mel_token=self.start_mel_token, stop_mel_token=self.stop_mel_token, weight_dtype=weight_dtype,
+                                kv_dtype=kv_dtype)
         self.inference_model = self.engine
         return self
 

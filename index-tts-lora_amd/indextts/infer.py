@@ -60,6 +60,16 @@ def _resolve_gpt_precision(gpt_p, quantization=None):
     return _resolve_dtype(gpt_p), ("fp8" if gpt_p == "fp8" else None), False
 
 
+def _resolve_kv_cache(name):
+    """The `kv_cache` entry of a precision config -> the engine's kv_dtype: "auto" (the default) = the activation type (None);
+    "fp8" = one E4M3 byte per cached element (GPTEngine(kv_dtype="fp8")).  Any other value is an error."""
+    if name is None or name == "auto":
+        return None
+    if name == "fp8":
+        return "fp8"
+    raise ValueError(f"precision_config: kv_cache must be 'auto' or 'fp8' (got {name!r})")
+
+
 class IndexTTS:
     def __init__(self, cfg_path="checkpoints/config.yaml", model_dir="checkpoints", is_fp16=True, device=None,
                  use_cuda_kernel=None, speaker_info_path=None, precision_config=None, gpt_path=None,
@@ -87,14 +97,17 @@ class IndexTTS:
                 precision_config, source = self.cfg["inference"], "config.yaml [inference]"
         self.use_quantization = self.load_in_8bit = self.load_in_4bit = False
         self.gpt_weight_dtype = None     # "fp8": E4M3 decode-step weights (precision_config gpt: "fp8")
+        self.kv_cache_dtype = None       # "fp8": E4M3 KV cache of the sampling loop (precision_config kv_cache: "fp8")
         if precision_config and isinstance(precision_config, dict):
             gpt_p = precision_config.get("gpt", "bf16")
             self.gpt_dtype, self.gpt_weight_dtype, fell_back = _resolve_gpt_precision(gpt_p, precision_config.get("quantization", {}))
             if fell_back:
                 print(">> [warning] bitsandbytes quantisation is not available in this build; using BF16 weights")
             self.vocoder_dtype = _resolve_dtype(precision_config.get("vocoder", "bf16"))
+            self.kv_cache_dtype = _resolve_kv_cache(precision_config.get("kv_cache", "auto"))
             gpt_s = "bf16 activations / e4m3 weights" if self.gpt_weight_dtype == "fp8" else str(self.gpt_dtype)
-            print(f">> [config] mixed precision ({source}): GPT={gpt_s} vocoder={self.vocoder_dtype}")
+            kv_s = "e4m3" if self.kv_cache_dtype == "fp8" else "auto"
+            print(f">> [config] mixed precision ({source}): GPT={gpt_s} kv_cache={kv_s} vocoder={self.vocoder_dtype}")
         elif self.is_fp16:
             self.gpt_dtype, self.vocoder_dtype = torch.bfloat16, torch.float32
             print(">> [config] BF16 GPT / FP32 vocoder (legacy is_fp16)")
@@ -127,7 +140,7 @@ class IndexTTS:
             self.gpt.load_state_dict(_weights["gpt"])
         self.gpt = self.gpt.to(self.device).to(self.gpt_dtype).eval()
         self.gpt.post_init_gpt2_config(use_deepspeed=False, kv_cache=True, half=self.gpt_dtype != torch.float32,
-                                       weight_dtype=self.gpt_weight_dtype)
+                                       weight_dtype=self.gpt_weight_dtype, kv_dtype=self.kv_cache_dtype)
         print(f">> [system] GPT loaded ({self.gpt_dtype})")
 
         self.bigvgan = Generator(self.cfg.bigvgan, use_cuda_kernel=True)
@@ -189,7 +202,7 @@ class IndexTTS:
         info = load_checkpoint(new_gpt, model_path)
         new_gpt = new_gpt.to(self.device).to(self.gpt_dtype).eval()
         new_gpt.post_init_gpt2_config(use_deepspeed=False, kv_cache=True, half=self.gpt_dtype != torch.float32,
-                                       weight_dtype=self.gpt_weight_dtype)
+                                       weight_dtype=self.gpt_weight_dtype, kv_dtype=self.kv_cache_dtype)
         del self.gpt
         self.torch_empty_cache()
         self.gpt = new_gpt
@@ -404,6 +417,29 @@ class IndexTTS:
             self._cache_spk = self.bigvgan.speaker_embedding(cond_mel.transpose(1, 2))
         return self._cache_spk
 
+    def calibrate_kv(self, audio_prompt, text):
+        """FP8 KV cache (precision_config kv_cache: "fp8"): choose the cache's scales from one prompt.  audio_prompt: a path (as
+        infer()) or a prompt mel tensor (as infer_batch()); text: a string (split into sentences as infer() does) or a list of
+        token-id rows.  Builds the prompt rows as infer does and runs GPTEngine.calibrate_kv_scales over them.  Until this is
+        called every scale is 1.0.  Returns the scale table [L, 2, H]."""
+        eng = self.gpt.engine
+        if eng.kv_dtype is None:
+            raise ValueError("calibrate_kv(): the KV cache is not FP8 (precision_config={'kv_cache': 'fp8'})")
+        cond_mel = audio_prompt if torch.is_tensor(audio_prompt) else self._prompt(audio_prompt)
+        if isinstance(text, str):
+            sents = self.tokenizer.split_sentences(self.tokenizer.tokenize(text), 120)
+            rows = [torch.tensor(self.tokenizer.convert_tokens_to_ids(sn), dtype=torch.int32) for sn in sents]
+        else:
+            rows = [torch.as_tensor(t).reshape(-1).to("cpu", torch.int32) for t in text]
+        if not rows:
+            raise ValueError("calibrate_kv(): no text rows")
+        conds = self._prompt_features(cond_mel, spk=False)[0] if torch.is_tensor(audio_prompt) else self._conds(cond_mel)
+        batch_h = torch.full((len(rows), max(int(t.numel()) for t in rows)), self.cfg.gpt.stop_text_token, dtype=torch.int32)
+        for i, t in enumerate(rows):
+            batch_h[i, : t.numel()] = t
+        emb, pad = self.gpt.prefix_rows(conds, batch_h)
+        return eng.calibrate_kv_scales(emb, pad)
+
     @staticmethod
     def _gen_kwargs(kw):
         return dict(do_sample=kw.pop("do_sample", True), top_p=kw.pop("top_p", 0.8), top_k=kw.pop("top_k", 30),
@@ -438,7 +474,7 @@ class IndexTTS:
         cache (GPTEngine.latent_mel_rows: same bits, ~40 % fewer GEMM rows).
         adapter_ids: the rows' adapters of an attached bank (with reuse_prefix: the ids the cached prompt was prefilled under)."""
         g, eng, dev = self.gpt, self.gpt.engine, self.device
-        if reuse_prefix and self.reuse_prompt_kv:
+        if reuse_prefix and self.reuse_prompt_kv and eng.kv_dtype is None:   # (an FP8 cache holds codes: the prompt rows are recomputed)
             cl = [int(c.numel()) for c in code_rows]
             flat = torch.cat([c.reshape(-1).long() for c in code_rows]).cpu().numpy() if code_rows else np.zeros(0, np.int64)
             # start | codes | stop of every row and the position of each token in its row, for all rows at once

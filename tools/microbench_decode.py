@@ -3,7 +3,9 @@
 
 Each experiment captures `reps` launches cycling through 24 layers' worth of distinct weights (so the weight stream is
 real HBM traffic, not L2 hits), replays the graph a few times and reports microseconds per launch.
-  --w8: only the FP8-weight comparison (w8_report: the "fold" step's five GEMMs and a 24-layer engine, FP8 against bf16)."""
+  --w8: only the FP8-weight comparison (w8_report: the "fold" step's five GEMMs and a 24-layer engine, FP8 against bf16).
+  --kv8: only the FP8 KV cache comparison (kv8_report: the decode attention per launch at config 3's contexts, paged 16-bit cache
+         against the E4M3 cache, and a 24-layer engine's us per token with both caches, bf16 and FP8 weights)."""
 import os
 import sys
 import time
@@ -122,6 +124,96 @@ def w8_report():
         del eng
         torch.cuda.empty_cache()
 
+
+def kv8_report():
+    """--kv8: itts_attn_decode (paged, 16-bit pool; its QKV GEMM appends) against itts_attn_decode_kv8 (E4M3 pool; appends itself)
+    per launch at config 3's contexts (75 / 151 / 216 keys), 32 rows, 24 layers' distinct pools; then the QKV GEMM with the
+    KV-append epilogue against the row-major STORE epilogue the FP8 cache uses; then a 24-layer engine's us per token, 16-bit
+    against FP8 cache, with bf16 and with FP8 weights.  Same method as the rest of this file."""
+    import weights as synth_weights
+    from indextts.gpt.engine import GPTEngine
+    log(f"==== kv8 microbench {time.strftime('%H:%M:%S')} B={B} (us per launch, graph replay; 16-bit | fp8 KV cache)")
+    log(f"library: {os.path.basename(os.environ['ITTS_HIP_LIB'])}")
+    R, bs = 4, 16
+    nblk = 320 // bs
+    tab = torch.zeros(B, 64, dtype=torch.int32)
+    tab[:, :nblk] = (1 + torch.randperm(B * nblk)).view(B, nblk).to(torch.int32)
+    tab = tab.to(dev)
+    blocks = 1 + B * nblk
+    kc16 = torch.randn(L, blocks, H, bs, 64, device=dev).to(T)
+    vc16 = torch.randn(L, blocks, H, bs, 64, device=dev).to(T)
+    kc8 = (torch.randn(L, blocks, H, bs, 64, device=dev) * 16).to(torch.float8_e4m3fn).view(torch.uint8)
+    vc8 = (torch.randn(L, blocks, H, bs, 64, device=dev) * 16).to(torch.float8_e4m3fn).view(torch.uint8)
+    scale = torch.full((L, 2, H), 2.0 ** -4, device=dev)
+    q = torch.randn(B, D, device=dev).to(T)
+    qkv = torch.randn(B, 3 * D, device=dev).to(T)
+    a = torch.zeros(nat.packed_rows(B) * D, device=dev, dtype=T)
+    pad = torch.zeros(B, dtype=torch.int32, device=dev)
+    for ctx in (75, 151, 216):
+        pos = torch.full((1,), ctx - 1, dtype=torch.int32, device=dev)
+
+        def run16():
+            for _ in range(R):
+                for i in range(L):
+                    nat.attn_decode(q, kc16[i], vc16[i], a, pad, pos, B, H, 0, out_packed=True, kv_tab=tab, kv_bs=bs)
+
+        def run8():
+            for _ in range(R):
+                for i in range(L):
+                    nat.attn_decode_kv8(qkv, kc8[i], vc8[i], a, pad, pos, scale[i], B, H, out_packed=True, kv_tab=tab, kv_bs=bs)
+        u16, u8 = timed_graph(run16, R * L), timed_graph(run8, R * L)
+        by = B * ctx * 2 * D
+        log(f"attn_decode ctx={ctx:3d}  16-bit {u16:6.2f} us ({by * 2 / u16 / 1e6:5.2f} TB/s) | fp8 + append {u8:6.2f} us ({by / u8 / 1e6:5.2f} TB/s)")
+    hb = torch.randn(nat.packed_rows(B) * D, device=dev).to(T)
+    c3, b3 = torch.zeros(3 * D, device=dev), torch.zeros(3 * D, device=dev)
+    ws = [rand_w(D, 3 * D) for _ in range(L)]
+    pos = torch.full((1,), 150, dtype=torch.int32, device=dev)
+
+    def qkv_cache():
+        for _ in range(R):
+            for i in range(L):
+                nat.gemm_skinny(T, B, 3 * D, D, ws[i], b3, x=hb, x_packed=True, epi=nat.EPI_QKV_CACHE, y=q, kcache=kc16[i], vcache=vc16[i],
+                                pos=pos, heads=H, smax=0, ln_c=c3, kv_tab=tab, kv_bs=bs)
+
+    def qkv_store():
+        for _ in range(R):
+            for i in range(L):
+                nat.gemm_skinny(T, B, 3 * D, D, ws[i], b3, x=hb, x_packed=True, epi=nat.EPI_STORE, y=qkv, ln_c=c3)
+    log(f"QKV' 1280x3840 fold: KV-append epilogue {timed_graph(qkv_cache, R * L):6.2f} us | row-major STORE {timed_graph(qkv_store, R * L):6.2f} us")
+    del ws, kc16, vc16, kc8, vc8
+    torch.cuda.empty_cache()
+    Wsd = {k: v.float() for k, v in synth_weights.gpt_state_dict(L, with_conditioner=False).items()}
+    emb = torch.randn(B, 60, D) * 0.5
+    pad_h = torch.zeros(B, dtype=torch.int32)
+    sp = dict(do_sample=True, top_p=0.8, top_k=30, temperature=1.0, repetition_penalty=10.0, seed=1)
+    steps = 120
+    for wd in (None, "fp8"):
+        for kvd in (None, "fp8"):
+            eng = GPTEngine(Wsd, L, D, H, dtype=T, device=dev, weight_dtype=wd, kv_dtype=kvd)
+            if kvd:
+                eng.calibrate_kv_scales(emb, pad_h)
+            best, pre = float("inf"), float("inf")
+            for rep in range(3):      # the first run captures the graph and is not counted
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                eng.prefill(emb, pad_h, steps + 2)
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                eng.decode(steps, sp, force_stop=[steps - 1] * B, check_every=steps)
+                torch.cuda.synchronize()
+                dt = (time.perf_counter() - t1) / (steps - 1) * 1e6
+                if rep > 0:
+                    best, pre = min(best, dt), min(pre, (t1 - t0) * 1e3)
+            pool = (eng.kv.kc.numel() * eng.kv.kc.element_size() * 2) / 1e6
+            log(f"engine 24 layers, {B} rows, weights {wd or 'bf16'}, KV cache {kvd or '16-bit'}: {best:7.1f} us / token, prefill {pre:6.2f} ms, "
+                f"pool {pool:.1f} MB, {eng.step_bytes(B, 151) / 1e6:.0f} MB per token at 151 keys")
+            del eng
+            torch.cuda.empty_cache()
+
+
+if "--kv8" in sys.argv[1:]:
+    kv8_report()
+    sys.exit(0)
 
 if "--w8" in sys.argv[1:]:
     w8_report()
