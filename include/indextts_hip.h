@@ -515,6 +515,9 @@ int itts_mha_small(const itts_mha_args* a, void* stream);
 int itts_glu_dwconv_ln_silu(const void* x, const float* w, const float* b, const float* ln_w, const float* ln_b, void* y, int T,
                             int C, int taps, int y_mtp, float eps, int dtype, void* stream);
 
+/* the three launches above over N prompts of different lengths at once (a device segment table) */
+#include "indextts_hip_prompts.h"
+
 /* Row operations on an fp32 residual stream [M][D] (D % 4 == 0, D <= 2048):
  *   v = (x ? x[m] : 0) + (bias ? bias : 0) + slab[0][m] + ... + slab[nslab-1][m]       (fixed order; slab fp32 [nslab][M][D])
  *   norm 1: v = LayerNorm(v; w, b, eps)     norm 2: v = v / max(|v|_2, 1e-12) * sqrt(D) * w     norm 0: as is

@@ -21,15 +21,15 @@ namespace itts {
 // and keeps its 3 x 3 input window in registers, a wave walks its share of the channels with the nine weights and the bias as
 // wave-uniform operands: nine FMAs per output; the wave's run of the row leaves through LDS as 16-byte vectors.
 // ---------------------------------------------------------------------------------------------------------------
+// One output row: `mel` is the first frame of the row's prompt, t the row's index within that prompt, yr the row's C * F2 outputs.
 template <typename T, bool STAGED>
-__global__ __launch_bounds__(512) void subsample_conv_kernel(const float* __restrict__ mel, const float* __restrict__ w,
-                                                             const float* __restrict__ b, T* __restrict__ y, int F, int C, int F2) {
+__device__ __forceinline__ void subsample_conv_row(const float* __restrict__ mel, const float* __restrict__ w,
+                                                   const float* __restrict__ b, T* __restrict__ yr, int t, int F, int C, int F2) {
   extern __shared__ __attribute__((aligned(16))) char sub_lds[];   // STAGED: the wave's run of the output row, written out as 16-byte vectors
-  const int t = blockIdx.x, lane = threadIdx.x & 63;
+  const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), NW = blockDim.x >> 6;
   const int cpw = (C + NW - 1) / NW;                 // channels per wave, a contiguous run
   const int c_begin = wave * cpw, c_end = min(C, c_begin + cpw);
-  T* yr = y + (int64_t)t * C * F2;
   T* stage = reinterpret_cast<T*>(sub_lds) + (size_t)wave * cpw * F2;
   for (int f0 = 0; f0 < F2; f0 += 64) {
     const int f = f0 + lane;
@@ -71,6 +71,45 @@ __global__ __launch_bounds__(512) void subsample_conv_kernel(const float* __rest
   }
 }
 
+template <typename T, bool STAGED>
+__global__ __launch_bounds__(512) void subsample_conv_kernel(const float* __restrict__ mel, const float* __restrict__ w,
+                                                             const float* __restrict__ b, T* __restrict__ y, int F, int C, int F2) {
+  const int t = blockIdx.x;
+  subsample_conv_row<T, STAGED>(mel, w, b, y + (int64_t)t * C * F2, t, F, C, F2);
+}
+
+// Segment lookup of the *_seg kernels (include/indextts_hip_prompts.h): the workgroup's 16-row tile of the launch's row space
+// names its segment, whose record is wave-uniform and goes to SGPRs.  false: the tile belongs to no segment.
+struct SegRec {
+  int row0, len, src0, src_len, kb_row0, kb_len, out_row0;
+};
+__device__ __forceinline__ bool seg_of_tile(const int32_t* __restrict__ seg, int nseg, int tile, SegRec& r) {
+  const int s = __builtin_amdgcn_readfirstlane(seg[nseg * ITTS_SEG_WORDS + tile]);
+  if (s < 0 || s >= nseg) return false;
+  const int32_t* q = seg + s * ITTS_SEG_WORDS;
+  r.row0 = __builtin_amdgcn_readfirstlane(q[0]);
+  r.len = __builtin_amdgcn_readfirstlane(q[1]);
+  r.src0 = __builtin_amdgcn_readfirstlane(q[2]);
+  r.src_len = __builtin_amdgcn_readfirstlane(q[3]);
+  r.kb_row0 = __builtin_amdgcn_readfirstlane(q[4]);
+  r.kb_len = __builtin_amdgcn_readfirstlane(q[5]);
+  r.out_row0 = __builtin_amdgcn_readfirstlane(q[6]);
+  return true;
+}
+
+// N prompts in one launch: one workgroup per row of the 16-aligned row space; mel is the prompts' frames one after another
+template <typename T, bool STAGED>
+__global__ __launch_bounds__(512) void subsample_conv_seg_kernel(const float* __restrict__ mel, const float* __restrict__ w,
+                                                                 const float* __restrict__ b, T* __restrict__ y,
+                                                                 const int32_t* __restrict__ seg, int nseg, int F, int C, int F2) {
+  const int m = blockIdx.x;
+  SegRec r;
+  if (!seg_of_tile(seg, nseg, m >> 4, r)) return;
+  const int t = m - r.row0;
+  if (t < 0 || t >= r.len) return;
+  subsample_conv_row<T, STAGED>(mel + (int64_t)r.src0 * F, w, b, y + (int64_t)m * C * F2, t, F, C, F2);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Small multi-head attention, head dim 64.  grid (ceil(Tq / 16), H): one 16-row query tile per workgroup, whose 4 waves SPLIT
 // THE KEYS (32-key steps dealt round-robin) and merge their partial softmax states through LDS at the end -- a prompt is ~150
@@ -99,8 +138,14 @@ constexpr int MHA_RS = 72;    // LDS row stride of the V image (elements): 144 b
 
 typedef short mha_v4s __attribute__((__vector_size__(4 * sizeof(short))));
 
-template <typename T, bool RELPOS>
-__global__ __launch_bounds__(256) void mha_small_kernel(MhaParams p) {
+// The segmented form's extras (wave-uniform): keys [0, ka_len) of the segment are rows ka_row0 + j of k / v, the rest rows
+// kb_row0 + j - ka_len; pos holds pos_tk rows per head; the output rows start at out_row0.  SEG = false: one range from row 0.
+struct MhaSeg {
+  int ka_len, ka_row0, kb_row0, pos_tk, out_row0;
+};
+
+template <typename T, bool RELPOS, bool SEG>
+__device__ __forceinline__ void mha_small_tile(const MhaParams& p, const MhaSeg& sg, const int q0, const int h) {
   typedef Elem<T> EL;
   typedef typename EL::frag frag;
   __shared__ __attribute__((aligned(16))) T Vimg[4][32 * MHA_RS];
@@ -108,9 +153,12 @@ __global__ __launch_bounds__(256) void mha_small_kernel(MhaParams p) {
   __shared__ float ml[4][16][2];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, r = lane & 15;
-  const int h = blockIdx.y;
-  const int q0 = (int)blockIdx.x * 16;
   T* Vi = Vimg[wave];
+  auto key_row = [&](int64_t j) -> int64_t {        // row of k / v that holds key j of this attention
+    if constexpr (SEG) return j < sg.ka_len ? sg.ka_row0 + j : sg.kb_row0 + (j - sg.ka_len);
+    else return j;
+  };
+  const int pos_tk = SEG ? sg.pos_tk : p.Tk;
 
   // query fragments (B operand: column = query row r, k = feature dims 32 kk + 8 g .. + 7), with the two position biases added
   frag qu[2], qv[2];
@@ -146,11 +194,11 @@ __global__ __launch_bounds__(256) void mha_small_kernel(MhaParams p) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int64_t key = min(kb + 16 * j + r, p.Tk - 1);        // rows past the end are masked below
-      const T* kr = (const T*)p.k + key * p.ks + h * 64 + 8 * g;
+      const T* kr = (const T*)p.k + key_row(key) * p.ks + h * 64 + 8 * g;
       kf[j][0] = ld16<frag>(kr);
       kf[j][1] = ld16<frag>(kr + 32);
       if constexpr (RELPOS) {
-        const T* pr = (const T*)p.pos + ((int64_t)h * p.Tk + key) * 64 + 8 * g;
+        const T* pr = (const T*)p.pos + ((int64_t)h * pos_tk + key) * 64 + 8 * g;
         pf_[j][0] = ld16<frag>(pr);
         pf_[j][1] = ld16<frag>(pr + 32);
       }
@@ -159,7 +207,7 @@ __global__ __launch_bounds__(256) void mha_small_kernel(MhaParams p) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int idx = lane + 64 * i, row = idx >> 3, seg = idx & 7;
-      vrow[i] = kb + row < p.Tk ? ld16<frag>((const T*)p.v + (int64_t)(kb + row) * p.vs + h * 64 + seg * 8) : zero_frag<frag>();
+      vrow[i] = kb + row < p.Tk ? ld16<frag>((const T*)p.v + key_row(kb + row) * p.vs + h * 64 + seg * 8) : zero_frag<frag>();
     }
     // ---- scores (transposed): lane (g, r): s[j][e] = query r against key kb + 16 j + 4 g + e
     f32x4 s[2];
@@ -249,7 +297,27 @@ __global__ __launch_bounds__(256) void mha_small_kernel(MhaParams p) {
   t4 ov;
 #pragma unroll
   for (int e = 0; e < 4; ++e) ov[e] = EL::from_f(acc[e] * inv);
-  *reinterpret_cast<t4*>((T*)p.out + pa_off<T>(q0 + r, h * 64 + 16 * wave + 4 * g, p.out_mtp)) = ov;
+  *reinterpret_cast<t4*>((T*)p.out + pa_off<T>((SEG ? sg.out_row0 : 0) + q0 + r, h * 64 + 16 * wave + 4 * g, p.out_mtp)) = ov;
+}
+
+template <typename T, bool RELPOS>
+__global__ __launch_bounds__(256) void mha_small_kernel(MhaParams p) {
+  mha_small_tile<T, RELPOS, false>(p, MhaSeg{}, (int)blockIdx.x * 16, blockIdx.y);
+}
+
+// grid (query tiles of the row space, H): p.q points at row 0 of the query row space, p.Tq / p.Tk are set per segment here
+template <typename T, bool RELPOS>
+__global__ __launch_bounds__(256) void mha_small_seg_kernel(MhaParams p, const int32_t* __restrict__ seg, int nseg, int pos_tk) {
+  SegRec r;
+  if (!seg_of_tile(seg, nseg, blockIdx.x, r)) return;
+  const int q0 = (int)blockIdx.x * 16 - r.row0;
+  if (q0 < 0 || q0 >= r.len) return;
+  p.q = (const T*)p.q + (int64_t)r.row0 * p.qs;
+  p.Tq = r.len;
+  p.Tk = r.src_len + r.kb_len;
+  MhaSeg sg;
+  sg.ka_len = r.src_len; sg.ka_row0 = r.src0; sg.kb_row0 = r.kb_row0; sg.pos_tk = pos_tk; sg.out_row0 = r.out_row0;
+  mha_small_tile<T, RELPOS, true>(p, sg, q0, blockIdx.y);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -268,20 +336,21 @@ __device__ __forceinline__ float block_sum(float v, float* red, int nw) {
   return s;
 }
 
+// One output row: row t of a sequence of Tn rows that starts at row `row0` of x and of the packed y
 template <typename T, int KT>
-__global__ __launch_bounds__(1024) void glu_dwconv_ln_silu_kernel(const T* __restrict__ x, const float* __restrict__ w,
-                                                                  const float* __restrict__ b, const float* __restrict__ lw,
-                                                                  const float* __restrict__ lb, T* __restrict__ y, int Tn, int C,
-                                                                  int mtp, float eps) {
+__device__ __forceinline__ void glu_dwconv_ln_silu_row(const T* __restrict__ x, const float* __restrict__ w,
+                                                       const float* __restrict__ b, const float* __restrict__ lw,
+                                                       const float* __restrict__ lb, T* __restrict__ y, const int row0, const int t,
+                                                       const int Tn, int C, int mtp, float eps) {
   __shared__ float red[16];
-  const int t = blockIdx.x, c = 2 * threadIdx.x;
+  const int c = 2 * threadIdx.x;
   typedef T t2 __attribute__((ext_vector_type(2)));
   t2 av[KT], gv[KT];
 #pragma unroll
   for (int j = 0; j < KT; ++j) {
     const int row = t + j - (KT - 1) / 2;
     const bool ok = row >= 0 && row < Tn;
-    const T* xr = x + (int64_t)(ok ? row : 0) * 2 * C;
+    const T* xr = x + (int64_t)(row0 + (ok ? row : 0)) * 2 * C;
     av[j] = *reinterpret_cast<const t2*>(xr + c);
     gv[j] = *reinterpret_cast<const t2*>(xr + C + c);
     if (!ok) av[j] = t2{Elem<T>::from_f(0.f), Elem<T>::from_f(0.f)};
@@ -305,7 +374,30 @@ __global__ __launch_bounds__(1024) void glu_dwconv_ln_silu_kernel(const T* __res
     const float v = (e == 0 ? d0 : d1) * rstd * lw[c + e] + lb[c + e];
     o[e] = Elem<T>::from_f(v / (1.f + __expf(-v)));
   }
-  *reinterpret_cast<t2*>(y + pa_off<T>(t, c, mtp)) = o;
+  *reinterpret_cast<t2*>(y + pa_off<T>(row0 + t, c, mtp)) = o;
+}
+
+template <typename T, int KT>
+__global__ __launch_bounds__(1024) void glu_dwconv_ln_silu_kernel(const T* __restrict__ x, const float* __restrict__ w,
+                                                                  const float* __restrict__ b, const float* __restrict__ lw,
+                                                                  const float* __restrict__ lb, T* __restrict__ y, int Tn, int C,
+                                                                  int mtp, float eps) {
+  glu_dwconv_ln_silu_row<T, KT>(x, w, b, lw, lb, y, 0, blockIdx.x, Tn, C, mtp, eps);
+}
+
+// N sequences in one launch: one workgroup per row of the 16-aligned row space; the taps stop at the segment's own ends
+template <typename T, int KT>
+__global__ __launch_bounds__(1024) void glu_dwconv_ln_silu_seg_kernel(const T* __restrict__ x, const float* __restrict__ w,
+                                                                      const float* __restrict__ b, const float* __restrict__ lw,
+                                                                      const float* __restrict__ lb, T* __restrict__ y,
+                                                                      const int32_t* __restrict__ seg, int nseg, int C, int mtp,
+                                                                      float eps) {
+  const int m = blockIdx.x;
+  SegRec r;
+  if (!seg_of_tile(seg, nseg, m >> 4, r)) return;
+  const int t = m - r.row0;
+  if (t < 0 || t >= r.len) return;
+  glu_dwconv_ln_silu_row<T, KT>(x, w, b, lw, lb, y, r.row0, t, r.len, C, mtp, eps);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -845,6 +937,114 @@ extern "C" int itts_glu_dwconv_ln_silu(const void* x, const float* w, const floa
     else ITTS_DW(31);
 #undef ITTS_DW
     return check_launch("itts_glu_dwconv_ln_silu");
+  });
+}
+
+// ---- the segmented forms (include/indextts_hip_prompts.h): N prompts per launch
+// The host mirror of the table is what is checked and what sizes the grid; the kernels read the device copy only.
+static int check_seg_table(const itts_seg_table* t, const char* who) {
+  ITTS_REQUIRE(t && t->dev && t->host, "%s: null segment table", who);
+  ITTS_REQUIRE(t->nseg > 0 && t->nseg <= 4096 && t->ntiles > 0 && t->ntiles <= (1 << 20), "%s: nseg = %d, ntiles = %d", who, t->nseg, t->ntiles);
+  const int32_t* map = t->host + (size_t)t->nseg * ITTS_SEG_WORDS;
+  int64_t owned = 0, mapped = 0;
+  for (int s = 0; s < t->nseg; ++s) {
+    const int32_t* q = t->host + (size_t)s * ITTS_SEG_WORDS;
+    const int row0 = q[0], len = q[1];
+    ITTS_REQUIRE(len > 0, "%s: segment %d has length %d", who, s, len);
+    ITTS_REQUIRE(row0 >= 0 && row0 % 16 == 0, "%s: segment %d starts at row %d (a multiple of 16 is needed)", who, s, row0);
+    ITTS_REQUIRE((int64_t)row0 + len <= (int64_t)t->ntiles * 16, "%s: segment %d ends past the %d row tiles", who, s, t->ntiles);
+    for (int tile = row0 / 16; tile < (row0 + len + 15) / 16; ++tile)
+      ITTS_REQUIRE(map[tile] == s, "%s: segments overlap, or the tile map disagrees with the records (tile %d, segment %d)", who, tile, s);
+    owned += (row0 + len + 15) / 16 - row0 / 16;
+  }
+  for (int tile = 0; tile < t->ntiles; ++tile) {
+    ITTS_REQUIRE(map[tile] >= -1 && map[tile] < t->nseg, "%s: tile %d names segment %d", who, tile, map[tile]);
+    mapped += map[tile] >= 0;
+  }
+  ITTS_REQUIRE(owned == mapped, "%s: the tile map names tiles no segment covers", who);
+  return ITTS_OK;
+}
+
+extern "C" int itts_subsample_conv_seg(const float* mel, const float* w, const float* b, void* y, const itts_seg_table* tab, int frames,
+                                       int F, int C, int dtype, void* stream) {
+  ITTS_REQUIRE(mel && w && b && y && frames >= 3 && F >= 3 && C > 0, "itts_subsample_conv_seg: bad arguments");
+  return by_dtype16(dtype, "itts_subsample_conv_seg", [&](auto tag) {
+    using TT = typename decltype(tag)::type;
+    if (const int rc = check_seg_table(tab, "itts_subsample_conv_seg")) return rc;
+    for (int s = 0; s < tab->nseg; ++s) {
+      const int32_t* q = tab->host + (size_t)s * ITTS_SEG_WORDS;
+      ITTS_REQUIRE(q[2] >= 0 && q[3] >= 3 && (int64_t)q[2] + q[3] <= frames && q[1] == (q[3] - 3) / 2 + 1,
+                   "itts_subsample_conv_seg: segment %d: frames [%d, +%d) of %d give (T - 3) / 2 + 1 rows, the record says %d", s, q[2], q[3],
+                   frames, q[1]);
+    }
+    const int F2 = (F - 3) / 2 + 1;
+    hipStream_t st = (hipStream_t)stream;
+    const int cpw = (C + 7) / 8;       // the staging rule of itts_subsample_conv
+    const bool staged = C % 8 == 0 && (cpw * F2) % 8 == 0 && (size_t)C * F2 * 2 <= 64 * 1024;
+    const size_t lds = staged ? (size_t)C * F2 * 2 : 0;
+    const dim3 grid(tab->ntiles * 16);
+    if (staged) hipLaunchKernelGGL((subsample_conv_seg_kernel<TT, true>), grid, dim3(512), lds, st, mel, w, b, (TT*)y, tab->dev, tab->nseg, F, C, F2);
+    else hipLaunchKernelGGL((subsample_conv_seg_kernel<TT, false>), grid, dim3(512), 0, st, mel, w, b, (TT*)y, tab->dev, tab->nseg, F, C, F2);
+    return check_launch("itts_subsample_conv_seg");
+  });
+}
+
+extern "C" int itts_mha_small_seg(const itts_mha_args* a, const itts_seg_table* tab, int pos_tk, void* stream) {
+  ITTS_REQUIRE(a && a->q && a->k && a->v && a->out, "itts_mha_small_seg: null args");
+  return by_dtype16(a->dtype, "itts_mha_small_seg", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    ITTS_REQUIRE(a->Tq > 0 && a->Tk > 0 && a->H > 0 && a->H <= 65535, "itts_mha_small_seg: bad shape Tq=%d Tk=%d H=%d", a->Tq, a->Tk, a->H);
+    ITTS_REQUIRE(a->q_stride % 8 == 0 && a->k_stride % 8 == 0 && a->v_stride % 8 == 0 && a->q_stride >= a->H * 64 &&
+                     a->k_stride >= a->H * 64 && a->v_stride >= a->H * 64,
+                 "itts_mha_small_seg: row strides must be multiples of 8 elements and cover H * 64");
+    const bool rel = a->pos != nullptr;
+    if (rel) ITTS_REQUIRE(a->bias_u && a->bias_v && pos_tk > 0, "itts_mha_small_seg: the relative-position form needs bias_u, bias_v and pos_tk");
+    if (const int rc = check_seg_table(tab, "itts_mha_small_seg")) return rc;
+    for (int s = 0; s < tab->nseg; ++s) {
+      const int32_t* q = tab->host + (size_t)s * ITTS_SEG_WORDS;
+      ITTS_REQUIRE((int64_t)q[0] + q[1] <= a->Tq, "itts_mha_small_seg: segment %d: queries past the %d rows of q", s, a->Tq);
+      ITTS_REQUIRE(q[2] >= 0 && q[3] > 0 && (int64_t)q[2] + q[3] <= a->Tk && q[5] >= 0 && (q[5] == 0 || (q[4] >= 0 && (int64_t)q[4] + q[5] <= a->Tk)),
+                   "itts_mha_small_seg: segment %d: key rows [%d, +%d) and [%d, +%d) of %d", s, q[2], q[3], q[4], q[5], a->Tk);
+      ITTS_REQUIRE(!rel || q[3] + q[5] <= pos_tk, "itts_mha_small_seg: segment %d has %d keys, pos holds %d", s, q[3] + q[5], pos_tk);
+      ITTS_REQUIRE(q[6] >= 0 && q[6] % 16 == 0 && (int64_t)q[6] + q[1] <= (int64_t)a->out_mtp * 16,
+                   "itts_mha_small_seg: segment %d: output rows [%d, +%d) of %d row tiles (a multiple of 16 is needed)", s, q[6], q[1], a->out_mtp);
+    }
+    MhaParams p;
+    p.Tq = 0; p.Tk = 0; p.H = a->H;          // set per segment by the kernel
+    p.q = a->q; p.k = a->k; p.v = a->v;
+    p.qs = a->q_stride; p.ks = a->k_stride; p.vs = a->v_stride;
+    p.pos = a->pos; p.bu = a->bias_u; p.bv = a->bias_v;
+    p.scale = a->scale;
+    p.out = a->out; p.out_mtp = a->out_mtp;
+    const dim3 grid(tab->ntiles, a->H), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (rel) hipLaunchKernelGGL((mha_small_seg_kernel<T, true>), grid, block, 0, st, p, tab->dev, tab->nseg, pos_tk);
+    else hipLaunchKernelGGL((mha_small_seg_kernel<T, false>), grid, block, 0, st, p, tab->dev, tab->nseg, pos_tk);
+    return check_launch("itts_mha_small_seg");
+  });
+}
+
+extern "C" int itts_glu_dwconv_ln_silu_seg(const void* x, const float* w, const float* b, const float* ln_w, const float* ln_b, void* y,
+                                           const itts_seg_table* tab, int C, int taps, int y_mtp, float eps, int dtype, void* stream) {
+  ITTS_REQUIRE(x && w && b && ln_w && ln_b && y, "itts_glu_dwconv_ln_silu_seg: bad arguments");
+  return by_dtype16(dtype, "itts_glu_dwconv_ln_silu_seg", [&](auto tag) {
+    using TT = typename decltype(tag)::type;
+    ITTS_REQUIRE(C % 128 == 0 && C <= 2048, "itts_glu_dwconv_ln_silu_seg: C = %d must be a multiple of 128, at most 2048", C);
+    ITTS_REQUIRE(taps == 15 || taps == 7 || taps == 31, "itts_glu_dwconv_ln_silu_seg: taps = %d (7, 15 and 31 are built)", taps);
+    if (const int rc = check_seg_table(tab, "itts_glu_dwconv_ln_silu_seg")) return rc;
+    ITTS_REQUIRE(y_mtp >= tab->ntiles, "itts_glu_dwconv_ln_silu_seg: y_mtp = %d row tiles do not cover the %d tiles of the row space", y_mtp,
+                 tab->ntiles);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(tab->ntiles * 16), block(C / 2);
+    if (eps <= 0.f) eps = 1e-5f;
+#define ITTS_DW(K_)                                                                                                             \
+  hipLaunchKernelGGL((glu_dwconv_ln_silu_seg_kernel<TT, K_>), grid, block, 0, st, (const TT*)x, w, b, ln_w, ln_b, (TT*)y, tab->dev, \
+                     tab->nseg, C, y_mtp, eps)
+    if (taps == 15) ITTS_DW(15);
+    else if (taps == 7) ITTS_DW(7);
+    else ITTS_DW(31);
+#undef ITTS_DW
+    return check_launch("itts_glu_dwconv_ln_silu_seg");
   });
 }
 

@@ -51,6 +51,14 @@ class MhaArgs(C.Structure):
                 ("bias_u", C.c_void_p), ("bias_v", C.c_void_p), ("scale", C.c_float), ("out", C.c_void_p), ("out_mtp", C.c_int)]
 
 
+class SegTableArgs(C.Structure):
+    """itts_seg_table (include/indextts_hip_prompts.h)."""
+    _fields_ = [("dev", C.c_void_p), ("host", C.c_void_p), ("nseg", C.c_int), ("ntiles", C.c_int)]
+
+
+SEG_WORDS = 8      # ITTS_SEG_WORDS
+
+
 class RowsArgs(C.Structure):
     _fields_ = [("dtype", C.c_int), ("M", C.c_int), ("D", C.c_int), ("x", C.c_void_p), ("slab", C.c_void_p), ("nslab", C.c_int),
                 ("bias", C.c_void_p), ("norm", C.c_int), ("w", C.c_void_p), ("b", C.c_void_p), ("eps", C.c_float),
@@ -191,10 +199,20 @@ _KV8_SIGNATURES = {
                                  C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
 }
 
+# include/indextts_hip_prompts.h: the sequence-mixing launches of the prompt front-end over N prompts at once
+_PROMPT_SIGNATURES = {
+    "itts_subsample_conv_seg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SegTableArgs), C.c_int, C.c_int,
+                                          C.c_int, C.c_int, C.c_void_p]),
+    "itts_mha_small_seg": (C.c_int, [C.POINTER(MhaArgs), C.POINTER(SegTableArgs), C.c_int, C.c_void_p]),
+    "itts_glu_dwconv_ln_silu_seg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(SegTableArgs), C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]),
+}
+
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)          # what include/indextts_hip.h declares itself
 ROW_SYMBOLS = tuple(_ROW_SIGNATURES)           # what include/indextts_hip_rows.h declares
 W8_SYMBOLS = tuple(_W8_SIGNATURES)             # what include/indextts_hip_w8.h declares
 KV8_SYMBOLS = tuple(_KV8_SIGNATURES)           # what include/indextts_hip_kv8.h declares
+PROMPT_SYMBOLS = tuple(_PROMPT_SIGNATURES)     # what include/indextts_hip_prompts.h declares
 _lib = None
 
 
@@ -207,7 +225,7 @@ def lib():
             raise NativeError(f"{path} not found: build it with `make -C index-tts-lora_amd/csrc` "
                               f"(or python -c 'import __graft_entry__ as g; g.build()'). There is no fallback path.")
         L = C.CDLL(path)
-        for name, (res, args) in {**_SIGNATURES, **_ROW_SIGNATURES, **_W8_SIGNATURES, **_KV8_SIGNATURES}.items():
+        for name, (res, args) in {**_SIGNATURES, **_ROW_SIGNATURES, **_W8_SIGNATURES, **_KV8_SIGNATURES, **_PROMPT_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -395,6 +413,64 @@ def glu_dwconv_ln_silu(x, w, b, ln_w, ln_b, y, T, Cn, y_mtp, eps=1e-5):
     _dev(x, w, b, ln_w, ln_b, y)
     _check(lib().itts_glu_dwconv_ln_silu(_p(x), _p(w), _p(b), _p(ln_w), _p(ln_b), _p(y), T, Cn, w.shape[1], int(y_mtp), float(eps),
                                          dt(y.dtype), _stream()), "itts_glu_dwconv_ln_silu")
+    return y
+
+
+def seg_words(records, ntiles, tile_map=None) -> torch.Tensor:
+    """The words of a segment table (include/indextts_hip_prompts.h) as a host int32 tensor: one record of up to SEG_WORDS ints
+    per segment (row0, len, ...; missing words are 0), then the segment of every 16-row tile of the row space (-1: none).
+    tile_map: given instead of derived (the derived map names, per tile, the last segment whose rows touch it)."""
+    recs = [list(map(int, r)) + [0] * (SEG_WORDS - len(r)) for r in records]
+    if not recs or any(len(r) != SEG_WORDS for r in recs):
+        raise ValueError(f"a segment table takes at least one record of at most {SEG_WORDS} words")
+    if tile_map is None:
+        tile_map = [-1] * int(ntiles)
+        for s, r in enumerate(recs):
+            for tile in range(max(r[0], 0) // 16, min((r[0] + max(r[1], 0) + 15) // 16, int(ntiles))):
+                tile_map[tile] = s
+    if len(tile_map) != int(ntiles):
+        raise ValueError("the tile map has one entry per row tile")
+    return torch.tensor([w for r in recs for w in r] + [int(v) for v in tile_map], dtype=torch.int32)
+
+
+class SegTable:
+    """A segment table on the host and on `device`, with the itts_seg_table that names both (the tensors live as long as this)."""
+
+    def __init__(self, records, ntiles, device, tile_map=None):
+        self.host = seg_words(records, ntiles, tile_map)
+        self.dev = self.host.to(device)
+        self.nseg, self.ntiles = len(records), int(ntiles)
+        self.args = SegTableArgs(C.c_void_p(self.dev.data_ptr()), C.c_void_p(self.host.data_ptr()), self.nseg, self.ntiles)
+
+
+def subsample_conv_seg(mel, w, b, y, tab: SegTable):
+    """subsample_conv over the prompts whose frames follow one another in mel fp32 [frames, F]; y T [ntiles * 16, C * F2]."""
+    _dev(mel, w, b, y)
+    frames, Fq = mel.shape
+    _check(lib().itts_subsample_conv_seg(_p(mel), _p(w), _p(b), _p(y), C.byref(tab.args), frames, Fq, w.shape[0], dt(y.dtype), _stream()),
+           "itts_subsample_conv_seg")
+    return y
+
+
+def mha_small_seg(q, k, v, out, q_rows, kv_rows, H, q_stride, k_stride, v_stride, out_mtp, scale, tab: SegTable, pos=None, bias_u=None,
+                  bias_v=None, pos_tk=0):
+    """mha_small over the segments of `tab`: q / k / v point at row 0 of their row spaces of q_rows / kv_rows rows; pos T
+    [H, pos_tk, 64] is indexed by the key's index within its segment."""
+    a = MhaArgs()
+    a.dtype, a.Tq, a.Tk, a.H = dt(out.dtype), q_rows, kv_rows, H
+    a.q, a.k, a.v = _p(q), _p(k), _p(v)
+    a.q_stride, a.k_stride, a.v_stride = q_stride, k_stride, v_stride
+    a.pos, a.bias_u, a.bias_v = _p(pos), _p(bias_u), _p(bias_v)
+    a.scale, a.out, a.out_mtp = float(scale), _p(out), int(out_mtp)
+    _check(lib().itts_mha_small_seg(C.byref(a), C.byref(tab.args), int(pos_tk), _stream()), "itts_mha_small_seg")
+    return out
+
+
+def glu_dwconv_ln_silu_seg(x, w, b, ln_w, ln_b, y, Cn, y_mtp, tab: SegTable, eps=1e-5):
+    """glu_dwconv_ln_silu over the segments of `tab`: x T [ntiles * 16, 2C] -> y T packed, y_mtp >= ntiles row tiles."""
+    _dev(x, w, b, ln_w, ln_b, y)
+    _check(lib().itts_glu_dwconv_ln_silu_seg(_p(x), _p(w), _p(b), _p(ln_w), _p(ln_b), _p(y), C.byref(tab.args), Cn, w.shape[1],
+                                             int(y_mtp), float(eps), dt(y.dtype), _stream()), "itts_glu_dwconv_ln_silu_seg")
     return y
 
 

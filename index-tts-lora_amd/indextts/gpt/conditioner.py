@@ -38,8 +38,43 @@ def _fold(W, b, gamma, beta, dtype):
     return nat.pack_weight(Wr.contiguous()), c, d.to(torch.float32).contiguous()
 
 
+def prompt_row_space(frames):
+    """The row space of a batch of prompts of `frames` mel frames each (pure host): prompt p has t_p = (T_p - 3) // 2 + 1
+    subsampled rows at row0_p, a multiple of 16 -- a 16-row tile of a packed operand never holds rows of two prompts -- and its
+    frames start at frame0_p of the concatenated mel.  M = sum of 16 * ceil(t_p / 16) rows, the tail of each prompt's last tile
+    being padding rows."""
+    frames = [int(T) for T in frames]
+    if not frames:
+        raise ValueError("no prompts")
+    if min(frames) < 3:
+        raise ValueError(f"a prompt needs at least 3 mel frames (got {min(frames)})")
+    t = [(T - 3) // 2 + 1 for T in frames]
+    row0, frame0, m, f = [], [], 0, 0
+    for T, tp in zip(frames, t):
+        row0.append(m)
+        frame0.append(f)
+        m += (tp + 15) // 16 * 16
+        f += T
+    return dict(frames=frames, t=t, row0=row0, frame0=frame0, M=m, total_frames=f)
+
+
+def prompt_seg_records(space, NL):
+    """The segment records (include/indextts_hip_prompts.h) of a row space, per launch kind: `conv` (frames -> rows), `enc` (the
+    Conformer's self-attention and convolution module: queries = keys = the prompt's rows) and `per` (the Perceiver's attention:
+    prompt p's NL latent rows at p * NL query the same latent rows and the prompt's context rows, which follow ALL latent rows
+    in the [latents ; contexts] operand; the output goes back to the latent rows).  Returns (records, row tiles) per kind."""
+    n = len(space["t"])
+    conv = [(r0, tp, f0, T) for r0, tp, f0, T in zip(space["row0"], space["t"], space["frame0"], space["frames"])]
+    enc = [(r0, tp, r0, tp, 0, 0, r0) for r0, tp in zip(space["row0"], space["t"])]
+    per = [(p * NL, NL, p * NL, NL, n * NL + r0, tp, p * NL) for p, (r0, tp) in enumerate(zip(space["row0"], space["t"]))]
+    return dict(conv=(conv, space["M"] // 16), enc=(enc, space["M"] // 16), per=(per, n * NL // 16))
+
+
 class ConditionerEngine:
     ROWS_PER_WG = 32     # row tiles dealt to grid.z: a ~150-row GEMM is ~240 workgroups of 32 rows x 2-3 column tiles
+    # batch(retain=False) buffer sets kept per thread (least recently used goes first).  A set for 32 prompts is ~0.3 GB (x0 alone is
+    # M x 25 088 fp16) and its key is the ORDERED tuple of lengths: a service creates a new key with almost every batch composition
+    MAX_UNRETAINED_SETS = 2
 
     def __init__(self, W: dict, heads: int = 8, dtype=torch.float16, device="cuda", enc="conditioning_encoder.",
                  per="perceiver_encoder."):
@@ -127,14 +162,39 @@ class ConditionerEngine:
             i += 1
         self.gamma = f32(per + "norm.gamma")
         self._bufs = {}
+        self._unretained = []     # keys of _bufs made by batch(retain=False), least recently used first
         self.launches = 0
 
     # ------------------------------------------------------------------------------------------------------------------
     def forget(self):
         """Drop the calling thread's per-length buffers (the caller holds no captured graph over them any more)."""
         me = threading.get_ident()
-        for k in [k for k in self._bufs if k[2] == me]:
+        for k in [k for k in list(self._bufs) if k[2] == me]:     # list(): another thread may add its buffers meanwhile
             del self._bufs[k]
+        self._unretained = [k for k in list(self._unretained) if k[2] != me]
+
+    def _keep(self, key, b, retain):
+        """Book a batch buffer set (pure host).  retain = True: the set stays until forget() -- a captured graph may replay into it.
+        retain = False: the caller holds no graph over it, so it is only a cache: at most MAX_UNRETAINED_SETS such sets per thread
+        stay, the least recently used is dropped (its memory goes back to the allocator once the stream is done with it).  A set
+        that was ever asked for with retain = True is never dropped here."""
+        self._bufs[key] = b
+        if retain:
+            if key in self._unretained:
+                self._unretained.remove(key)
+            return b
+        if key in self._unretained:                       # used again: now the most recent
+            self._unretained.remove(key)
+            self._unretained.append(key)
+            return b
+        if b.get("retained"):
+            return b
+        self._unretained.append(key)
+        mine = [k for k in self._unretained if k[2] == key[2]]
+        for k in mine[: max(0, len(mine) - self.MAX_UNRETAINED_SETS)]:
+            self._unretained.remove(k)
+            self._bufs.pop(k, None)
+        return b
 
     def _buffers(self, T, Fq):
         # per prompt length AND per host thread: replicas of one model (infer.RequestPool: one thread + stream each) share this
@@ -234,3 +294,121 @@ class ConditionerEngine:
         nat.rows(NL, DL, dt, x=lat, norm=2, w=self.gamma, y=b["out"])
         self.launches = n + 1
         return b["out"]
+
+    # ------------------------------------------------------------------------------------------------------------------
+    def _batch_buffers(self, Ts, Fq, retain=True):
+        # per tuple of prompt lengths and per host thread (see _buffers); the segment tables are device DATA of these buffers
+        key = (tuple(Ts), Fq, threading.get_ident())
+        b = self._bufs.get(key)
+        if b is not None:
+            b["retained"] = b["retained"] or retain
+            return self._keep(key, b, retain)
+        dev, dt, d, H, NL = self.device, self.dtype, self.d, self.H, self.NL
+        f2 = (Fq - 3) // 2 + 1
+        if self.C * f2 != self.KE:
+            raise ValueError(f"{Fq} mel bins give {self.C * f2} features, embed.out takes {self.KE}")
+        sp = prompt_row_space(Ts)
+        n, M = len(Ts), sp["M"]
+        rows_lat = n * NL
+        rows_all = rows_lat + M
+        b = dict(retained=bool(retain), space=sp, n=n, M=M, mtp=M // 16, rows_lat=rows_lat, rows_all=rows_all, mtp_all=rows_all // 16, t_max=max(sp["t"]))
+        for kind, (recs, ntiles) in prompt_seg_records(sp, NL).items():
+            b["tab_" + kind] = nat.SegTable(recs, ntiles, dev)
+        z = lambda *s, dtype=dt: torch.zeros(*s, dtype=dtype, device=dev)      # noqa: E731  (padding rows start as 0 and stay finite)
+        b["mel"] = z(sp["total_frames"], Fq, dtype=torch.float32)
+        b["x0"] = z(M, self.KE)
+        tiles = ((M + 127) // 128) * (d // 128)
+        b["ks_e"] = max(1, min(64, 256 // tiles, self.KE // 32))
+        b["slab"] = z(b["ks_e"], M, d, dtype=torch.float32)
+        b["x"] = z(M, d, dtype=torch.float32)
+        b["hb"] = z(M * d)
+        b["qkv"] = z(M, 3 * d)
+        b["att"] = z(M * d)
+        b["pw1"] = z(M, 2 * d)
+        b["dw"] = z(M * d)
+        b["ff"] = z(M * self.FF)
+        pos = sinusoid_table(b["t_max"], d, dev, torch.float32)     # row j of the table does not depend on the table's length
+        b["pos"] = [torch.nn.functional.linear(pos, blk["w_pos"]).view(b["t_max"], H, 64).transpose(0, 1).to(dt).contiguous()
+                    for blk in self.blocks]
+        b["lat0"] = self.lat0.repeat(n, 1).contiguous()
+        b["xall"] = z(rows_all * self.DL)
+        b["lat"] = z(rows_lat, self.DL, dtype=torch.float32)
+        b["qkv2"] = z(rows_all, 3 * d)
+        b["att2"] = z(rows_lat * d)
+        kp = max(L["kp"] for L in self.players)
+        b["h1"] = z(rows_lat, 2 * kp)
+        b["g"] = z(rows_lat * kp)
+        b["out"] = z(rows_lat, self.DL, dtype=torch.float32)
+        return self._keep(key, b, retain)
+
+    def batch(self, mels, retain=True) -> torch.Tensor:
+        """mels: list of fp32 [T_p, F] (time-major, on the device; views are fine), any lengths -> conds fp32 [N, NL, DL], each
+        prompt conditioned as if alone, in ONE pass of the same 72 kernel launches: the GEMMs and the row operations run over the
+        concatenated rows of all prompts (prompt_row_space), the three launches that mix rows of a sequence take a segment table
+        (include/indextts_hip_prompts.h).  In front of the 72 kernels go N device-to-device copies that put the prompts' frames one
+        after another (`launches` counts the kernels, not these).  The result is a view of the set's output buffer: clone it.
+        retain = True (default): the buffer set of this ordered tuple of lengths stays until forget(), so the pass is
+        graph-capturable from the second call on.  retain = False: the caller captures no graph; the set is only a cache, bounded at
+        MAX_UNRETAINED_SETS per thread (_keep) -- what a service with ever-changing batch compositions must use."""
+        mels = list(mels)
+        if not mels:
+            raise ValueError("ConditionerEngine.batch: no prompts")
+        for m in mels:
+            if m.dim() != 2 or m.dtype != torch.float32 or not m.is_cuda or m.shape[1] != mels[0].shape[1]:
+                raise nat.NativeError("ConditionerEngine.batch takes fp32 device tensors [T_p, F] of one F")
+        Fq = int(mels[0].shape[1])
+        b = self._batch_buffers([int(m.shape[0]) for m in mels], Fq, retain)
+        sp = b["space"]
+        for m, f0, T in zip(mels, sp["frame0"], sp["frames"]):
+            b["mel"][f0:f0 + T].copy_(m)
+        dt, d, H, M, mtp, R = self.dtype, self.d, self.H, b["M"], b["mtp"], self.ROWS_PER_WG
+        enc, per = b["tab_enc"], b["tab_per"]
+        n = 0
+        x, hb = b["x"], b["hb"]
+        # ---- front
+        nat.subsample_conv_seg(b["mel"], self.w_conv, self.b_conv, b["x0"], b["tab_conv"])
+        nat.gemm_conv(dt, 1, M, M, self.KE, d, self.w_embed, b["x0"], b["slab"], y_f32=True, ksplit=b["ks_e"])
+        nat.rows(M, d, dt, slab=b["slab"], nslab=b["ks_e"], bias=self.b_embed, y=x, y_packed=hb)
+        n += 3
+        scale = 1.0 / math.sqrt(64)
+        for blk, pos in zip(self.blocks, b["pos"]):
+            qkv = b["qkv"]
+            nat.gemm_skinny(dt, M, 3 * d, d, blk["w_qkv"], blk["d_qkv"], x=hb, epi=nat.EPI_STORE, y=qkv, x_packed=True,
+                            ln_c=blk["c_qkv"], rows_per_wg=R)
+            nat.mha_small_seg(qkv, qkv[:, d:], qkv[:, 2 * d:], b["att"], M, M, H, 3 * d, 3 * d, 3 * d, mtp, scale, enc, pos=pos,
+                              bias_u=blk["u"], bias_v=blk["v"], pos_tk=b["t_max"])
+            nat.gemm_skinny(dt, M, d, d, blk["w_o"], blk["b_o"], x=b["att"], epi=nat.EPI_RESID_F32, yf=x, y=hb, x_packed=True,
+                            y_packed=True, rows_per_wg=R)
+            nat.gemm_skinny(dt, M, 2 * d, d, blk["w_pw1"], blk["d_pw1"], x=hb, epi=nat.EPI_STORE, y=b["pw1"], x_packed=True,
+                            ln_c=blk["c_pw1"], rows_per_wg=R)
+            nat.glu_dwconv_ln_silu_seg(b["pw1"], blk["w_dw"], blk["b_dw"], blk["ln_dw"][0], blk["ln_dw"][1], b["dw"], d, mtp, enc)
+            nat.gemm_skinny(dt, M, d, d, blk["w_pw2"], blk["b_pw2"], x=b["dw"], epi=nat.EPI_RESID_F32, yf=x, y=hb, x_packed=True,
+                            y_packed=True, rows_per_wg=R)
+            nat.gemm_skinny(dt, M, self.FF, d, blk["w_ff1"], blk["d_ff1"], x=hb, epi=nat.EPI_SILU_STORE, y=b["ff"], x_packed=True,
+                            y_packed=True, ln_c=blk["c_ff1"], rows_per_wg=R)
+            nat.gemm_skinny(dt, M, d, self.FF, blk["w_ff2"], blk["b_ff2"], x=b["ff"], epi=nat.EPI_RESID_F32, yf=x, x_packed=True,
+                            rows_per_wg=R)
+            nat.rows(M, d, dt, x=x, norm=1, w=blk["ln_final"][0], b=blk["ln_final"][1], y=x, y_packed=hb)
+            n += 9
+        # ---- perceiver: operand rows [0, N * NL) = every prompt's latents, [N * NL, N * NL + M) = proj_context(after_norm(x))
+        NL, DL, ma, ra, rl = self.NL, self.DL, b["mtp_all"], b["rows_all"], b["rows_lat"]
+        lat, xall = b["lat"], b["xall"]
+        nat.gemm_skinny(dt, M, DL, d, self.w_ctx, self.d_ctx, x=hb, epi=nat.EPI_STORE, y=xall, x_packed=True, y_packed=True,
+                        ln_c=self.c_ctx, rows_per_wg=R, y_row0=rl, y_mtp=ma)
+        nat.rows(rl, DL, dt, x=b["lat0"], y=lat, y_packed=xall, y_row0=0, y_mtp=ma)
+        n += 2
+        for L in self.players:
+            qkv2, kp = b["qkv2"], L["kp"]
+            nat.gemm_skinny(dt, ra, 3 * d, DL, L["w_qkv"], None, x=xall, epi=nat.EPI_STORE, y=qkv2, x_packed=True, rows_per_wg=R)
+            nat.mha_small_seg(qkv2, qkv2[:, d:], qkv2[:, 2 * d:], b["att2"], rl, ra, H, 3 * d, 3 * d, 3 * d, rl // 16, scale, per)
+            nat.gemm_skinny(dt, rl, DL, d, L["w_o"], None, x=b["att2"], epi=nat.EPI_RESID_F32, yf=lat, y=xall, x_packed=True,
+                            y_packed=True, y_row0=0, y_mtp=ma, rows_per_wg=R)
+            nat.gemm_skinny(dt, rl, 2 * kp, DL, L["w_ff1"], L["b_ff1"], x=xall, epi=nat.EPI_STORE, y=b["h1"], x_packed=True, x_mtp=ma,
+                            rows_per_wg=R)
+            nat.geglu(b["h1"], b["g"], rl, kp)
+            nat.gemm_skinny(dt, rl, DL, kp, L["w_ff2"], L["b_ff2"], x=b["g"], epi=nat.EPI_RESID_F32, yf=lat, y=xall, x_packed=True,
+                            y_packed=True, y_row0=0, y_mtp=ma, rows_per_wg=R)
+            n += 6
+        nat.rows(rl, DL, dt, x=lat, norm=2, w=self.gamma, y=b["out"])
+        self.launches = n + 1
+        return b["out"].view(b["n"], NL, DL)

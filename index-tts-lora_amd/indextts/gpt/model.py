@@ -158,7 +158,12 @@ class UnifiedVoice:
 
     # ---- conditioning / prefix --------------------------------------------------------------------------------
     def get_conditioning(self, speech_conditioning_input, cond_mel_lengths=None, speaker_ids=None):
-        """model.py:487-546 (conformer_perceiver branch, plus the stored mean_condition_{id} shortcut)."""
+        """model.py:487-546 (conformer_perceiver branch, plus the stored mean_condition_{id} shortcut).
+        Several padded prompts (mel [B > 1, 100, Tmax] with cond_mel_lengths [B]) mean different things by precision: a 16-bit
+        model conditions each prompt AS IF ALONE on its first cond_mel_lengths[b] frames (ConditionerEngine.batch: t_b =
+        (len_b - 3) // 2 + 1 rows, whatever the padding holds); an fp32 model keeps the reference's masked, padded form (the
+        parity mode: the subsampled mask mask[:, :, 2::2] and the padded convolutions are the reference's, and are not exactly
+        the prompt alone).  IndexTTS's prompt lists do not come through here in fp32: they loop the unpadded form per prompt."""
         if speaker_ids is not None and speech_conditioning_input is None:
             out = []
             for sid in speaker_ids:
@@ -173,6 +178,13 @@ class UnifiedVoice:
         mel = speech_conditioning_input.to(self.device, torch.float32)
         if mel.ndim == 2:
             mel = mel[None]
+        if cond_mel_lengths is not None and mel.shape[0] > 1 and self.conditioner() is not None:
+            # several padded prompts, 16-bit model: each conditioned as if alone on its first cond_mel_lengths[b] frames, all in one
+            # pass of the HIP conditioner (ConditionerEngine.batch)
+            lens = [int(v) for v in torch.as_tensor(cond_mel_lengths).reshape(-1).tolist()]
+            if len(lens) != mel.shape[0] or min(lens) < 3 or max(lens) > mel.shape[2]:
+                raise ValueError(f"cond_mel_lengths {lens} do not fit {mel.shape[0]} prompts of up to {mel.shape[2]} frames")
+            return self.conditioner().batch([mel[i, :, :n].t().contiguous() for i, n in enumerate(lens)]).clone()
         eng = self.conditioner() if cond_mel_lengths is None else None
         if eng is not None:                  # unpadded prompts: the HIP conditioner, one prompt per pass
             rows = mel.transpose(1, 2).contiguous()

@@ -60,6 +60,25 @@ def _resolve_gpt_precision(gpt_p, quantization=None):
     return _resolve_dtype(gpt_p), ("fp8" if gpt_p == "fp8" else None), False
 
 
+def dedupe_prompts(cond_mel, n_rows, who="infer_batch"):
+    """A prompt list (one [1, 100, T_i] mel per utterance) -> (the distinct prompts in the order they first appear, for every
+    utterance the index of its prompt among them).  Two entries are the same prompt when they are the same tensor OBJECT: a
+    service keeps one tensor per speaker, and comparing contents would cost a device pass per pair."""
+    if len(cond_mel) != n_rows:
+        raise ValueError(f"{who}: {len(cond_mel)} prompts for {n_rows} utterances (a prompt list names one prompt per utterance)")
+    uniq, seen, idx = [], {}, []
+    for m in cond_mel:
+        if not torch.is_tensor(m) or m.dim() != 3 or m.shape[0] != 1:
+            raise ValueError(f"{who}: every prompt of a list is a mel tensor [1, n_mels, T]")
+        if id(m) not in seen:
+            seen[id(m)] = len(uniq)
+            uniq.append(m)
+        idx.append(seen[id(m)])
+    if len({int(m.shape[1]) for m in uniq}) != 1:
+        raise ValueError(f"{who}: the prompts of a list have one number of mel bins")
+    return uniq, idx
+
+
 def _resolve_kv_cache(name):
     """The `kv_cache` entry of a precision config -> the engine's kv_dtype: "auto" (the default) = the activation type (None);
     "fp8" = one E4M3 byte per cached element (GPTEngine(kv_dtype="fp8")).  Any other value is an error."""
@@ -131,6 +150,7 @@ class IndexTTS:
         self._cache_conds = None
         self._feat_graphs = {}
         self._batch_feat = None   # (prompt tensor, its version counter, conds, spk) of the last infer_batch prompt
+        self._batch_feat_rows = None   # the same of the last prompt LIST (_prompt_features_rows)
         # the latent pass takes the prompt's keys / values from the KV cache the decode loop leaves behind (same bits)
         self.reuse_prompt_kv = os.environ.get("ITTS_REUSE_PROMPT_KV", "1") == "1"
         self.gpt = UnifiedVoice(**self.cfg.gpt)
@@ -189,7 +209,7 @@ class IndexTTS:
         self._gpt = module
         self._cache_conds = None
         self._feat_graphs = {}
-        self._batch_feat = None
+        self._batch_feat = self._batch_feat_rows = None
 
     @gpt.deleter
     def gpt(self):   # `del tts.gpt` before the swap (api.py:160)
@@ -222,7 +242,7 @@ class IndexTTS:
         import copy
         r = copy.copy(self)
         r.gpt = self.gpt.replica()
-        r.cache_audio_prompt = r.cache_cond_mel = r._cache_conds = r._cache_spk = r._batch_feat = None
+        r.cache_audio_prompt = r.cache_cond_mel = r._cache_conds = r._cache_spk = r._batch_feat = r._batch_feat_rows = None
         r._feat_graphs = {}       # captured graphs replay into their own static buffers: one set per instance
         return r
 
@@ -394,12 +414,47 @@ class IndexTTS:
         keeps them per prompt path (the cache holds a reference, so the storage cannot be recycled under it).  spk = False:
         the speaker embedding (ECAPA, vocoder input) is not on the first token's critical path; it is computed when first
         asked for and is None until then."""
+        if isinstance(cond_mel, (list, tuple)):
+            return self._prompt_features_rows(cond_mel, spk)
         bf = self._batch_feat
         if bf is None or bf[0] is not cond_mel or bf[1] != cond_mel._version:
             bf = self._batch_feat = [cond_mel, cond_mel._version, self._prompt_conds(cond_mel), None]
         if spk and bf[3] is None:
             bf[3] = self._prompt_spk(cond_mel)
         return bf[2], bf[3]
+
+    def _prompt_features_rows(self, cond_mel, spk=True):
+        """_prompt_features of a prompt list: (conds [B, 32, D], speaker embeddings [B, 1, 512]), row i those of utterance i's own
+        prompt.  Every distinct prompt (dedupe_prompts) is conditioned once, each as if alone: a 16-bit model runs all of them
+        through ONE pass of the HIP conditioner (ConditionerEngine.batch, run eagerly with a bounded buffer cache),
+        fp32 loops the functional form; the speaker encoder runs once per distinct prompt.  Kept like the single prompt's
+        features, per list of the same tensor objects at the same versions."""
+        uniq, idx = dedupe_prompts(cond_mel, len(cond_mel))
+        key = (tuple((id(m), m._version) for m in uniq), tuple(idx))
+        bf = self._batch_feat_rows
+        rows = torch.tensor(idx, device=self.device)
+        if bf is None or bf[0] != key:
+            ce = self.gpt.conditioner()
+            if len(uniq) > 1 and ce is not None:
+                # straight into the engine (the frames are copied once, into its concatenated mel); retain=False: no graph is
+                # captured over this pass, so the engine keeps a bounded number of buffer sets however the batches are composed
+                cu = ce.batch([m[0].to(self.device, torch.float32).t() for m in uniq], retain=False).clone()
+            else:
+                cu = torch.cat([self._prompt_conds(m) for m in uniq], 0)
+            bf = self._batch_feat_rows = [key, uniq, cu[rows].contiguous(), None]     # (uniq: the ids in the key stay those tensors')
+        if spk and bf[3] is None:
+            bf[3] = torch.cat([self._prompt_spk(m) for m in uniq], 0)[rows].contiguous()
+        return bf[2], bf[3]
+
+    def _check_prompts(self, cond_mel, n_rows, gen, who):
+        """A prompt list is checked before anything is launched; a list that names one prompt for every utterance IS that prompt
+        (the single-tensor path, shared prefix and all)."""
+        if not isinstance(cond_mel, (list, tuple)):
+            return cond_mel
+        uniq, _ = dedupe_prompts(cond_mel, n_rows, who)
+        if int(gen.get("num_beams", 1)) > 1:
+            raise NotImplementedError(f"{who}: beam search with a prompt per utterance is not built (num_beams = 1)")
+        return uniq[0] if len(uniq) == 1 else list(cond_mel)
 
     def _conds(self, cond_mel, speaker_id=None):
         """Conditioning latents of the call.  The reference passes BOTH the prompt mel and speaker_ids=[speaker_id] to
@@ -474,6 +529,8 @@ class IndexTTS:
         cache (GPTEngine.latent_mel_rows: same bits, ~40 % fewer GEMM rows).
         adapter_ids: the rows' adapters of an attached bank (with reuse_prefix: the ids the cached prompt was prefilled under)."""
         g, eng, dev = self.gpt, self.gpt.engine, self.device
+        if conds.shape[0] not in (1, len(text_rows)):    # a subset of the rows with all rows' conds would speak in the wrong voices
+            raise ValueError(f"_latents: conds holds {conds.shape[0]} prompts for {len(text_rows)} rows (one for all, or one per row)")
         if reuse_prefix and self.reuse_prompt_kv and eng.kv_dtype is None:   # (an FP8 cache holds codes: the prompt rows are recomputed)
             cl = [int(c.numel()) for c in code_rows]
             flat = torch.cat([c.reshape(-1).long() for c in code_rows]).cpu().numpy() if code_rows else np.zeros(0, np.int64)
@@ -516,7 +573,7 @@ class IndexTTS:
                            np.concatenate(pos[0] + pos[1])]).astype(np.int64)
         idx = torch.from_numpy(packed).to(dev)
         batch = torch.zeros(len(tl), S, conds.shape[2], dtype=torch.float32, device=dev)
-        batch[:, :nc] = conds[0].to(dev, torch.float32)
+        batch[:, :nc] = (conds if conds.shape[0] == len(tl) else conds[0]).to(dev, torch.float32)   # the row's own prompt, or the one
         batch[idx[0, :n_t], idx[1, :n_t]] = eng.text_emb[idx[2, :n_t]] + eng.text_pos[idx[3, :n_t]]
         batch[idx[0, n_t:], idx[1, n_t:]] = eng.mel_emb[idx[2, n_t:]] + eng.mel_pos[idx[3, n_t:]]
         enc = eng.latent(batch, lengths=[s0 + n + 2 for s0, n in spans], adapter_ids=adapter_ids)   # real rows only (cond | text | mel incl. start/stop)
@@ -550,10 +607,15 @@ class IndexTTS:
     VOCODER_BUCKET_RATIO = 2.0
 
     def _vocode_ragged(self, lat, spk):
-        """lat: list of [T_i, D] latents of one speaker.  Returns the list of waveforms [T_i * hop], each bit-identical to
+        """lat: list of [T_i, D] latents; spk [1, 1, 512] (one speaker) or [len(lat), 1, 512] (row i's own speaker, gathered per
+        bucket).  Returns the list of waveforms [T_i * hop], each bit-identical to
         vocoding that utterance alone (BigVGAN.forward(lens=...)): utterances are sorted by length and vocoded in
         buckets of similar length -- one launch sequence per bucket instead of one per distinct length."""
         outs = [None] * len(lat)
+        per_row = spk.shape[0] != 1
+        if per_row and spk.shape[0] != len(lat):
+            raise ValueError(f"{spk.shape[0]} speaker embeddings for {len(lat)} utterances")
+        spk_all = spk
         order = sorted(range(len(lat)), key=lambda i: int(lat[i].shape[0]))
         k = 0
         while k < len(order):
@@ -568,6 +630,8 @@ class IndexTTS:
             idx = order[k:e]
             lens = [int(lat[i].shape[0]) for i in idx]
             t_max = lens[-1]
+            if per_row:
+                spk = spk_all[torch.tensor(idx, device=spk_all.device)]
             if lens[0] == t_max:
                 wav = self._vocode(torch.stack([lat[i] for i in idx], 0), spk)
             else:
@@ -692,7 +756,12 @@ class IndexTTS:
         model -- each utterance is spoken with, in the token loop and in the latent pass.
         sampling (a list of dicts, one per utterance, in the order of text_token_rows): each utterance under its own request's
         settings -- any of do_sample, temperature, top_k, top_p, repetition_penalty, seed; what an entry leaves out comes from
-        generation_kwargs and seed (gpt.model.row_sampling_params).  num_beams = 1 only."""
+        generation_kwargs and seed (gpt.model.row_sampling_params).  num_beams = 1 only.
+        cond_mel may be a LIST of [1, 100, T_i] prompt mels, one per utterance (any lengths): every utterance is cloned from its
+        own reference audio, as if synthesised alone with that prompt.  Entries that are the same tensor object are one prompt
+        and are conditioned once (_prompt_features_rows); nothing is shared between the rows' prefixes in the prefill.  Works
+        together with adapter_ids and sampling; num_beams = 1 only; a list whose length is not the number of utterances is a
+        ValueError.  One tensor is one prompt for all utterances, as before."""
         st = self._batch_tokens(cond_mel, text_token_rows, max_mel_tokens, force_stop, seed, phase_events, lazy_spk=True,
                                 adapter_ids=adapter_ids, sampling=sampling, **generation_kwargs)
         outs = self._batch_waveforms(st, phase_events, reuse_prefix=True)   # serial: the KV cache still holds this batch's prompt
@@ -711,7 +780,8 @@ class IndexTTS:
         queue continues in a fresh loop after that); check_every / staged: how often the loop looks for finished rows and whether
         a refill's prefill runs on a second stream under the loop's next steps (GPTEngine.decode_refill).  Returns the waveforms
         in the order of text_token_rows, as infer_batch.  sampling: as in infer_batch -- an utterance keeps its own settings, seed
-        and draw stream in whichever slot, and at whichever step, it enters."""
+        and draw stream in whichever slot, and at whichever step, it enters.  cond_mel: one prompt, or a list with one prompt per
+        utterance as in infer_batch -- an utterance takes its own prompt's latents into whichever slot it enters."""
         gen, _ = self._gen_kwargs(generation_kwargs)
         if int(gen.get("num_beams", 1)) != 1:
             raise NotImplementedError("infer_queue: num_beams = 1 only (beam rows cannot be refilled one at a time)")
@@ -719,12 +789,14 @@ class IndexTTS:
             sampling = row_sampling_params(sampling, len(text_token_rows), gen, seed)
         if self.gpt.engine.bank is not None:
             raise NotImplementedError("infer_queue: slot refill with an adapter bank is not built (use infer_batch)")
+        cond_mel = self._check_prompts(cond_mel, len(text_token_rows), gen, "infer_queue")
         if not text_token_rows:
             return ([], []) if return_codes else []
         if int(slots) < 1:
             raise ValueError("infer_queue: slots must be >= 1")
         self._mark(phase_events, "start")
         conds, spk = self._prompt_features(cond_mel)
+        per_row = isinstance(cond_mel, list)      # conds / spk hold a row per utterance: every group below gathers its own
         g, eng = self.gpt, self.gpt.engine
         N = len(text_token_rows)
         texts = [t.reshape(-1).to(torch.int32).cpu() for t in text_token_rows]
@@ -738,8 +810,9 @@ class IndexTTS:
             bh = torch.full((len(ids), L), stop_text, dtype=torch.int32)
             for j, i in enumerate(ids):
                 bh[j, : texts[i].numel()] = texts[i]
-            return g.prefix_rows(conds, bh)
+            return g.prefix_rows(conds[torch.tensor(ids, device=conds.device)] if per_row else conds, bh)
 
+        shared = 0 if per_row else (int(conds.shape[1]) if conds.shape[0] == 1 else 0)
         queue = sorted(range(N), key=lambda i: -int(texts[i].numel()))     # longest first: every later prompt fits
         rows: List[torch.Tensor | None] = [None] * N
         self._mark(phase_events, "conditioned")
@@ -750,13 +823,13 @@ class IndexTTS:
             if eng.paged:
                 # paged cache: one loop serves the whole queue -- a slot's blocks go back to the pool when its row stops.  The pool
                 # holds `slots` windows of (longest prompt + start token + max_mel_tokens + the steps up to the second next poll)
-                eng.prefill(emb, pad, max_mel_tokens + ce + 1, shared_rows=int(conds.shape[1]) if conds.shape[0] == 1 else 0,
+                eng.prefill(emb, pad, max_mel_tokens + ce + 1, shared_rows=shared,
                             slots_window=emb.shape[1] + 1 + max_mel_tokens + 2 * ce + 2)
             else:
                 # contiguous strips: the loop runs whole blocks of check_every steps, the cache has to hold that many positions
                 # past max_mel_tokens; cache positions only grow, so a loop ends when `cache_positions` are used up
                 eng.prefill(emb, pad, max(max_mel_tokens + ce + 1, int(cache_positions) - emb.shape[1] - 2),
-                            shared_rows=int(conds.shape[1]) if conds.shape[0] == 1 else 0, paged=False)
+                            shared_rows=shared, paged=False)
             entered = list(first)
 
             def feed(k):
@@ -791,8 +864,9 @@ class IndexTTS:
         order = sorted(range(N), key=lambda i: int(squeezed[i].numel()))
         for k in range(0, N, slots):
             ids = order[k: k + slots]
-            lat = self._latents(conds, [texts[i] for i in ids], [squeezed[i] for i in ids])
-            for i, w in zip(ids, self._vocode_ragged(lat, spk)):
+            sel = torch.tensor(ids, device=conds.device) if per_row else None
+            lat = self._latents(conds[sel] if per_row else conds, [texts[i] for i in ids], [squeezed[i] for i in ids])
+            for i, w in zip(ids, self._vocode_ragged(lat, spk[sel] if per_row else spk)):
                 outs[i] = w
         self._mark(phase_events, "vocoded")
         return (outs, squeezed) if return_codes else outs
@@ -817,6 +891,7 @@ class IndexTTS:
             if int(gen.get("num_beams", 1)) > 1:
                 raise NotImplementedError("beam search with per-row sampling settings is not built (num_beams = 1)")
             sampling = row_sampling_params(sampling, len(text_token_rows), gen, seed)
+        cond_mel = self._check_prompts(cond_mel, len(text_token_rows), gen, "infer_batch")
         self._mark(phase_events, "start")
         conds, spk = self._prompt_features(cond_mel, spk=not lazy_spk)   # lazy_spk: stage B asks for the speaker embedding
         L = max(int(t.numel()) for t in text_token_rows)
@@ -832,6 +907,8 @@ class IndexTTS:
         self._mark(phase_events, "conditioned")
         nb = int(gen.get("num_beams", 1))
         shared = int(conds.shape[1]) if conds.shape[0] == 1 else 0   # one prompt: every row starts with the same latents
+        if isinstance(cond_mel, list):
+            shared = 0                                               # a prompt per row: nothing is shared, kv_share stays cleared
         if nb > 1:
             if force_stop is not None:
                 raise NotImplementedError("force_stop is a measurement aid of the num_beams=1 loop")
@@ -858,7 +935,9 @@ class IndexTTS:
         With reuse_prefix = False it touches no decode-loop state, so it may run on another stream beside the next batch's
         stage A (BatchPipeline, whose prefill overwrites the KV cache: it must not reuse the prompt's keys / values)."""
         conds, spk = st["conds"], st["spk"]
-        if spk is None:                                   # lazy_spk: first batch of this prompt
+        if spk is None and isinstance(st["cond_mel"], list):
+            spk = self._prompt_features(st["cond_mel"])[1]   # lazy_spk, a prompt per row: one pass per distinct prompt, then kept
+        elif spk is None:                                 # lazy_spk: first batch of this prompt
             spk = self._prompt_spk(st["cond_mel"])
             bf = self._batch_feat
             if bf is not None and bf[0] is st["cond_mel"] and bf[2] is conds:
