@@ -14,31 +14,43 @@ constexpr int BM_MAXV = 8448;   // logits staged in LDS (33 x 256)
 constexpr int BM_MAXC = 1024;   // candidate cap per row after top-k, and of the pool
 constexpr int BM_MAXB = 8;      // num_beams cap
 
-struct BeamParams {
+// beam_step_kernel takes its arguments in two parts.  BEAM_LEAD: what its first trip needs -- the loop state, the done flags, the
+// candidate arrays it pools, the histories, the shape -- as plain leading parameters, 14 dwords: what gfx950 delivers in SGPRs at
+// wave launch (kernarg preload, csrc/Makefile; a by-value struct is never preloaded).  BeamTail: everything read behind that trip,
+// one trailing struct.  BeamParams is both, as itts_beam_step fills it and both kernels' bodies read it (beam_rows_kernel takes it
+// whole).
+struct BeamTail {
   const float* logits;
-  int B, nb, V, ldl;
+  int V, ldl;
   int32_t* tokens;
   int32_t* src;
   float* beam_scores;
-  int32_t* hist;       // [2][R][cap]
   int cap;
   float* hyp_score;
   int32_t* hyp_len;
   int32_t* hyp_tok;    // [B][nb][cap]
   int32_t* n_hyp;
   float* worst;
-  int32_t* done;
-  int32_t* state;
   const int32_t* extra_ids;
   int n_extra;
   float rep_penalty, temperature, top_p, length_penalty;
   int top_k, do_sample;
   uint32_t seed_lo, seed_hi;
   int eos;
+};
+
+struct BeamParams : BeamTail {
+  int32_t* state;
+  int32_t* done;
+  int32_t* cand_n;     // [R]
   float* cand_s;       // [R][BM_MAXC] phase-1 output: candidate score + running beam score
   int32_t* cand_i;     // [R][BM_MAXC]                 beam * V + token
-  int32_t* cand_n;     // [R]
+  int32_t* hist;       // [2][R][cap]
+  int B, nb;
 };
+#define BEAM_LEAD_PARAMS int32_t* state, int32_t* done, int32_t* cand_n, float* cand_s, int32_t* cand_i, int32_t* hist, int B, int nb
+#define BEAM_LEAD_NAMES state, done, cand_n, cand_s, cand_i, hist, B, nb
+#define BEAM_LEAD_ARGS(p) (p).state, (p).done, (p).cand_n, (p).cand_s, (p).cand_i, (p).hist, (p).B, (p).nb
 
 __device__ __forceinline__ uint32_t bkey(float f) {
   uint32_t u = __float_as_uint(f);
@@ -260,7 +272,8 @@ __global__ __launch_bounds__(256) void beam_rows_kernel(BeamParams p) {
 
 // ---- Phase 2: one workgroup per batch element pools its beams' candidates (in beam order, capped at BM_MAXC), draws
 // 2*num_beams of them without replacement (or takes the best), runs BeamSearchScorer.process and moves the histories.
-__global__ __launch_bounds__(256) void beam_step_kernel(BeamParams p) {
+__global__ __launch_bounds__(256) void beam_step_kernel(BEAM_LEAD_PARAMS, BeamTail tail) {
+  const BeamParams p{tail, BEAM_LEAD_NAMES};
   __shared__ float cs[BM_MAXC];   // exp weights of the pool
   __shared__ int ci[BM_MAXC];     // alive flags of the pool
   __shared__ float ss[BM_MAXC];   // sorted pool scores
@@ -278,7 +291,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamParams p) {
   __shared__ float sh_worst;
 
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int nb = p.nb, V = p.V;
+  const int V = p.V;
   const int k = p.state[0];                 // step = tokens generated so far per row
   const int R = p.B * nb;
   const int32_t* hin = p.hist + (int64_t)(k & 1) * R * p.cap;
@@ -555,7 +568,8 @@ extern "C" int itts_beam_step(const itts_beam_args* a, void* stream) {
   p.cand_n = a->cand_n;
 
   hipLaunchKernelGGL(beam_rows_kernel, dim3(a->B * a->num_beams), dim3(256), 0, (hipStream_t)stream, p);
-  hipLaunchKernelGGL(beam_step_kernel, dim3(a->B), dim3(256), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(beam_step_kernel, dim3(a->B), dim3(256), 0, (hipStream_t)stream, BEAM_LEAD_ARGS(p),
+                     static_cast<const BeamTail&>(p));
   return check_launch("itts_beam_step");
 }
 

@@ -515,31 +515,39 @@ __global__ __launch_bounds__(64) void ln_reduce_kernel(float* __restrict__ h, co
 
 // One float4 per thread, D/4 threads (D/256 waves) per row: a fifth of the per-lane load queue of the one-wave-per-row
 // form for D = 1280; the two row statistics cross the waves through LDS.
+// Argument order: what the row, slab, bias and first-LayerNorm requests need leads (14 dwords, preloaded into SGPRs at wave
+// launch); the second LayerNorm's vectors, the output and the bump word follow (the bump, which nothing in the launch reads, is
+// done last for that reason: at the head it would put the trailing arguments' load in front of the first request).
 template <typename T, int NSLAB, bool LN2>
 __global__ __launch_bounds__(1024) void ln_reduce_wide_kernel(float* __restrict__ h, const float* __restrict__ slab,
                                                               const float* __restrict__ bias, const float* __restrict__ w,
-                                                              const float* __restrict__ b, const float* __restrict__ w2,
-                                                              const float* __restrict__ b2, T* __restrict__ y, int M, int D,
-                                                              int32_t* __restrict__ bump, int y_pa, int sstride,
-                                                              const float* __restrict__ lora_b, int lora_r) {
+                                                              const float* __restrict__ b, int M, int D, int sstride, int lora_r,
+                                                              const float* __restrict__ w2, const float* __restrict__ b2,
+                                                              T* __restrict__ y, int32_t* __restrict__ bump, int y_pa,
+                                                              const float* __restrict__ lora_b) {
   __shared__ float red[2][2][16];
   __shared__ float xa[64];   // runtime LoRA: (x A) of this row, summed over the split-K slabs
-  const int row = blockIdx.x, tid = threadIdx.x, nw = blockDim.x >> 6;
-  if (bump != nullptr && row == 0 && tid == 0) { bump[0] += 1; bump[1] += 1; }   // nobody in this launch reads them
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const int nw = D >> 8;   // D / 4 threads: the waves per workgroup, from a preloaded argument (blockDim.x is a word of the argument buffer)
   float* hr = h + (int64_t)row * D;
   f32x4 v = ld16<f32x4>(hr + tid * 4);
   const f32x4 lw = ld16<f32x4>(w + tid * 4), lb = ld16<f32x4>(b + tid * 4);
   f32x4 lw2 = {0.f, 0.f, 0.f, 0.f}, lb2 = lw2;
-  if constexpr (LN2) {
-    lw2 = ld16<f32x4>(w2 + tid * 4);
-    lb2 = ld16<f32x4>(b2 + tid * 4);
-  }
+  // the second LayerNorm's vectors: trailing arguments, requested behind everything the preloaded ones address
+  auto ln2_requests = [&]() {
+    if constexpr (LN2) {
+      lw2 = ld16<f32x4>(w2 + tid * 4);
+      lb2 = ld16<f32x4>(b2 + tid * 4);
+    }
+  };
+  if constexpr (NSLAB == 0) ln2_requests();
   if constexpr (NSLAB > 0) {
     f32x4 sl[NSLAB];
     f32x4 bs = {0.f, 0.f, 0.f, 0.f};
     if (bias != nullptr) bs = ld16<f32x4>(bias + tid * 4);
 #pragma unroll
     for (int sidx = 0; sidx < NSLAB; ++sidx) sl[sidx] = ld16<f32x4>(slab + ((int64_t)sidx * M + row) * sstride + tid * 4);
+    ln2_requests();
     v += bs;
 #pragma unroll
     for (int sidx = 0; sidx < NSLAB; ++sidx) v += sl[sidx];  // same association order as the one-wave form
@@ -565,6 +573,7 @@ __global__ __launch_bounds__(1024) void ln_reduce_wide_kernel(float* __restrict_
   }
   wide_layernorm<LN2>(v, lw, lb, lw2, lb2, &red[0][0][0], tid, nw, D, true);
   store_row4<T>(y + (y_pa ? pa_off<T>(row, tid * 4, (M + 15) >> 4) : (int64_t)row * D + tid * 4), v);
+  if (bump != nullptr && row == 0 && tid == 0) { bump[0] += 1; bump[1] += 1; }   // nobody in this launch reads them
 }
 
 template <typename T, int NV>
@@ -585,7 +594,7 @@ static int launch_ln_reduce(const itts_ln_reduce_args& a, hipStream_t s) {
   const bool two = w2 != nullptr;
 #define ITTS_LNR_L2(NS, L2)                                                                                                \
   do {                                                                                                                     \
-    if (wide) hipLaunchKernelGGL((ln_reduce_wide_kernel<T, NS, L2>), grid, block, 0, s, h, slab, bias, w, b, w2, b2, y, M, D, bump, y_pa, sstride, lora_b, lora_r); \
+    if (wide) hipLaunchKernelGGL((ln_reduce_wide_kernel<T, NS, L2>), grid, block, 0, s, h, slab, bias, w, b, M, D, sstride, lora_r, w2, b2, y, bump, y_pa, lora_b); \
     else hipLaunchKernelGGL((ln_reduce_kernel<T, NV, NS, L2>), grid, block, 0, s, h, slab, bias, w, b, w2, b2, y, M, D, bump);     \
   } while (0)
 #define ITTS_LNR(NS)                                                  \
@@ -606,13 +615,14 @@ static int launch_ln_reduce(const itts_ln_reduce_args& a, hipStream_t s) {
 // h[b] = table[tokens[b]] + pos_table[p], p = *step - row_step0[b] + pos_add clamped to the table (a slot whose row has
 // finished keeps stepping formally until the loop ends; its value is discarded, its read must stay inside the table).
 // hp (optional): the same rows as T in the packed activation layout -- what the LayerNorm-folded QKV GEMM multiplies.
+// Argument order: the token, step and row-step words and the two table rows lead (14 dwords, preloaded into SGPRs at wave launch);
+// the outputs and the bump word follow.
 template <typename T>
-__global__ __launch_bounds__(256) void embed_step_kernel(const int32_t* __restrict__ tokens, const float* __restrict__ table,
-                                                          const float* __restrict__ pos_table,
-                                                          const int32_t* __restrict__ step, int pos_add,
-                                                          float* __restrict__ h, int D, int32_t* __restrict__ bump,
-                                                          const int32_t* __restrict__ row_step0, int pos_rows,
-                                                          T* __restrict__ hp, int mtp) {
+__global__ __launch_bounds__(256) void embed_step_kernel(const int32_t* __restrict__ tokens, const int32_t* __restrict__ step,
+                                                          const int32_t* __restrict__ row_step0, const float* __restrict__ table,
+                                                          const float* __restrict__ pos_table, int pos_add, int D, int pos_rows,
+                                                          int mtp, float* __restrict__ h, T* __restrict__ hp,
+                                                          int32_t* __restrict__ bump) {
   constexpr int E = Elem<T>::E;
   int b = blockIdx.x;
   int tok = tokens[b];
@@ -819,8 +829,8 @@ extern "C" int itts_embed_step(const int32_t* tokens, const float* table, const 
   const int mtp = (B + 15) / 16;
   return by_dtype(dtype, "itts_embed_step", [&](auto tag) {
     using T = typename decltype(tag)::type;
-    hipLaunchKernelGGL(embed_step_kernel<T>, dim3(B), dim3(256), 0, s, tokens, table, pos_table, step, pos_add, h, D, bump, row_step0,
-                       pos_rows, (T*)h_packed, mtp);
+    hipLaunchKernelGGL(embed_step_kernel<T>, dim3(B), dim3(256), 0, s, tokens, step, row_step0, table, pos_table, pos_add, D, pos_rows,
+                       mtp, h, (T*)h_packed, bump);
     return check_launch("itts_embed_step");
   });
 }

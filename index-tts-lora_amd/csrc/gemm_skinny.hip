@@ -99,7 +99,7 @@ static int launch_skinny_mt(const SkinnyParams& p, const SkinnyPlan& q, hipStrea
   const int maxw = q.NW == 16 ? 16 : 8;
 #define ITTS_SK(SPW_, NTB_, MAXW_)                                                                         \
   if (q.SPWc == SPW_ && q.ntb == NTB_ && maxw == MAXW_) {                                                  \
-    hipLaunchKernelGGL((gemm_skinny_kernel<T, MT, SPW_, NTB_, FOLD, MAXW_>), grid, block, q.lds, s, p);    \
+    hipLaunchKernelGGL((gemm_skinny_kernel<T, MT, SPW_, NTB_, FOLD, MAXW_>), grid, block, q.lds, s, SKINNY_LEAD_ARGS(p, q), static_cast<const SkinnyTail&>(p));    \
     return check_launch("itts_gemm_skinny");                                                               \
   }
   ITTS_SK(5, 1, 8)

@@ -21,28 +21,29 @@ __device__ __forceinline__ F ldw(const void* p) {
   else return ld16<F>(p);
 }
 
-struct SkinnyParams {
-  int M, N, K;
-  const void* wp;
+// The kernel's arguments come in two parts.  SKINNY_LEAD: what the first operand requests need -- the weight image, the activations,
+// the cache position word, the shape, the split, the packed-x geometry, the waves per workgroup (blockDim.x is itself a word of the
+// argument buffer: reading it would put the scalar load back in front of the first request) -- as plain leading parameters, 14 dwords:
+// exactly what gfx950 delivers in SGPRs at wave launch (kernarg preload, csrc/Makefile; a by-value struct is never preloaded).
+// SkinnyTail: what only the bias / residual requests and the epilogue read, one trailing struct whose scalar load is issued beside
+// the first requests and waited for at its first consumer.  SkinnyParams is both, as the launchers fill it and the kernel body
+// reads it.
+struct SkinnyTail {
   const float* bias;
-  const void* x;
-  int epi;
   void* y;
   float* yf;
   void* kcache;
   void* vcache;
-  const int32_t* pos;
+  int epi;
   int heads, smax;
-  int ksplit;
   int slab_rows;
   const int32_t* kv_tab;   // QKV epilogue into a paged cache: block table [rows][ITTS_KV_TAB], or NULL
   int kv_bs_log2;
   const float* cvec;       // FOLD: c_j = sum_k gamma_k W_kj (bias then holds d_j)
   float ln_eps;
   int32_t* bump;           // one device word this launch increments (it must not read it)
-  int x_pa, y_pa;          // packed-activation layout for x / y
-  int mtp, row0;           // row tiles of the WHOLE operand, first row of this launch (a multiple of 16)
-  int y_mtp, y_row0;       // the same for a packed y (the rows may land inside a taller packed operand)
+  int y_pa;                // packed-activation layout for y
+  int y_mtp, y_row0;       // row tiles and first row of a packed y (the rows may land inside a taller packed operand)
   const float* post_scale; // RELU_AFFINE epilogues: y = relu(v) * post_scale[n] + post_shift[n]
   const float* post_shift;
   const float* w_scale;    // W8: one fp32 scale per output column, applied to the accumulator in front of the epilogue
@@ -53,6 +54,21 @@ struct SkinnyParams {
   int exp;   // diagnostic ablations: bit 0 = every activation fragment is k-step 0's (L1-resident), bit 1 = every weight block is block 0
 #endif
 };
+
+struct SkinnyParams : SkinnyTail {
+  const void* wp;
+  const void* x;
+  const int32_t* pos;      // QKV epilogue: the cache position word; NULL for every other epilogue
+  int M, N, K;
+  int ksplit;
+  int x_pa;                // packed-activation layout for x
+  int mtp, row0;           // row tiles of the WHOLE operand, first row of this launch (a multiple of 16)
+  int nw;                  // waves per workgroup (the plan's NW; the launch sites pass it)
+};
+#define SKINNY_LEAD_PARAMS                                                                                               \
+  const void* wp, const void* x, const int32_t* pos, int M, int N, int K, int ksplit, int x_pa, int mtp, int row0, int nw
+#define SKINNY_LEAD_NAMES wp, x, pos, M, N, K, ksplit, x_pa, mtp, row0, nw
+#define SKINNY_LEAD_ARGS(p, q) (p).wp, (p).x, (p).pos, (p).M, (p).N, (p).K, (p).ksplit, (p).x_pa, (p).mtp, (p).row0, (q).NW
 
 #if ITTS_STAMPS
 #define ITTS_STAMP(i) ITTS_STAMP_IF(p.stamps != nullptr, i)
@@ -145,7 +161,8 @@ __device__ __forceinline__ F ones_frag() {
 // over the waves, SPW per pass) then counts weight blocks, each with XPS = 2 activation fragments per row tile; the accumulator
 // is multiplied by the column's scale in front of the epilogue.  T is bf16 or f16.
 template <typename T, int MT, int SPW, int NTB, bool FOLD, int MAXW, bool W8 = false>
-__global__ __launch_bounds__(MAXW * 64) void gemm_skinny_kernel(SkinnyParams p) {
+__global__ __launch_bounds__(MAXW * 64) void gemm_skinny_kernel(SKINNY_LEAD_PARAMS, SkinnyTail tail) {
+  const SkinnyParams p{tail, SKINNY_LEAD_NAMES};
   typedef Elem<T> EL;
   typedef typename EL::frag frag;
   typedef typename std::conditional<W8, u32x4, frag>::type wfrag;   // a lane's 16 bytes of a weight block, as loaded
@@ -161,7 +178,7 @@ __global__ __launch_bounds__(MAXW * 64) void gemm_skinny_kernel(SkinnyParams p) 
   if (p.stamps != nullptr && threadIdx.x == 0) rt0_ = __builtin_amdgcn_s_memrealtime();
 #endif
   ITTS_STAMP(0);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NW = blockDim.x >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NW = p.nw;
   const int nt0 = (int)blockIdx.x * NTB, ks = blockIdx.y;
   const int mt0 = (int)blockIdx.z * MT;       // first row tile of this workgroup inside the launch's rows
   const int NTtot = (p.N + 15) / 16;
@@ -177,13 +194,16 @@ __global__ __launch_bounds__(MAXW * 64) void gemm_skinny_kernel(SkinnyParams p) 
   const char* bp = (const char*)p.wp + ((int64_t)nt0 * KT * 64 + lane) * 16;  // tile t of this workgroup: + t*KT*1024
   const T* X = (const T*)p.x;
 
-  // Epilogue operands of this wave's output units are requested now, in front of the weight stream: their latency overlaps it
-  // and the epilogue issues no load of its own.  pre2 = the residual values the RESID epilogue adds to, or (FOLD) c.
-  // UPRE units per wave cover every launch with >= 8 waves; launches with fewer waves (tiny K) finish in a second loop.
+  // Epilogue operands of this wave's output units are requested behind the first pass's operand requests, under the weight
+  // stream: their latency overlaps it and the epilogue issues no load of its own.  Their addresses are the first thing that needs
+  // the trailing argument struct, so its scalar load -- issued at the head, beside the operand requests, which need preloaded
+  // arguments only -- is waited for here and not in front of the weight stream.  pre2 = the residual values the RESID epilogue adds
+  // to, or (FOLD) c.  UPRE units per wave cover every launch with >= 8 waves; launches with fewer waves (tiny K) finish in a
+  // second loop.
   constexpr int UPRE = (NTB * MT + 7) / 8;
   f32x4 bias_pre[UPRE], pre2[UPRE], scale_pre[W8 ? UPRE : 1];
   int pos_pre = 0;
-  {
+  auto epi_requests = [&]() {
     // range-checked loads: a null bias, another K slice, columns past N (the 8194-column head), rows past M read zeros -- no
     // branch, so no join at which the compiler would wait for this round trip before the weight requests go out
     const __amdgpu_buffer_rsrc_t rbias = __builtin_amdgcn_make_buffer_rsrc(
@@ -204,7 +224,7 @@ __global__ __launch_bounds__(MAXW * 64) void gemm_skinny_kernel(SkinnyParams p) 
       const unsigned o2 = !uok ? 0x80000000u : FOLD ? (unsigned)col0 * 4u : (row < p.M ? (unsigned)(row * p.N + col0) * 4u : 0x80000000u);
       pre2[ui] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r2, o2, 0, 0));
     }
-  }
+  };
   // W8: the columns' scales, the same way (N % 4 != 0: element by element, columns past N read zeros).  Requested with the bias; the
   // forms with more than 16 output units per workgroup (SCALE_LATE: 6 row tiles x 3 column tiles, whose K walk fills the register
   // file) request them behind the K walk, where the accumulators have gone to LDS, and the reduction's barrier covers the trip.
@@ -221,8 +241,9 @@ __global__ __launch_bounds__(MAXW * 64) void gemm_skinny_kernel(SkinnyParams p) 
         scale_pre[ui][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsc, soff + 4u * e, 0, 0));
     }
   };
-  if constexpr (W8 && !SCALE_LATE) scale_requests();
-  if (wave < NTB * MT && p.epi == ITTS_EPI_QKV_CACHE) pos_pre = p.pos[0];
+  // the cache position word (QKV epilogue): its pointer is preloaded, so this request leaves with the first operand requests.  A
+  // readable word either way -- a select, no branch, so no join at which the compiler would wait for it in front of them
+  pos_pre = *(p.pos != nullptr ? p.pos : (const int32_t*)p.wp);
 
   f32x4 acc[NTB][MT];
 #pragma unroll
@@ -275,11 +296,14 @@ __global__ __launch_bounds__(MAXW * 64) void gemm_skinny_kernel(SkinnyParams p) 
   // requests (round 3: together with the branch-free bias preload and the LDS-only barrier, 5.65 -> 5.29 us per launch
   // over a block's four GEMMs against the round-2 kernel on the same box, tools/probes/ab_r02_gemm.py).
   // paged KV cache (QKV epilogue): the block that holds the append position of each of this wave's output rows.  Requested
-  // BEHIND the first pass's operand requests (it needs the position word, and nothing before the epilogue needs it).
+  // BEHIND the first pass's operand requests (it needs the position word, and nothing before the epilogue needs it), with the
+  // other epilogue operands.
   int blk_pre[UPRE];
 #pragma unroll
   for (int ui = 0; ui < UPRE; ++ui) blk_pre[ui] = 0;
-  auto table_requests = [&]() {
+  auto late_requests = [&]() {
+    epi_requests();
+    if constexpr (W8 && !SCALE_LATE) scale_requests();
     const int32_t* tp = p.kv_tab != nullptr ? p.kv_tab : (const int32_t*)p.wp;   // a readable word either way: a select, no branch
 #pragma unroll
     for (int ui = 0; ui < UPRE; ++ui) {
@@ -317,7 +341,7 @@ __global__ __launch_bounds__(MAXW * 64) void gemm_skinny_kernel(SkinnyParams p) 
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) af[i][j][mt] = x_frag(base + i, j, mt);
       }
-      if constexpr (FIRST_PASS) table_requests();
+      if constexpr (FIRST_PASS) late_requests();
       ITTS_STAMP(1);
 #if ITTS_STAMPS
       ITTS_STAMP_DRAIN();
@@ -355,7 +379,7 @@ __global__ __launch_bounds__(MAXW * 64) void gemm_skinny_kernel(SkinnyParams p) 
       for (int t = 0; t < NTB; ++t)
 #pragma unroll
         for (int i = 0; i < SPW; ++i) bf[t][i] = w_frag(base + i, t);
-      if constexpr (FIRST_PASS) table_requests();
+      if constexpr (FIRST_PASS) late_requests();
       ITTS_STAMP(1);
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
@@ -584,7 +608,8 @@ static SkinnyParams skinny_params_of(const A* a, int r0, int rows, size_t esz, i
   p.vcache = a->vcache ? (char*)a->vcache + (paged ? 0 : (size_t)r0 * crow) : nullptr;
   p.kv_tab = a->kv_tab;
   p.kv_bs_log2 = kv_bs_log2;
-  p.pos = a->pos;
+  p.pos = a->epi == ITTS_EPI_QKV_CACHE ? a->pos : nullptr;
+  p.nw = 0;   // (the launch sites pass the plan's NW)
   p.heads = a->heads;
   p.smax = a->smax;
   p.ksplit = 1;

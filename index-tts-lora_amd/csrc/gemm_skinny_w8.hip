@@ -69,7 +69,7 @@ static int launch_skinny_w8_mt(const SkinnyParams& p, const SkinnyPlan& q, hipSt
   dim3 grid(q.gx, q.gy, q.gz), block(q.NW * 64);
 #define ITTS_SK8(SPW_, NTB_)                                                                                  \
   if (q.SPWc == SPW_ && q.ntb == NTB_) {                                                                      \
-    hipLaunchKernelGGL((gemm_skinny_kernel<T, MT, SPW_, NTB_, FOLD, 8, true>), grid, block, q.lds, s, p);     \
+    hipLaunchKernelGGL((gemm_skinny_kernel<T, MT, SPW_, NTB_, FOLD, 8, true>), grid, block, q.lds, s, SKINNY_LEAD_ARGS(p, q), static_cast<const SkinnyTail&>(p));     \
     return check_launch("itts_gemm_skinny_w8");                                                               \
   }
   ITTS_SK8(3, 1)

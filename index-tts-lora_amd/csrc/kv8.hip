@@ -64,17 +64,19 @@ __device__ __forceinline__ void kv8_load16(typename Elem<T>::frag a, typename El
 // (attention.hip): everything of a pass is requested before the first use, all K before all V, selects instead of branches, the
 // skip word and the context come back in the first trip.  A lane owns 16 dims of a key (16 bytes of codes), 4 lanes a key, a
 // wave-load 16 keys; key groups are cut from the left padding rounded down to 16, so a request's block id is wave-uniform.
+// The arguments of the first trip lead (14 dwords, preloaded into SGPRs at wave launch); the pools and the output follow.
 // The first pass is context-sized: 1..4 chunks per wave for up to 64 / 128 / 192 / 256 key slots.
 // The new key (position pos[0]) is not in the pool yet: every lane quantises its 16 dims of the row's new k / v, the decoded codes
 // enter the softmax through wave 0's first lane group, and those four lanes store the codes at the end.
 // ---------------------------------------------------------------------------------------------------------------------
 template <typename T>
-__global__ __launch_bounds__(K8_NWV * 64) void attn_decode_kv8_kernel(const T* __restrict__ qkv, uint8_t* __restrict__ kc,
-                                                                      uint8_t* __restrict__ vc, T* __restrict__ out,
-                                                                      const int32_t* __restrict__ pad, const int32_t* __restrict__ pos,
-                                                                      const float* __restrict__ kv_scale, int H, int out_mtp,
+__global__ __launch_bounds__(K8_NWV * 64) void attn_decode_kv8_kernel(const T* __restrict__ qkv, const int32_t* __restrict__ pad,
+                                                                      const int32_t* __restrict__ pos,
                                                                       const int32_t* __restrict__ skip_rows,
-                                                                      const int32_t* __restrict__ kv_tab, int bs_log2) {
+                                                                      const int32_t* __restrict__ kv_tab,
+                                                                      const float* __restrict__ kv_scale, int H, int bs_log2,
+                                                                      uint8_t* __restrict__ kc, uint8_t* __restrict__ vc,
+                                                                      T* __restrict__ out, int out_mtp) {
   typedef Elem<T> EL;
   typedef typename EL::frag frag;
   constexpr int E = K8_E, LPR = K8_LPR, RPW = K8_RPW, NWV = K8_NWV, CH = K8_CH;
@@ -99,6 +101,7 @@ __global__ __launch_bounds__(K8_NWV * 64) void attn_decode_kv8_kernel(const T* _
   const bool skipped = skip_rows != nullptr && skip_raw != 0;
   int pos0 = pos[0];
   asm volatile("" : "+s"(pos0));
+  asm volatile("" : "+s"(kc), "+s"(vc), "+s"(out));   // the pools and the output (trailing arguments): their scalar load is issued beside the device words, not behind their wait
   const int ctx = skipped ? j0 : pos0;    // pool keys [j0, ctx); the new key is position pos0
 
   float qf[E], vn[E];
@@ -307,7 +310,7 @@ extern "C" int itts_attn_decode_kv8(const void* qkv, void* kcache, void* vcache,
   return by_dtype16(dtype, "itts_attn_decode_kv8", [&](auto tag) {
     using T = typename decltype(tag)::type;
     hipLaunchKernelGGL(attn_decode_kv8_kernel<T>, dim3(H, B), dim3(K8_NWV * 64), 0, (hipStream_t)stream, (const T*)qkv,
-                       (uint8_t*)kcache, (uint8_t*)vcache, (T*)out, pad, pos, kv_scale, H, out_mtp, skip_rows, kv_tab, bs_log2);
+                       pad, pos, skip_rows, kv_tab, kv_scale, H, bs_log2, (uint8_t*)kcache, (uint8_t*)vcache, (T*)out, out_mtp);
     return check_launch("itts_attn_decode_kv8");
   });
 }

@@ -10,29 +10,42 @@ namespace itts {
 constexpr int SM_MAXV = 8448;   // logits staged in LDS (33 x 256)
 constexpr int SM_MAXC = 1024;   // candidate cap after top-k
 
-struct SampleParams {
-  const float* logits;
-  int B, V, ldl;
+// The kernel's arguments come in two parts.  SAMPLE_LEAD: what the first trip needs -- the logits, the loop state, the rows' step,
+// finished and forced-stop words, the per-row records -- as plain leading parameters, 14 dwords: what gfx950 delivers in SGPRs at
+// wave launch (kernarg preload, csrc/Makefile; a by-value struct is never preloaded).  SampleTail: everything read behind that
+// trip, one trailing struct.  SampleParams is both, as the entry points fill it and the kernel body reads it.
+struct SampleTail {
+  int B;
   int32_t* tokens;
   int32_t* history;
   int hist_cap;
-  int32_t* finished;
-  int32_t* state;
   const int32_t* extra_ids;
   int n_extra;
-  const int32_t* force_stop;
   float rep_penalty, temperature, top_p;
   int top_k, do_sample;
   uint32_t seed_lo, seed_hi;
   int stop_token;
   float* dbg_scores;
   int advance;
-  const int32_t* row_step0;
-  const itts_sample_row* rows;   // itts_sample_rows: one record per row instead of the scalars above
 #if ITTS_STAMPS
   unsigned long long* stamps;
 #endif
 };
+
+struct SampleParams : SampleTail {
+  const float* logits;
+  int32_t* state;
+  const int32_t* row_step0;
+  int32_t* finished;
+  const int32_t* force_stop;
+  const itts_sample_row* rows;   // itts_sample_rows: one record per row instead of the tail's scalar settings
+  int V, ldl;
+};
+#define SAMPLE_LEAD_PARAMS                                                                                                   \
+  const float* logits, int32_t* state, const int32_t* row_step0, int32_t* finished, const int32_t* force_stop,             \
+      const itts_sample_row* rows, int V, int ldl
+#define SAMPLE_LEAD_NAMES logits, state, row_step0, finished, force_stop, rows, V, ldl
+#define SAMPLE_LEAD_ARGS(p) (p).logits, (p).state, (p).row_step0, (p).finished, (p).force_stop, (p).rows, (p).V, (p).ldl
 
 // The sampling settings of one workgroup's row, in scalar registers either way: the launch arguments (itts_sample) or the row's
 // 32-byte record (itts_sample_rows; two 16-byte loads issued with the first round trip, every lane reads the same words).  A
@@ -99,7 +112,8 @@ __device__ __forceinline__ uint32_t philox_first(uint32_t c0, uint32_t c1, uint3
 }
 
 template <bool ROWS>
-__global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
+__global__ __launch_bounds__(256) void sample_kernel(SAMPLE_LEAD_PARAMS, SampleTail tail) {
+  SampleParams p{tail, SAMPLE_LEAD_NAMES};
   __shared__ float sv[SM_MAXV];
   __shared__ uint32_t flag[SM_MAXV / 32];
   __shared__ int hist[256];
@@ -115,8 +129,12 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int kg = p.state[0];                                                  // loop step: the Philox counter
   const int k = kg - (p.row_step0 != nullptr ? p.row_step0[b] : 0);           // the ROW's step (a refilled slot starts at 0)
-  const int V = p.V;
   const float* lg = p.logits + (int64_t)b * p.ldl;
+  // the trailing arguments, pinned here: their scalar load is issued beside the loads of the device words above (one wait covers
+  // both) -- the compiler would otherwise sink it below that wait, a second, cold trip in front of the bitmap pass
+  asm volatile("" : "+s"(p.B), "+s"(p.tokens), "+s"(p.history), "+s"(p.hist_cap), "+s"(p.extra_ids), "+s"(p.n_extra), "+s"(p.rep_penalty),
+               "+s"(p.temperature), "+s"(p.top_p), "+s"(p.top_k), "+s"(p.do_sample), "+s"(p.seed_lo), "+s"(p.seed_hi), "+s"(p.stop_token),
+               "+s"(p.dbg_scores), "+s"(p.advance));
   const RowSettings rs = row_settings<ROWS>(p, b, kg, k);
 #if ITTS_STAMPS
   unsigned long long st_[16];
@@ -464,7 +482,8 @@ extern "C" int itts_sample(const itts_sample_args* a, void* stream) {
   p.do_sample = a->do_sample;
   p.seed_lo = (uint32_t)(a->seed & 0xFFFFFFFFull);
   p.seed_hi = (uint32_t)(a->seed >> 32);
-  hipLaunchKernelGGL(sample_kernel<false>, dim3(a->B), dim3(256), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(sample_kernel<false>, dim3(a->B), dim3(256), 0, (hipStream_t)stream, SAMPLE_LEAD_ARGS(p),
+                     static_cast<const SampleTail&>(p));
   return check_launch("itts_sample");
 }
 
@@ -479,6 +498,7 @@ extern "C" int itts_sample_rows(const itts_sample_rows_args* a, void* stream) {
   ITTS_REQUIRE(a->rows != nullptr && (reinterpret_cast<uintptr_t>(a->rows) & 15) == 0,
                "itts_sample_rows: rows must be a 16-byte aligned table of B records");
   p.rows = a->rows;
-  hipLaunchKernelGGL(sample_kernel<true>, dim3(a->B), dim3(256), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(sample_kernel<true>, dim3(a->B), dim3(256), 0, (hipStream_t)stream, SAMPLE_LEAD_ARGS(p),
+                     static_cast<const SampleTail&>(p));
   return check_launch("itts_sample_rows");
 }
