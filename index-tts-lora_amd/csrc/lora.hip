@@ -128,6 +128,139 @@ static int launch_lora_shrink(const LoraShrinkParams& p, int rows, hipStream_t s
   return check_launch("itts_lora_shrink");
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The same launch over weighted MIXES of bank voices (itts_lora_shrink_mix, include/indextts_hip_mix.h): a row names up to four
+// adapters, the slot of entry j gets w_j s_{a_j} (x A_{a_j}^T).  lora_shrink_kernel's shape with a wave-uniform loop over the
+// record's entries around its K loop: per entry the same pieces, the same rp accumulators, the same butterfly, the same partials
+// in wave order -- so a record {a, 1.0f} gives lora_shrink_kernel's bits for id a (w * s is one fp32 multiply in front of the one
+// rounding to T, exact at 1.0f), and the order of the entries moves no bit (an entry's partials meet nobody else's).
+// A lane's x pieces are its own in every entry.  Its first piece is requested in the kernel's first lines, beside the row's record
+// (two 16-byte words of one address for the whole workgroup: the compiler makes them one scalar request), and stays in registers:
+// one trip for x and the record, then the A requests.  The first entry fetches the lane's later pieces and keeps LORA_MIX_XT of them
+// (K <= 18432 in the 16-bit types, 9216 in fp32) in LDS slots private to the lane -- no barrier -- for the entries that follow;
+// pieces of a longer row are requested again (L2 hits).  K = 1280 in bf16 is one piece per lane: no LDS traffic at all.
+// Leading arguments: what the first requests need, for the kernarg preload; the output's description trails.
+constexpr int LORA_MIX_XT = 8;
+
+template <typename T, int NCH>
+__global__ __launch_bounds__(LORA_NWV * 64) void lora_shrink_mix_kernel(const void* x, const itts_lora_mix_row* mix, const void* a_bank,
+                                                                        int M, int K, int n, int rp, int x_packed, int x_mtp, void* u,
+                                                                        int Kx, int u_packed, int u_mtp, int64_t ldu) {
+  typedef Elem<T> EL;
+  typedef typename EL::frag frag;
+  constexpr int E = EL::E, NE = ITTS_LORA_MIX_ENTRIES;
+  __shared__ float part[NE][LORA_NWV][NCH * 16];
+  __shared__ B16 xs[LORA_MIX_XT][LORA_NWV * 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int m = blockIdx.x;   // < M, or a padding row of the packed tail (written as zeros)
+  const T* X = (const T*)x;
+  // the lane's first piece of x and the row's record are requested together, in front of the first wait: one trip for both
+  const int kf = (wave * 64 + lane) * E;
+  frag x0 = zero_frag<frag>();
+  if (m < M && kf < K) x0 = ld16<frag>(x_packed ? X + pa_off<T>(m, kf, x_mtp) : X + (int64_t)m * K + kf);
+  int id[NE];
+  float wt[NE];
+#pragma unroll
+  for (int j = 0; j < NE; ++j) id[j] = -1, wt[j] = 0.f;
+  if (m < M) {   // block-uniform; the record is the same 32 bytes for every lane
+    const u32x4 r0 = ld16<u32x4>(mix + m), r1 = ld16<u32x4>((const char*)(mix + m) + 16);
+#pragma unroll
+    for (int j = 0; j < NE; ++j) {
+      const u32x4 r = j < 2 ? r0 : r1;
+      id[j] = __builtin_amdgcn_readfirstlane((int)r[(j & 1) * 2]);
+      wt[j] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(r[(j & 1) * 2 + 1]));
+      if (id[j] >= n) id[j] = -1;   // (the host checks the ids; an id outside the bank must still not read outside it)
+    }
+  }
+  bool have_x = false;   // a lane's later pieces are in xs[] once one entry has gone over the row
+
+#pragma unroll
+  for (int j = 0; j < NE; ++j) {
+    if (id[j] < 0) continue;   // wave-uniform
+    const T* A = (const T*)a_bank + (int64_t)id[j] * rp * K;
+    float acc[NCH][16];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[c][i] = 0.f;
+    int t = 0;
+    for (int k0 = (wave * 64 + lane) * E; k0 < K; k0 += LORA_NWV * 64 * E, ++t) {
+      frag xf = x0;
+      if (t > 0) {
+        if (have_x && t <= LORA_MIX_XT) {
+          xf = ld16<frag>(&xs[t - 1][tid]);
+        } else {
+          xf = ld16<frag>(x_packed ? X + pa_off<T>(m, k0, x_mtp) : X + (int64_t)m * K + k0);
+          if (!have_x && t <= LORA_MIX_XT) st16(&xs[t - 1][tid], xf);
+        }
+      }
+      float xv[E];
+#pragma unroll
+      for (int e = 0; e < E; ++e) xv[e] = EL::to_f(xf[e]);
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        frag af[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) af[i] = ld16<frag>(A + (int64_t)(c * 16 + i) * K + k0);
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+#pragma unroll
+          for (int e = 0; e < E; ++e) acc[c][i] = fmaf(xv[e], EL::to_f(af[i][e]), acc[c][i]);
+      }
+    }
+    have_x = true;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const float s = reduce16(acc[c], lane);
+      if ((lane & 3) == 0) part[j][wave][c * 16 + (lane >> 2)] = s;
+    }
+  }
+  __syncthreads();
+  // every column of the row's K_x, every call: the named slots from their entry's partials (wave order) times its weight, zeros
+  // everywhere else
+  T* U = (T*)u;
+  for (int col0 = tid * E; col0 < Kx; col0 += LORA_NWV * 64 * E) {
+    int own = -1, j0 = 0;   // rp % 16 == 0 and E | 16: a piece lies inside one slot or outside all
+    float w = 0.f;
+#pragma unroll
+    for (int j = NE - 1; j >= 0; --j) {
+      const int d = col0 - id[j] * rp;
+      if (id[j] >= 0 && d >= 0 && d < rp) own = j, j0 = d, w = wt[j];
+    }
+    frag o;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      float s = 0.f;
+      if (own >= 0) {
+        const int slot = j0 + e;   // reduce16 leaves accumulator i of a chunk in lane group i = lane >> 2
+        s = part[own][0][slot];
+#pragma unroll
+        for (int wv = 1; wv < LORA_NWV; ++wv) s += part[own][wv][slot];
+        s *= w;
+      }
+      o[e] = EL::from_f(s);
+    }
+    st16(u_packed ? U + pa_off<T>(m, col0, u_mtp) : U + (int64_t)m * ldu + col0, o);
+  }
+}
+
+template <typename T>
+static int launch_lora_shrink_mix(const itts_lora_shrink_mix_args& a, int x_mtp, int u_mtp, hipStream_t s) {
+  const int rows = a.u_packed ? u_mtp * 16 : a.M;   // the packed tail's padding rows are written too (zeros)
+  dim3 grid(rows), block(LORA_NWV * 64);
+#define ITTS_MIX_LAUNCH(NCH)                                                                                                       \
+  hipLaunchKernelGGL((lora_shrink_mix_kernel<T, NCH>), grid, block, 0, s, a.x, a.mix, a.a_bank, a.M, a.K, a.n, a.rp, a.x_packed ? 1 : 0, \
+                     x_mtp, a.u, a.Kx, a.u_packed ? 1 : 0, u_mtp, a.ldu)
+  switch (a.rp / 16) {
+    case 1: ITTS_MIX_LAUNCH(1); break;
+    case 2: ITTS_MIX_LAUNCH(2); break;
+    case 3: ITTS_MIX_LAUNCH(3); break;
+    default: ITTS_MIX_LAUNCH(4); break;
+  }
+#undef ITTS_MIX_LAUNCH
+  return check_launch("itts_lora_shrink_mix");
+}
+
 }  // namespace itts
 
 using namespace itts;
@@ -167,5 +300,28 @@ extern "C" int itts_lora_shrink(const itts_lora_shrink_args* a, void* stream) {
     p.u_mtp = u_mtp;
     const int rows = p.u_packed ? u_mtp * 16 : a->M;   // the packed tail's padding rows are written too (zeros)
     return launch_lora_shrink<T>(p, rows, (hipStream_t)stream);
+  });
+}
+
+extern "C" int itts_lora_shrink_mix(const itts_lora_shrink_mix_args* a, void* stream) {
+  ITTS_REQUIRE(a && a->x && a->mix && a->a_bank && a->u, "itts_lora_shrink_mix: null args");
+  return by_dtype(a->dtype, "itts_lora_shrink_mix", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    constexpr int ks = Elem<T>::KS, e = Elem<T>::E;
+    ITTS_REQUIRE(a->M >= 0 && a->K > 0 && a->K % ks == 0, "itts_lora_shrink_mix: bad shape M=%d K=%d (K %% %d != 0)", a->M, a->K, ks);
+    ITTS_REQUIRE(a->n >= 1 && a->rp >= 16 && a->rp <= 64 && a->rp % 16 == 0,
+                 "itts_lora_shrink_mix: n=%d adapters of padded rank rp=%d (1 <= n, rank <= 64, rp %% 16 == 0)", a->n, a->rp);
+    ITTS_REQUIRE(a->Kx <= 512 && a->Kx == ((int64_t)a->n * a->rp + 31) / 32 * 32,
+                 "itts_lora_shrink_mix: Kx=%d must be n * rp rounded up to a multiple of 32, and <= 512", a->Kx);
+    const int mtp = (a->M + 15) / 16;
+    const int x_mtp = a->x_mtp > 0 ? a->x_mtp : mtp, u_mtp = a->u_mtp > 0 ? a->u_mtp : mtp;
+    ITTS_REQUIRE((a->x_packed || a->x_mtp == 0) && x_mtp * 16 >= a->M, "itts_lora_shrink_mix: x_mtp is for a packed x of at least M rows");
+    ITTS_REQUIRE((a->u_packed || a->u_mtp == 0) && u_mtp * 16 >= a->M, "itts_lora_shrink_mix: u_mtp is for a packed u of at least M rows");
+    ITTS_REQUIRE(a->u_packed || (a->ldu >= a->Kx && a->ldu % e == 0), "itts_lora_shrink_mix: a row-major u needs ldu >= Kx, ldu %% %d == 0", e);
+    ITTS_REQUIRE(((uintptr_t)a->x & 15) == 0 && ((uintptr_t)a->u & 15) == 0 && ((uintptr_t)a->a_bank & 15) == 0 &&
+                     ((uintptr_t)a->mix & 15) == 0,
+                 "itts_lora_shrink_mix: x, u, a_bank and mix must be 16-byte aligned");
+    if (a->M == 0) return ITTS_OK;
+    return launch_lora_shrink_mix<T>(*a, x_mtp, u_mtp, (hipStream_t)stream);
   });
 }

@@ -78,6 +78,26 @@ class LoraShrinkArgs(C.Structure):
                 ("u_packed", C.c_int), ("u_mtp", C.c_int), ("ldu", C.c_int64)]
 
 
+class LoraMixEntry(C.Structure):
+    _fields_ = [("id", C.c_int32), ("weight", C.c_float)]
+
+
+LORA_MIX_ENTRIES = 4     # ITTS_LORA_MIX_ENTRIES
+LORA_MIX_ROW_BYTES = 32
+
+
+class LoraMixRow(C.Structure):
+    """itts_lora_mix_row: one row's weighted mix of bank voices, 32 bytes (include/indextts_hip_mix.h)."""
+    _fields_ = [("e", LoraMixEntry * LORA_MIX_ENTRIES)]
+
+
+class LoraShrinkMixArgs(C.Structure):
+    """itts_lora_shrink_mix_args: LoraShrinkArgs with the records' pointer in the place of the ids'."""
+    _fields_ = [("dtype", C.c_int), ("M", C.c_int), ("K", C.c_int), ("x", C.c_void_p), ("x_packed", C.c_int), ("x_mtp", C.c_int),
+                ("mix", C.c_void_p), ("a_bank", C.c_void_p), ("n", C.c_int), ("rp", C.c_int), ("Kx", C.c_int), ("u", C.c_void_p),
+                ("u_packed", C.c_int), ("u_mtp", C.c_int), ("ldu", C.c_int64)]
+
+
 class ConvArgs(C.Structure):
     _fields_ = [("dtype", C.c_int), ("B", C.c_int), ("Tin", C.c_int), ("Tout", C.c_int), ("Cin", C.c_int),
                 ("N", C.c_int), ("taps", C.c_int), ("off0", C.c_int), ("dil", C.c_int), ("x", C.c_void_p),
@@ -208,11 +228,17 @@ _PROMPT_SIGNATURES = {
                                               C.POINTER(SegTableArgs), C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]),
 }
 
+# include/indextts_hip_mix.h: the adapter bank's shrink launch over weighted mixes of voices
+_MIX_SIGNATURES = {
+    "itts_lora_shrink_mix": (C.c_int, [C.POINTER(LoraShrinkMixArgs), C.c_void_p]),
+}
+
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)          # what include/indextts_hip.h declares itself
 ROW_SYMBOLS = tuple(_ROW_SIGNATURES)           # what include/indextts_hip_rows.h declares
 W8_SYMBOLS = tuple(_W8_SIGNATURES)             # what include/indextts_hip_w8.h declares
 KV8_SYMBOLS = tuple(_KV8_SIGNATURES)           # what include/indextts_hip_kv8.h declares
 PROMPT_SYMBOLS = tuple(_PROMPT_SIGNATURES)     # what include/indextts_hip_prompts.h declares
+MIX_SYMBOLS = tuple(_MIX_SIGNATURES)           # what include/indextts_hip_mix.h declares
 _lib = None
 
 
@@ -225,7 +251,8 @@ def lib():
             raise NativeError(f"{path} not found: build it with `make -C index-tts-lora_amd/csrc` "
                               f"(or python -c 'import __graft_entry__ as g; g.build()'). There is no fallback path.")
         L = C.CDLL(path)
-        for name, (res, args) in {**_SIGNATURES, **_ROW_SIGNATURES, **_W8_SIGNATURES, **_KV8_SIGNATURES, **_PROMPT_SIGNATURES}.items():
+        for name, (res, args) in {**_SIGNATURES, **_ROW_SIGNATURES, **_W8_SIGNATURES, **_KV8_SIGNATURES, **_PROMPT_SIGNATURES,
+                                       **_MIX_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -639,6 +666,38 @@ def lora_shrink(x, ids, a_bank, u, M, K, x_packed=False, x_mtp=0, u_packed=False
     a.ids, a.a_bank, a.n, a.rp, a.Kx = _p(ids), _p(a_bank), n, rp, lora_kx(n, rp)
     a.u, a.u_packed, a.u_mtp, a.ldu = _p(u), int(bool(u_packed)), int(u_mtp), int(ldu)
     _check(lib().itts_lora_shrink(C.byref(a), _stream()), "itts_lora_shrink")
+
+
+def pack_lora_mix(mixes):
+    """Normalised mixes (one tuple of up to four (id, weight) per row: GPTEngine.check_adapter_mix) -> numpy uint8 [len(mixes), 32]:
+    the records itts_lora_shrink_mix reads (itts_lora_mix_row; unused entries are id -1, weight 0)."""
+    import numpy as np
+    recs = (LoraMixRow * max(len(mixes), 1))()
+    for rec, mix in zip(recs, mixes):
+        if len(mix) > LORA_MIX_ENTRIES:
+            raise ValueError(f"a mix holds at most {LORA_MIX_ENTRIES} entries (got {len(mix)})")
+        for j in range(LORA_MIX_ENTRIES):
+            rec.e[j].id, rec.e[j].weight = (int(mix[j][0]), float(mix[j][1])) if j < len(mix) else (-1, 0.0)
+    return np.frombuffer(bytes(recs), dtype=np.uint8).reshape(-1, LORA_MIX_ROW_BYTES)[: len(mixes)].copy()
+
+
+def lora_shrink_mix(x, mix, a_bank, u, M, K, x_packed=False, x_mtp=0, u_packed=False, u_mtp=0, ldu=0):
+    """lora_shrink over weighted mixes (itts_lora_shrink_mix): for every entry (a, w) of row m's record u[m][a * rp + j] =
+    w * (x[m] . a_bank[a][j]), every other column of u[m][:Kx] zero.  mix: uint8 device tensor [>= M, 32] of packed records
+    (pack_lora_mix; the values are checked on the host before the upload, the kernel only guards memory); the other arguments are
+    lora_shrink's."""
+    _dev(mix, a_bank)
+    if mix.dtype != torch.uint8 or mix.numel() < M * LORA_MIX_ROW_BYTES:
+        raise NativeError("itts_lora_shrink_mix: mix must be a uint8 device tensor of M 32-byte records")
+    n, rp, Ka = a_bank.shape
+    if Ka != K or a_bank.dtype != x.dtype or u.dtype != x.dtype:
+        raise NativeError("itts_lora_shrink_mix: a_bank must be T [n, rp, K] of the operand's type")
+    a = LoraShrinkMixArgs()
+    a.dtype, a.M, a.K = dt(x.dtype), int(M), int(K)
+    a.x, a.x_packed, a.x_mtp = _p(x), int(bool(x_packed)), int(x_mtp)
+    a.mix, a.a_bank, a.n, a.rp, a.Kx = _p(mix), _p(a_bank), n, rp, lora_kx(n, rp)
+    a.u, a.u_packed, a.u_mtp, a.ldu = _p(u), int(bool(u_packed)), int(u_mtp), int(ldu)
+    _check(lib().itts_lora_shrink_mix(C.byref(a), _stream()), "itts_lora_shrink_mix")
 
 
 def embed_step(tokens, table, pos_table, step, pos_add, h, bump=None, row_step0=None, h_packed=None):

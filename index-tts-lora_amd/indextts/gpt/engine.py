@@ -236,6 +236,7 @@ class GPTEngine:
         self.lora = False
         self.bank = None     # per-row adapter bank (attach_lora_bank): n, rp, Kx and the signature the graph key carries
         self._ids_host = None   # adapter id per row of the batch the last prefill() cached
+        self._mix_host = None   # ... or, prefilled with adapter_mix, every row's mix (check_adapter_mix); at most one of the two is set
         self.layers = []
 
         def folded(ln, wkey, bkey):
@@ -464,8 +465,11 @@ class GPTEngine:
                 del l[k]
         self.bank = None
         self._ids_host = None
+        self._mix_host = None
         if getattr(self, "adapter_ids", None) is not None:
             self.adapter_ids.fill_(-1)
+        if getattr(self, "adapter_mix", None) is not None:
+            self.adapter_mix.copy_(self._mix_records([()] * self.adapter_mix.shape[0]))
         self._graphs.clear()
 
     def _row_adapters(self, adapter_ids, B):
@@ -481,6 +485,72 @@ class GPTEngine:
         if any(v < -1 or v >= self.bank.n for v in ids):
             raise ValueError(f"adapter_ids must lie in [-1, {self.bank.n}): {ids}")
         return ids
+
+    def check_adapter_mix(self, mix, B):
+        """The batch's adapter mixes, normalised and checked on the host before anything is launched: one tuple of up to four
+        (id, weight) per row, sorted by id (the order of a record's entries moves no bit of the result).  Every element of `mix` is
+        None or -1 (the base voice), an int id (that adapter at weight 1), a {id: weight} dict or a sequence of (id, weight).
+        ValueError: no bank attached, a wrong number of rows, an id outside [0, n), a repeated id within a row, more than four
+        entries, a weight that is not finite."""
+        import math
+        import numbers
+        if self.bank is None:
+            raise ValueError("adapter_mix was given but no adapter bank is attached (attach_lora_bank)")
+        mix = mix.tolist() if torch.is_tensor(mix) else list(mix)
+        if len(mix) != B:
+            raise ValueError(f"adapter_mix holds {len(mix)} mixes for a batch of {B}")
+        out = []
+        for b, el in enumerate(mix):
+            if el is None or (isinstance(el, numbers.Integral) and int(el) == -1):
+                out.append(())
+                continue
+            if isinstance(el, numbers.Integral):
+                pairs = [(el, 1.0)]
+            elif isinstance(el, dict):
+                pairs = list(el.items())
+            else:
+                try:
+                    pairs = [(i, w) for i, w in el]
+                except (TypeError, ValueError):
+                    raise ValueError(f"adapter_mix[{b}]: a mix is None, -1, an id, a {{id: weight}} dict or a sequence of (id, weight) "
+                                     f"(got {el!r})") from None
+            if len(pairs) > nat.LORA_MIX_ENTRIES:
+                raise ValueError(f"adapter_mix[{b}]: a mix holds at most {nat.LORA_MIX_ENTRIES} entries (got {len(pairs)})")
+            row = []
+            for i, w in pairs:
+                if not isinstance(i, numbers.Integral) or not 0 <= int(i) < self.bank.n:
+                    raise ValueError(f"adapter_mix[{b}]: ids must lie in [0, {self.bank.n}) (got {i!r})")
+                if not isinstance(w, numbers.Real) or not math.isfinite(w):
+                    raise ValueError(f"adapter_mix[{b}]: the weight of adapter {int(i)} must be a finite number (got {w!r})")
+                row.append((int(i), float(w)))
+            if len({i for i, _ in row}) != len(row):
+                raise ValueError(f"adapter_mix[{b}]: adapter ids repeat within the row: {[i for i, _ in row]}")
+            out.append(tuple(sorted(row)))
+        return out
+
+    def _voices(self, adapter_ids, adapter_mix, B):
+        """(ids, mix) of a batch, checked: adapter ids (_row_adapters) or -- exclusive -- adapter mixes (check_adapter_mix)."""
+        if adapter_mix is None:
+            return self._row_adapters(adapter_ids, B), None
+        if adapter_ids is not None:
+            raise ValueError("adapter_ids and adapter_mix are mutually exclusive: a row is an id or a mix (an int in adapter_mix is "
+                             "that adapter at weight 1)")
+        return None, self.check_adapter_mix(adapter_mix, B)
+
+    def _mix_records(self, mixes):
+        """uint8 device tensor [len(mixes), 32]: the itts_lora_mix_row records of normalised mixes."""
+        return torch.from_numpy(nat.pack_lora_mix(mixes)).to(self.device)
+
+    def _row_mix(self, mixes, rows_per_element):
+        """Element b's record repeated over its rows (the large-M passes): the counterpart of _row_ids."""
+        import numpy as np
+        return torch.from_numpy(np.repeat(nat.pack_lora_mix(mixes), np.asarray(rows_per_element, dtype=np.int64), axis=0)).to(self.device)
+
+    def _row_voices(self, ids, mix, rows_per_element):
+        """Keyword arguments of _big_m_layers / _blocks_full for a batch's checked (ids, mix)."""
+        if mix is not None:
+            return dict(row_mix=self._row_mix(mix, rows_per_element))
+        return dict(row_ids=None if ids is None else self._row_ids(ids, rows_per_element))
 
     def _row_ids(self, ids, rows_per_element):
         """int32 device tensor: element b's adapter id repeated over its rows (the large-M passes)."""
@@ -501,6 +571,8 @@ class GPTEngine:
         e._beam_cap = (0, 0, 0)
         e._kv_rows = None
         e._ids_host = None
+        e._mix_host = None
+        e.adapter_mix = None            # (its own table of mixes comes with the fork's own row buffers)
         e.row_sampling = None           # (allocated with the fork's own row buffers)
         if self.kv_scale is not None:
             e.kv_scale = self.kv_scale.clone()   # the scales belong to the engine's cache, not to the shared weights
@@ -531,6 +603,7 @@ class GPTEngine:
             self.pad = torch.zeros(B, dtype=torch.int32, device=dev)
             self.force_stop = torch.full((B,), -1, dtype=torch.int32, device=dev)
             self.adapter_ids = torch.full((B,), -1, dtype=torch.int32, device=dev)   # adapter of each row (bank attached), -1 = base
+            self.adapter_mix = self._mix_records([()] * B)                           # ... or its weighted mix of adapters (itts_lora_mix_row)
             self.row_step0 = torch.zeros(B, dtype=torch.int32, device=dev)   # loop step at which each row started (decode_refill)
             self.row_sampling = RowSampling(B, dev)                          # each row's own sampling settings (sp given as a list)
             self.kv_share = torch.zeros(1, dtype=torch.int32, device=dev)    # (p0 << 8) | C: rows' first C keys == row 0's at p0 (itts_attn_decode)
@@ -657,18 +730,19 @@ class GPTEngine:
         best = min((1, 2, 3), key=lambda ks: (cost(ks), ks))
         return best if cost(best) < 0.9 * cost(rule) else rule
 
-    def _big_m_layers(self, h, attn, row_ids=None):
+    def _big_m_layers(self, h, attn, row_ids=None, row_mix=None):
         """The 24 blocks over packed rows h fp32 [M, D] (in place): LayerNorm -> QKV -> attn(i, qkv, att) -> out-projection ->
         LayerNorm -> FC -> FC2.  With few rows the two N = D projections run split-K into slabs and the NEXT LayerNorm launch folds
         them into h (see _proj_ksplit); returns h with every block applied.
         With an adapter bank (row_ids int32 [M]: the adapter of every row, default -1) an adapted GEMM reads [x | u] row-major:
         x is copied into a [M, K + Kx] operand, itts_lora_shrink writes u behind it, and the GEMM runs with Cin = K + Kx over the
-        extended weight -- one extra copy of the operand per adapted GEMM."""
+        extended weight -- one extra copy of the operand per adapted GEMM.  row_mix (uint8 [M, 32]: a mix record per row) in the
+        place of row_ids: itts_lora_shrink_mix writes u."""
         T, D, dev = self.dtype, self.D, self.device
         M = h.shape[0]
         bank = self.bank
         if bank is not None:
-            if row_ids is None:
+            if row_ids is None and row_mix is None:
                 row_ids = torch.full((M,), -1, dtype=torch.int32, device=dev)
             xc = {D: torch.empty(M, D + bank.Kx, dtype=T, device=dev), 4 * D: torch.empty(M, 4 * D + bank.Kx, dtype=T, device=dev)}
 
@@ -678,7 +752,10 @@ class GPTEngine:
                 return l.get(wkey + "_merged", l[wkey]), x, K
             c = xc[K]
             c[:, :K].copy_(x)
-            nat.lora_shrink(x, row_ids, l["bank_a_" + wkey], c[:, K:], M, K, ldu=K + bank.Kx)
+            if row_mix is not None:
+                nat.lora_shrink_mix(x, row_mix, l["bank_a_" + wkey], c[:, K:], M, K, ldu=K + bank.Kx)
+            else:
+                nat.lora_shrink(x, row_ids, l["bank_a_" + wkey], c[:, K:], M, K, ldu=K + bank.Kx)
             return l["bank_" + wkey], c, K + bank.Kx
         xn = torch.empty(M, D, dtype=T, device=dev)
         qkv = torch.empty(M, 3 * D, dtype=T, device=dev)
@@ -714,7 +791,7 @@ class GPTEngine:
             nat.ln_reduce(h, self.ln_f[0], self.ln_f[1], xn, slab=slab, nslab=ks, bias=pending)
         return h
 
-    def _blocks_full(self, h, B, S, pad, use_cache, row_off=None, cache_shift=None, row_ids=None):
+    def _blocks_full(self, h, B, S, pad, use_cache, row_off=None, cache_shift=None, row_ids=None, row_mix=None):
         """All transformer blocks over h fp32 [M, D] (in place).  Padded form: M = B*S rows, pad int32 [B] (left padding)
         or None.  Packed form (row_off int32 [B+1] on device): only real rows exist, batch element b owns rows
         [row_off[b], row_off[b+1]), S is the longest element, cache row = cache_shift[b] + local row."""
@@ -731,7 +808,7 @@ class GPTEngine:
                 nat.attn_prefill(qkv, att, kc, vc, pad, B, S, H, self._cap_s)
             else:
                 nat.attn_prefill_packed(qkv, att, kc, vc, row_off, cache_shift, B, S, H, self._cap_s, **({} if kc is None else kva))
-        return self._big_m_layers(h, attn, row_ids)
+        return self._big_m_layers(h, attn, row_ids, row_mix)
 
     def _head(self, h_rows, B):
         """ln_f -> final_norm -> mel_head on fp32 rows."""
@@ -787,7 +864,7 @@ class GPTEngine:
         return h[last_rows].contiguous()
 
     def prefill(self, prefix_emb: torch.Tensor, pad: torch.Tensor, max_new: int, beams: int = 1, shared_rows: int = 0, paged=None,
-                slots_window: int = 0, adapter_ids=None):
+                slots_window: int = 0, adapter_ids=None, adapter_mix=None):
         """prefix_emb fp32 [B,P,D] (left-padded with zeros), pad int [B].  Runs prefix + start token (mel position 0,
         model.py:152-162), fills the KV cache rows [pad_b, P] of every element, leaves logits of the last position in
         self.logits.  The left-padding rows are never computed: the real rows are packed (one gather), the GEMMs run over
@@ -806,16 +883,22 @@ class GPTEngine:
         (decode_refill's pool): size the pool for B rows of up to that many live positions each instead of this batch's.
         adapter_ids (host ints, one per element; needs attach_lora_bank): the adapter every row speaks with, -1 = the base voice;
         None with a bank attached = all base.  The ids reach the device as self.adapter_ids, which the decode step's shrink
-        launches read: they are data, a captured step serves every assignment."""
+        launches read: they are data, a captured step serves every assignment.
+        adapter_mix (one mix per element, see check_adapter_mix; exclusive with adapter_ids): every row speaks with a weighted blend
+        of up to four adapters.  The records reach the device as self.adapter_mix and the decode step's shrink launches become
+        itts_lora_shrink_mix: that is structure (the graph key says which of the two launches a captured step holds), the
+        records are data."""
         B, P, D = prefix_emb.shape
         S = P + 1
         beams = int(beams)
-        ids = self._row_adapters(adapter_ids, B)
+        ids, mix = self._voices(adapter_ids, adapter_mix, B)
         if self.kv_dtype is not None:
             if beams > 1:
                 raise NotImplementedError("beam search over the FP8 KV cache (kv_dtype='fp8') is not built")
             if paged is not None and not paged:
                 raise NotImplementedError("the FP8 KV cache (kv_dtype='fp8') is built for the paged cache only (paged=False)")
+        if mix is not None and beams > 1:
+            raise NotImplementedError("beam search with adapter mixes is not built")
         if ids is not None and beams > 1:
             raise NotImplementedError("beam search with an adapter bank is not built")
         if beams > 1 and self.beam_kv != "table":
@@ -847,12 +930,14 @@ class GPTEngine:
         self._pad_host = pad_h             # latent_mel_rows() finds the prompt's K/V in the cache through it
         self.pad[:B] = torch.tensor(pad_h, dtype=torch.int32).to(dev)
         self.kv_share.zero_()
-        self._ids_host = ids
+        self._ids_host, self._mix_host = ids, mix
         if ids is not None:
             self.adapter_ids[:B] = torch.tensor(ids, dtype=torch.int32).to(dev)
+        if mix is not None:
+            self.adapter_mix[:B] = self._mix_records(mix)
         # (with a bank the conditioning rows' hidden states depend on the row's adapter: nothing is shared)
         # (FP8 KV cache: the shared-prefix path is off in this version -- the un-shared prefill runs and kv_share stays 0)
-        if shared_rows and B > 1 and self.share_prefix and ids is None and self.kv_dtype is None:
+        if shared_rows and B > 1 and self.share_prefix and ids is None and mix is None and self.kv_dtype is None:
             # every element starts with the same `shared_rows` rows (the caller's promise: one prompt's conditioning latents)
             self._head(self._prefill_shared(emb, pad_h, S, int(shared_rows)), B)
             if beams == 1 and int(shared_rows) <= 255 and self.share_kv_reads:
@@ -867,8 +952,7 @@ class GPTEngine:
             meta = torch.tensor(off + [b_off - 1 for b_off in off[1:]], dtype=torch.int32).to(dev)   # row_off | last rows
             row_off, last_rows = meta[: B + 1], meta[B + 1:].long()
             h = emb.view(B * S, D)[idx.to(dev)]
-            h = self._blocks_full(h, B, S, None, True, row_off=row_off, cache_shift=self.pad[:B],
-                                  row_ids=None if ids is None else self._row_ids(ids, lens))
+            h = self._blocks_full(h, B, S, None, True, row_off=row_off, cache_shift=self.pad[:B], **self._row_voices(ids, mix, lens))
             self._head(h[last_rows].contiguous(), B)
         self.state.zero_()                 # step, cache position, finished rows, arrival counter, seed (lo, hi)
         self.state[1] = S - 1
@@ -896,19 +980,19 @@ class GPTEngine:
         return self.prefill(prefix_emb.repeat_interleave(beams, dim=0), pad.repeat_interleave(beams), max_new, shared_rows=shared_rows,
                             paged=False)
 
-    def latent(self, emb: torch.Tensor, lengths=None, adapter_ids=None) -> torch.Tensor:
+    def latent(self, emb: torch.Tensor, lengths=None, adapter_ids=None, adapter_mix=None) -> torch.Tensor:
         """Teacher-forced pass (model.py:459-474): emb fp32 [B,S,D] (right-padded rows allowed) ->
         final_norm(ln_f(blocks(emb))) fp32 [B,S,D].  With `lengths` (host ints, real rows per element) only the real rows
-        are computed (packed); the padding rows of the result are zero.  adapter_ids: as in prefill()."""
+        are computed (packed); the padding rows of the result are zero.  adapter_ids / adapter_mix: as in prefill()."""
         B, S, D = emb.shape
-        ids = self._row_adapters(adapter_ids, B)
+        ids, mix = self._voices(adapter_ids, adapter_mix, B)
         if self._cap_b == 0:
             self._ensure(1, 64)
         dev = self.device
         src = emb.to(dev, torch.float32).contiguous().view(B * S, D)
         if lengths is None:
             h = src.clone()
-            self._blocks_full(h, B, S, None, False, row_ids=None if ids is None else self._row_ids(ids, [S] * B))
+            self._blocks_full(h, B, S, None, False, **self._row_voices(ids, mix, [S] * B))
             out = torch.empty_like(h)
             nat.layernorm(h, self.ln_f[0], self.ln_f[1], out, self.final_norm[0], self.final_norm[1])
             return out.view(B, S, D)
@@ -919,14 +1003,14 @@ class GPTEngine:
         idx = torch.cat([torch.arange(b * S, b * S + lens[b]) for b in range(B)]).to(dev)
         row_off = torch.tensor(off, dtype=torch.int32).to(dev)
         h = src[idx]
-        self._blocks_full(h, B, max(lens), None, False, row_off=row_off, row_ids=None if ids is None else self._row_ids(ids, lens))
+        self._blocks_full(h, B, max(lens), None, False, row_off=row_off, **self._row_voices(ids, mix, lens))
         packed = torch.empty_like(h)
         nat.layernorm(h, self.ln_f[0], self.ln_f[1], packed, self.final_norm[0], self.final_norm[1])
         out = torch.zeros(B * S, D, dtype=torch.float32, device=dev)
         out[idx] = packed
         return out.view(B, S, D)
 
-    def latent_mel_rows(self, mel_emb: torch.Tensor, m_lens, cache_rows=None, adapter_ids=None) -> torch.Tensor:
+    def latent_mel_rows(self, mel_emb: torch.Tensor, m_lens, cache_rows=None, adapter_ids=None, adapter_mix=None) -> torch.Tensor:
         """The teacher-forced pass (model.py:459-474, :548-597) over the MEL rows only, for the batch whose prompt the last
         prefill() cached.  In cond | text | mel the causal mask lets no prompt position see a mel position, so the prompt's
         keys and values in every layer are exactly what prefill() computed for the decode loop -- same kernels, same inputs,
@@ -938,6 +1022,7 @@ class GPTEngine:
         mel_emb fp32 [sum(m_lens), D]: the mel segments' embeddings, elements in prefill order; cache_rows: the cache row that
         holds element b's prompt (default b; b * num_beams after a beam prefill that copied rows).
         adapter_ids: the ids prefill() was given (the default): the cached prompt K / V were computed under them, other ids are refused.
+        adapter_mix: likewise the mixes prefill() was given (the default after such a prefill); other mixes, or ids, are refused.
         Returns final_norm(ln_f(hidden)) fp32 [sum(m_lens), D]."""
         import numpy as np
         if self.kv_dtype is not None:
@@ -945,7 +1030,12 @@ class GPTEngine:
                                       "(kv_dtype='fp8') run latent() on the whole sequence")
         T, D, H, dev = self.dtype, self.D, self.H, self.device
         B, P = len(m_lens), self._S - 1
-        ids = self._ids_host if adapter_ids is None else self._row_adapters(adapter_ids, B)
+        if adapter_ids is None and adapter_mix is None:
+            ids, mix = self._ids_host, self._mix_host
+        else:
+            ids, mix = self._voices(adapter_ids, adapter_mix, B)
+        if mix is not None and mix != self._mix_host:
+            raise ValueError("latent_mel_rows(): the cached prompt was prefilled under other adapter mixes")
         if ids is not None and (self._ids_host is None or list(ids) != list(self._ids_host[:B]) or len(self._ids_host) != B):
             raise ValueError("latent_mel_rows(): the cached prompt was prefilled under other adapter ids")
         cache_rows = list(range(B)) if cache_rows is None else [int(r) for r in cache_rows]
@@ -965,7 +1055,7 @@ class GPTEngine:
         # the prompt's keys / values straight from the decode cache (itts_attn_prefill_prefix), the mel rows' from qkv
         h = self._big_m_layers(h, lambda i, qkv, att: nat.attn_prefill_prefix(
             qkv, att, self.kc[i], self.vc[i], row_off, pre_len, pre_row, pre_pos0, B, max(m), H, self._cap_s, **kva),
-            None if ids is None else self._row_ids(ids, m))
+            **self._row_voices(ids, mix, m))
         out = torch.empty_like(h)
         nat.layernorm(h, self.ln_f[0], self.ln_f[1], out, self.final_norm[0], self.final_norm[1])
         return out
@@ -1010,7 +1100,7 @@ class GPTEngine:
                 bump = getattr(self, "_pending_bump", False)
             self._pending_bump = False
         skip = lambda *a, **kw: None   # noqa: E731
-        k = SimpleNamespace(embed_step=skip, attn_decode=skip, attn_decode_kv8=skip, ln_reduce=skip, lora_shrink=skip) if gemm_only else nat   # every other launch
+        k = SimpleNamespace(embed_step=skip, attn_decode=skip, attn_decode_kv8=skip, ln_reduce=skip, lora_shrink=skip, lora_shrink_mix=skip) if gemm_only else nat   # every other launch
         tally = [0, 0]
 
         def gemm(M, N, K, w, bias, epi, scale=None, **kw):
@@ -1082,7 +1172,10 @@ class GPTEngine:
                 the GEMM runs over K + Kx with [W ; B_bank^T]."""
                 if bank is None or "bank_" + wkey not in l:
                     return l.get(wkey + "_lora", l[wkey]), K
-                k.lora_shrink(x, self.adapter_ids, l["bank_a_" + wkey], x.view(-1)[K * Bp:], B, K, x_packed=True, u_packed=True)
+                if self._mix_host is not None:   # the batch was prefilled with adapter_mix: weighted slots from the rows' records
+                    k.lora_shrink_mix(x, self.adapter_mix, l["bank_a_" + wkey], x.view(-1)[K * Bp:], B, K, x_packed=True, u_packed=True)
+                else:
+                    k.lora_shrink(x, self.adapter_ids, l["bank_a_" + wkey], x.view(-1)[K * Bp:], B, K, x_packed=True, u_packed=True)
                 return l["bank_" + wkey], K + bank.Kx
             for i, l in enumerate(self.layers):
                 last = i + 1 == self.L
@@ -1132,7 +1225,10 @@ class GPTEngine:
                None if self.kv is None else self.kv.bs, tuple(sorted(sp.items())), ("weights", self.weight_dtype),
                ("kv", self.kv_dtype))
         # an adapter bank: its shape and targets (what the captured launches were built from) -- never the rows' ids, which are data
-        return key if self.bank is None else key + (("bank",) + self.bank.sig,)
+        # ... nor their mixes; but WHICH shrink launch the step holds (ids or mix records) is structure
+        if self.bank is None:
+            return key
+        return key + (("bank-mix" if self._mix_host is not None else "bank",) + self.bank.sig,)
 
     def _graph(self, key, body):
         """The CUDA graph of one decode step `body`, captured on first use and kept under `key` (see _graph_key)."""

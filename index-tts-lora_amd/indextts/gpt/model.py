@@ -233,19 +233,25 @@ class UnifiedVoice:
     def inference_speech(self, speech_conditioning_mel, text_inputs, cond_mel_lengths=None, input_tokens=None,
                          num_return_sequences=1, max_generate_length=None, typical_sampling=False, typical_mass=.9,
                          speaker_ids=None, force_stop=None, seed=None, return_logits=False, adapter_ids=None, sampling=None,
-                         **hf):
+                         adapter_mix=None, **hf):
         """model.py:669-720.  Accepted generate() keywords: do_sample, top_p, top_k, temperature, repetition_penalty,
         num_beams, length_penalty.  Returns codes [B * num_return_sequences, n] (stop-token padded), like
         `output[:, trunc_index:]`: with beams the num_return_sequences best hypotheses of each element, best first; with
         sampling that many independent draws per element.
         adapter_ids (host ints, one per batch element; needs attach_lora_bank): the LoRA adapter -- the voice -- each element
         speaks with, -1 = the base model; expanded with num_return_sequences like the rows themselves.
+        adapter_mix (one mix per batch element, exclusive with adapter_ids): a weighted blend of up to four adapters of the bank --
+        None / -1 (base), an id (weight 1), a {id: weight} dict or a sequence of (id, weight); GPTEngine.check_adapter_mix.
         sampling (a list of dicts, one per batch element: row_sampling_params): each element under its own sampling settings and
         seed; what an entry leaves out comes from this call's keywords.  num_beams = 1 and num_return_sequences = 1 only."""
         if self.engine is None:
             raise RuntimeError("call post_init_gpt2_config() first")
         if adapter_ids is not None:     # checked here, before the conditioner launches anything
             adapter_ids = self.engine._row_adapters(adapter_ids, int(text_inputs.shape[0]))
+        if adapter_mix is not None:
+            adapter_mix = self.engine._voices(adapter_ids, adapter_mix, int(text_inputs.shape[0]))[1]
+            if int(hf.get("num_beams", 1)) > 1:
+                raise NotImplementedError("beam search with adapter mixes is not built (num_beams = 1)")
         if int(hf.get("num_beams", 1)) > 1 and (adapter_ids is not None or self.engine.bank is not None):
             raise NotImplementedError("beam search with an adapter bank is not built (num_beams = 1)")
         if sampling is not None and int(hf.get("num_beams", 1)) > 1:
@@ -292,7 +298,9 @@ class UnifiedVoice:
                 force_stop = [v for v in force_stop for _ in range(nrs)]
             if adapter_ids is not None:
                 adapter_ids = [v for v in adapter_ids for _ in range(nrs)]
-        self.engine.prefill(emb, pad, max_new, shared_rows=shared, adapter_ids=adapter_ids)
+            if adapter_mix is not None:
+                adapter_mix = [v for v in adapter_mix for _ in range(nrs)]
+        self.engine.prefill(emb, pad, max_new, shared_rows=shared, adapter_ids=adapter_ids, adapter_mix=adapter_mix)
         out = self.engine.decode(max_new, sp if sampling is None else sampling, force_stop=force_stop, return_logits=return_logits)
         return out
 
@@ -305,7 +313,7 @@ class UnifiedVoice:
         return self
 
     def attach_lora_bank(self, bank):
-        """A bank of LoRA adapter sets -- one per fine-tuned voice -- chosen per batch element with adapter_ids: a list of
+        """A bank of LoRA adapter sets -- one per fine-tuned voice -- chosen per batch element with adapter_ids, or blended per element with adapter_mix: a list of
         (adapters, scaling) in the attach_lora format (see GPTEngine.attach_lora_bank).  Exclusive with attach_lora."""
         if self.engine is None:
             raise RuntimeError("call post_init_gpt2_config() first")
@@ -329,15 +337,18 @@ class UnifiedVoice:
     # ---- teacher-forced latent pass -----------------------------------------------------------------------------
     def forward(self, speech_conditioning_latent, text_inputs, text_lengths, mel_codes, wav_lengths,
                 cond_mel_lengths=None, types=None, text_first=True, raw_mels=None, return_attentions=False,
-                return_latent=False, clip_inputs=False, speaker_ids=None, conds=None, adapter_ids=None):
+                return_latent=False, clip_inputs=False, speaker_ids=None, conds=None, adapter_ids=None,
+                adapter_mix=None):
         """model.py:548-597 with return_latent=True (the only mode infer.py uses): -> latent [B, T, D] fp32.
-        adapter_ids: as in inference_speech."""
+        adapter_ids / adapter_mix: as in inference_speech."""
         if not return_latent:
             raise NotImplementedError("training losses are out of scope; call with return_latent=True")
         eng = self.engine
         dev = self.device
         if adapter_ids is not None:
             adapter_ids = eng._row_adapters(adapter_ids, int(text_inputs.shape[0]))
+        if adapter_mix is not None:
+            adapter_mix = eng._voices(adapter_ids, adapter_mix, int(text_inputs.shape[0]))[1]
         if conds is None:
             conds = self.get_conditioning(speech_conditioning_latent, cond_mel_lengths, speaker_ids)
         text_inputs = text_inputs.to(dev).long()
@@ -360,7 +371,7 @@ class UnifiedVoice:
         if c.shape[0] == 1 and B > 1:
             c = c.expand(B, -1, -1)
         emb = torch.cat([c, te, me], dim=1)
-        enc = eng.latent(emb, adapter_ids=adapter_ids)[:, c.shape[1]:]
+        enc = eng.latent(emb, adapter_ids=adapter_ids, adapter_mix=adapter_mix)[:, c.shape[1]:]
         mel_part = enc[:, -mi.shape[1]:]
         return mel_part[:, :-2]
 

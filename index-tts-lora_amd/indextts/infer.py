@@ -506,7 +506,8 @@ class IndexTTS:
         """gpt.inference_speech with precomputed conditioning latents (same values as recomputing them per call)."""
         g = self.gpt
         if g.engine.bank is not None:   # infer / infer_fast, the REST service's calls: no way to name a voice per request yet
-            raise NotImplementedError("infer / infer_fast with an adapter bank is not built: use infer_batch(adapter_ids=...)")
+            raise NotImplementedError("infer / infer_fast with an adapter bank is not built: use infer_batch(adapter_ids=...) or "
+                                      "infer_batch(adapter_mix=...)")
         emb, pad = g.prefix_rows(conds, text_tokens)
         shared = int(conds.shape[1]) if conds.shape[0] == 1 else 0   # one prompt: every row starts with the same latents
         sp = sampling_params(gen, extra.pop("seed", torch.initial_seed() & 0x7FFFFFFFFFFFFFFF))
@@ -519,7 +520,7 @@ class IndexTTS:
         return g.engine.decode(max_mel_tokens, sp, force_stop=extra.pop("force_stop", None))
 
     def _latents(self, conds, text_rows: List[torch.Tensor], code_rows: List[torch.Tensor], reuse_prefix=False, cache_rows=None,
-                 adapter_ids=None):
+                 adapter_ids=None, adapter_mix=None):
         """Teacher-forced pass for several utterances at once (right-padded; causal attention makes padding inert).
         Each row reproduces gpt(cond, text, [L], codes, code_len*1024, return_latent=True) of infer.py:864-874.
         The [cond | text | mel] embedding batch is assembled with two gathers from index arrays built on the host (one
@@ -527,7 +528,8 @@ class IndexTTS:
         reuse_prefix: the rows are, in order, the batch the engine's LAST prefill() cached (same conds, same texts) and nothing
         has touched its KV cache since -- then only the mel rows are recomputed and the prompt's keys / values come from the
         cache (GPTEngine.latent_mel_rows: same bits, ~40 % fewer GEMM rows).
-        adapter_ids: the rows' adapters of an attached bank (with reuse_prefix: the ids the cached prompt was prefilled under)."""
+        adapter_ids: the rows' adapters of an attached bank (with reuse_prefix: the ids the cached prompt was prefilled under).
+        adapter_mix: or the rows' mixes of adapters, under the same rule."""
         g, eng, dev = self.gpt, self.gpt.engine, self.device
         if conds.shape[0] not in (1, len(text_rows)):    # a subset of the rows with all rows' conds would speak in the wrong voices
             raise ValueError(f"_latents: conds holds {conds.shape[0]} prompts for {len(text_rows)} rows (one for all, or one per row)")
@@ -544,7 +546,7 @@ class IndexTTS:
             ids[(pos > 0) & (pos <= np.repeat(cln, m))] = flat
             idx = torch.from_numpy(np.stack([ids, pos])).to(dev)
             enc = eng.latent_mel_rows(eng.mel_emb[idx[0]] + eng.mel_pos[idx[1]], [c + 2 for c in cl], cache_rows,
-                                      adapter_ids=adapter_ids)
+                                      adapter_ids=adapter_ids, adapter_mix=adapter_mix)
             return [enc[int(offs[i]): int(offs[i]) + cl[i]] for i in range(len(cl))]
 
         def flat_host(rows):
@@ -576,7 +578,7 @@ class IndexTTS:
         batch[:, :nc] = (conds if conds.shape[0] == len(tl) else conds[0]).to(dev, torch.float32)   # the row's own prompt, or the one
         batch[idx[0, :n_t], idx[1, :n_t]] = eng.text_emb[idx[2, :n_t]] + eng.text_pos[idx[3, :n_t]]
         batch[idx[0, n_t:], idx[1, n_t:]] = eng.mel_emb[idx[2, n_t:]] + eng.mel_pos[idx[3, n_t:]]
-        enc = eng.latent(batch, lengths=[s0 + n + 2 for s0, n in spans], adapter_ids=adapter_ids)   # real rows only (cond | text | mel incl. start/stop)
+        enc = eng.latent(batch, lengths=[s0 + n + 2 for s0, n in spans], adapter_ids=adapter_ids, adapter_mix=adapter_mix)   # real rows only (cond | text | mel incl. start/stop)
         return [enc[i, s0: s0 + n] for i, (s0, n) in enumerate(spans)]
 
     def _finish(self, wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, sampling_rate=24000):
@@ -746,7 +748,7 @@ class IndexTTS:
 
     def infer_batch(self, cond_mel: torch.Tensor, text_token_rows: List[torch.Tensor], max_mel_tokens=600, force_stop=None,
                     seed=1234, return_codes=False, phase_events: dict | None = None, adapter_ids=None, sampling=None,
-                    **generation_kwargs):
+                    adapter_mix=None, **generation_kwargs):
         """Utterance-batch data path used by bench.py / the multi-GPU sharder (not in the reference API): one shared
         prompt, N independent texts decoded as ONE left-padded batch, one batched latent pass, and one vocoder call per
         group of equal-length utterances (batching unequal lengths would change the tail of the shorter waveforms).
@@ -754,16 +756,20 @@ class IndexTTS:
         phase_events, if given, receives torch.cuda.Event marks at the phase boundaries.
         adapter_ids (host ints, one per utterance; needs gpt.attach_lora_bank): the voice -- LoRA adapter of the bank, -1 = base
         model -- each utterance is spoken with, in the token loop and in the latent pass.
+        adapter_mix (one mix per utterance, exclusive with adapter_ids): a weighted blend of up to four voices of the bank per
+        utterance -- None / -1 (base), an id (that voice at weight 1), {id: weight} ("this voice at 0.6": {3: 0.6}; "70 % A, 30 % B":
+        {0: 0.7, 1: 0.3}) or a sequence of (id, weight); weights are any finite numbers (GPTEngine.check_adapter_mix).  The mixes
+        are data of the captured decode step: no re-attach, no new graph per assignment.
         sampling (a list of dicts, one per utterance, in the order of text_token_rows): each utterance under its own request's
         settings -- any of do_sample, temperature, top_k, top_p, repetition_penalty, seed; what an entry leaves out comes from
         generation_kwargs and seed (gpt.model.row_sampling_params).  num_beams = 1 only.
         cond_mel may be a LIST of [1, 100, T_i] prompt mels, one per utterance (any lengths): every utterance is cloned from its
         own reference audio, as if synthesised alone with that prompt.  Entries that are the same tensor object are one prompt
         and are conditioned once (_prompt_features_rows); nothing is shared between the rows' prefixes in the prefill.  Works
-        together with adapter_ids and sampling; num_beams = 1 only; a list whose length is not the number of utterances is a
+        together with adapter_ids / adapter_mix and sampling; num_beams = 1 only; a list whose length is not the number of utterances is a
         ValueError.  One tensor is one prompt for all utterances, as before."""
         st = self._batch_tokens(cond_mel, text_token_rows, max_mel_tokens, force_stop, seed, phase_events, lazy_spk=True,
-                                adapter_ids=adapter_ids, sampling=sampling, **generation_kwargs)
+                                adapter_ids=adapter_ids, sampling=sampling, adapter_mix=adapter_mix, **generation_kwargs)
         outs = self._batch_waveforms(st, phase_events, reuse_prefix=True)   # serial: the KV cache still holds this batch's prompt
         return (outs, st["rows"]) if return_codes else outs
 
@@ -879,7 +885,7 @@ class IndexTTS:
             phase_events[name] = e
 
     def _batch_tokens(self, cond_mel, text_token_rows, max_mel_tokens=600, force_stop=None, seed=1234, phase_events=None,
-                      lazy_spk=False, adapter_ids=None, sampling=None, **generation_kwargs):
+                      lazy_spk=False, adapter_ids=None, sampling=None, adapter_mix=None, **generation_kwargs):
         """Stage A of infer_batch: prompt conditioning -> prefill -> sampling loop -> silence squeeze (host).  Everything
         here is latency-bound small launches; it ends with the codes on the host, as infer.py:848-861 does."""
         gen, _ = self._gen_kwargs(generation_kwargs)
@@ -887,6 +893,10 @@ class IndexTTS:
             adapter_ids = self.gpt.engine._row_adapters(adapter_ids, len(text_token_rows))
             if int(gen.get("num_beams", 1)) > 1:
                 raise NotImplementedError("beam search with an adapter bank is not built (num_beams = 1)")
+        if adapter_mix is not None:     # likewise
+            adapter_mix = self.gpt.engine._voices(adapter_ids, adapter_mix, len(text_token_rows))[1]
+            if int(gen.get("num_beams", 1)) > 1:
+                raise NotImplementedError("beam search with adapter mixes is not built (num_beams = 1)")
         if sampling is not None:        # checked before anything is launched
             if int(gen.get("num_beams", 1)) > 1:
                 raise NotImplementedError("beam search with per-row sampling settings is not built (num_beams = 1)")
@@ -917,7 +927,7 @@ class IndexTTS:
             self._mark(phase_events, "prefilled")
             codes = g.engine.decode_beam(max_mel_tokens, sp, nb)
         else:
-            g.engine.prefill(emb, pad, max_mel_tokens, shared_rows=shared, adapter_ids=adapter_ids)
+            g.engine.prefill(emb, pad, max_mel_tokens, shared_rows=shared, adapter_ids=adapter_ids, adapter_mix=adapter_mix)
             self._mark(phase_events, "prefilled")
             codes = g.engine.decode(max_mel_tokens, sp if sampling is None else sampling, force_stop=force_stop)
         self._mark(phase_events, "decoded")
@@ -928,7 +938,7 @@ class IndexTTS:
         # expanded the rows (beam_kv = "copy")
         crows = [b * nb for b in range(len(rows))] if nb > 1 and g.engine.beam_kv != "table" else None
         return dict(conds=conds, spk=spk, rows=rows, texts=[t.reshape(-1) for t in text_token_rows], cache_rows=crows,
-                    cond_mel=cond_mel, adapter_ids=adapter_ids)
+                    cond_mel=cond_mel, adapter_ids=adapter_ids, adapter_mix=adapter_mix)
 
     def _batch_waveforms(self, st, phase_events=None, reuse_prefix=False):
         """Stage B of infer_batch: batched teacher-forced latent pass + vocoder (large MFMA-bound launches, no host sync).
@@ -943,7 +953,7 @@ class IndexTTS:
             if bf is not None and bf[0] is st["cond_mel"] and bf[2] is conds:
                 bf[3] = spk
         lat = self._latents(conds, st["texts"], st["rows"], reuse_prefix=reuse_prefix, cache_rows=st.get("cache_rows"),
-                            adapter_ids=st.get("adapter_ids"))
+                            adapter_ids=st.get("adapter_ids"), adapter_mix=st.get("adapter_mix"))
         self._mark(phase_events, "latents")
         outs = self._vocode_ragged(lat, spk)
         self._mark(phase_events, "vocoded")
