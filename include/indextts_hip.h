@@ -253,6 +253,8 @@ typedef struct itts_lora_shrink_args {
 int itts_lora_shrink(const itts_lora_shrink_args* a, void* stream);
 /* The same launch over weighted mixes of up to four bank voices per row (record, argument struct and prototype): */
 #include "indextts_hip_mix.h"
+/* Continuous batching: the launch that takes staged rows, with their voice records, into a running decode loop: */
+#include "indextts_hip_refill.h"
 
 /* LayerNorm over the last dim of fp32 rows; y is T (y_f32 = 0) or fp32 (y_f32 = 1).  If w2 != NULL a second LayerNorm
  * (w2,b2) is applied to the result of the first (ln_f followed by final_norm). */

@@ -98,6 +98,17 @@ class LoraShrinkMixArgs(C.Structure):
                 ("u_packed", C.c_int), ("u_mtp", C.c_int), ("ldu", C.c_int64)]
 
 
+class RefillJoinArgs(C.Structure):
+    """itts_refill_join_args (include/indextts_hip_refill.h)."""
+    _fields_ = [("dtype", C.c_int), ("M", C.c_int), ("L", C.c_int), ("H", C.c_int), ("kst", C.c_void_p), ("vst", C.c_void_p),
+                ("kc", C.c_void_p), ("vc", C.c_void_p), ("s_l", C.c_int64), ("s_b", C.c_int64), ("s_h", C.c_int64), ("s_p", C.c_int64),
+                ("n_b", C.c_int), ("n_p", C.c_int), ("i_b", C.c_void_p), ("i_p", C.c_void_p), ("k", C.c_int), ("n_slots", C.c_int),
+                ("rows", C.c_void_p), ("tok", C.c_void_p), ("fin", C.c_void_p), ("stops", C.c_void_p), ("pads", C.c_void_p),
+                ("mix_new", C.c_void_p), ("step0", C.c_int), ("hist_cap", C.c_int), ("tokens", C.c_void_p), ("history", C.c_void_p),
+                ("finished", C.c_void_p), ("force_stop", C.c_void_p), ("row_step0", C.c_void_p), ("pad", C.c_void_p),
+                ("mix", C.c_void_p), ("state", C.c_void_p)]
+
+
 class ConvArgs(C.Structure):
     _fields_ = [("dtype", C.c_int), ("B", C.c_int), ("Tin", C.c_int), ("Tout", C.c_int), ("Cin", C.c_int),
                 ("N", C.c_int), ("taps", C.c_int), ("off0", C.c_int), ("dil", C.c_int), ("x", C.c_void_p),
@@ -233,12 +244,18 @@ _MIX_SIGNATURES = {
     "itts_lora_shrink_mix": (C.c_int, [C.POINTER(LoraShrinkMixArgs), C.c_void_p]),
 }
 
+# include/indextts_hip_refill.h: the join of continuous batching (staged rows and their voices enter a running loop)
+_REFILL_SIGNATURES = {
+    "itts_refill_join": (C.c_int, [C.POINTER(RefillJoinArgs), C.c_void_p]),
+}
+
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)          # what include/indextts_hip.h declares itself
 ROW_SYMBOLS = tuple(_ROW_SIGNATURES)           # what include/indextts_hip_rows.h declares
 W8_SYMBOLS = tuple(_W8_SIGNATURES)             # what include/indextts_hip_w8.h declares
 KV8_SYMBOLS = tuple(_KV8_SIGNATURES)           # what include/indextts_hip_kv8.h declares
 PROMPT_SYMBOLS = tuple(_PROMPT_SIGNATURES)     # what include/indextts_hip_prompts.h declares
 MIX_SYMBOLS = tuple(_MIX_SIGNATURES)           # what include/indextts_hip_mix.h declares
+REFILL_SYMBOLS = tuple(_REFILL_SIGNATURES)     # what include/indextts_hip_refill.h declares
 _lib = None
 
 
@@ -252,7 +269,7 @@ def lib():
                               f"(or python -c 'import __graft_entry__ as g; g.build()'). There is no fallback path.")
         L = C.CDLL(path)
         for name, (res, args) in {**_SIGNATURES, **_ROW_SIGNATURES, **_W8_SIGNATURES, **_KV8_SIGNATURES, **_PROMPT_SIGNATURES,
-                                       **_MIX_SIGNATURES}.items():
+                                       **_MIX_SIGNATURES, **_REFILL_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -679,6 +696,45 @@ def pack_lora_mix(mixes):
         for j in range(LORA_MIX_ENTRIES):
             rec.e[j].id, rec.e[j].weight = (int(mix[j][0]), float(mix[j][1])) if j < len(mix) else (-1, 0.0)
     return np.frombuffer(bytes(recs), dtype=np.uint8).reshape(-1, LORA_MIX_ROW_BYTES)[: len(mixes)].copy()
+
+
+def refill_join(kst, vst, kc, vc, i_b, i_p, rows, tok, fin, stops, pads, step0, tokens, history, finished, force_stop, row_step0,
+                pad, state, mix_new=None, mix=None):
+    """The join of continuous batching in one launch (itts_refill_join).  kst / vst T [M, L, H, 64]: the staged keys / values of M
+    positions; they go to (i_b[m], i_p[m]) of the caches kc / vc, T [L, n_b, H, n_p, 64] -- the paged pool (block, offset) or the
+    contiguous rows (cache row, position); i_b / i_p int32 [M].  rows int32 [k]: the slots the k new rows take; tok / fin / stops /
+    pads int32 [k] and mix_new uint8 [k, 32] are written to tokens / history[:, 0] / finished / force_stop / pad / mix of those slots,
+    row_step0 of those slots <- step0, and state[2] -= k.  An i_b, i_p or slot outside its table is skipped."""
+    _dev(kst, vst, kc, vc, i_b, i_p, rows, tok, fin, stops, pads, tokens, history, finished, force_stop, row_step0, pad, state, mix_new, mix)
+    M, L, H = int(kst.shape[0]), int(kc.shape[0]), int(kc.shape[2])
+    k = int(rows.numel())
+    if kc.dim() != 5 or kc.shape[4] != 64 or kc.shape != vc.shape or kc.dtype != vc.dtype or kc.dtype not in _DT:
+        raise NativeError("itts_refill_join: the caches must be T [L, n_b, H, n_p, 64], K and V alike")
+    if kst.shape != (M, L, H, 64) or vst.shape != kst.shape or kst.dtype != kc.dtype or vst.dtype != kc.dtype:
+        raise NativeError("itts_refill_join: kst / vst must be [M, L, H, 64] of the cache's type")
+    ints = (i_b, i_p, rows, tok, fin, stops, pads, tokens, history, finished, force_stop, row_step0, pad, state)
+    if any(t.dtype != torch.int32 for t in ints) or i_b.numel() != M or i_p.numel() != M:
+        raise NativeError("itts_refill_join: indices and row state must be int32 (i_b, i_p: [M])")
+    if any(t.numel() != k for t in (tok, fin, stops, pads)) or state.numel() < 3 or history.dim() != 2:
+        raise NativeError("itts_refill_join: tok, fin, stops and pads hold one entry per entering row; history is [slots, cap]")
+    n_slots = min(int(t.shape[0]) for t in (tokens, history, finished, force_stop, row_step0, pad))
+    if (mix is None) != (mix_new is None):
+        raise NativeError("itts_refill_join: mix and mix_new go together")
+    if mix is not None:
+        if mix.dtype != torch.uint8 or mix_new.dtype != torch.uint8 or mix_new.numel() != k * LORA_MIX_ROW_BYTES or \
+                mix.numel() % LORA_MIX_ROW_BYTES:
+            raise NativeError("itts_refill_join: mix / mix_new must be uint8 tables of 32-byte records (mix_new: k of them)")
+        n_slots = min(n_slots, mix.numel() // LORA_MIX_ROW_BYTES)
+    a = RefillJoinArgs()
+    a.dtype, a.M, a.L, a.H = dt(kc.dtype), M, L, H
+    a.kst, a.vst, a.kc, a.vc = _p(kst), _p(vst), _p(kc), _p(vc)
+    a.s_l, a.s_b, a.s_h, a.s_p = (int(v) for v in kc.stride()[:4])
+    a.n_b, a.n_p, a.i_b, a.i_p = int(kc.shape[1]), int(kc.shape[3]), _p(i_b), _p(i_p)
+    a.k, a.n_slots, a.rows, a.tok, a.fin, a.stops, a.pads, a.mix_new = k, n_slots, _p(rows), _p(tok), _p(fin), _p(stops), _p(pads), _p(mix_new)
+    a.step0, a.hist_cap = int(step0), int(history.shape[1])
+    a.tokens, a.history, a.finished, a.force_stop, a.row_step0, a.pad = (_p(t) for t in (tokens, history, finished, force_stop, row_step0, pad))
+    a.mix, a.state = _p(mix), _p(state)
+    _check(lib().itts_refill_join(C.byref(a), _stream()), "itts_refill_join")
 
 
 def lora_shrink_mix(x, mix, a_bank, u, M, K, x_packed=False, x_mtp=0, u_packed=False, u_mtp=0, ldu=0):

@@ -1306,14 +1306,16 @@ class GPTEngine:
         return (codes, torch.stack(logits_trace, 0)) if return_logits else codes
 
     # ------------------------------------------------------------------------------------------------ slot refill
-    def _stage(self, rows, prefixes, stops, n):
+    def _stage(self, rows, prefixes, stops, n, mixes=None):
         """Prepare new utterances for the decode slots `rows`, to JOIN a running loop at the moment every row has been given
         n tokens' worth of steps (state[0] = n - 1 with the bump pending, the next step writes cache position S+n-1).
         prefixes: fp32 [P_j, D] each (cond | text, no padding).  A new row is laid out exactly like an initial row of a batch
         whose loop started n - 1 steps later: prompt + start token at cache positions [pad, S+n-2] of its slot, left padding
         pad = S+n-1-(P_j+1).  One packed prefill pass over all new rows; their keys / values are kept aside ([M, L, H, 64]) and
         the logits of their last positions computed on buffers of their own -- nothing the running loop reads or writes is
-        touched, so this may run on another stream beside the loop's steps."""
+        touched, so this may run on another stream beside the loop's steps.
+        mixes (a loop with voices: one normalised mix per new row): the pass runs under the rows' records, which travel with the
+        staged rows to the join, and so do int32 copies of the indices (what itts_refill_join reads)."""
         import numpy as np
         T, D, H, dev = self.dtype, self.D, self.H, self.device
         k = len(rows)
@@ -1337,6 +1339,9 @@ class GPTEngine:
               "pads": meta[2 * M + 3 * k + 1:2 * M + 4 * k + 1].to(torch.int32), "stops": meta[2 * M + 4 * k + 1:].to(torch.int32)}
         row_off = meta[2 * M:2 * M + k + 1].to(torch.int32)
         last = meta[2 * M + k + 1:2 * M + 2 * k + 1]
+        if mixes is not None:
+            m32 = meta.to(torch.int32)
+            st.update(mix=self._mix_records(mixes), i_b32=m32[:M], i_p32=m32[M:2 * M], rows32=m32[2 * M + 2 * k + 1:2 * M + 3 * k + 1])
         Tkv = T if self.kv_dtype is None else torch.uint8
         kst = torch.empty(M, self.L, H, 64, dtype=Tkv, device=dev)
         vst = torch.empty(M, self.L, H, 64, dtype=Tkv, device=dev)
@@ -1352,7 +1357,7 @@ class GPTEngine:
             kst[:, i] = q4[:, 1]
             vst[:, i] = q4[:, 2]
             nat.attn_prefill_packed(qkv, att, None, None, row_off, None, k, Smax, H, self._cap_s)
-        h = self._big_m_layers(h, attn)
+        h = self._big_m_layers(h, attn, row_mix=None if mixes is None else self._row_mix(mixes, lens))
         xn_t = torch.zeros(nat.packed_rows(k), D, dtype=T, device=dev)
         lg_t = torch.empty(k, self.V, dtype=torch.float32, device=dev)
         nat.ln_reduce(h[last].contiguous(), self.ln_f[0], self.ln_f[1], xn_t, w2=self.final_norm[0], b2=self.final_norm[1],
@@ -1361,27 +1366,33 @@ class GPTEngine:
         st.update(kst=kst, vst=vst, logits=lg_t)
         return st
 
-    def _join(self, st, sp, ev=None, row_sp=None):
+    def _join(self, st, sp, ev=None, row_sp=None, kernel=False):
         """The staged rows enter the loop (between two of its steps, at the n they were staged for): keys / values into the
         slots' cache rows, the first token of every new row sampled from its prefill logits -- on buffers of its own, the
         running rows' logits stay --, and the per-row state: left padding, stop step, own clock row_step0 = n - 1 (mel
         positions, history index and the repetition-penalty window count from the row's own first token).  ev: _stage ran
         on another stream and recorded it; the loop's stream waits for it and takes its buffers over.  row_sp (sp is PER_ROW): the
-        new rows' own settings -- their first tokens are drawn under them and their slots' records written here, with row_step0."""
+        new rows' own settings -- their first tokens are drawn under them and their slots' records written here, with row_step0.
+        A loop with voices (st["mix"]: the new rows' records) also writes each entering slot's record into self.adapter_mix.
+        kernel: everything behind the sample launch -- the two cache scatters, the row state, the voice records, state[2] -= k --
+        is ONE launch (itts_refill_join); the torch form is kept as its oracle (decode_refill(join="torch"))."""
         k, n, dev = st["k"], st["n"], self.device
+        kernel = kernel and "mix" in st
         if ev is not None:
             main = torch.cuda.current_stream(dev)
             main.wait_event(ev)
             for t in st.values():                       # allocated on the side stream, last used on this one
                 if torch.is_tensor(t):
                     t.record_stream(main)
-        self.kc[:, st["i_b"], :, st["i_p"]] = st["kst"]    # [M, L, H, 64] -> positions [pad, S+n-2] of the slots (rows | blocks)
-        self.vc[:, st["i_b"], :, st["i_p"]] = st["vst"]
+        if not kernel:
+            self.kc[:, st["i_b"], :, st["i_p"]] = st["kst"]    # [M, L, H, 64] -> positions [pad, S+n-2] of the slots (rows | blocks)
+            self.vc[:, st["i_b"], :, st["i_p"]] = st["vst"]
         tok_t = torch.zeros(k, dtype=torch.int32, device=dev)
         hist_t = torch.zeros(k, 8, dtype=torch.int32, device=dev)
         fin_t = torch.zeros(k, dtype=torch.int32, device=dev)
         step0_t = torch.full((k,), n - 1, dtype=torch.int32, device=dev)
-        self.state[2:3] -= k                               # these slots were counted as finished
+        if not kernel:
+            self.state[2:3] -= k                           # these slots were counted as finished
         if sp is PER_ROW:
             self.row_sampling.set(st["rows_h"], row_sp)
             self.row_sampling.flush()
@@ -1392,6 +1403,11 @@ class GPTEngine:
             nat.sample(st["logits"], tok_t, hist_t, fin_t, self.state, self.extra_ids, st["stops"], sp["repetition_penalty"],
                        sp["temperature"], sp["top_k"], sp["top_p"], sp["do_sample"], sp["seed"], self.stop_mel, None,
                        no_advance=True, row_step0=step0_t)
+        if kernel:
+            nat.refill_join(st["kst"], st["vst"], self.kc, self.vc, st["i_b32"], st["i_p32"], st["rows32"], tok_t, fin_t, st["stops"],
+                            st["pads"], n - 1, self.tokens, self.history, self.finished, self.force_stop, self.row_step0, self.pad,
+                            self.state, mix_new=st["mix"], mix=self.adapter_mix)
+            return
         i_rows = st["i_rows"]
         self.tokens[i_rows] = tok_t
         self.history[i_rows, 0] = tok_t
@@ -1399,17 +1415,21 @@ class GPTEngine:
         self.force_stop[i_rows] = st["stops"]
         self.row_step0[i_rows] = step0_t
         self.pad[i_rows] = st["pads"]
+        if "mix" in st:
+            self.adapter_mix[i_rows] = st["mix"]
 
-    def _stage_beside(self, side, fed, rows, prefixes, stops, n):
+    def _stage_beside(self, side, fed, rows, prefixes, stops, n, mixes=None):
         """_stage on the stream `side` behind the event `fed`: (staged rows, the event that marks them ready)."""
         with torch.cuda.stream(side):
             side.wait_event(fed)
             for p in prefixes:
                 p.record_stream(side)                   # allocated on the loop's stream, read on this one
-            st = self._stage(rows, prefixes, stops, n)
+            st = self._stage(rows, prefixes, stops, n, mixes)
             ev = torch.cuda.Event()
             ev.record(side)
         return st, ev
+
+    refill_join = "kernel"      # decode_refill(join=None) of a loop with voices: the one-launch join (profiles/refill_voices.txt)
 
     @staticmethod
     def _fed_settings(item, sp_default):
@@ -1418,6 +1438,12 @@ class GPTEngine:
         if own is None and sp_default is None:
             raise ValueError("decode_refill(): a fed item brings no sampling settings and no sp_default was given")
         return sp_default if own is None else nat.check_sample_row(own, "a fed item's settings")
+
+    @staticmethod
+    def _fed_voice(item):
+        """The voice a fed item names -- its fourth element, (prefix, stop step, settings or None, voice): anything
+        check_adapter_mix takes for one row.  The 2- and 3-tuples name none: the base voice."""
+        return item[3] if len(item) > 3 else None
 
     def _collect_stopped(self, owner, start, n):
         """The refill loop's poll after n steps: {utterance id: codes ending with the stop token} of the rows that have stopped;
@@ -1439,7 +1465,7 @@ class GPTEngine:
         return out
 
     def decode_refill(self, max_new: int, sp, feed, force_stop=None, use_graph=True, check_every=16, positions=None,
-                      staged=True, sp_default=None):
+                      staged=True, sp_default=None, voices=None, join=None):
         """Continuous batching: the sampling loop after prefill(), with every slot whose row has emitted its stop token
         refilled from a queue (the mitigation for mixed output lengths).  num_beams = 1 only.
         feed(k) -> up to k items (prefix_emb fp32 [P, D] = cond | text without padding, stop step or -1); fewer than k means
@@ -1459,7 +1485,17 @@ class GPTEngine:
         sp as a list of B dicts (check_row_settings): every row under its own settings.  A fed item may then carry its own dict as
         a third element, (prefix, stop step, settings); one that brings none gets sp_default.  The settings are written into the
         slot's record at the poll where the row enters; the row draws from (its seed, its stream, its own step), wherever and
-        whenever it entered."""
+        whenever it entered.
+        voices (needs attach_lora_bank, and is needed with one): the prefilled rows' voices, one entry per row, each anything
+        check_adapter_mix takes -- None / -1 (base), an id, {id: weight}, [(id, weight), ...]; they must be the voices the rows were
+        prefilled under (prefill(adapter_mix=...) or adapter_ids=...).  A fed item names its voice as a fourth element,
+        (prefix, stop step, settings or None, voice); an item without one speaks with the base voice.  Every voice is checked on
+        the host, a fed item's at the poll where it is fed, before anything is launched for it.  The loop always runs the
+        itts_lora_shrink_mix step (an id is the record {id, 1.0f}, bit-equal to the id launch): one captured graph serves the whole
+        queue, whatever voices pass through a slot.  A row's record is written into self.adapter_mix[slot] when it joins; a freed
+        slot gets the empty record at the poll that frees it.  join: "kernel" = the join is one launch behind the first-token
+        sample (itts_refill_join), "torch" = the indexed writes it replaces, kept as its oracle; None = the engine's
+        refill_join.  Loops without voices always run the torch form."""
         per_row = isinstance(sp, (list, tuple))
         if per_row:
             sp = self.check_row_settings(sp, self._B)
@@ -1467,11 +1503,24 @@ class GPTEngine:
                 sp_default = nat.check_sample_row(sp_default, "sp_default")
         elif sp_default is not None:
             raise ValueError("decode_refill(): sp_default belongs to per-row settings (sp given as a list)")
-        if self.bank is not None:
-            raise NotImplementedError("decode_refill(): slot refill with an adapter bank is not built")
+        join = self.refill_join if join is None else join
+        if join not in ("kernel", "torch"):
+            raise ValueError(f"decode_refill(): join must be 'kernel' or 'torch' (got {join!r})")
+        if self.bank is None and voices is not None:
+            raise ValueError("decode_refill(): voices were given but no adapter bank is attached (attach_lora_bank)")
+        if self.bank is not None and voices is None:
+            raise NotImplementedError("decode_refill(): with an adapter bank attached the loop has to be told its rows' voices: "
+                                      "voices=[...], one entry per prefilled row (None / -1 = the base voice, an id, or a mix), and "
+                                      "a fed item's voice as its fourth element (prefix, stop step, settings or None, voice)")
         B, S, ce = self._B, self._S, int(check_every)
         if self._shared_prefix is not None or self._kv_rows is not None:
             raise ValueError("decode_refill(): num_beams = 1 only")
+        voiced = voices is not None
+        if voiced:
+            mix = self.check_adapter_mix(voices, B)
+            had = self._mix_host if self._mix_host is not None else [() if i < 0 else ((i, 1.0),) for i in self._ids_host or [-1] * B]
+            if mix != list(had):
+                raise ValueError("decode_refill(): voices differ from the voices the rows were prefilled under")
         kv = self.kv
         if kv is not None:
             # paged cache: the loop's position counter may grow for as long as the queue lasts -- a row only has to keep its own
@@ -1491,6 +1540,10 @@ class GPTEngine:
         fs = [max_new - 1 if v < 0 else min(v, max_new - 1) for v in fs]
         self.force_stop[:B] = torch.tensor(fs, dtype=torch.int32).to(dev)
         sp = self._rows_to_table(sp) if per_row else self._seed_to_state(sp)
+        if voiced:      # from here on the step is the mix launch (graph key "bank-mix"), whichever launch the prefill ran
+            self._ids_host, self._mix_host = None, mix
+            self.adapter_mix[:B] = self._mix_records(mix)
+            idle = self._mix_records([()])
         self.kv_share.zero_()                                # a refilled row 0 no longer holds the shared block where the others expect it
         owner, start = list(range(B)), [0] * B              # owner: utterance id | None (free) | -1 (reserved for staged rows)
         ids, codes, leftover, fed_out, pending, row_sp = itertools.count(B), {}, [], False, None, None
@@ -1508,7 +1561,7 @@ class GPTEngine:
             # ---- A: rows staged during the last steps join here
             if pending is not None:
                 st, ev, rows, row_sp = pending
-                self._join(st, sp, ev, row_sp)
+                self._join(st, sp, ev, row_sp, kernel=join == "kernel")
                 for r in rows:
                     owner[r], start[r] = next(ids), n - 1
                 pending = None
@@ -1519,12 +1572,18 @@ class GPTEngine:
                 items = list(feed(len(free)))
                 if len(items) > len(free):
                     raise ValueError(f"decode_refill(): feed({len(free)}) returned {len(items)} items")
-                if per_row:      # (prefix, stop step[, settings]) -> the old pairs + the rows' checked settings
-                    fed_items, fed_sp = items, [self._fed_settings(it, sp_default) for it in items]
-                    items = [tuple(it)[:2] for it in items]
-                elif any(len(it) > 2 for it in items):
+                fed_items = items    # (prefix, stop step[, settings[, voice]]) -> the old pairs + the rows' checked settings and voices
+                if per_row:
+                    fed_sp = [self._fed_settings(it, sp_default) for it in items]
+                elif any(len(it) > 2 and it[2] is not None for it in items):
                     raise ValueError("decode_refill(): a fed item carries sampling settings but the loop runs under one dict "
                                      "(pass sp as a list)")
+                if voiced:
+                    fed_mix = self.check_adapter_mix([self._fed_voice(it) for it in items], len(items))
+                elif any(self._fed_voice(it) is not None for it in items):
+                    raise ValueError("decode_refill(): a fed item names a voice but the loop runs without voices "
+                                     "(attach_lora_bank, voices=[...])")
+                items = [tuple(it)[:2] for it in items]
                 fed_out = len(items) < len(free)
                 n_join = n + ce if staged else n
                 if limit - (S + n_join + 1) < max_new + ce:     # steps the loop could still take
@@ -1532,17 +1591,18 @@ class GPTEngine:
                 elif kv is not None:
                     k = admit(kv, free, items, S + n_join - 1, max_new, ce)
                     items, leftover = items[:k], items[k:]
-                if per_row and leftover:
-                    leftover = fed_items[len(fed_items) - len(leftover):]   # as they were fed, settings included
+                if leftover:
+                    leftover = fed_items[len(fed_items) - len(leftover):]   # as they were fed, settings and voice included
                 fed_out = fed_out or bool(leftover)
             if items:
                 rows, prefixes = free[: len(items)], [p for p, _ in items]
                 row_sp = fed_sp[: len(items)] if per_row else None
+                row_mix = fed_mix[: len(items)] if voiced else None
                 stops = [max_new - 1 if int(v) < 0 else min(int(v), max_new - 1) for _, v in items]
                 stats["refill_calls"] += 1
                 stats["rows_refilled"] += len(rows)
                 if not staged:
-                    self._join(self._stage(rows, prefixes, stops, n), sp, row_sp=row_sp)
+                    self._join(self._stage(rows, prefixes, stops, n, row_mix), sp, row_sp=row_sp, kernel=join == "kernel")
                     for r in rows:
                         owner[r], start[r] = next(ids), n - 1
                     items = []
@@ -1560,13 +1620,17 @@ class GPTEngine:
             n = self._token_loop(n, n + ce, step, key, use_graph)
             # ---- D: the new rows' prompts, enqueued behind the steps on the host and run beside them on the GPU
             if items:
-                st, ev = self._stage_beside(side, fed, rows, prefixes, stops, n_join)
+                st, ev = self._stage_beside(side, fed, rows, prefixes, stops, n_join, row_mix)
                 pending = (st, ev, rows, row_sp)
                 for r in rows:
                     owner[r] = -1
             # ---- E: one host synchronisation: which rows have stopped
             stats["steps"], stats["polls"] = n, stats["polls"] + 1
+            live = [r for r in range(B) if owner[r] is not None and owner[r] >= 0]
             codes.update(self._collect_stopped(owner, start, n))
+            freed = [r for r in live if owner[r] is None]
+            if voiced and freed:                            # an idle slot is the base voice (nothing reads what it computes)
+                self.adapter_mix[torch.tensor(freed, device=dev)] = idle
         return [codes[i] for i in range(len(codes))], leftover
 
     # ------------------------------------------------------------------------------------------------ beam search

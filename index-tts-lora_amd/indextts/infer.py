@@ -775,7 +775,7 @@ class IndexTTS:
 
     def infer_queue(self, cond_mel: torch.Tensor, text_token_rows: List[torch.Tensor], slots=32, max_mel_tokens=600,
                     force_stop=None, seed=1234, return_codes=False, cache_positions=4096, check_every=16, staged=True,
-                    phase_events: dict | None = None, sampling=None, **generation_kwargs):
+                    phase_events: dict | None = None, sampling=None, adapter_ids=None, adapter_mix=None, **generation_kwargs):
         """Continuous batching (not in the reference API; SURVEY.md section 8e's mitigation for mixed output lengths): any
         number of utterances of one prompt through `slots` decode slots.  The longest texts start; whenever a row emits its
         stop token its codes are taken and its slot is refilled with the next utterance (GPTEngine.decode_refill: the new
@@ -787,14 +787,22 @@ class IndexTTS:
         a refill's prefill runs on a second stream under the loop's next steps (GPTEngine.decode_refill).  Returns the waveforms
         in the order of text_token_rows, as infer_batch.  sampling: as in infer_batch -- an utterance keeps its own settings, seed
         and draw stream in whichever slot, and at whichever step, it enters.  cond_mel: one prompt, or a list with one prompt per
-        utterance as in infer_batch -- an utterance takes its own prompt's latents into whichever slot it enters."""
+        utterance as in infer_batch -- an utterance takes its own prompt's latents into whichever slot it enters.
+        adapter_ids / adapter_mix (one entry per utterance, exclusive, the rules of infer_batch; needs gpt.attach_lora_bank, and with a
+        bank attached one of them is needed: adapter_ids=[-1] * N is the base voice): an utterance takes its voice into whichever
+        slot, and at whichever step, it enters (GPTEngine.decode_refill(voices=...)), and into its latent pass."""
         gen, _ = self._gen_kwargs(generation_kwargs)
         if int(gen.get("num_beams", 1)) != 1:
             raise NotImplementedError("infer_queue: num_beams = 1 only (beam rows cannot be refilled one at a time)")
         if sampling is not None:        # checked before anything is launched
             sampling = row_sampling_params(sampling, len(text_token_rows), gen, seed)
-        if self.gpt.engine.bank is not None:
-            raise NotImplementedError("infer_queue: slot refill with an adapter bank is not built (use infer_batch)")
+        voices = None                   # likewise: one voice per utterance, host ints or normalised mixes
+        if adapter_ids is not None or adapter_mix is not None:
+            adapter_ids, adapter_mix = self.gpt.engine._voices(adapter_ids, adapter_mix, len(text_token_rows))
+            voices = adapter_ids if adapter_mix is None else adapter_mix
+        elif self.gpt.engine.bank is not None:
+            raise NotImplementedError("infer_queue: an adapter bank is attached and no voices were named: pass adapter_ids=[...] or "
+                                      "adapter_mix=[...], one entry per utterance (adapter_ids=[-1] * N is the base voice)")
         cond_mel = self._check_prompts(cond_mel, len(text_token_rows), gen, "infer_queue")
         if not text_token_rows:
             return ([], []) if return_codes else []
@@ -809,6 +817,12 @@ class IndexTTS:
         stops = [-1] * N if force_stop is None else [int(v) for v in force_stop]
         sp = sampling_params(gen, seed)
         stop_text = self.cfg.gpt.stop_text_token
+
+        def voiced(ids):
+            """the keyword that names the voices of the utterances `ids` to prefill() / _latents() (none without voices)"""
+            if voices is None:
+                return {}
+            return {"adapter_ids" if adapter_mix is None else "adapter_mix": [voices[i] for i in ids]}
 
         def prefixes(ids):
             """(left-padded prefix batch, pad) of the utterances `ids` -- one itts_prefix_rows launch"""
@@ -830,12 +844,12 @@ class IndexTTS:
                 # paged cache: one loop serves the whole queue -- a slot's blocks go back to the pool when its row stops.  The pool
                 # holds `slots` windows of (longest prompt + start token + max_mel_tokens + the steps up to the second next poll)
                 eng.prefill(emb, pad, max_mel_tokens + ce + 1, shared_rows=shared,
-                            slots_window=emb.shape[1] + 1 + max_mel_tokens + 2 * ce + 2)
+                            slots_window=emb.shape[1] + 1 + max_mel_tokens + 2 * ce + 2, **voiced(first))
             else:
                 # contiguous strips: the loop runs whole blocks of check_every steps, the cache has to hold that many positions
                 # past max_mel_tokens; cache positions only grow, so a loop ends when `cache_positions` are used up
                 eng.prefill(emb, pad, max(max_mel_tokens + ce + 1, int(cache_positions) - emb.shape[1] - 2),
-                            shared_rows=shared, paged=False)
+                            shared_rows=shared, paged=False, **voiced(first))
             entered = list(first)
 
             def feed(k):
@@ -846,6 +860,8 @@ class IndexTTS:
                 e, p = prefixes(take)
                 p = p.tolist()
                 entered.extend(take)
+                if voices is not None:
+                    return [(e[j, p[j]:], stops[i], None if sampling is None else sampling[i], voices[i]) for j, i in enumerate(take)]
                 if sampling is not None:
                     return [(e[j, p[j]:], stops[i], sampling[i]) for j, i in enumerate(take)]
                 return [(e[j, p[j]:], stops[i]) for j, i in enumerate(take)]
@@ -854,7 +870,8 @@ class IndexTTS:
                                                 force_stop=[stops[i] for i in first],
                                                 positions=None if eng.kv is not None else
                                                 max(int(cache_positions), eng._S + max_mel_tokens + int(check_every) + 1),
-                                                check_every=int(check_every), staged=bool(staged))
+                                                check_every=int(check_every), staged=bool(staged),
+                                                **({} if voices is None else {"voices": [voices[i] for i in first]}))
             if leftover:                                               # fed but not placed: back to the head of the queue
                 back = entered[len(entered) - len(leftover):]
                 entered = entered[: len(entered) - len(leftover)]
@@ -871,7 +888,7 @@ class IndexTTS:
         for k in range(0, N, slots):
             ids = order[k: k + slots]
             sel = torch.tensor(ids, device=conds.device) if per_row else None
-            lat = self._latents(conds[sel] if per_row else conds, [texts[i] for i in ids], [squeezed[i] for i in ids])
+            lat = self._latents(conds[sel] if per_row else conds, [texts[i] for i in ids], [squeezed[i] for i in ids], **voiced(ids))
             for i, w in zip(ids, self._vocode_ragged(lat, spk[sel] if per_row else spk)):
                 outs[i] = w
         self._mark(phase_events, "vocoded")
