@@ -364,6 +364,8 @@ int itts_attn_prefill_shared(const void* qkv, void* out, void* kcache, void* vca
  * {extra_ids} U history[b][0..k), temperature, top-k, top-p, draws (Philox4x32-10 keyed by seed, counter (row,k,0,0))
  * or takes the argmax, then appends to history, updates tokens/finished, and increments state[0], state[1].
  * Rows already finished, or with force_stop[b] == k, emit stop_token.
+ * Capacity: a row keeps at most 1024 candidates.  If more than 1024 scores are at or above the k-th value (ties with it are kept),
+ * the 1024 that stay are whichever reach the candidate store first: the token is one of the tied set, but not reproducible.
  * ------------------------------------------------------------------------------------------------------------------ */
 typedef struct itts_sample_args {
   const float* logits;
@@ -426,6 +428,8 @@ typedef struct itts_sample_row {
  * min_tokens_to_keep = 2 when do_sample), running beam scores, 2*num_beams candidates drawn without replacement (own
  * Philox stream: counter (b, step, draw, 0)) or taken, scorer bookkeeping, hypothesis store, per-row token histories.
  * state[0] = step, state[1] = cache position (both advanced by the call), state[2] = finished batch elements.
+ * Capacity: a batch element's pool is its beams' sorted candidate lists concatenated in beam order and cut at 1024 entries BEFORE
+ * it is sorted, so when ties at a row's k-th score make the lists longer than 1024 in all, the last beams lose their lowest candidates.
  * ------------------------------------------------------------------------------------------------------------------ */
 typedef struct itts_beam_args {
   const float* logits; /* [B*num_beams][ldl] */
