@@ -9,7 +9,7 @@ import math
 import numpy as np
 import torch
 
-PREC = {torch.float16: (11, -14), torch.bfloat16: (8, -126)}   # significand bits, smallest normal exponent
+PREC = {torch.float16: (11, -14), torch.bfloat16: (8, -126), torch.float32: (24, -126)}   # significand bits, smallest normal exponent
 
 
 def ulp(v, dtype):
@@ -46,7 +46,7 @@ def must_fail(what, control, y, ref, bound, valid=None):
 
 
 def tname(dtype):
-    return "f16" if dtype == torch.float16 else "bf16"
+    return "f32" if dtype == torch.float32 else "f16" if dtype == torch.float16 else "bf16"
 
 
 def note(kind, what, ratio):

@@ -37,3 +37,24 @@ GEMM_SHAPES = [
     (800, 1184, 1), (1040, 96, 1), (1040, 160, 4), (1040, 1184, 4), (1360, 320, 1), (1360, 5248, 3), (2064, 160, 4), (2080, 1184, 1),
     (4100, 1184, 1), (4100, 1280, 1), (4112, 1184, 1), (4112, 1408, 1), (4128, 1280, 1), (8194, 160, 1), (8194, 1408, 1),
     (8194, 5248, 1), (8196, 320, 1)]
+
+
+# fp32 (Elem<float>: KS = 16): launch_skinny refuses the folded form and builds MT = 1 only -- the entry point cuts the rows 16 at a
+# time (skinny_row_tiles) --, so plan_skinny's rules leave  SPW 5 with NTB 1, 2, 3;  SPW 10 with NTB 1, 2;  16 waves: <10, 1, 16>.
+REACHABLE_F32 = {(1, 5, _ntb, False, 8) for _ntb in (1, 2, 3)} | {(1, 10, _ntb, False, 8) for _ntb in (1, 2)} | {(1, 10, 1, False, 16)}
+assert REACHABLE_F32 <= REACHABLE
+
+# K of the fp32 pins (tests/test_fp32_kernels_gpu.py), in k-steps of 16: 1; 6; 40 | 41 (SPW 5 -> 10); 80 (one 10-step pass of every
+# wave); 81 (a second pass of one step); 320 (four passes).  The N with 2 and 3 column tiles per workgroup come from skinny_plan.
+F32_K = (16, 96, 640, 656, 1280, 1296, 5120)
+F32_N = (50, 64)
+F32_M = (1, 13, 16, 17, 32, 33)
+
+
+def first_n_with_tiles(nat, dtype, ntb, K=16):
+    """The smallest N for which skinny_plan gives a workgroup `ntb` column tiles (K = 16: one k-step, the SPW 5 form)."""
+    for nt in range(1, 4097):
+        N = (nt - 1) * 16 + 1
+        if nat.skinny_plan(dtype, 1, N, K)["tiles_per_wg"] >= ntb:
+            return N
+    raise AssertionError(f"no N up to 65521 plans {ntb} column tiles per workgroup")
