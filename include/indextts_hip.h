@@ -48,7 +48,7 @@ extern "C" {
 #define ITTS_BF16 1
 #define ITTS_F16 2
 
-#define ITTS_ABI_VERSION 9 /* 9: itts_last_kernel (read-only: the kernel form the last itts_gemm_conv / itts_aa_snake_fwd launched), itts_lora_shrink (a new symbol: no existing struct or signature changed), and the entry points of indextts_hip_rows.h; 8: prompt front-end (itts_subsample_conv, itts_mha_small, itts_glu_dwconv_ln_silu, itts_rows, itts_geglu, itts_prefix_rows) and speaker encoder (itts_im2col_reflect, itts_res2_step, itts_se_gate, itts_scale_resid, itts_col_stats, ITTS_EPI_RELU_AFFINE_*), itts_kv_share_rows, ITTS_EPI_SILU_STORE, y_row0 / y_mtp and any M with rows_per_wg in itts_gemm_skinny, itts_gemm_conv ksplit <= 64; 7: LayerNorm folded into the consuming skinny GEMM (ln_c), residual epilogue with a packed T copy, rows_per_wg / wide_wg, bump words in itts_gemm_skinny / itts_embed_step (+ clamp, packed copy); the reducer tail is gone; paged KV cache (kv_tab / kv_bs); 6: per-row clocks (row_step0) in itts_embed_step / itts_sample_args (slot refill), itts_attn_prefill_prefix / _shared, kv_share in itts_attn_decode; 5: itts_ln_reduce takes up to 6 slabs */
+#define ITTS_ABI_VERSION 10 /* 10: one header and one argument struct per launch family -- itts_skinny_args gains w_scale (itts_gemm_skinny_w8 takes that struct), itts_sample_args gains rows (itts_sample_rows takes that struct), itts_lora_shrink_args gains mix (itts_lora_shrink_mix takes that struct), the three near-copy structs of those entry points are gone; no symbol was renamed or removed; 9: itts_last_kernel (read-only: the kernel form the last itts_gemm_conv / itts_aa_snake_fwd launched), itts_lora_shrink (a new symbol: no existing struct or signature changed), and itts_sample_rows; 8: prompt front-end (itts_subsample_conv, itts_mha_small, itts_glu_dwconv_ln_silu, itts_rows, itts_geglu, itts_prefix_rows) and speaker encoder (itts_im2col_reflect, itts_res2_step, itts_se_gate, itts_scale_resid, itts_col_stats, ITTS_EPI_RELU_AFFINE_*), itts_kv_share_rows, ITTS_EPI_SILU_STORE, y_row0 / y_mtp and any M with rows_per_wg in itts_gemm_skinny, itts_gemm_conv ksplit <= 64; 7: LayerNorm folded into the consuming skinny GEMM (ln_c), residual epilogue with a packed T copy, rows_per_wg / wide_wg, bump words in itts_gemm_skinny / itts_embed_step (+ clamp, packed copy); the reducer tail is gone; paged KV cache (kv_tab / kv_bs); 6: per-row clocks (row_step0) in itts_embed_step / itts_sample_args (slot refill), itts_attn_prefill_prefix / _shared, kv_share in itts_attn_decode; 5: itts_ln_reduce takes up to 6 slabs */
 
 int itts_abi_version(void);
 const char* itts_last_error(void);
@@ -168,16 +168,92 @@ typedef struct itts_skinny_args {
   int y_row0, y_mtp, x_mtp;
   const float* post_scale; /* [N], ITTS_EPI_RELU_AFFINE_* only */
   const float* post_shift;
+  const float* w_scale; /* [N]: itts_gemm_skinny_w8 only (wp holds packed E4M3 codes, see below); itts_gemm_skinny refuses a
+                           non-NULL w_scale, so an FP8 image is never read as 16-bit weights */
 } itts_skinny_args;
 int itts_gemm_skinny(const itts_skinny_args* a, void* stream);
 /* launch geometry itts_gemm_skinny would use: out8 = {grid.x, grid.y, waves per workgroup, column tiles per workgroup,
  * k-steps per wave, dynamic LDS bytes, grid.z, row tiles per workgroup} (host-only, launches nothing) */
 int itts_skinny_plan(int dtype, int M, int N, int K, int ksplit, int rows_per_wg, int wide_wg, int fold, int* out8);
-/* The same GEMM over FP8 (E4M3) weights with one fp32 scale per output column -- itts_gemm_skinny_w8, its packed weight layout,
- * packer and planner -- is declared in indextts_hip_w8.h (new symbols: no struct or signature above changed), which this header
- * pulls in: */
-#include "indextts_hip_w8.h"
-#include "indextts_hip_kv8.h"
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * FP8 (OCP E4M3, "e4m3fn") weight-only forms of the decode-step GEMM.
+ *
+ * Scheme.  A weight matrix W[K][N] is stored as one E4M3 code per element plus one fp32 scale per output column:
+ *     W[k][n] ~ w_scale[n] * decode(code[k][n]),   w_scale[n] = max_k |W[k][n]| / 448   (indextts/utils/quant.py).
+ * Codes are OCP e4m3fn: 1 sign, 4 exponent (bias 7), 3 mantissa bits; no infinities; 0x7f / 0xff are NaN and never produced by
+ * the quantiser (the kernel does not treat them specially: they must not be fed).  Activations,
+ * accumulation (fp32), the KV cache, the LayerNorm statistics and every epilogue stay as in the 16-bit kernel: a code is
+ * converted IN REGISTERS to the activation type T (bf16 or f16; exact, every finite E4M3 value -- subnormals included -- is
+ * representable in both) and feeds the same 16x16x32 MFMA as the A operand.
+ *
+ * Packed FP8 weight layout.  1-KiB blocks, each 16 columns x 64 k:
+ *     block(nt, kb),  nt = n / 16 in [0, ceil(N / 16)),  kb = k / 64 in [0, ceil(K / 64)),  at byte ((nt * KB + kb) * 1024),
+ *                     KB = ceil(K / 64); zero codes (0x00) pad K to a multiple of 64 and N to a multiple of 16.
+ *     inside a block: lane l = (g << 4) | c (g = 0..3, c = 0..15) owns 16 contiguous bytes:
+ *                     byte e     (e = 0..7) = code[kb * 64      + g * 8 + e][nt * 16 + c]
+ *                     byte 8 + e (e = 0..7) = code[kb * 64 + 32 + g * 8 + e][nt * 16 + c]
+ * i.e. the low 8 bytes are lane l's fragment of the 32-k step 2 kb and the high 8 bytes its fragment of step 2 kb + 1, in the k
+ * order of the 16-bit packed weight layout and of the packed activation layout (lane (g, r) of k-step s holds k = 32 s + 8 g +
+ * 0..7): one 16-byte load per lane yields the two complete 16x16x32 A fragments the 16-bit kernel loads as two blocks, and the
+ * activations are read unchanged.
+ * ------------------------------------------------------------------------------------------------------------------ */
+/* bytes of the packed image: ceil(N / 16) * ceil(K / 64) * 1024 */
+int64_t itts_packed_bytes_w8(int K, int N);
+/* codes uint8 [K][N] row-major (device) -> packed (device), the layout above */
+int itts_pack_weight_w8(const void* codes, void* packed, int K, int N, void* stream);
+
+/* Y[M][N] = epi( w_scale[n] * (X[M][K] @ decode(codes)[K][N]) + bias ): itts_gemm_skinny over FP8 weights, with wp = the packed
+ * E4M3 codes (itts_pack_weight_w8) and w_scale [N] (required).  Epilogue order: the accumulator is multiplied by w_scale[n] FIRST,
+ * then everything the 16-bit epilogue does; LayerNorm folded (ln_c != NULL):
+ *     v = rstd[m] * ( w_scale[n] * acc[m][n] - mean[m] * ln_c[n] ) + bias[n],   ln_c[n] = w_scale[n] * sum_k decode(code[k][n])
+ * (the caller sums in float64), so a constant row cancels as in the 16-bit form.
+ * dtype: ITTS_BF16 or ITTS_F16 (the activation type; ITTS_F32 is refused).  Epilogues: ITTS_EPI_STORE, _GELU_STORE, _RESID_F32,
+ * _QKV_CACHE, _STORE_F32 (what the "fold" decode step and the head use); the split-K slab, _SILU_STORE and the
+ * ITTS_EPI_RELU_AFFINE_* epilogues are refused (post_scale / post_shift are therefore never read), as is ksplit > 1.
+ * wide_wg is the hint it is in itts_gemm_skinny: there is no 16-wave FP8 form, so it is ignored.
+ * K % 32 == 0 (the activations' k-steps; the weight image is padded to 64).  Up to 96 rows per launch; more rows go 96 at a time
+ * or, with rows_per_wg > 0, in one launch whose row tiles are dealt to grid.z. */
+int itts_gemm_skinny_w8(const itts_skinny_args* a, void* stream);
+/* launch geometry itts_gemm_skinny_w8 would use: out8 = {grid.x, grid.y, waves per workgroup, column tiles per workgroup,
+ * 64-k weight blocks per wave, dynamic LDS bytes, grid.z, row tiles per workgroup} (host-only, launches nothing) */
+int itts_skinny_plan_w8(int dtype, int M, int N, int K, int rows_per_wg, int fold, int* out8);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * FP8 (OCP E4M3, "e4m3fn") KV cache of the paged sampling loop.
+ *
+ * Format.  The paged pool ("Paged KV cache" above) holds one E4M3 code per cached element, uint8 [blocks][H][bs][64]
+ * per layer, K and V separate, addressed through the same block table as the 16-bit pool.  One fp32 scale per (layer, K | V,
+ * head): kv_scale float [2][H] of the layer a call works on (k scales, then v scales),
+ *     k[j][d] ~ kv_scale[0][h] * decode(kcode[j][d]),     v[j][d] ~ kv_scale[1][h] * decode(vcode[j][d]).
+ * Scales are positive powers of two: multiplying by the inverse is exact, so the device quantiser and the host quantiser
+ * (indextts/utils/quant.py, quantize_kv_e4m3) give the same code for every input, and dequantisation commutes with every sum.
+ * Quantiser: code = rne_e4m3( clamp(x / scale, -448, 448) ); the clamp is done in fp32 in front of the hardware conversion, so
+ * nothing rests on a conversion's overflow rule.  0x7f / 0xff (NaN) are never produced.
+ * ------------------------------------------------------------------------------------------------------------------ */
+/* One decode step's attention of one layer over an FP8 paged cache, INCLUDING the append of the step's own key / value.
+ *   qkv      T [B][3 * H * 64] row-major (the QKV GEMM's ITTS_EPI_STORE output): q | k | v of the step's token, per row.
+ *   kcache / vcache  uint8 pools of this layer; kv_tab int32 [B][ITTS_KV_TAB]; kv_bs in {16, 32, 64}.
+ *   kv_scale float [2][H].   pad int32 [B], pos int32 [1] (device): the row's keys are positions [pad[b], pos[0]) of the pool
+ *   plus the new key, whose codes are stored at position pos[0] (64 + 64 bytes per (row, head), one owner per element: the
+ *   workgroup of that (row, head)).  The new key takes part through its DECODED codes: the token sees what later tokens will see.
+ *   skip_rows int32 [B] or NULL: a row with a nonzero entry neither appends nor writes its slice of `out`.
+ *   out T: packed activation layout (out_packed != 0) or row-major [B][H * 64], as itts_attn_decode.
+ * dtype: ITTS_BF16 or ITTS_F16 (ITTS_F32 is refused).  No beam row table, no shared-prefix reads, no contiguous cache. */
+int itts_attn_decode_kv8(const void* qkv, void* kcache, void* vcache, void* out, const int32_t* pad, const int32_t* pos,
+                         const float* kv_scale, int B, int H, int dtype, int out_packed, const int32_t* skip_rows,
+                         const int32_t* kv_tab, int kv_bs, void* stream);
+
+/* The prefill's keys / values of one layer into the FP8 pool: reads the k / v thirds of qkv T [rows][3 * H * 64], quantises with
+ * the head's scales and scatters through the block table.  Two row addressings (those of itts_attn_prefill):
+ *   row_off == NULL: rows [B][S]; local row s of element b goes to position s; rows in front of pad[b] (pad may be NULL) are
+ *                    not stored.
+ *   row_off != NULL: packed rows, element b owns rows [row_off[b], row_off[b + 1]) (at most S of them); local row s goes to
+ *                    position cache_shift[b] + s (cache_shift may be NULL: 0).
+ * 16 bytes of codes per thread. */
+int itts_kv8_store(const void* qkv, void* kcache, void* vcache, const float* kv_scale, const int32_t* pad,
+                   const int32_t* row_off, const int32_t* cache_shift, int B, int S, int H, int dtype, const int32_t* kv_tab,
+                   int kv_bs, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Tiled MFMA GEMM / 1-D convolution, channels-last.
@@ -238,6 +314,28 @@ int itts_gemm_conv(const itts_conv_args* a, void* stream);
  *           of a [M][K + Kx] operand).
  * K % KS == 0; x, u and a_bank 16-byte aligned.
  * ------------------------------------------------------------------------------------------------------------------ */
+/* Per-row adapter BLENDS of the bank: the shrink half over weighted mixes of bank voices (itts_lora_shrink_mix).
+ * The bank's identity holds for a weighted sum of adapters as it stands:
+ *   y = x W + sum_j w_j s_{a_j} (x A_{a_j}^T) B_{a_j}^T = [x | u] [W ; B_bank^T]
+ * with u non-zero in the slot of EVERY adapter the row names, each slot scaled by that entry's weight.  The consuming GEMMs, the
+ * [W ; B_bank^T] weights and a_bank are those of itts_lora_shrink; only the launch that writes u differs. */
+#define ITTS_LORA_MIX_ENTRIES 4
+
+/* One row's mix: 32 bytes, 16-byte aligned.  Entry j = (id[j], weight[j]) is laid out as {int32 id; float weight} at byte 8 * j.
+ *   id      adapter of the bank, in [0, n); -1 = empty entry.  Empty entries may stand anywhere; the ids of one record are
+ *           distinct (the host enforces it; of two entries with one id the kernel writes the earlier).  An id outside the bank is
+ *           treated as empty and reads nothing.
+ *   weight  any finite fp32: not necessarily positive, no sum is prescribed.  1.0f = the adapter at the strength it was trained at.
+ * A record with four empty entries is the base voice (u = 0). */
+typedef struct __attribute__((aligned(16))) itts_lora_mix_row {
+  struct {
+    int32_t id;
+    float weight;
+  } e[ITTS_LORA_MIX_ENTRIES];
+} itts_lora_mix_row;
+
+/* One argument struct for both launches: itts_lora_shrink needs `ids` (and does not read `mix`), itts_lora_shrink_mix needs `mix`
+ * (and does not read `ids`); every other field means the same to both (same layouts, limits and refusals). */
 typedef struct itts_lora_shrink_args {
   int dtype;
   int M, K;
@@ -249,12 +347,75 @@ typedef struct itts_lora_shrink_args {
   void* u;
   int u_packed, u_mtp;
   int64_t ldu;
+  const itts_lora_mix_row* mix; /* itts_lora_shrink_mix: [M] on the device, 16-byte aligned */
 } itts_lora_shrink_args;
 int itts_lora_shrink(const itts_lora_shrink_args* a, void* stream);
-/* The same launch over weighted mixes of up to four bank voices per row (record, argument struct and prototype): */
-#include "indextts_hip_mix.h"
-/* Continuous batching: the launch that takes staged rows, with their voice records, into a running decode loop: */
-#include "indextts_hip_refill.h"
+
+/* itts_lora_shrink over mixes: `mix` takes the part of `ids`.
+ *   u[m][a_j * rp + r] = round_T( w_j * sum_k x[m][k] A_bank[a_j][r][k] )   for every non-empty entry j of mix[m]   (r < rp)
+ *   every other column of u[m][0 .. Kx) = 0; the padding rows of a packed tail = 0.  ALL Kx columns are written on every call.
+ * The sum is accumulated in fp32 in the order of itts_lora_shrink, the weight is applied in fp32, and the product is rounded to T
+ * once: a record {a, 1.0f} gives the bits itts_lora_shrink gives for ids[m] = a.  No atomics; the order of a record's entries
+ * does not change a bit of the result.
+ *   mix     itts_lora_mix_row [M] on the device, read by the kernel: a captured graph serves any assignment of mixes to rows */
+int itts_lora_shrink_mix(const itts_lora_shrink_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The JOIN of continuous batching: staged rows enter a running decode loop in one launch.
+ *
+ * Between two replays of the captured decode step, GPTEngine.decode_refill hands the slots of finished rows to new utterances
+ * whose prompts were prefilled beside the loop (keys / values kept aside, first token sampled from their own logits).  This
+ * launch moves all of it into the loop's buffers: the staged keys and values into the cache, and each entering row's state --
+ * with the 32-byte voice record of its slot (itts_lora_mix_row) -- into the per-slot tables the captured step reads.
+ * ------------------------------------------------------------------------------------------------------------------ */
+/* Keys / values.  For every staged position m in [0, M), layer l in [0, L) and head h in [0, H):
+ *   kc[l * s_l + i_b[m] * s_b + h * s_h + i_p[m] * s_p + (0 .. 63)] = kst[((m * L + l) * H + h) * 64 + (0 .. 63)]    (vc <- vst alike)
+ * The strides are in ELEMENTS, so one kernel serves the paged pool T [L][blocks][H][bs][64] (i_b = block, i_p = offset in the
+ * block: s_l = blocks*H*bs*64, s_b = H*bs*64, s_h = bs*64, s_p = 64) and the contiguous cache T [L][rows][H][Smax][64] (i_b = cache
+ * row, i_p = position).  Every stride is a multiple of 16 bytes' worth of elements and s_p >= 64 (checked); every 16-byte piece
+ * has one owner, loaded and stored once.  A position with i_b[m] outside [0, n_b) or i_p[m] outside [0, n_p) is skipped
+ * (memory guard; the host deals the positions), its neighbours are written.  The (i_b, i_p) pairs of one call are distinct.
+ * dtype: ITTS_BF16 / ITTS_F16 (the serving types), or ITTS_F32 (the parity engine); the kernel moves bytes, no value is converted.
+ *
+ * Row state.  For every entering row j in [0, k) with slot s = rows[j] (skipped when s is outside [0, n_slots); the slots of one
+ * call are distinct):
+ *   tokens[s] = tok[j]     history[s * hist_cap] = tok[j]     finished[s] = fin[j]     force_stop[s] = stops[j]
+ *   row_step0[s] = step0   pad[s] = pads[j]                   mix[s] = mix_new[j]      (mix / mix_new may both be NULL: no bank)
+ * tok / fin are what the sample launch in front of this one (same stream) wrote for the new rows.
+ * state[2] -= k (the entering slots were counted as finished): one thread, an ordinary read-modify-write -- nothing else touches
+ * that word between two replays.
+ * No allocation, no host synchronisation, no atomics; safe between graph replays on the loop's stream. */
+typedef struct itts_refill_join_args {
+  int dtype;
+  int M, L, H;
+  const void* kst; /* T [M][L][H][64] */
+  const void* vst;
+  void* kc;
+  void* vc;
+  int64_t s_l, s_b, s_h, s_p;
+  int n_b, n_p;
+  const int32_t* i_b; /* [M] */
+  const int32_t* i_p; /* [M] */
+  int k;
+  int n_slots;
+  const int32_t* rows; /* [k] */
+  const int32_t* tok;  /* [k] */
+  const int32_t* fin;
+  const int32_t* stops;
+  const int32_t* pads;
+  const itts_lora_mix_row* mix_new; /* [k] or NULL */
+  int step0;
+  int hist_cap;
+  int32_t* tokens; /* [n_slots] each */
+  int32_t* history; /* [n_slots][hist_cap] */
+  int32_t* finished;
+  int32_t* force_stop;
+  int32_t* row_step0;
+  int32_t* pad;
+  itts_lora_mix_row* mix; /* [n_slots] or NULL */
+  int32_t* state;         /* the loop's state words; [2] = finished rows */
+} itts_refill_join_args;
+int itts_refill_join(const itts_refill_join_args* a, void* stream);
 
 /* LayerNorm over the last dim of fp32 rows; y is T (y_f32 = 0) or fp32 (y_f32 = 1).  If w2 != NULL a second LayerNorm
  * (w2,b2) is applied to the result of the first (ln_f followed by final_norm). */
@@ -367,6 +528,32 @@ int itts_attn_prefill_shared(const void* qkv, void* out, void* kcache, void* vca
  * Capacity: a row keeps at most 1024 candidates.  If more than 1024 scores are at or above the k-th value (ties with it are kept),
  * the 1024 that stay are whichever reach the candidate store first: the token is one of the tied set, but not reproducible.
  * ------------------------------------------------------------------------------------------------------------------ */
+/* itts_sample_rows: the step with PER-ROW sampling settings.  A device table of one record per row replaces the scalar parameters, so a
+ * row of a batch -- or a slot of a refilled loop -- keeps its own request's settings and one captured launch serves every
+ * assignment (the records are data, like the adapter ids of itts_lora_shrink).  Row b is processed exactly as itts_sample
+ * processes a row under the scalars of rows[b]; greedy and sampling rows may share a launch.
+ * Record: 32 bytes, 16-byte aligned (a workgroup fetches its row's record as two 16-byte words):
+ *   byte  0  float    rep_penalty
+ *         4  float    temperature
+ *         8  float    top_p
+ *        12  int32    top_k
+ *        16  uint64   seed       Philox key = seed + the 64-bit value in state[4..5]
+ *        24  uint32   stream     Philox counter = (stream, k_b, 0, 0) with the row's OWN step k_b = state[0] - row_step0[b]:
+ *                                what a request draws depends on its seed, stream and step, not on its slot or on when it
+ *                                entered.  stream = b without row_step0 is itts_sample's counter.
+ *        28  int32    do_sample  0 = argmax (temperature, top_k, top_p unused)
+ * The library cannot see the records at launch time.  The caller validates them before the upload (sampling rows: 1 <= top_k
+ * <= 1024, 0 < top_p <= 1, temperature > 0; every row: rep_penalty > 0); the kernel itself only stays memory-safe for any
+ * record: a sampling row's top_k is clamped into [1, min(V, 1024)], a temperature or penalty that is not > 0 is taken as 1,
+ * the emitted token is clamped into [0, V).  The arguments are itts_sample_args with `rows` set; the scalar settings
+ * (rep_penalty, temperature, top_p, top_k, do_sample, seed) are ignored. */
+typedef struct itts_sample_row {
+  float rep_penalty, temperature, top_p;
+  int32_t top_k;
+  uint64_t seed;
+  uint32_t stream;
+  int32_t do_sample;
+} itts_sample_row;
 typedef struct itts_sample_args {
   const float* logits;
   int B, V, ldl; /* ldl = row stride of logits */
@@ -389,36 +576,12 @@ typedef struct itts_sample_args {
   const int32_t* row_step0; /* [B] or NULL (= zeros): loop step at which row b started (slot refill).  Row b's own step
                         k_b = state[0] - row_step0[b] indexes its history, bounds its repetition-penalty window and is what
                         force_stop[b] is compared with; the Philox counter stays (b, state[0]). */
+  const itts_sample_row* rows; /* itts_sample_rows: [B] on the device, 16-byte aligned; itts_sample refuses a non-NULL rows */
 } itts_sample_args;
 int itts_sample(const itts_sample_args* a, void* stream);
 
-/* The same step with PER-ROW sampling settings: a device table of one record per row replaces the scalar parameters, so a
- * row of a batch -- or a slot of a refilled loop -- keeps its own request's settings and one captured launch serves every
- * assignment (the records are data, like the adapter ids of itts_lora_shrink).  Row b is processed exactly as itts_sample
- * processes a row under the scalars of rows[b]; greedy and sampling rows may share a launch.
- * Record: 32 bytes, 16-byte aligned (a workgroup fetches its row's record as two 16-byte words):
- *   byte  0  float    rep_penalty
- *         4  float    temperature
- *         8  float    top_p
- *        12  int32    top_k
- *        16  uint64   seed       Philox key = seed + the 64-bit value in state[4..5]
- *        24  uint32   stream     Philox counter = (stream, k_b, 0, 0) with the row's OWN step k_b = state[0] - row_step0[b]:
- *                                what a request draws depends on its seed, stream and step, not on its slot or on when it
- *                                entered.  stream = b without row_step0 is itts_sample's counter.
- *        28  int32    do_sample  0 = argmax (temperature, top_k, top_p unused)
- * The library cannot see the records at launch time.  The caller validates them before the upload (sampling rows: 1 <= top_k
- * <= 1024, 0 < top_p <= 1, temperature > 0; every row: rep_penalty > 0); the kernel itself only stays memory-safe for any
- * record: a sampling row's top_k is clamped into [1, min(V, 1024)], a temperature or penalty that is not > 0 is taken as 1,
- * the emitted token is clamped into [0, V).  Every other field of the arguments is as in itts_sample_args. */
-typedef struct itts_sample_row {
-  float rep_penalty, temperature, top_p;
-  int32_t top_k;
-  uint64_t seed;
-  uint32_t stream;
-  int32_t do_sample;
-} itts_sample_row;
-/* The argument struct and the prototype are in indextts_hip_rows.h (see there why), which this header pulls in: */
-#include "indextts_hip_rows.h"
+/* itts_sample with the per-row settings of `rows` (the record and its rules: above, in front of itts_sample_args) */
+int itts_sample_rows(const itts_sample_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Beam search / beam-sample step (num_beams > 1) -- replaces, for the generate() call at indextts/gpt/model.py:710-715,
@@ -523,8 +686,65 @@ int itts_mha_small(const itts_mha_args* a, void* stream);
 int itts_glu_dwconv_ln_silu(const void* x, const float* w, const float* b, const float* ln_w, const float* ln_b, void* y, int T,
                             int C, int taps, int y_mtp, float eps, int dtype, void* stream);
 
-/* the three launches above over N prompts of different lengths at once (a device segment table) */
-#include "indextts_hip_prompts.h"
+/* ------------------------------------------------------------------------------------------------------------------
+ * The prompt front-end over N prompts of different lengths in one launch each.
+ *
+ * The row-wise launches of the conditioner (the GEMMs, itts_rows, itts_geglu) run unchanged over the concatenated rows of all
+ * prompts.  The three launches that mix rows of a sequence -- the subsampling convolution, the attention and the convolution
+ * module -- exist here in a segmented form: the same kernel bodies as itts_subsample_conv, itts_mha_small and
+ * itts_glu_dwconv_ln_silu behind a segment lookup, and a segment's result has the bits the single-prompt entry point gives for
+ * that segment alone.
+ *
+ * Row space.  Segment s owns rows [row0, row0 + len) of the launch's row space, row0 a multiple of 16: a 16-row tile of a packed
+ * operand never holds rows of two segments.  The rows between a segment's end and the next multiple of 16 are padding rows:
+ * row-wise launches may compute on them, no entry point here reads them as data or writes them.
+ *
+ * Segment table.  int32 words: nseg records of ITTS_SEG_WORDS words, then `ntiles` words that name the segment of every 16-row
+ * tile of the row space (-1: none).  It exists twice: `dev` in device memory is what the kernels read -- device DATA, so a captured
+ * graph depends on the geometry (nseg, ntiles, and through the caller's buffers the lengths), never on the pointer's contents
+ * being known at capture time -- and `host`, the same words in host memory, which the entry point checks (row0 % 16, len > 0,
+ * no tile in two segments, every range inside its buffer) before it launches: an invalid table returns ITTS_ERR_INVALID and
+ * launches nothing.  The caller keeps the two copies equal.
+ *
+ *   word  itts_subsample_conv_seg        itts_mha_small_seg                       itts_glu_dwconv_ln_silu_seg
+ *   0     row0: first output row         row0: first query row                    row0: first row of x and y
+ *   1     len = (T_p - 3) / 2 + 1        len: queries                             len: rows
+ *   2     first frame of the prompt      first row of the first key range         -
+ *   3     T_p: frames of the prompt      rows of the first key range (> 0)        -
+ *   4     -                              first row of the second key range        -
+ *   5     -                              rows of the second key range (0: none)   -
+ *   6     -                              first output row (a multiple of 16)      -
+ *   7     reserved (0)
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define ITTS_SEG_WORDS 8
+
+typedef struct itts_seg_table {
+  const int32_t* dev;  /* device: nseg * ITTS_SEG_WORDS + ntiles words */
+  const int32_t* host; /* the same words in host memory */
+  int nseg, ntiles;
+} itts_seg_table;
+
+/* itts_subsample_conv over N prompts: mel fp32 [frames][F] holds the prompts' frames one after another (segment s: frames
+ * [word 2, word 2 + word 3)), a 3 x 3 stride-2 window never leaves its prompt; y T [ntiles * 16][C * F2], row row0 + t of a
+ * segment = what itts_subsample_conv writes to row t for that prompt alone.  Rows of y outside every segment are not written. */
+int itts_subsample_conv_seg(const float* mel, const float* w, const float* b, void* y, const itts_seg_table* tab, int frames, int F,
+                            int C, int dtype, void* stream);
+
+/* itts_mha_small over N segments, one (segment, head, 16-query tile) per workgroup.  The fields of `a` keep their meaning with
+ * these differences: q / k / v point at row 0 of their row spaces, a->Tq = rows of q and a->Tk = rows of k and v that exist
+ * (bounds of the table); a segment's queries are rows [row0, row0 + len) of q, its keys and values the rows of its first key
+ * range followed by those of its second; pos is T [H][pos_tk][64] and, like bias_u / bias_v, indexed by the key's index WITHIN
+ * its segment (pos_tk >= the longest segment's key count; the first Tk rows of every head are those of the single-prompt table
+ * for Tk keys); the output of query i of a segment goes to row (word 6) + i of the packed out operand of a->out_mtp row tiles.
+ * Output rows outside every segment are not written; the caller keeps the segments' output rows apart. */
+int itts_mha_small_seg(const itts_mha_args* a, const itts_seg_table* tab, int pos_tk, void* stream);
+
+/* itts_glu_dwconv_ln_silu over N segments of x T [ntiles * 16][2 C] -> packed y of y_mtp >= ntiles row tiles: the depthwise
+ * taps see zeros beyond the segment's first and last row, never the neighbouring segment's rows.  Rows outside every segment
+ * are neither read nor written. */
+int itts_glu_dwconv_ln_silu_seg(const void* x, const float* w, const float* b, const float* ln_w, const float* ln_b, void* y,
+                                const itts_seg_table* tab, int C, int taps, int y_mtp, float eps, int dtype, void* stream);
+
 
 /* Row operations on an fp32 residual stream [M][D] (D % 4 == 0, D <= 2048):
  *   v = (x ? x[m] : 0) + (bias ? bias : 0) + slab[0][m] + ... + slab[nslab-1][m]       (fixed order; slab fp32 [nslab][M][D])

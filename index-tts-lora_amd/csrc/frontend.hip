@@ -78,7 +78,7 @@ __global__ __launch_bounds__(512) void subsample_conv_kernel(const float* __rest
   subsample_conv_row<T, STAGED>(mel, w, b, y + (int64_t)t * C * F2, t, F, C, F2);
 }
 
-// Segment lookup of the *_seg kernels (include/indextts_hip_prompts.h): the workgroup's 16-row tile of the launch's row space
+// Segment lookup of the *_seg kernels (include/indextts_hip.h): the workgroup's 16-row tile of the launch's row space
 // names its segment, whose record is wave-uniform and goes to SGPRs.  false: the tile belongs to no segment.
 struct SegRec {
   int row0, len, src0, src_len, kb_row0, kb_len, out_row0;
@@ -940,7 +940,7 @@ extern "C" int itts_glu_dwconv_ln_silu(const void* x, const float* w, const floa
   });
 }
 
-// ---- the segmented forms (include/indextts_hip_prompts.h): N prompts per launch
+// ---- the segmented forms (include/indextts_hip.h): N prompts per launch
 // The host mirror of the table is what is checked and what sizes the grid; the kernels read the device copy only.
 static int check_seg_table(const itts_seg_table* t, const char* who) {
   ITTS_REQUIRE(t && t->dev && t->host, "%s: null segment table", who);

@@ -38,54 +38,6 @@ int g_tune_ntb = 0, g_tune_nw = 0;  // diagnostic build: itts_debug_set(1|2, v) 
 int g_skinny_exp = 0;               // itts_debug_set(6, bits): load ablations of the skinny GEMM (SkinnyParams::exp)
 #endif
 
-// MTall = 16-row tiles of the launch; rows_per_wg (0 = all of them in every workgroup, else 16 / 32: the row tiles are dealt
-// to grid.z -- more, lighter workgroups for the GEMMs that run WITHOUT split-K); wide: up to 16 waves per workgroup
-template <typename T>
-static SkinnyPlan plan_skinny(int N, int K, int ksplit, int MTall, int rows_per_wg, bool wide, bool fold) {
-  constexpr int KS = Elem<T>::KS;
-  fold = fold && sizeof(T) == 2;   // fp32 has no folded form: the launcher refuses it
-  wide = wide && !fold;            // a folded launch never takes 16 waves
-  SkinnyPlan q;
-  int MT = MTall;
-  if (rows_per_wg > 0 && rows_per_wg / 16 < MTall) MT = rows_per_wg / 16;
-  const int gz = (MTall + MT - 1) / MT;
-  const int KT = K / KS;
-  const int SB = (KT + ksplit - 1) / ksplit;
-  // waves per workgroup: 8 whenever the slice has 8 k-steps (measured: the split-K 3 out-projection, 14 k-steps, takes
-  // 3.8 us with 8 waves x 2 steps against 4.4 us with 3 waves x 5; more than 8 waves change nothing there).  `wide`: 16 waves
-  // when that keeps the slice to ONE pass of <= 10 k-steps per wave (a second pass is a second memory round trip)
-  int NW = SB > 8 ? 8 : SB;
-  if (wide && MT == 1 && SB > 80) NW = 16;
-  if (NW < 1) NW = 1;
-#if ITTS_DIAG
-  if (g_tune_nw > 0) NW = g_tune_nw > 8 ? 8 : g_tune_nw;
-#endif
-  const int spw = (SB + NW - 1) / NW;
-  const int NT = (N + 15) / 16;
-  int ntb = (NT * ksplit * gz + 255) / 256;   // keep the grid within one round of the 256 CUs
-#if ITTS_DIAG
-  if (g_tune_ntb > 0) ntb = g_tune_ntb;
-#endif
-  const int SPWc = spw <= 5 ? 5 : 10;     // register-chunk variant
-  const int ntb_max = (fold && MT <= 2 && SPWc == 5) ? 4 : 3;   // 4 tiles: the folded GEMMs of a many-row step with the rows dealt to grid.z
-  if (ntb > ntb_max) ntb = ntb_max;
-  if (SPWc == 10 && ntb > 2) ntb = 2;     // register budget of the 10-step variant
-  if (MT > 2 && SPWc == 10) ntb = 1;      // 4-6 row tiles with 10-step chunks: accumulators + weight fragments
-  if (NW == 16) ntb = 1;                  // 128 registers per lane
-  if (fold && MT > 2 && ntb > 2) ntb = 2; // the statistics accumulators take 8 registers per row tile
-  q.NW = NW;
-  q.spw = spw;
-  q.ntb = ntb;
-  q.SPWc = SPWc;
-  q.MT = MT;
-  q.gx = (NT + ntb - 1) / ntb;
-  q.gy = ksplit;
-  q.gz = gz;
-  q.lds = (size_t)NW * ntb * MT * 256 * 4 + (fold ? (size_t)NW * MT * 32 * 4 : 0);
-  if (q.lds < 1024) q.lds = 1024;
-  return q;
-}
-
 static int skinny_no_form(const SkinnyPlan& q, bool fold) {
   set_error("itts_gemm_skinny: no form <%d,%d,%d,%d,%d> is built", q.MT, q.SPWc, q.ntb, (int)fold, q.NW);
   return ITTS_ERR_INVALID;
@@ -141,53 +93,13 @@ static int launch_skinny(const SkinnyParams& p, const SkinnyPlan& q, hipStream_t
 using namespace itts;
 
 extern "C" int itts_gemm_skinny(const itts_skinny_args* a, void* stream) {
-  ITTS_REQUIRE(a && a->wp && a->x, "itts_gemm_skinny: null args");
-  const int ks = a->dtype == ITTS_F32 ? 16 : 32;
+  int ksplit, y_mtp, kv_bs_log2;
+  if (int rc = skinny_check(a, "itts_gemm_skinny", false, &ksplit, &y_mtp, &kv_bs_log2)) return rc;
   const size_t esz = a->dtype == ITTS_F32 ? 4 : 2;
-  ITTS_REQUIRE(a->M >= 0 && a->N > 0 && a->K > 0 && a->K % ks == 0, "itts_gemm_skinny: bad shape M=%d N=%d K=%d (K %% %d != 0)",
-               a->M, a->N, a->K, ks);
-  const int ksplit = a->ksplit > 0 ? a->ksplit : 1;
-  ITTS_REQUIRE(ksplit <= a->K / ks && ksplit <= 64, "itts_gemm_skinny: ksplit=%d too large", ksplit);
-  ITTS_REQUIRE(ksplit == 1 || a->epi == ITTS_EPI_SLAB_F32, "itts_gemm_skinny: ksplit > 1 requires the slab epilogue");
-  // (the block size is checked where the table is used: the QKV epilogue)
-  const int kv_bs_log2 = kv_block_log2(a->epi == ITTS_EPI_QKV_CACHE && a->kv_tab != nullptr, a->kv_bs);
-  if (a->epi == ITTS_EPI_QKV_CACHE)
-    ITTS_REQUIRE(a->y && a->kcache && a->vcache && a->pos && a->N % 3 == 0 && a->N / 3 == a->heads * 64 &&
-                     (a->kv_tab != nullptr ? kv_bs_log2 >= 0 : a->smax > 0),
-                 "itts_gemm_skinny: bad QKV epilogue arguments (paged cache: kv_bs must be 16, 32 or 64)");
-  else if (a->epi == ITTS_EPI_RESID_F32 || a->epi == ITTS_EPI_STORE_F32 || a->epi == ITTS_EPI_SLAB_F32)
-    ITTS_REQUIRE(a->yf, "itts_gemm_skinny: yf is null");
-  else
-    ITTS_REQUIRE((a->epi == ITTS_EPI_STORE || a->epi == ITTS_EPI_GELU_STORE || a->epi == ITTS_EPI_SILU_STORE ||
-                  a->epi == ITTS_EPI_RELU_AFFINE_STORE || a->epi == ITTS_EPI_RELU_AFFINE_TANH_STORE) && a->y,
-                 "itts_gemm_skinny: bad epilogue %d", a->epi);
-  if (a->epi == ITTS_EPI_RELU_AFFINE_STORE || a->epi == ITTS_EPI_RELU_AFFINE_TANH_STORE)
-    ITTS_REQUIRE(a->post_scale && a->post_shift, "itts_gemm_skinny: the ReLU + affine epilogues need post_scale and post_shift");
-  if (a->epi == ITTS_EPI_RESID_F32)
-    ITTS_REQUIRE(a->N % 4 == 0 && (int64_t)a->M * a->N < (1ll << 29), "itts_gemm_skinny: the residual epilogue needs N %% 4 == 0");
-  if (a->ln_c != nullptr)
-    ITTS_REQUIRE(ksplit == 1 && a->bias && a->N % 4 == 0 && a->epi != ITTS_EPI_RESID_F32 && a->epi != ITTS_EPI_SLAB_F32 &&
-                     a->dtype != ITTS_F32,
-                 "itts_gemm_skinny: the LayerNorm-folded form needs ksplit 1, bias (= d), N %% 4 == 0, a storing epilogue, bf16 / f16");
-  ITTS_REQUIRE(a->rows_per_wg == 0 || a->rows_per_wg == 16 || a->rows_per_wg == 32, "itts_gemm_skinny: rows_per_wg must be 0, 16 or 32");
-  if (a->y_packed)
-    ITTS_REQUIRE((a->epi == ITTS_EPI_STORE || a->epi == ITTS_EPI_GELU_STORE || a->epi == ITTS_EPI_SILU_STORE ||
-                  a->epi == ITTS_EPI_RELU_AFFINE_STORE || a->epi == ITTS_EPI_RELU_AFFINE_TANH_STORE ||
-                  a->epi == ITTS_EPI_RESID_F32) && a->N % ks == 0 && a->y,
-                 "itts_gemm_skinny: a packed y needs the STORE / GELU_STORE / SILU_STORE / RESID_F32 epilogue and N %% %d == 0", ks);
-  const int y_mtp = a->y_mtp > 0 ? a->y_mtp : (a->M + 15) / 16;
-  ITTS_REQUIRE(a->y_row0 >= 0 && a->y_row0 % 16 == 0 && (!a->y_packed || a->y_row0 + a->M <= y_mtp * 16) &&
-                   (a->y_packed || (a->y_row0 == 0 && a->y_mtp == 0)),
-               "itts_gemm_skinny: y_row0 / y_mtp place the rows of a PACKED y inside a taller operand (y_row0 %% 16 == 0)");
-  ITTS_REQUIRE(a->x_mtp == 0 || (a->x_packed && a->x_mtp * 16 >= a->M), "itts_gemm_skinny: x_mtp is for a packed x of at least M rows");
-  if (a->M == 0) return ITTS_OK;
-  ITTS_REQUIRE(a->M <= 96 || a->rows_per_wg == 0 || (a->M + 15) / 16 / (a->rows_per_wg / 16) < 65535, "itts_gemm_skinny: too many rows");
   hipStream_t s = (hipStream_t)stream;
   for (int r0 = 0, rows = 0; r0 < a->M; r0 += rows) {
     const int MTall = skinny_row_tiles(a->dtype, a->M - r0, a->rows_per_wg, &rows);
     SkinnyParams p = skinny_params_of(a, r0, rows, esz, y_mtp, kv_bs_log2);
-    p.post_scale = a->post_scale;
-    p.post_shift = a->post_shift;
     p.ksplit = ksplit;
 #if ITTS_STAMPS
     p.stamps = g_stamp_buf;
@@ -197,7 +109,7 @@ extern "C" int itts_gemm_skinny(const itts_skinny_args* a, void* stream) {
 #endif
     const int rc = by_dtype(a->dtype, "itts_gemm_skinny", [&](auto tag) {
       using T = typename decltype(tag)::type;
-      return launch_skinny<T>(p, plan_skinny<T>(p.N, p.K, p.ksplit, MTall, a->rows_per_wg, a->wide_wg != 0, p.cvec != nullptr), s);
+      return launch_skinny<T>(p, plan_skinny(skinny_walk<T>(p.K), p.N, p.ksplit, MTall, a->rows_per_wg, a->wide_wg != 0, p.cvec != nullptr), s);
     });
     if (rc != ITTS_OK) return rc;
   }
@@ -209,9 +121,8 @@ extern "C" int itts_skinny_plan(int dtype, int M, int N, int K, int ksplit, int 
   int rows;
   const int MTall = skinny_row_tiles(dtype, M, rows_per_wg, &rows);   // (of the first launch, when the rows take several)
   return by_dtype(dtype, "itts_skinny_plan", [&](auto tag) {
-    const SkinnyPlan q = plan_skinny<typename decltype(tag)::type>(N, K, ksplit, MTall, rows_per_wg, wide_wg != 0, fold != 0);
-    out8[0] = q.gx; out8[1] = q.gy; out8[2] = q.NW; out8[3] = q.ntb; out8[4] = q.spw; out8[5] = (int)q.lds; out8[6] = q.gz; out8[7] = q.MT;
-    return ITTS_OK;
+    using T = typename decltype(tag)::type;
+    return skinny_plan_out8(plan_skinny(skinny_walk<T>(K), N, ksplit, MTall, rows_per_wg, wide_wg != 0, fold != 0), out8);
   });
 }
 

@@ -156,7 +156,7 @@ __device__ __forceinline__ F ones_frag() {
 // round for this kernel), SPW = k-steps a wave keeps in registers per pass, MT = 16-row tiles per workgroup (grid.z walks
 // the row tiles of the launch in groups of MT), FOLD = LayerNorm folded into this GEMM (see the head of the file),
 // MAXW = most waves per workgroup (16: the register budget of a 1024-thread workgroup, 128 per lane).
-// W8 = FP8 E4M3 weights (include/indextts_hip_w8.h): a weight block is still 1 KiB and one 16-byte load per lane, but it covers
+// W8 = FP8 E4M3 weights (include/indextts_hip.h): a weight block is still 1 KiB and one 16-byte load per lane, but it covers
 // 64 k -- the lane's fragments of TWO activation k-steps, converted to T in registers in front of the MFMAs.  The K walk (split
 // over the waves, SPW per pass) then counts weight blocks, each with XPS = 2 activation fragments per row tile; the accumulator
 // is multiplied by the column's scale in front of the epilogue.  T is bf16 or f16.
@@ -579,12 +579,148 @@ static int skinny_row_tiles(int dtype, int m, int rows_per_wg, int* rows) {
   return r <= 16 ? 1 : r <= 32 ? 2 : r <= 64 ? 4 : r <= 96 ? 6 : (r + 15) / 16;
 }
 
-// The SkinnyParams of one launch over rows [r0, r0 + rows) of the call `a` (itts_skinny_args or itts_skinny_w8_args: the fields
-// the two share carry the same names): operand and output pointers advanced to the chunk, the packed-layout geometry, the KV append
-// and the folded LayerNorm.  esz = bytes of a T element.  What only one entry point has (split-K, the affine epilogues' vectors,
-// the weight scales, the diagnostic build's words) is set by that entry point.
-template <typename A>
-static SkinnyParams skinny_params_of(const A* a, int r0, int rows, size_t esz, int y_mtp, int kv_bs_log2) {
+#if ITTS_DIAG
+extern int g_tune_ntb, g_tune_nw;   // diagnostic build: itts_debug_set(1|2, v) overrides of the 16-bit / fp32 plan (0 = heuristic)
+#endif
+
+// The K walk of a form: KT steps of the walk's unit (a k-step of KS columns; FP8: a 64-k weight block), and the two register-chunk
+// classes -- steps a wave keeps per pass.  The FP8 classes 3 / 5 blocks are 6 / 10 activation fragments per row tile: the register
+// classes of the 16-bit kernel's 5- and 10-step forms with half the weight registers, so one set of column-tile limits serves both.
+struct SkinnyWalk {
+  int KT, c_lo, c_hi;
+  bool can_fold;   // fp32 has no folded form: the launcher refuses it
+  bool w8;         // no split-K, no 16-wave form
+};
+template <typename T>
+static SkinnyWalk skinny_walk(int K) {
+  return {K / Elem<T>::KS, 5, 10, sizeof(T) == 2, false};
+}
+static SkinnyWalk skinny_walk_w8(int K) {
+  return {(K / 32 + 1) / 2, 3, 5, true, true};
+}
+
+// MTall = 16-row tiles of the launch; rows_per_wg (0 = all of them in every workgroup, else 16 / 32: the row tiles are dealt
+// to grid.z -- more, lighter workgroups for the GEMMs that run WITHOUT split-K); wide: up to 16 waves per workgroup (a hint:
+// ignored by the folded and the FP8 forms, which have no 16-wave instantiation)
+static SkinnyPlan plan_skinny(const SkinnyWalk& w, int N, int ksplit, int MTall, int rows_per_wg, bool wide, bool fold) {
+  fold = fold && w.can_fold;
+  wide = wide && !fold && !w.w8;   // a folded launch never takes 16 waves
+  SkinnyPlan q;
+  int MT = MTall;
+  if (rows_per_wg > 0 && rows_per_wg / 16 < MTall) MT = rows_per_wg / 16;
+  const int gz = (MTall + MT - 1) / MT;
+  const int SB = (w.KT + ksplit - 1) / ksplit;
+  // waves per workgroup: 8 whenever the slice has 8 k-steps (measured: the split-K 3 out-projection, 14 k-steps, takes
+  // 3.8 us with 8 waves x 2 steps against 4.4 us with 3 waves x 5; more than 8 waves change nothing there).  `wide`: 16 waves
+  // when that keeps the slice to ONE pass of <= 10 k-steps per wave (a second pass is a second memory round trip)
+  int NW = SB > 8 ? 8 : SB;
+  if (wide && MT == 1 && SB > 80) NW = 16;
+  if (NW < 1) NW = 1;
+#if ITTS_DIAG
+  if (g_tune_nw > 0 && !w.w8) NW = g_tune_nw > 8 ? 8 : g_tune_nw;
+#endif
+  const int spw = (SB + NW - 1) / NW;
+  const int NT = (N + 15) / 16;
+  int ntb = (NT * ksplit * gz + 255) / 256;   // keep the grid within one round of the 256 CUs
+#if ITTS_DIAG
+  if (g_tune_ntb > 0 && !w.w8) ntb = g_tune_ntb;
+#endif
+  const int SPWc = spw <= w.c_lo ? w.c_lo : w.c_hi;   // register-chunk variant
+  const bool big = SPWc == w.c_hi;
+  const int ntb_max = (fold && MT <= 2 && !big) ? 4 : 3;   // 4 tiles: the folded GEMMs of a many-row step with the rows dealt to grid.z
+  if (ntb > ntb_max) ntb = ntb_max;
+  if (big && ntb > 2) ntb = 2;            // register budget of the big-chunk variant
+  if (MT > 2 && big) ntb = 1;             // 4-6 row tiles with big chunks: accumulators + weight fragments
+  if (NW == 16) ntb = 1;                  // 128 registers per lane
+  if (fold && MT > 2 && ntb > 2) ntb = 2; // the statistics accumulators take 8 registers per row tile
+  q.NW = NW;
+  q.spw = spw;
+  q.ntb = ntb;
+  q.SPWc = SPWc;
+  q.MT = MT;
+  q.gx = (NT + ntb - 1) / ntb;
+  q.gy = ksplit;
+  q.gz = gz;
+  q.lds = (size_t)NW * ntb * MT * 256 * 4 + (fold ? (size_t)NW * MT * 32 * 4 : 0);
+  if (q.lds < 1024) q.lds = 1024;
+  return q;
+}
+
+// the out8 words of itts_skinny_plan / itts_skinny_plan_w8
+static int skinny_plan_out8(const SkinnyPlan& q, int* out8) {
+  out8[0] = q.gx; out8[1] = q.gy; out8[2] = q.NW; out8[3] = q.ntb; out8[4] = q.spw; out8[5] = (int)q.lds; out8[6] = q.gz; out8[7] = q.MT;
+  return ITTS_OK;
+}
+
+// The argument check of itts_gemm_skinny and itts_gemm_skinny_w8 (`who` in every message).  w8: the entry point is built for FP8
+// weights -- it needs w_scale, bf16 / f16 activations, no split-K and one of the decode step's epilogues; the 16-bit entry point
+// refuses w_scale instead.  Out: the split-K factor, the row tiles of a packed y and log2 of the paged cache's block size.
+static int skinny_check(const itts_skinny_args* a, const char* who, bool w8, int* ksplit_out, int* y_mtp_out, int* kv_bs_log2_out) {
+  ITTS_REQUIRE(a && a->wp && a->x, "%s: null args", who);
+  if (w8) {
+    ITTS_REQUIRE(a->w_scale, "%s: w_scale is null", who);
+    ITTS_REQUIRE(a->dtype == ITTS_BF16 || a->dtype == ITTS_F16, "%s: the activation type must be bf16 or f16 (dtype %d)", who, a->dtype);
+    ITTS_REQUIRE(a->ksplit <= 1, "%s: ksplit=%d is not built (the FP8 forms run without split-K)", who, a->ksplit);
+  } else {
+    ITTS_REQUIRE(!a->w_scale, "%s: w_scale is set: FP8 weights go to itts_gemm_skinny_w8", who);
+  }
+  const int ks = a->dtype == ITTS_F32 ? 16 : 32;
+  ITTS_REQUIRE(a->M >= 0 && a->N > 0 && a->K > 0 && a->K % ks == 0, "%s: bad shape M=%d N=%d K=%d (K %% %d != 0)", who, a->M, a->N, a->K, ks);
+  const int ksplit = a->ksplit > 0 ? a->ksplit : 1;
+  ITTS_REQUIRE(ksplit <= a->K / ks && ksplit <= 64, "%s: ksplit=%d too large", who, ksplit);
+  ITTS_REQUIRE(ksplit == 1 || a->epi == ITTS_EPI_SLAB_F32, "%s: ksplit > 1 requires the slab epilogue", who);
+  // (the block size is checked where the table is used: the QKV epilogue)
+  const int kv_bs_log2 = kv_block_log2(a->epi == ITTS_EPI_QKV_CACHE && a->kv_tab != nullptr, a->kv_bs);
+  const bool slab = a->epi == ITTS_EPI_SLAB_F32 && !w8;
+  const bool store = a->epi == ITTS_EPI_STORE || a->epi == ITTS_EPI_GELU_STORE;
+  const bool affine = (a->epi == ITTS_EPI_RELU_AFFINE_STORE || a->epi == ITTS_EPI_RELU_AFFINE_TANH_STORE) && !w8;
+  const bool store_any = store || ((a->epi == ITTS_EPI_SILU_STORE || affine) && !w8);
+  if (a->epi == ITTS_EPI_QKV_CACHE)
+    ITTS_REQUIRE(a->y && a->kcache && a->vcache && a->pos && a->N % 3 == 0 && a->N / 3 == a->heads * 64 &&
+                     (a->kv_tab != nullptr ? kv_bs_log2 >= 0 : a->smax > 0),
+                 "%s: bad QKV epilogue arguments (paged cache: kv_bs must be 16, 32 or 64)", who);
+  else if (a->epi == ITTS_EPI_RESID_F32 || a->epi == ITTS_EPI_STORE_F32 || slab)
+    ITTS_REQUIRE(a->yf, "%s: yf is null", who);
+  else if (w8)
+    ITTS_REQUIRE(store && a->y, "%s: epilogue %d is not built (STORE, GELU_STORE, RESID_F32, QKV_CACHE, STORE_F32)", who, a->epi);
+  else
+    ITTS_REQUIRE(store_any && a->y, "%s: bad epilogue %d", who, a->epi);
+  if (affine) ITTS_REQUIRE(a->post_scale && a->post_shift, "%s: the ReLU + affine epilogues need post_scale and post_shift", who);
+  if (a->epi == ITTS_EPI_RESID_F32)
+    ITTS_REQUIRE(a->N % 4 == 0 && (int64_t)a->M * a->N < (1ll << 29), "%s: the residual epilogue needs N %% 4 == 0", who);
+  if (a->ln_c != nullptr) {
+    const bool ok = a->bias && a->N % 4 == 0 && a->epi != ITTS_EPI_RESID_F32;
+    if (w8)
+      ITTS_REQUIRE(ok, "%s: the LayerNorm-folded form needs bias (= d), N %% 4 == 0, a storing epilogue", who);
+    else
+      ITTS_REQUIRE(ok && ksplit == 1 && a->epi != ITTS_EPI_SLAB_F32 && a->dtype != ITTS_F32,
+                   "%s: the LayerNorm-folded form needs ksplit 1, bias (= d), N %% 4 == 0, a storing epilogue, bf16 / f16", who);
+  }
+  ITTS_REQUIRE(a->rows_per_wg == 0 || a->rows_per_wg == 16 || a->rows_per_wg == 32, "%s: rows_per_wg must be 0, 16 or 32", who);
+  if (a->y_packed) {
+    const bool ok = (store_any || a->epi == ITTS_EPI_RESID_F32) && a->N % ks == 0 && a->y;
+    if (w8)
+      ITTS_REQUIRE(ok, "%s: a packed y needs the STORE / GELU_STORE / RESID_F32 epilogue and N %% 32 == 0", who);
+    else
+      ITTS_REQUIRE(ok, "%s: a packed y needs the STORE / GELU_STORE / SILU_STORE / RESID_F32 epilogue and N %% %d == 0", who, ks);
+  }
+  const int y_mtp = a->y_mtp > 0 ? a->y_mtp : (a->M + 15) / 16;
+  ITTS_REQUIRE(a->y_row0 >= 0 && a->y_row0 % 16 == 0 && (!a->y_packed || a->y_row0 + a->M <= y_mtp * 16) &&
+                   (a->y_packed || (a->y_row0 == 0 && a->y_mtp == 0)),
+               "%s: y_row0 / y_mtp place the rows of a PACKED y inside a taller operand (y_row0 %% 16 == 0)", who);
+  ITTS_REQUIRE(a->x_mtp == 0 || (a->x_packed && a->x_mtp * 16 >= a->M), "%s: x_mtp is for a packed x of at least M rows", who);
+  ITTS_REQUIRE(a->M <= 96 || a->rows_per_wg == 0 || (a->M + 15) / 16 / (a->rows_per_wg / 16) < 65535, "%s: too many rows", who);
+  *ksplit_out = ksplit;
+  *y_mtp_out = y_mtp;
+  *kv_bs_log2_out = kv_bs_log2;
+  return ITTS_OK;
+}
+
+// The SkinnyParams of one launch over rows [r0, r0 + rows) of the call `a`: operand and output pointers advanced to the chunk, the
+// packed-layout geometry, the KV append, the folded LayerNorm and the vectors only some forms read (the affine epilogues', the FP8
+// weight scales: NULL where the entry point refuses or ignores them).  esz = bytes of a T element.  Split-K and the diagnostic
+// build's words are set by the 16-bit entry point.
+static SkinnyParams skinny_params_of(const itts_skinny_args* a, int r0, int rows, size_t esz, int y_mtp, int kv_bs_log2) {
   SkinnyParams p;
   p.M = rows;
   p.N = a->N;
@@ -617,8 +753,9 @@ static SkinnyParams skinny_params_of(const A* a, int r0, int rows, size_t esz, i
   p.cvec = a->ln_c;
   p.ln_eps = a->ln_eps > 0.f ? a->ln_eps : 1e-5f;
   p.bump = r0 == 0 ? a->bump : nullptr;
-  p.post_scale = p.post_shift = nullptr;
-  p.w_scale = nullptr;
+  p.post_scale = a->post_scale;
+  p.post_shift = a->post_shift;
+  p.w_scale = a->w_scale;
 #if ITTS_STAMPS
   p.stamps = nullptr;
 #endif

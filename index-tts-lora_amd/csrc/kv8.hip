@@ -1,4 +1,4 @@
-// FP8 (OCP E4M3) KV cache of the paged sampling loop (include/indextts_hip_kv8.h).
+// FP8 (OCP E4M3) KV cache of the paged sampling loop (include/indextts_hip.h).
 //   attn_decode_kv8 : the decode step's attention over a one-byte paged pool.  It also APPENDS: the step's QKV GEMM stores
 //                     q | k | v row-major (ITTS_EPI_STORE), and the workgroup of a (row, head) quantises that head's new key and
 //                     value, stores the 64 + 64 codes at the write position and attends over the pool's keys plus the new one.

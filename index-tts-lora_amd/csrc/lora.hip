@@ -129,7 +129,7 @@ static int launch_lora_shrink(const LoraShrinkParams& p, int rows, hipStream_t s
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// The same launch over weighted MIXES of bank voices (itts_lora_shrink_mix, include/indextts_hip_mix.h): a row names up to four
+// The same launch over weighted MIXES of bank voices (itts_lora_shrink_mix, include/indextts_hip.h): a row names up to four
 // adapters, the slot of entry j gets w_j s_{a_j} (x A_{a_j}^T).  lora_shrink_kernel's shape with a wave-uniform loop over the
 // record's entries around its K loop: per entry the same pieces, the same rp accumulators, the same butterfly, the same partials
 // in wave order -- so a record {a, 1.0f} gives lora_shrink_kernel's bits for id a (w * s is one fp32 multiply in front of the one
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(LORA_NWV * 64) void lora_shrink_mix_kernel(const vo
 }
 
 template <typename T>
-static int launch_lora_shrink_mix(const itts_lora_shrink_mix_args& a, int x_mtp, int u_mtp, hipStream_t s) {
+static int launch_lora_shrink_mix(const itts_lora_shrink_args& a, int x_mtp, int u_mtp, hipStream_t s) {
   const int rows = a.u_packed ? u_mtp * 16 : a.M;   // the packed tail's padding rows are written too (zeros)
   dim3 grid(rows), block(LORA_NWV * 64);
 #define ITTS_MIX_LAUNCH(NCH)                                                                                                       \
@@ -265,23 +265,35 @@ static int launch_lora_shrink_mix(const itts_lora_shrink_mix_args& a, int x_mtp,
 
 using namespace itts;
 
+// The checks itts_lora_shrink and itts_lora_shrink_mix share (`who` in every message), after the entry point's own null check; the
+// mix adds only the alignment of its records.  Out: the row tiles of a packed x / u.
+template <typename T>
+static int lora_shrink_check(const itts_lora_shrink_args* a, const char* who, bool mix, int* x_mtp_out, int* u_mtp_out) {
+  constexpr int ks = Elem<T>::KS, e = Elem<T>::E;
+  ITTS_REQUIRE(a->M >= 0 && a->K > 0 && a->K % ks == 0, "%s: bad shape M=%d K=%d (K %% %d != 0)", who, a->M, a->K, ks);
+  ITTS_REQUIRE(a->n >= 1 && a->rp >= 16 && a->rp <= 64 && a->rp % 16 == 0,
+               "%s: n=%d adapters of padded rank rp=%d (1 <= n, rank <= 64, rp %% 16 == 0)", who, a->n, a->rp);
+  ITTS_REQUIRE(a->Kx <= 512 && a->Kx == ((int64_t)a->n * a->rp + 31) / 32 * 32,
+               "%s: Kx=%d must be n * rp rounded up to a multiple of 32, and <= 512", who, a->Kx);
+  const int mtp = (a->M + 15) / 16;
+  const int x_mtp = a->x_mtp > 0 ? a->x_mtp : mtp, u_mtp = a->u_mtp > 0 ? a->u_mtp : mtp;
+  ITTS_REQUIRE((a->x_packed || a->x_mtp == 0) && x_mtp * 16 >= a->M, "%s: x_mtp is for a packed x of at least M rows", who);
+  ITTS_REQUIRE((a->u_packed || a->u_mtp == 0) && u_mtp * 16 >= a->M, "%s: u_mtp is for a packed u of at least M rows", who);
+  ITTS_REQUIRE(a->u_packed || (a->ldu >= a->Kx && a->ldu % e == 0), "%s: a row-major u needs ldu >= Kx, ldu %% %d == 0", who, e);
+  ITTS_REQUIRE(((uintptr_t)a->x & 15) == 0 && ((uintptr_t)a->u & 15) == 0 && ((uintptr_t)a->a_bank & 15) == 0 &&
+                   (!mix || ((uintptr_t)a->mix & 15) == 0),
+               mix ? "%s: x, u, a_bank and mix must be 16-byte aligned" : "%s: x, u and a_bank must be 16-byte aligned", who);
+  *x_mtp_out = x_mtp;
+  *u_mtp_out = u_mtp;
+  return ITTS_OK;
+}
+
 extern "C" int itts_lora_shrink(const itts_lora_shrink_args* a, void* stream) {
   ITTS_REQUIRE(a && a->x && a->ids && a->a_bank && a->u, "itts_lora_shrink: null args");
   return by_dtype(a->dtype, "itts_lora_shrink", [&](auto tag) {
     using T = typename decltype(tag)::type;
-    constexpr int ks = Elem<T>::KS, e = Elem<T>::E;
-    ITTS_REQUIRE(a->M >= 0 && a->K > 0 && a->K % ks == 0, "itts_lora_shrink: bad shape M=%d K=%d (K %% %d != 0)", a->M, a->K, ks);
-    ITTS_REQUIRE(a->n >= 1 && a->rp >= 16 && a->rp <= 64 && a->rp % 16 == 0,
-                 "itts_lora_shrink: n=%d adapters of padded rank rp=%d (1 <= n, rank <= 64, rp %% 16 == 0)", a->n, a->rp);
-    ITTS_REQUIRE(a->Kx <= 512 && a->Kx == ((int64_t)a->n * a->rp + 31) / 32 * 32,
-                 "itts_lora_shrink: Kx=%d must be n * rp rounded up to a multiple of 32, and <= 512", a->Kx);
-    const int mtp = (a->M + 15) / 16;
-    const int x_mtp = a->x_mtp > 0 ? a->x_mtp : mtp, u_mtp = a->u_mtp > 0 ? a->u_mtp : mtp;
-    ITTS_REQUIRE((a->x_packed || a->x_mtp == 0) && x_mtp * 16 >= a->M, "itts_lora_shrink: x_mtp is for a packed x of at least M rows");
-    ITTS_REQUIRE((a->u_packed || a->u_mtp == 0) && u_mtp * 16 >= a->M, "itts_lora_shrink: u_mtp is for a packed u of at least M rows");
-    ITTS_REQUIRE(a->u_packed || (a->ldu >= a->Kx && a->ldu % e == 0), "itts_lora_shrink: a row-major u needs ldu >= Kx, ldu %% %d == 0", e);
-    ITTS_REQUIRE(((uintptr_t)a->x & 15) == 0 && ((uintptr_t)a->u & 15) == 0 && ((uintptr_t)a->a_bank & 15) == 0,
-                 "itts_lora_shrink: x, u and a_bank must be 16-byte aligned");
+    int x_mtp, u_mtp;
+    if (int rc = lora_shrink_check<T>(a, "itts_lora_shrink", false, &x_mtp, &u_mtp)) return rc;
     if (a->M == 0) return ITTS_OK;
     LoraShrinkParams p;
     p.x = a->x;
@@ -303,24 +315,12 @@ extern "C" int itts_lora_shrink(const itts_lora_shrink_args* a, void* stream) {
   });
 }
 
-extern "C" int itts_lora_shrink_mix(const itts_lora_shrink_mix_args* a, void* stream) {
+extern "C" int itts_lora_shrink_mix(const itts_lora_shrink_args* a, void* stream) {
   ITTS_REQUIRE(a && a->x && a->mix && a->a_bank && a->u, "itts_lora_shrink_mix: null args");
   return by_dtype(a->dtype, "itts_lora_shrink_mix", [&](auto tag) {
     using T = typename decltype(tag)::type;
-    constexpr int ks = Elem<T>::KS, e = Elem<T>::E;
-    ITTS_REQUIRE(a->M >= 0 && a->K > 0 && a->K % ks == 0, "itts_lora_shrink_mix: bad shape M=%d K=%d (K %% %d != 0)", a->M, a->K, ks);
-    ITTS_REQUIRE(a->n >= 1 && a->rp >= 16 && a->rp <= 64 && a->rp % 16 == 0,
-                 "itts_lora_shrink_mix: n=%d adapters of padded rank rp=%d (1 <= n, rank <= 64, rp %% 16 == 0)", a->n, a->rp);
-    ITTS_REQUIRE(a->Kx <= 512 && a->Kx == ((int64_t)a->n * a->rp + 31) / 32 * 32,
-                 "itts_lora_shrink_mix: Kx=%d must be n * rp rounded up to a multiple of 32, and <= 512", a->Kx);
-    const int mtp = (a->M + 15) / 16;
-    const int x_mtp = a->x_mtp > 0 ? a->x_mtp : mtp, u_mtp = a->u_mtp > 0 ? a->u_mtp : mtp;
-    ITTS_REQUIRE((a->x_packed || a->x_mtp == 0) && x_mtp * 16 >= a->M, "itts_lora_shrink_mix: x_mtp is for a packed x of at least M rows");
-    ITTS_REQUIRE((a->u_packed || a->u_mtp == 0) && u_mtp * 16 >= a->M, "itts_lora_shrink_mix: u_mtp is for a packed u of at least M rows");
-    ITTS_REQUIRE(a->u_packed || (a->ldu >= a->Kx && a->ldu % e == 0), "itts_lora_shrink_mix: a row-major u needs ldu >= Kx, ldu %% %d == 0", e);
-    ITTS_REQUIRE(((uintptr_t)a->x & 15) == 0 && ((uintptr_t)a->u & 15) == 0 && ((uintptr_t)a->a_bank & 15) == 0 &&
-                     ((uintptr_t)a->mix & 15) == 0,
-                 "itts_lora_shrink_mix: x, u, a_bank and mix must be 16-byte aligned");
+    int x_mtp, u_mtp;
+    if (int rc = lora_shrink_check<T>(a, "itts_lora_shrink_mix", true, &x_mtp, &u_mtp)) return rc;
     if (a->M == 0) return ITTS_OK;
     return launch_lora_shrink_mix<T>(*a, x_mtp, u_mtp, (hipStream_t)stream);
   });

@@ -1,4 +1,4 @@
-// The join of continuous batching (itts_refill_join, include/indextts_hip_refill.h): the staged keys / values of the utterances
+// The join of continuous batching (itts_refill_join, include/indextts_hip.h): the staged keys / values of the utterances
 // that take freed decode slots go into the KV cache, and the entering rows' state -- first token, stop step, own clock, left
 // padding, voice record -- into the per-slot tables the captured decode step reads.  One launch between two graph replays, in
 // the place of two advanced-index scatters and seven small indexed writes.

@@ -439,9 +439,8 @@ __global__ __launch_bounds__(256) void sample_kernel(SAMPLE_LEAD_PARAMS, SampleT
 
 using namespace itts;
 
-// What both argument structs share (same field names), checked and copied once.
-template <class Args>
-static int common_params(const Args* a, const char* who, SampleParams& p) {
+// What itts_sample and itts_sample_rows share, checked and copied once.
+static int common_params(const itts_sample_args* a, const char* who, SampleParams& p) {
   ITTS_REQUIRE(a && a->logits && a->tokens && a->history && a->finished && a->state, "%s: null pointer", who);
   ITTS_REQUIRE(a->B > 0 && a->V > 0 && a->V <= SM_MAXV && a->ldl >= a->V, "%s: bad shape B=%d V=%d (max %d)", who, a->B, a->V, SM_MAXV);
   p = SampleParams{};
@@ -470,6 +469,7 @@ static int common_params(const Args* a, const char* who, SampleParams& p) {
 extern "C" int itts_sample(const itts_sample_args* a, void* stream) {
   SampleParams p;
   if (int rc = common_params(a, "itts_sample", p)) return rc;
+  ITTS_REQUIRE(a->rows == nullptr, "itts_sample: rows is set: per-row settings go to itts_sample_rows");
   ITTS_REQUIRE(a->rep_penalty > 0.f && a->temperature > 0.f, "itts_sample: rep_penalty/temperature must be positive");
   ITTS_REQUIRE(a->top_k <= SM_MAXC, "itts_sample: top_k=%d exceeds %d", a->top_k, SM_MAXC);
   // the candidate store holds SM_MAXC entries: sampling from the whole vocabulary (top-k disabled) would be truncated to
@@ -490,7 +490,7 @@ extern "C" int itts_sample(const itts_sample_args* a, void* stream) {
 static_assert(sizeof(itts_sample_row) == 32 && offsetof(itts_sample_row, seed) == 16 && offsetof(itts_sample_row, do_sample) == 28,
               "itts_sample_row is read as two 16-byte words");
 
-extern "C" int itts_sample_rows(const itts_sample_rows_args* a, void* stream) {
+extern "C" int itts_sample_rows(const itts_sample_args* a, void* stream) {
   SampleParams p;
   if (int rc = common_params(a, "itts_sample_rows", p)) return rc;
   // the records are device data: their VALUES are the caller's to check before the upload (the kernel clamps what could

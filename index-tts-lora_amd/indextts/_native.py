@@ -32,17 +32,7 @@ class SkinnyArgs(C.Structure):
                 ("smax", C.c_int), ("ksplit", C.c_int), ("ln_c", C.c_void_p), ("ln_eps", C.c_float), ("bump", C.c_void_p),
                 ("rows_per_wg", C.c_int), ("wide_wg", C.c_int), ("kv_tab", C.c_void_p), ("kv_bs", C.c_int),
                 ("x_packed", C.c_int), ("y_packed", C.c_int), ("y_row0", C.c_int), ("y_mtp", C.c_int), ("x_mtp", C.c_int),
-                ("post_scale", C.c_void_p), ("post_shift", C.c_void_p)]
-
-
-class SkinnyW8Args(C.Structure):
-    """itts_skinny_w8_args (include/indextts_hip_w8.h)."""
-    _fields_ = [("dtype", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("wp", C.c_void_p), ("w_scale", C.c_void_p),
-                ("bias", C.c_void_p), ("x", C.c_void_p), ("epi", C.c_int), ("y", C.c_void_p), ("yf", C.c_void_p),
-                ("kcache", C.c_void_p), ("vcache", C.c_void_p), ("pos", C.c_void_p), ("heads", C.c_int), ("smax", C.c_int),
-                ("ksplit", C.c_int), ("ln_c", C.c_void_p), ("ln_eps", C.c_float), ("bump", C.c_void_p), ("rows_per_wg", C.c_int),
-                ("kv_tab", C.c_void_p), ("kv_bs", C.c_int), ("x_packed", C.c_int), ("y_packed", C.c_int), ("y_row0", C.c_int),
-                ("y_mtp", C.c_int), ("x_mtp", C.c_int)]
+                ("post_scale", C.c_void_p), ("post_shift", C.c_void_p), ("w_scale", C.c_void_p)]
 
 
 class MhaArgs(C.Structure):
@@ -52,7 +42,7 @@ class MhaArgs(C.Structure):
 
 
 class SegTableArgs(C.Structure):
-    """itts_seg_table (include/indextts_hip_prompts.h)."""
+    """itts_seg_table (include/indextts_hip.h)."""
     _fields_ = [("dev", C.c_void_p), ("host", C.c_void_p), ("nseg", C.c_int), ("ntiles", C.c_int)]
 
 
@@ -75,7 +65,7 @@ class LnReduceArgs(C.Structure):
 class LoraShrinkArgs(C.Structure):
     _fields_ = [("dtype", C.c_int), ("M", C.c_int), ("K", C.c_int), ("x", C.c_void_p), ("x_packed", C.c_int), ("x_mtp", C.c_int),
                 ("ids", C.c_void_p), ("a_bank", C.c_void_p), ("n", C.c_int), ("rp", C.c_int), ("Kx", C.c_int), ("u", C.c_void_p),
-                ("u_packed", C.c_int), ("u_mtp", C.c_int), ("ldu", C.c_int64)]
+                ("u_packed", C.c_int), ("u_mtp", C.c_int), ("ldu", C.c_int64), ("mix", C.c_void_p)]
 
 
 class LoraMixEntry(C.Structure):
@@ -87,19 +77,12 @@ LORA_MIX_ROW_BYTES = 32
 
 
 class LoraMixRow(C.Structure):
-    """itts_lora_mix_row: one row's weighted mix of bank voices, 32 bytes (include/indextts_hip_mix.h)."""
+    """itts_lora_mix_row: one row's weighted mix of bank voices, 32 bytes (include/indextts_hip.h)."""
     _fields_ = [("e", LoraMixEntry * LORA_MIX_ENTRIES)]
 
 
-class LoraShrinkMixArgs(C.Structure):
-    """itts_lora_shrink_mix_args: LoraShrinkArgs with the records' pointer in the place of the ids'."""
-    _fields_ = [("dtype", C.c_int), ("M", C.c_int), ("K", C.c_int), ("x", C.c_void_p), ("x_packed", C.c_int), ("x_mtp", C.c_int),
-                ("mix", C.c_void_p), ("a_bank", C.c_void_p), ("n", C.c_int), ("rp", C.c_int), ("Kx", C.c_int), ("u", C.c_void_p),
-                ("u_packed", C.c_int), ("u_mtp", C.c_int), ("ldu", C.c_int64)]
-
-
 class RefillJoinArgs(C.Structure):
-    """itts_refill_join_args (include/indextts_hip_refill.h)."""
+    """itts_refill_join_args (include/indextts_hip.h)."""
     _fields_ = [("dtype", C.c_int), ("M", C.c_int), ("L", C.c_int), ("H", C.c_int), ("kst", C.c_void_p), ("vst", C.c_void_p),
                 ("kc", C.c_void_p), ("vc", C.c_void_p), ("s_l", C.c_int64), ("s_b", C.c_int64), ("s_h", C.c_int64), ("s_p", C.c_int64),
                 ("n_b", C.c_int), ("n_p", C.c_int), ("i_b", C.c_void_p), ("i_p", C.c_void_p), ("k", C.c_int), ("n_slots", C.c_int),
@@ -124,20 +107,13 @@ class SampleArgs(C.Structure):
                 ("extra_ids", C.c_void_p), ("n_extra", C.c_int), ("force_stop", C.c_void_p),
                 ("rep_penalty", C.c_float), ("temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_int),
                 ("do_sample", C.c_int), ("seed", C.c_uint64), ("stop_token", C.c_int), ("dbg_scores", C.c_void_p),
-                ("no_advance", C.c_int), ("row_step0", C.c_void_p)]
+                ("no_advance", C.c_int), ("row_step0", C.c_void_p), ("rows", C.c_void_p)]
 
 
 class SampleRow(C.Structure):
     """itts_sample_row: one row's sampling settings, 32 bytes (include/indextts_hip.h)."""
     _fields_ = [("rep_penalty", C.c_float), ("temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_int32),
                 ("seed", C.c_uint64), ("stream", C.c_uint32), ("do_sample", C.c_int32)]
-
-
-class SampleRowsArgs(C.Structure):
-    _fields_ = [("logits", C.c_void_p), ("B", C.c_int), ("V", C.c_int), ("ldl", C.c_int), ("tokens", C.c_void_p),
-                ("history", C.c_void_p), ("hist_cap", C.c_int), ("finished", C.c_void_p), ("state", C.c_void_p),
-                ("extra_ids", C.c_void_p), ("n_extra", C.c_int), ("force_stop", C.c_void_p), ("rows", C.c_void_p),
-                ("stop_token", C.c_int), ("dbg_scores", C.c_void_p), ("no_advance", C.c_int), ("row_step0", C.c_void_p)]
 
 
 class BeamArgs(C.Structure):
@@ -207,55 +183,31 @@ _SIGNATURES = {
                                      C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "itts_prefix_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-}
-
-# include/indextts_hip_rows.h: the entry points whose per-row settings are a device table
-_ROW_SIGNATURES = {
-    "itts_sample_rows": (C.c_int, [C.POINTER(SampleRowsArgs), C.c_void_p]),
-}
-
-# include/indextts_hip_w8.h: the FP8 (E4M3) weight-only forms of the skinny GEMM
-_W8_SIGNATURES = {
+    # the entry points whose per-row settings are a device table
+    "itts_sample_rows": (C.c_int, [C.POINTER(SampleArgs), C.c_void_p]),
+    # the FP8 (E4M3) weight-only forms of the skinny GEMM
     "itts_packed_bytes_w8": (C.c_int64, [C.c_int, C.c_int]),
     "itts_pack_weight_w8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    "itts_gemm_skinny_w8": (C.c_int, [C.POINTER(SkinnyW8Args), C.c_void_p]),
+    "itts_gemm_skinny_w8": (C.c_int, [C.POINTER(SkinnyArgs), C.c_void_p]),
     "itts_skinny_plan_w8": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
-}
-
-# include/indextts_hip_kv8.h: the FP8 (E4M3) KV cache of the paged sampling loop
-_KV8_SIGNATURES = {
+    # the FP8 (E4M3) KV cache of the paged sampling loop
     "itts_attn_decode_kv8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                        C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "itts_kv8_store": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                  C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
-}
-
-# include/indextts_hip_prompts.h: the sequence-mixing launches of the prompt front-end over N prompts at once
-_PROMPT_SIGNATURES = {
+    # the sequence-mixing launches of the prompt front-end over N prompts at once
     "itts_subsample_conv_seg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SegTableArgs), C.c_int, C.c_int,
                                           C.c_int, C.c_int, C.c_void_p]),
     "itts_mha_small_seg": (C.c_int, [C.POINTER(MhaArgs), C.POINTER(SegTableArgs), C.c_int, C.c_void_p]),
     "itts_glu_dwconv_ln_silu_seg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.POINTER(SegTableArgs), C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]),
-}
-
-# include/indextts_hip_mix.h: the adapter bank's shrink launch over weighted mixes of voices
-_MIX_SIGNATURES = {
-    "itts_lora_shrink_mix": (C.c_int, [C.POINTER(LoraShrinkMixArgs), C.c_void_p]),
-}
-
-# include/indextts_hip_refill.h: the join of continuous batching (staged rows and their voices enter a running loop)
-_REFILL_SIGNATURES = {
+    # the adapter bank's shrink launch over weighted mixes of voices
+    "itts_lora_shrink_mix": (C.c_int, [C.POINTER(LoraShrinkArgs), C.c_void_p]),
+    # the join of continuous batching (staged rows and their voices enter a running loop)
     "itts_refill_join": (C.c_int, [C.POINTER(RefillJoinArgs), C.c_void_p]),
 }
 
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)          # what include/indextts_hip.h declares itself
-ROW_SYMBOLS = tuple(_ROW_SIGNATURES)           # what include/indextts_hip_rows.h declares
-W8_SYMBOLS = tuple(_W8_SIGNATURES)             # what include/indextts_hip_w8.h declares
-KV8_SYMBOLS = tuple(_KV8_SIGNATURES)           # what include/indextts_hip_kv8.h declares
-PROMPT_SYMBOLS = tuple(_PROMPT_SIGNATURES)     # what include/indextts_hip_prompts.h declares
-MIX_SYMBOLS = tuple(_MIX_SIGNATURES)           # what include/indextts_hip_mix.h declares
-REFILL_SYMBOLS = tuple(_REFILL_SIGNATURES)     # what include/indextts_hip_refill.h declares
+EXPORTED_SYMBOLS = tuple(_SIGNATURES)          # every entry point include/indextts_hip.h declares
 _lib = None
 
 
@@ -268,12 +220,11 @@ def lib():
             raise NativeError(f"{path} not found: build it with `make -C index-tts-lora_amd/csrc` "
                               f"(or python -c 'import __graft_entry__ as g; g.build()'). There is no fallback path.")
         L = C.CDLL(path)
-        for name, (res, args) in {**_SIGNATURES, **_ROW_SIGNATURES, **_W8_SIGNATURES, **_KV8_SIGNATURES, **_PROMPT_SIGNATURES,
-                                       **_MIX_SIGNATURES, **_REFILL_SIGNATURES}.items():
+        for name, (res, args) in _SIGNATURES.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
-        if L.itts_abi_version() != 9:
+        if L.itts_abi_version() != 10:
             raise NativeError("libindextts_hip.so ABI version mismatch")
         _lib = L
     return _lib
@@ -371,12 +322,13 @@ def aa_snake(x, alpha_log, beta_log, up_f, down_f, layout=0, out=None, valid_row
 
 def gemm_skinny(dtype, M, N, K, wp, bias=None, x=None, epi=EPI_STORE, y=None, yf=None, kcache=None, vcache=None, pos=None,
                 heads=0, smax=0, ksplit=1, x_packed=False, y_packed=False, ln_c=None, ln_eps=1e-5, bump=None, rows_per_wg=0,
-                wide_wg=False, kv_tab=None, kv_bs=0, y_row0=0, y_mtp=0, x_mtp=0, post=None):
+                wide_wg=False, kv_tab=None, kv_bs=0, y_row0=0, y_mtp=0, x_mtp=0, post=None, w_scale=None):
     """ln_c fp32 [N]: LayerNorm folded into the GEMM -- x holds the RAW rows, wp = pack(gamma . W), bias = beta W + b
     (see itts_skinny_args).  EPI_RESID_F32: yf += x W + bias, and y (optional, T) receives a copy of the new rows.
     bump: int32 device word the launch increments.  rows_per_wg / wide_wg: launch-geometry hints.
     y_row0 / y_mtp: a packed y's rows land at [y_row0, y_row0 + M) of an operand of y_mtp row tiles; x_mtp: a packed x is the
-    first M rows of an operand of x_mtp row tiles.  post = (scale, shift) fp32 [N]: the EPI_RELU_AFFINE_* epilogues."""
+    first M rows of an operand of x_mtp row tiles.  post = (scale, shift) fp32 [N]: the EPI_RELU_AFFINE_* epilogues.
+    w_scale fp32 [N]: wp = pack_weight_w8(codes), FP8 weights -- the launch goes to itts_gemm_skinny_w8 (see gemm_skinny_w8)."""
     a = SkinnyArgs()
     a.dtype, a.M, a.N, a.K = dt(dtype), M, N, K
     a.wp, a.bias, a.x = _p(wp), _p(bias), _p(x)
@@ -389,12 +341,16 @@ def gemm_skinny(dtype, M, N, K, wp, bias=None, x=None, epi=EPI_STORE, y=None, yf
     a.y_row0, a.y_mtp, a.x_mtp = int(y_row0), int(y_mtp), int(x_mtp)
     if post is not None:
         a.post_scale, a.post_shift = _p(post[0]), _p(post[1])
-    _check(lib().itts_gemm_skinny(C.byref(a), _stream()), "itts_gemm_skinny")
+    if w_scale is None:
+        _check(lib().itts_gemm_skinny(C.byref(a), _stream()), "itts_gemm_skinny")
+    else:
+        a.w_scale = _p(w_scale)
+        _check(lib().itts_gemm_skinny_w8(C.byref(a), _stream()), "itts_gemm_skinny_w8")
 
 
 def pack_weight_w8(codes: torch.Tensor) -> torch.Tensor:
     """codes uint8 [K, N] (device; E4M3 codes of utils/quant.quantize_e4m3_cols) -> the packed FP8 weight image
-    (include/indextts_hip_w8.h: 1-KiB blocks of 16 columns x 64 k)."""
+    (include/indextts_hip.h: 1-KiB blocks of 16 columns x 64 k)."""
     codes = codes.contiguous()
     _dev(codes)
     if codes.dtype != torch.uint8 or codes.dim() != 2:
@@ -405,30 +361,25 @@ def pack_weight_w8(codes: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def gemm_skinny_w8(dtype, M, N, K, wp, w_scale, bias=None, x=None, epi=EPI_STORE, y=None, yf=None, kcache=None, vcache=None,
-                   pos=None, heads=0, smax=0, ksplit=1, x_packed=False, y_packed=False, ln_c=None, ln_eps=1e-5, bump=None,
-                   rows_per_wg=0, kv_tab=None, kv_bs=0, y_row0=0, y_mtp=0, x_mtp=0):
+def gemm_skinny_w8(dtype, M, N, K, wp, w_scale, *args, **kw):
     """gemm_skinny over FP8 weights: wp = pack_weight_w8(codes), w_scale fp32 [N]; the accumulator is scaled per column in front
-    of the epilogue.  dtype: the activation type (bf16 / f16).  ln_c = w_scale * column sums of the decoded codes (folded form)."""
-    a = SkinnyW8Args()
-    a.dtype, a.M, a.N, a.K = dt(dtype), M, N, K
-    a.wp, a.w_scale, a.bias, a.x = _p(wp), _p(w_scale), _p(bias), _p(x)
-    a.epi, a.y, a.yf = epi, _p(y), _p(yf)
-    a.kcache, a.vcache, a.pos, a.heads, a.smax, a.ksplit = _p(kcache), _p(vcache), _p(pos), heads, smax, ksplit
-    a.x_packed, a.y_packed = int(bool(x_packed)), int(bool(y_packed))
-    a.ln_c, a.ln_eps, a.bump = _p(ln_c), float(ln_eps), _p(bump)
-    a.rows_per_wg = int(rows_per_wg)
-    a.kv_tab, a.kv_bs = _p(kv_tab), int(kv_bs)
-    a.y_row0, a.y_mtp, a.x_mtp = int(y_row0), int(y_mtp), int(x_mtp)
-    _check(lib().itts_gemm_skinny_w8(C.byref(a), _stream()), "itts_gemm_skinny_w8")
+    of the epilogue.  dtype: the activation type (bf16 / f16).  ln_c = w_scale * column sums of the decoded codes (folded form).
+    The other arguments are gemm_skinny's (wide_wg is ignored: there is no 16-wave FP8 form)."""
+    if w_scale is None:
+        raise NativeError("itts_gemm_skinny_w8 failed (code 1): itts_gemm_skinny_w8: w_scale is null")
+    gemm_skinny(dtype, M, N, K, wp, *args, w_scale=w_scale, **kw)
+
+
+def _plan_dict(out) -> dict:
+    return dict(grid=(out[0], out[1], out[6]), waves=out[2], tiles_per_wg=out[3], ksteps_per_wave=out[4], lds=out[5],
+                row_tiles_per_wg=out[7])
 
 
 def skinny_plan_w8(dtype, M, N, K, rows_per_wg=0, fold=False) -> dict:
     """Launch geometry itts_gemm_skinny_w8 would use (host-only); ksteps_per_wave counts 64-k weight blocks."""
     out = (C.c_int * 8)()
     _check(lib().itts_skinny_plan_w8(dt(dtype), M, N, K, int(rows_per_wg), int(bool(fold)), out), "itts_skinny_plan_w8")
-    return dict(grid=(out[0], out[1], out[6]), waves=out[2], tiles_per_wg=out[3], ksteps_per_wave=out[4], lds=out[5],
-                row_tiles_per_wg=out[7])
+    return _plan_dict(out)
 
 
 def subsample_conv(mel, w, b, y):
@@ -439,15 +390,20 @@ def subsample_conv(mel, w, b, y):
     return y
 
 
-def mha_small(q, k, v, out, Tq, Tk, H, q_stride, k_stride, v_stride, out_mtp, scale, pos=None, bias_u=None, bias_v=None):
-    """Short-sequence attention (head dim 64) into the packed layout; pos / bias_u / bias_v: the Conformer's relative-position term.
-    q / k / v may be views into one buffer (pointer + row stride in elements)."""
+def _mha_args(q, k, v, out, Tq, Tk, H, q_stride, k_stride, v_stride, out_mtp, scale, pos, bias_u, bias_v):
     a = MhaArgs()
     a.dtype, a.Tq, a.Tk, a.H = dt(out.dtype), Tq, Tk, H
     a.q, a.k, a.v = _p(q), _p(k), _p(v)
     a.q_stride, a.k_stride, a.v_stride = q_stride, k_stride, v_stride
     a.pos, a.bias_u, a.bias_v = _p(pos), _p(bias_u), _p(bias_v)
     a.scale, a.out, a.out_mtp = float(scale), _p(out), int(out_mtp)
+    return a
+
+
+def mha_small(q, k, v, out, Tq, Tk, H, q_stride, k_stride, v_stride, out_mtp, scale, pos=None, bias_u=None, bias_v=None):
+    """Short-sequence attention (head dim 64) into the packed layout; pos / bias_u / bias_v: the Conformer's relative-position term.
+    q / k / v may be views into one buffer (pointer + row stride in elements)."""
+    a = _mha_args(q, k, v, out, Tq, Tk, H, q_stride, k_stride, v_stride, out_mtp, scale, pos, bias_u, bias_v)
     _check(lib().itts_mha_small(C.byref(a), _stream()), "itts_mha_small")
     return out
 
@@ -461,7 +417,7 @@ def glu_dwconv_ln_silu(x, w, b, ln_w, ln_b, y, T, Cn, y_mtp, eps=1e-5):
 
 
 def seg_words(records, ntiles, tile_map=None) -> torch.Tensor:
-    """The words of a segment table (include/indextts_hip_prompts.h) as a host int32 tensor: one record of up to SEG_WORDS ints
+    """The words of a segment table (include/indextts_hip.h) as a host int32 tensor: one record of up to SEG_WORDS ints
     per segment (row0, len, ...; missing words are 0), then the segment of every 16-row tile of the row space (-1: none).
     tile_map: given instead of derived (the derived map names, per tile, the last segment whose rows touch it)."""
     recs = [list(map(int, r)) + [0] * (SEG_WORDS - len(r)) for r in records]
@@ -500,12 +456,7 @@ def mha_small_seg(q, k, v, out, q_rows, kv_rows, H, q_stride, k_stride, v_stride
                   bias_v=None, pos_tk=0):
     """mha_small over the segments of `tab`: q / k / v point at row 0 of their row spaces of q_rows / kv_rows rows; pos T
     [H, pos_tk, 64] is indexed by the key's index within its segment."""
-    a = MhaArgs()
-    a.dtype, a.Tq, a.Tk, a.H = dt(out.dtype), q_rows, kv_rows, H
-    a.q, a.k, a.v = _p(q), _p(k), _p(v)
-    a.q_stride, a.k_stride, a.v_stride = q_stride, k_stride, v_stride
-    a.pos, a.bias_u, a.bias_v = _p(pos), _p(bias_u), _p(bias_v)
-    a.scale, a.out, a.out_mtp = float(scale), _p(out), int(out_mtp)
+    a = _mha_args(q, k, v, out, q_rows, kv_rows, H, q_stride, k_stride, v_stride, out_mtp, scale, pos, bias_u, bias_v)
     _check(lib().itts_mha_small_seg(C.byref(a), C.byref(tab.args), int(pos_tk), _stream()), "itts_mha_small_seg")
     return out
 
@@ -609,8 +560,7 @@ def skinny_plan(dtype, M, N, K, ksplit=1, rows_per_wg=0, wide_wg=False, fold=Fal
     out = (C.c_int * 8)()
     _check(lib().itts_skinny_plan(dt(dtype), M, N, K, ksplit, int(rows_per_wg), int(bool(wide_wg)), int(bool(fold)), out),
            "itts_skinny_plan")
-    return dict(grid=(out[0], out[1], out[6]), waves=out[2], tiles_per_wg=out[3], ksteps_per_wave=out[4], lds=out[5],
-                row_tiles_per_wg=out[7])
+    return _plan_dict(out)
 
 
 def gemm_conv(dtype, B, Tin, Tout, Cin, N, wp, x, y, taps=1, off0=0, dil=1, x_bstride=None, bias=None, bias2=None,
@@ -666,23 +616,33 @@ def lora_kx(n: int, rp: int) -> int:
     return (n * rp + 31) // 32 * 32
 
 
-def lora_shrink(x, ids, a_bank, u, M, K, x_packed=False, x_mtp=0, u_packed=False, u_mtp=0, ldu=0):
+def lora_shrink(x, ids, a_bank, u, M, K, x_packed=False, x_mtp=0, u_packed=False, u_mtp=0, ldu=0, mix=None):
     """The shrink half of the per-row LoRA adapter bank (itts_lora_shrink): u[m][ids[m] * rp + j] = x[m] . a_bank[ids[m]][j], every
     other column of u[m][:Kx] zero.  x T [M, K] (row-major or packed), ids int32 [M] on the device (-1 = no adapter), a_bank T
     [n, rp, K]; u: the packed operand's tail (u_packed: a tensor that starts at the first appended block) or row-major with the
-    leading dimension ldu (a view that starts at the row's first extra column)."""
-    _dev(ids, a_bank)
-    if ids.dtype != torch.int32 or ids.numel() < M:
-        raise NativeError("itts_lora_shrink: ids must be int32 [M]")
+    leading dimension ldu (a view that starts at the row's first extra column).
+    mix (instead of ids, which is then None): the launch over weighted mixes, itts_lora_shrink_mix (see lora_shrink_mix)."""
+    if (ids is None) == (mix is None):
+        raise ValueError("lora_shrink takes ids or mix, one of them")
+    if mix is None:
+        who, fn = "itts_lora_shrink", lib().itts_lora_shrink
+        _dev(ids, a_bank)
+        if ids.dtype != torch.int32 or ids.numel() < M:
+            raise NativeError("itts_lora_shrink: ids must be int32 [M]")
+    else:
+        who, fn = "itts_lora_shrink_mix", lib().itts_lora_shrink_mix
+        _dev(mix, a_bank)
+        if mix.dtype != torch.uint8 or mix.numel() < M * LORA_MIX_ROW_BYTES:
+            raise NativeError("itts_lora_shrink_mix: mix must be a uint8 device tensor of M 32-byte records")
     n, rp, Ka = a_bank.shape
     if Ka != K or a_bank.dtype != x.dtype or u.dtype != x.dtype:
-        raise NativeError("itts_lora_shrink: a_bank must be T [n, rp, K] of the operand's type")
+        raise NativeError(f"{who}: a_bank must be T [n, rp, K] of the operand's type")
     a = LoraShrinkArgs()
     a.dtype, a.M, a.K = dt(x.dtype), int(M), int(K)
     a.x, a.x_packed, a.x_mtp = _p(x), int(bool(x_packed)), int(x_mtp)
-    a.ids, a.a_bank, a.n, a.rp, a.Kx = _p(ids), _p(a_bank), n, rp, lora_kx(n, rp)
+    a.ids, a.mix, a.a_bank, a.n, a.rp, a.Kx = _p(ids), _p(mix), _p(a_bank), n, rp, lora_kx(n, rp)
     a.u, a.u_packed, a.u_mtp, a.ldu = _p(u), int(bool(u_packed)), int(u_mtp), int(ldu)
-    _check(lib().itts_lora_shrink(C.byref(a), _stream()), "itts_lora_shrink")
+    _check(fn(C.byref(a), _stream()), who)
 
 
 def pack_lora_mix(mixes):
@@ -737,23 +697,12 @@ def refill_join(kst, vst, kc, vc, i_b, i_p, rows, tok, fin, stops, pads, step0, 
     _check(lib().itts_refill_join(C.byref(a), _stream()), "itts_refill_join")
 
 
-def lora_shrink_mix(x, mix, a_bank, u, M, K, x_packed=False, x_mtp=0, u_packed=False, u_mtp=0, ldu=0):
+def lora_shrink_mix(x, mix, a_bank, u, M, K, **kw):
     """lora_shrink over weighted mixes (itts_lora_shrink_mix): for every entry (a, w) of row m's record u[m][a * rp + j] =
     w * (x[m] . a_bank[a][j]), every other column of u[m][:Kx] zero.  mix: uint8 device tensor [>= M, 32] of packed records
     (pack_lora_mix; the values are checked on the host before the upload, the kernel only guards memory); the other arguments are
     lora_shrink's."""
-    _dev(mix, a_bank)
-    if mix.dtype != torch.uint8 or mix.numel() < M * LORA_MIX_ROW_BYTES:
-        raise NativeError("itts_lora_shrink_mix: mix must be a uint8 device tensor of M 32-byte records")
-    n, rp, Ka = a_bank.shape
-    if Ka != K or a_bank.dtype != x.dtype or u.dtype != x.dtype:
-        raise NativeError("itts_lora_shrink_mix: a_bank must be T [n, rp, K] of the operand's type")
-    a = LoraShrinkMixArgs()
-    a.dtype, a.M, a.K = dt(x.dtype), int(M), int(K)
-    a.x, a.x_packed, a.x_mtp = _p(x), int(bool(x_packed)), int(x_mtp)
-    a.mix, a.a_bank, a.n, a.rp, a.Kx = _p(mix), _p(a_bank), n, rp, lora_kx(n, rp)
-    a.u, a.u_packed, a.u_mtp, a.ldu = _p(u), int(bool(u_packed)), int(u_mtp), int(ldu)
-    _check(lib().itts_lora_shrink_mix(C.byref(a), _stream()), "itts_lora_shrink_mix")
+    lora_shrink(x, None, a_bank, u, M, K, mix=mix, **kw)
 
 
 def embed_step(tokens, table, pos_table, step, pos_add, h, bump=None, row_step0=None, h_packed=None):
@@ -779,14 +728,14 @@ def attn_decode(q, kcache, vcache, out, pad, pos, B, H, smax, out_packed=False, 
 
 def attn_decode_kv8(qkv, kcache, vcache, out, pad, pos, kv_scale, B, H, out_packed=False, skip_rows=None, kv_tab=None, kv_bs=0):
     """The decode step's attention over an FP8 paged cache, with the append of the step's own key / value
-    (include/indextts_hip_kv8.h).  qkv T [B][3 * H * 64]; kcache / vcache uint8 pools of one layer; kv_scale fp32 [2][H]."""
+    (include/indextts_hip.h).  qkv T [B][3 * H * 64]; kcache / vcache uint8 pools of one layer; kv_scale fp32 [2][H]."""
     _check(lib().itts_attn_decode_kv8(_p(qkv), _p(kcache), _p(vcache), _p(out), _p(pad), _p(pos), _p(kv_scale), B, H, dt(qkv.dtype),
                                       int(bool(out_packed)), _p(skip_rows), _p(kv_tab), int(kv_bs), _stream()), "itts_attn_decode_kv8")
 
 
 def kv8_store(qkv, kcache, vcache, kv_scale, B, S, H, pad=None, row_off=None, cache_shift=None, kv_tab=None, kv_bs=0):
     """The prefill's k / v thirds of qkv T [rows][3 * H * 64] -> E4M3 codes in the paged pool of one layer
-    (include/indextts_hip_kv8.h): rows [B][S] with pad, or packed rows with row_off / cache_shift."""
+    (include/indextts_hip.h): rows [B][S] with pad, or packed rows with row_off / cache_shift."""
     _dev(qkv, kcache, vcache, kv_scale)
     _check(lib().itts_kv8_store(_p(qkv), _p(kcache), _p(vcache), _p(kv_scale), _p(pad), _p(row_off), _p(cache_shift), B, S, H,
                                 dt(qkv.dtype), _p(kv_tab), int(kv_bs), _stream()), "itts_kv8_store")
@@ -832,20 +781,24 @@ def kv_share_rows(kc, vc, B, H, Cn, p0, pad, smax, kv_tab=None, kv_bs=0):
                                     dt(kc.dtype), _stream()), "itts_kv_share_rows")
 
 
-def sample(logits, tokens, history, finished, state, extra_ids, force_stop, rep_penalty, temperature, top_k, top_p,
-           do_sample, seed, stop_token, dbg_scores=None, no_advance=False, row_step0=None):
+def _sample_args(logits, tokens, history, finished, state, extra_ids, force_stop, stop_token, dbg_scores, no_advance, row_step0):
+    """What sample and sample_rows share of itts_sample_args."""
     a = SampleArgs()
     B, V = logits.shape
     a.logits, a.B, a.V, a.ldl = _p(logits), B, V, logits.stride(0)
     a.tokens, a.history, a.hist_cap = _p(tokens), _p(history), history.shape[1]
     a.finished, a.state = _p(finished), _p(state)
     a.extra_ids, a.n_extra = _p(extra_ids), 0 if extra_ids is None else extra_ids.numel()
-    a.force_stop = _p(force_stop)
+    a.force_stop, a.stop_token = _p(force_stop), int(stop_token)
+    a.dbg_scores, a.no_advance, a.row_step0 = _p(dbg_scores), int(bool(no_advance)), _p(row_step0)
+    return a
+
+
+def sample(logits, tokens, history, finished, state, extra_ids, force_stop, rep_penalty, temperature, top_k, top_p,
+           do_sample, seed, stop_token, dbg_scores=None, no_advance=False, row_step0=None):
+    a = _sample_args(logits, tokens, history, finished, state, extra_ids, force_stop, stop_token, dbg_scores, no_advance, row_step0)
     a.rep_penalty, a.temperature, a.top_p = float(rep_penalty), float(temperature), float(top_p)
-    a.top_k, a.do_sample, a.seed, a.stop_token = int(top_k), int(bool(do_sample)), int(seed), int(stop_token)
-    a.dbg_scores = _p(dbg_scores)
-    a.no_advance = int(bool(no_advance))
-    a.row_step0 = _p(row_step0)
+    a.top_k, a.do_sample, a.seed = int(top_k), int(bool(do_sample)), int(seed)
     _check(lib().itts_sample(C.byref(a), _stream()), "itts_sample")
 
 
@@ -905,13 +858,8 @@ def sample_rows(logits, tokens, history, finished, state, extra_ids, force_stop,
     _dev(rows)
     if rows.dtype != torch.uint8 or rows.numel() < B * SAMPLE_ROW_BYTES:
         raise NativeError("itts_sample_rows: rows must be a uint8 device tensor of B 32-byte records")
-    a = SampleRowsArgs()
-    a.logits, a.B, a.V, a.ldl = _p(logits), B, V, logits.stride(0)
-    a.tokens, a.history, a.hist_cap = _p(tokens), _p(history), history.shape[1]
-    a.finished, a.state = _p(finished), _p(state)
-    a.extra_ids, a.n_extra = _p(extra_ids), 0 if extra_ids is None else extra_ids.numel()
-    a.force_stop, a.rows, a.stop_token = _p(force_stop), _p(rows), int(stop_token)
-    a.dbg_scores, a.no_advance, a.row_step0 = _p(dbg_scores), int(bool(no_advance)), _p(row_step0)
+    a = _sample_args(logits, tokens, history, finished, state, extra_ids, force_stop, stop_token, dbg_scores, no_advance, row_step0)
+    a.rows = _p(rows)
     _check(lib().itts_sample_rows(C.byref(a), _stream()), "itts_sample_rows")
 
 

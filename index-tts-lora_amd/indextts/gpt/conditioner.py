@@ -59,7 +59,7 @@ def prompt_row_space(frames):
 
 
 def prompt_seg_records(space, NL):
-    """The segment records (include/indextts_hip_prompts.h) of a row space, per launch kind: `conv` (frames -> rows), `enc` (the
+    """The segment records (include/indextts_hip.h) of a row space, per launch kind: `conv` (frames -> rows), `enc` (the
     Conformer's self-attention and convolution module: queries = keys = the prompt's rows) and `per` (the Perceiver's attention:
     prompt p's NL latent rows at p * NL query the same latent rows and the prompt's context rows, which follow ALL latent rows
     in the [latents ; contexts] operand; the output goes back to the latent rows).  Returns (records, row tiles) per kind."""
@@ -345,7 +345,7 @@ class ConditionerEngine:
         """mels: list of fp32 [T_p, F] (time-major, on the device; views are fine), any lengths -> conds fp32 [N, NL, DL], each
         prompt conditioned as if alone, in ONE pass of the same 72 kernel launches: the GEMMs and the row operations run over the
         concatenated rows of all prompts (prompt_row_space), the three launches that mix rows of a sequence take a segment table
-        (include/indextts_hip_prompts.h).  In front of the 72 kernels go N device-to-device copies that put the prompts' frames one
+        (include/indextts_hip.h).  In front of the 72 kernels go N device-to-device copies that put the prompts' frames one
         after another (`launches` counts the kernels, not these).  The result is a view of the set's output buffer: clone it.
         retain = True (default): the buffer set of this ordered tuple of lengths stays until forget(), so the pass is
         graph-capturable from the second call on.  retain = False: the caller captures no graph; the set is only a cache, bounded at

@@ -752,10 +752,7 @@ class GPTEngine:
                 return l.get(wkey + "_merged", l[wkey]), x, K
             c = xc[K]
             c[:, :K].copy_(x)
-            if row_mix is not None:
-                nat.lora_shrink_mix(x, row_mix, l["bank_a_" + wkey], c[:, K:], M, K, ldu=K + bank.Kx)
-            else:
-                nat.lora_shrink(x, row_ids, l["bank_a_" + wkey], c[:, K:], M, K, ldu=K + bank.Kx)
+            nat.lora_shrink(x, None if row_mix is not None else row_ids, l["bank_a_" + wkey], c[:, K:], M, K, ldu=K + bank.Kx, mix=row_mix)
             return l["bank_" + wkey], c, K + bank.Kx
         xn = torch.empty(M, D, dtype=T, device=dev)
         qkv = torch.empty(M, 3 * D, dtype=T, device=dev)
@@ -817,11 +814,8 @@ class GPTEngine:
 
     def _head_gemm(self, M, xn, logits):
         """mel_head over M normalised rows (fp32 logits); FP8 weights when the engine has them."""
-        kw = dict(x=xn, epi=nat.EPI_STORE_F32, yf=logits, x_packed=self.pa)
-        if self.s_head is None:
-            nat.gemm_skinny(self.dtype, M, self.V, self.D, self.w_head, self.b_head, **kw)
-        else:
-            nat.gemm_skinny_w8(self.dtype, M, self.V, self.D, self.w_head, self.s_head, self.b_head, **kw)
+        nat.gemm_skinny(self.dtype, M, self.V, self.D, self.w_head, self.b_head, x=xn, epi=nat.EPI_STORE_F32, yf=logits, x_packed=self.pa,
+                        w_scale=self.s_head)
 
     def _prefill_shared(self, emb, pad_h, S, C):
         """The packed prefill pass for a batch whose elements all begin with the SAME C rows (one prompt's conditioning
@@ -1100,16 +1094,12 @@ class GPTEngine:
                 bump = getattr(self, "_pending_bump", False)
             self._pending_bump = False
         skip = lambda *a, **kw: None   # noqa: E731
-        k = SimpleNamespace(embed_step=skip, attn_decode=skip, attn_decode_kv8=skip, ln_reduce=skip, lora_shrink=skip, lora_shrink_mix=skip) if gemm_only else nat   # every other launch
+        k = SimpleNamespace(embed_step=skip, attn_decode=skip, attn_decode_kv8=skip, ln_reduce=skip, lora_shrink=skip) if gemm_only else nat   # every other launch
         tally = [0, 0]
 
         def gemm(M, N, K, w, bias, epi, scale=None, **kw):
             """scale (fp32 [N]): w is a packed E4M3 image (weight_dtype "fp8"), one byte per weight."""
-            if scale is None:
-                nat.gemm_skinny(T, M, N, K, w, bias, epi=epi, **kw)
-            else:
-                kw.pop("wide_wg", None)     # (the FP8 forms have no 16-wave workgroups)
-                nat.gemm_skinny_w8(T, M, N, K, w, scale, bias, epi=epi, **kw)
+            nat.gemm_skinny(T, M, N, K, w, bias, epi=epi, w_scale=scale, **kw)
             out = {nat.EPI_QKV_CACHE: es, nat.EPI_STORE: es, nat.EPI_GELU_STORE: es, nat.EPI_RESID_F32: 2 * 4 + es,    # (h read and written, T copy)
                    nat.EPI_SLAB_F32: 4 * kw.get("ksplit", 1), nat.EPI_STORE_F32: 4}[epi]
             tally[0] += 1
@@ -1134,24 +1124,17 @@ class GPTEngine:
                 r_o, r_p = max(r_o, 32), max(r_p, 32)
             kv8 = self.kv_dtype is not None
             for i, l in enumerate(self.layers):
+                qkv_kw = dict(x=hb, x_packed=True, ln_c=l["c_qkv"], bump=step if (bump and i == 0) else None, rows_per_wg=r_c, scale=l.get("s_qkv"))
                 if kv8:
                     # FP8 KV cache: the existing row-major STORE epilogue writes q | k | v, and the attention launch quantises and
                     # appends the new key itself (still 5 launches per block); `bump` travels as before (it is not tied to an epilogue)
-                    gemm(B, 3 * D, D, l["wf_qkv"], l["d_qkv"], nat.EPI_STORE, x=hb, y=self.qkv, x_packed=True, ln_c=l["c_qkv"],
-                         bump=step if (bump and i == 0) else None, rows_per_wg=r_c, scale=l.get("s_qkv"))
+                    gemm(B, 3 * D, D, l["wf_qkv"], l["d_qkv"], nat.EPI_STORE, y=self.qkv, **qkv_kw)
                     k.attn_decode_kv8(self.qkv, self.kc[i], self.vc[i], self.a, self.pad, pos, self.kv_scale[i], B, H, out_packed=pa,
                                       skip_rows=attn_kw["skip_rows"], **kva)
-                    gemm(B, D, D, l["w8_o" if w8 else "w_o"], l["b_o"], nat.EPI_RESID_F32, x=self.a, yf=h, y=hb, x_packed=pa,
-                         y_packed=True, rows_per_wg=r_o, wide_wg=self.fold_wide, scale=l.get("s_o"))
-                    gemm(B, 4 * D, D, l["wf_fc"], l["d_fc"], nat.EPI_GELU_STORE, x=hb, y=self.f, x_packed=True, y_packed=pa,
-                         ln_c=l["c_fc"], rows_per_wg=r_c, scale=l.get("s_fc"))
-                    gemm(B, D, 4 * D, l["w8_pr" if w8 else "w_pr"], l["b_pr"], nat.EPI_RESID_F32, x=self.f, yf=h, y=hb, x_packed=pa,
-                         y_packed=True, rows_per_wg=r_p, wide_wg=self.fold_wide, scale=l.get("s_pr"))
-                    continue
-                gemm(B, 3 * D, D, l["wf_qkv"], l["d_qkv"], nat.EPI_QKV_CACHE, x=hb, y=self.q, kcache=self.kc[i], vcache=self.vc[i],
-                     pos=pos, heads=H, smax=self._cap_s, x_packed=True, ln_c=l["c_qkv"], bump=step if (bump and i == 0) else None,
-                     rows_per_wg=r_c, scale=l.get("s_qkv"), **kva)
-                k.attn_decode(self.q, self.kc[i], self.vc[i], self.a, self.pad, pos, B, H, self._cap_s, out_packed=pa, **attn_kw)
+                else:
+                    gemm(B, 3 * D, D, l["wf_qkv"], l["d_qkv"], nat.EPI_QKV_CACHE, y=self.q, kcache=self.kc[i], vcache=self.vc[i],
+                         pos=pos, heads=H, smax=self._cap_s, **qkv_kw, **kva)
+                    k.attn_decode(self.q, self.kc[i], self.vc[i], self.a, self.pad, pos, B, H, self._cap_s, out_packed=pa, **attn_kw)
                 gemm(B, D, D, l["w8_o" if w8 else "w_o"], l["b_o"], nat.EPI_RESID_F32, x=self.a, yf=h, y=hb, x_packed=pa, y_packed=True,
                      rows_per_wg=r_o, wide_wg=self.fold_wide, scale=l.get("s_o"))
                 gemm(B, 4 * D, D, l["wf_fc"], l["d_fc"], nat.EPI_GELU_STORE, x=hb, y=self.f, x_packed=True, y_packed=pa,
@@ -1172,10 +1155,9 @@ class GPTEngine:
                 the GEMM runs over K + Kx with [W ; B_bank^T]."""
                 if bank is None or "bank_" + wkey not in l:
                     return l.get(wkey + "_lora", l[wkey]), K
-                if self._mix_host is not None:   # the batch was prefilled with adapter_mix: weighted slots from the rows' records
-                    k.lora_shrink_mix(x, self.adapter_mix, l["bank_a_" + wkey], x.view(-1)[K * Bp:], B, K, x_packed=True, u_packed=True)
-                else:
-                    k.lora_shrink(x, self.adapter_ids, l["bank_a_" + wkey], x.view(-1)[K * Bp:], B, K, x_packed=True, u_packed=True)
+                mixed = self._mix_host is not None   # the batch was prefilled with adapter_mix: weighted slots from the rows' records
+                k.lora_shrink(x, None if mixed else self.adapter_ids, l["bank_a_" + wkey], x.view(-1)[K * Bp:], B, K, x_packed=True,
+                              u_packed=True, mix=self.adapter_mix if mixed else None)
                 return l["bank_" + wkey], K + bank.Kx
             for i, l in enumerate(self.layers):
                 last = i + 1 == self.L

@@ -5,7 +5,7 @@
 E4M3: 1 sign bit, 4 exponent bits (bias 7), 3 mantissa bits; subnormals m * 2^-9; largest finite value 448 (0x7e); 0x7f / 0xff are
 NaN and are never produced here.  The rounding is round-to-nearest-even on the E4M3 grid, done on float64 values (one rounding: no
 detour through fp32), and equals torch's float8_e4m3fn cast of the same values (tests/test_w8_cpu.py pins that).  Host code: the
-engine quantises once at load time; the kernel side is include/indextts_hip_w8.h."""
+engine quantises once at load time; the kernel side is include/indextts_hip.h."""
 import torch
 
 E4M3_MAX = 448.0
@@ -80,7 +80,7 @@ def dequantized_gpt_weights(W, layers):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# FP8 KV cache (include/indextts_hip_kv8.h): the same E4M3 codes, one fp32 POWER-OF-TWO scale per (layer,
+# FP8 KV cache (include/indextts_hip.h): the same E4M3 codes, one fp32 POWER-OF-TWO scale per (layer,
 # K | V, head).  Multiplying by the inverse of a power of two is exact, so these host functions and the device quantiser
 # (csrc/kv8.hip) give the same code for every input, and dequantisation commutes with every sum.
 # ---------------------------------------------------------------------------------------------------------------------------------

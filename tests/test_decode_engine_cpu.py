@@ -44,19 +44,20 @@ def recorded(monkeypatch):
     def other(*a, **kw):
         calls["other"] += 1
     monkeypatch.setattr(nat, "pack_weight", lambda w: w.contiguous())
+    monkeypatch.setattr(nat, "pack_weight_w8", lambda codes: codes.contiguous())
     monkeypatch.setattr(nat, "gemm_skinny", gemm)
-    for name in ("embed_step", "attn_decode", "ln_reduce"):
+    for name in ("embed_step", "attn_decode", "attn_decode_kv8", "ln_reduce"):
         monkeypatch.setattr(nat, name, other)
 
-    def make(mode, B, lora=False):
+    def make(mode, B, lora=False, paged=False, **kw):
         monkeypatch.setenv("ITTS_DECODE_MODE", mode)
-        eng = GPTEngine(tiny_weights(), L, D, H, dtype=torch.bfloat16, device="cpu")
+        eng = GPTEngine(tiny_weights(), L, D, H, dtype=torch.bfloat16, device="cpu", **kw)
         if lora:
             r = 8
             ad = {f"gpt.h.{i}.{n}": (torch.randn(r, k) * 0.1, torch.randn(D, r) * 0.1)
                   for i in range(L) for n, k in (("attn.c_proj", D), ("mlp.c_proj", 4 * D))}
             eng.attach_lora(ad, 2.0)
-        eng._ensure(B, 64)
+        eng._ensure(B, 64, paged=paged, blocks=16)
         return eng
     return make, calls
 
@@ -88,6 +89,27 @@ def test_gemm_launches_of_step_are_the_decode_steps_gemms(recorded, mode, B, lor
         per_layer += 2 * (2 * B * D * 4 + B * D * es) if mode == "fold" else 2 * KS * B * D * 4
         assert nbytes == L * per_layer + V * D * es + B * D * es + B * V * 4
         assert nbytes == {"fold": 1203200, "launch": 1235968}[mode]
+
+
+@pytest.mark.parametrize("B", [32, 96])
+@pytest.mark.parametrize("weight_dtype, kv_dtype", [("fp8", None), (None, "fp8"), ("fp8", "fp8")])
+def test_gemm_launches_of_the_fp8_steps(recorded, B, weight_dtype, kv_dtype):
+    """The folded step over FP8 weights, an FP8 KV cache and both: the same five launches per block, the weight scales ride on the
+    four GEMMs (and the head) of an FP8-weight engine and on none of a 16-bit one, one byte per weight in the tally."""
+    make, calls = recorded
+    eng = make("fold", B, paged=kv_dtype is not None, weight_dtype=weight_dtype, kv_dtype=kv_dtype)
+    traced, others, (n, nbytes) = _gemms_of(calls, lambda: eng.gemm_launches_of_step(B))
+    assert others == 0 and n == len(traced) == 4 * L + 1
+    real, others, _ = _gemms_of(calls, lambda: eng._step_transformer(B))
+    assert others == L + 2 and traced == real              # embed, one attention per block, the final norms: nothing else
+    scaled = [dict(kw).get("w_scale") is not None for _, kw in real]
+    assert scaled == [weight_dtype == "fp8"] * len(real)
+    epis = [dict(kw)["epi"] for _, kw in real[:4]]
+    assert epis == [nat.EPI_STORE if kv_dtype else nat.EPI_QKV_CACHE, nat.EPI_RESID_F32, nat.EPI_GELU_STORE, nat.EPI_RESID_F32]
+    if B == 32:
+        es, ws = 2, 1 if weight_dtype else 2
+        per_layer = 12 * D * D * ws + B * D * es * (1 + 1 + 1 + 4) + B * es * (3 * D + 4 * D) + 2 * (2 * B * D * 4 + B * D * es)
+        assert nbytes == L * per_layer + V * D * ws + B * D * es + B * V * 4
 
 
 def test_graph_key_covers_every_setting_of_the_captured_step(recorded):

@@ -105,6 +105,7 @@ def calls(nat):
     """name -> (dtype -> return code), with arguments that pass every check in front of the dtype dispatch; "name/what" is a
     second dispatch site of the same entry point."""
     L = nat.lib()
+    SEG = struct(nat.SegTableArgs, dev=P, host=P, nseg=1, ntiles=1)   # (the table is looked at behind the dtype dispatch)
     return {
         "itts_pack_weight": lambda d: L.itts_pack_weight(P, P, 1, 64, 64, d, None),
         "itts_aa_snake_fwd": lambda d: L.itts_aa_snake_fwd(P, P, P, P, FIRP, FIRP, 1, 64, 32, d, 0, None, None),
@@ -124,6 +125,11 @@ def calls(nat):
         "itts_kv_share_rows": lambda d: L.itts_kv_share_rows(P, P, 1, 1024, 2, 2, 4, 0, P, 64, None, 0, d, None),
         "itts_beam_reorder_kv": lambda d: L.itts_beam_reorder_kv(P, P, P, P, 1, 1, 2, 2, 64, 1024, d, None),
         "itts_tanh_pcm": lambda d: L.itts_tanh_pcm(P, P, None, 16, d, 0, None),
+        "itts_lora_shrink_mix": lambda d: L.itts_lora_shrink_mix(struct(nat.LoraShrinkArgs, dtype=d, M=4, K=64, x=P, mix=P, a_bank=P, u=P, n=3, rp=16, Kx=64, ldu=128), None),
+        "itts_refill_join": lambda d: L.itts_refill_join(struct(nat.RefillJoinArgs, dtype=d, L=1, H=1, hist_cap=8), None),
+        # ---- FP8 weights: the activation type is bf16 / f16
+        "itts_gemm_skinny_w8": lambda d: L.itts_gemm_skinny_w8(struct(nat.SkinnyArgs, dtype=d, M=4, N=64, K=64, wp=P, x=P, y=P, w_scale=P, epi=nat.EPI_STORE), None),
+        "itts_skinny_plan_w8": lambda d: L.itts_skinny_plan_w8(d, 4, 64, 64, 0, 0, (C.c_int * 8)()),
         # ---- built for bf16 / f16 only
         "itts_subsample_conv": lambda d: L.itts_subsample_conv(P, P, P, P, 8, 8, 8, d, None),
         "itts_mha_small": lambda d: L.itts_mha_small(struct(nat.MhaArgs, dtype=d, Tq=4, Tk=4, H=1, q=P, k=P, v=P, out=P, q_stride=64, k_stride=64, v_stride=64, out_mtp=1), None),
@@ -135,14 +141,23 @@ def calls(nat):
         "itts_se_gate": lambda d: L.itts_se_gate(P, P, P, P, P, P, 8, 64, 16, 1, d, None),
         "itts_scale_resid": lambda d: L.itts_scale_resid(P, P, P, P, 8, 32, 1, d, None),
         "itts_col_stats": lambda d: L.itts_col_stats(P, None, None, None, P, 8, 64, 1, d, None),
+        "itts_attn_decode_kv8": lambda d: L.itts_attn_decode_kv8(P, P, P, P, P, P, P, 2, 2, d, 0, None, P, 16, None),
+        "itts_kv8_store": lambda d: L.itts_kv8_store(P, P, P, P, None, None, None, 2, 8, 2, d, P, 16, None),
+        "itts_subsample_conv_seg": lambda d: L.itts_subsample_conv_seg(P, P, P, P, SEG, 8, 8, 8, d, None),
+        "itts_mha_small_seg": lambda d: L.itts_mha_small_seg(struct(nat.MhaArgs, dtype=d, Tq=4, Tk=4, H=1, q=P, k=P, v=P, out=P, q_stride=64, k_stride=64, v_stride=64, out_mtp=1), SEG, 0, None),
+        "itts_glu_dwconv_ln_silu_seg": lambda d: L.itts_glu_dwconv_ln_silu_seg(P, P, P, P, P, P, SEG, 128, 15, 1, 1e-5, d, None),
     }
 
 
 ONLY_16BIT = ("itts_subsample_conv", "itts_mha_small", "itts_glu_dwconv_ln_silu", "itts_rows", "itts_geglu", "itts_im2col_reflect",
-              "itts_res2_step", "itts_se_gate", "itts_scale_resid", "itts_col_stats")
+              "itts_res2_step", "itts_se_gate", "itts_scale_resid", "itts_col_stats", "itts_attn_decode_kv8", "itts_kv8_store",
+              "itts_subsample_conv_seg", "itts_mha_small_seg", "itts_glu_dwconv_ln_silu_seg")
+# FP8 weights under 16-bit activations: these two word their refusal of ITTS_F32 (and of any other dtype) themselves
+ACT_16BIT = ("itts_gemm_skinny_w8", "itts_skinny_plan_w8")
+ACT_16BIT_SAYS = "the activation type must be bf16 or f16"
 # no dtype among the arguments -- or, itts_packed_bytes, one that only sizes a buffer: it returns a byte count, not a status
 NO_DTYPE = ("itts_abi_version", "itts_last_error", "itts_last_kernel", "itts_packed_bytes", "itts_sample", "itts_beam_step",
-            "itts_beam_kv_rows", "itts_prefix_rows")
+            "itts_beam_kv_rows", "itts_prefix_rows", "itts_packed_bytes_w8", "itts_pack_weight_w8", "itts_sample_rows")
 # the three prefill variants run the launcher of itts_attn_prefill, which reports under that name
 REPORTS_AS = {"itts_attn_prefill_packed": "itts_attn_prefill", "itts_attn_prefill_prefix": "itts_attn_prefill",
               "itts_attn_prefill_shared": "itts_attn_prefill"}
@@ -151,7 +166,7 @@ REPORTS_AS = {"itts_attn_prefill_packed": "itts_attn_prefill", "itts_attn_prefil
 def test_every_entry_point_is_classified(nat):
     table = {name.split("/")[0] for name in calls(nat)}
     assert set(table) | set(NO_DTYPE) == set(nat.EXPORTED_SYMBOLS) and not set(table) & set(NO_DTYPE)
-    assert set(ONLY_16BIT) <= set(table)
+    assert set(ONLY_16BIT) <= set(table) and set(ACT_16BIT) <= set(table) and not set(ONLY_16BIT) & set(ACT_16BIT)
 
 
 def test_unknown_dtype_is_refused_by_name(nat):
@@ -169,3 +184,12 @@ def test_fp32_is_refused_by_the_16_bit_entry_points(nat):
         assert table[name](nat.dt(F32)) == 1, (name, L.itts_last_error())
         err = L.itts_last_error().decode()
         assert err.startswith(name + ":") and "bf16 / f16" in err, (name, err)
+
+
+def test_fp32_is_refused_by_the_fp8_weight_entry_points(nat):
+    L, table = nat.lib(), calls(nat)
+    for name in ACT_16BIT:
+        for d in (nat.dt(F32), 7):
+            assert table[name](d) == 1, (name, L.itts_last_error())
+            err = L.itts_last_error().decode()
+            assert err.startswith(name + ":") and ACT_16BIT_SAYS in err, (name, err)

@@ -1,5 +1,5 @@
 """FP8 KV cache, host side (no GPU): the E4M3 quantiser of keys / values against torch's float8_e4m3fn cast, the power-of-two
-scale choice, the precision_config key, and the C ABI's two new entry points (include/indextts_hip_kv8.h)."""
+scale choice, the precision_config key, and the C ABI's two FP8-cache entry points (include/indextts_hip.h)."""
 import ctypes
 import os
 import re
@@ -90,20 +90,14 @@ def test_engine_refuses_without_a_gpu_what_it_can():
 def test_abi_declares_and_exports_the_kv8_entry_points():
     from indextts import _native as nat
     L = nat.lib()
-    assert L.itts_abi_version() == 9
+    assert L.itts_abi_version() == 10
     main = open(os.path.join(ROOT, "include", "indextts_hip.h")).read()
-    assert '#include "indextts_hip_kv8.h"' in main and re.search(r"#define ITTS_ABI_VERSION (\d+)", main).group(1) == "9"
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "indextts_hip_kv8.h")).read(), flags=re.S)
-    syms = sorted(set(re.findall(r"\b(itts_[a-z0-9_]+)\s*\(", txt)))
-    # the registry rule of the W8 and row headers: a header of its own, a list of its own (EXPORTED_SYMBOLS is held against
-    # indextts_hip.h's own prototypes by test_native_abi.py and against the dtype table of test_host_launch_cpu.py)
-    assert syms == sorted(nat.KV8_SYMBOLS) == ["itts_attn_decode_kv8", "itts_kv8_store"]
+    assert re.search(r"#define ITTS_ABI_VERSION (\d+)", main).group(1) == "10"
+    declared = set(re.findall(r"\b(itts_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", main, flags=re.S)))
+    # the registry rule (EXPORTED_SYMBOLS is held against the header's prototypes by test_native_abi.py and against the dtype
+    # table of test_host_launch_cpu.py): declared, exported, bound
     plain = ctypes.CDLL(nat.LIB_PATH)
-    assert all(hasattr(plain, s_) for s_ in syms)
-    assert not set(syms) & (set(nat.EXPORTED_SYMBOLS) | set(nat.ROW_SYMBOLS) | set(nat.W8_SYMBOLS))
-    # the existing structs are what they were (LP64)
-    assert ctypes.sizeof(nat.SkinnyArgs) == 184 and ctypes.sizeof(nat.SkinnyW8Args) == ctypes.sizeof(nat.SkinnyW8Args())
-    assert ctypes.sizeof(nat.ConvArgs) == 160 and ctypes.sizeof(nat.SampleRowsArgs) == 128
+    assert all(s_ in declared and hasattr(plain, s_) and s_ in nat.EXPORTED_SYMBOLS for s_ in ("itts_attn_decode_kv8", "itts_kv8_store"))
 
 
 def test_entry_points_refuse_bad_calls_without_launching():

@@ -1,4 +1,4 @@
-"""The two FP8 KV cache kernels through the C ABI (include/indextts_hip_kv8.h), bf16 and f16.
+"""The two FP8 KV cache kernels through the C ABI (include/indextts_hip.h), bf16 and f16.
 
 itts_kv8_store: the codes it writes equal the host quantiser's (indextts/utils/quant.py) bit for bit, and every other byte of the
 pool keeps its sentinel.

@@ -16,7 +16,7 @@ def args(nat, **kw):
 def test_lora_shrink_reports_bad_calls_without_launching():
     from indextts import _native as nat
     L = nat.lib()
-    assert "itts_lora_shrink" in nat.EXPORTED_SYMBOLS and L.itts_abi_version() == 9
+    assert "itts_lora_shrink" in nat.EXPORTED_SYMBOLS and L.itts_abi_version() == 10
     assert nat.lora_kx(3, 48) == 160 and nat.lora_kx(8, 16) == 128 and nat.lora_kx(1, 16) == 32
     assert L.itts_lora_shrink(ctypes.byref(nat.LoraShrinkArgs()), None) == 1 and b"null" in L.itts_last_error()
     for kw, word in ((dict(n=0, Kx=0), b"adapters"), (dict(rp=80, Kx=256), b"rank"), (dict(rp=24, Kx=96), b"rp"),

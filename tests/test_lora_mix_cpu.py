@@ -1,4 +1,4 @@
-"""Per-row adapter blends on the host side (include/indextts_hip_mix.h): the entry point is declared, exported and bound, the
+"""Per-row adapter blends on the host side (include/indextts_hip.h): the entry point is declared, exported and bound, the
 32-byte record packs as the header lays it out, bad calls are reported without a launch, and GPTEngine.check_adapter_mix accepts
 every input form and refuses every bad one before anything reaches the device (no GPU needed: validation comes first)."""
 import ctypes
@@ -16,22 +16,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_abi_declares_exports_and_binds_the_mix_entry_point():
     from indextts import _native as nat
     L = nat.lib()
-    assert L.itts_abi_version() == 9
+    assert L.itts_abi_version() == 10
     main = open(os.path.join(ROOT, "include", "indextts_hip.h")).read()
-    assert '#include "indextts_hip_mix.h"' in main and re.search(r"#define ITTS_ABI_VERSION (\d+)", main).group(1) == "9"
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "indextts_hip_mix.h")).read(), flags=re.S)
-    syms = sorted(set(re.findall(r"\b(itts_[a-z0-9_]+)\s*\(", txt)))
-    assert syms == sorted(nat.MIX_SYMBOLS) == ["itts_lora_shrink_mix"]
-    plain = ctypes.CDLL(nat.LIB_PATH)
-    assert all(hasattr(plain, s_) for s_ in syms)
+    assert re.search(r"#define ITTS_ABI_VERSION (\d+)", main).group(1) == "10"
+    txt = re.sub(r"/\*.*?\*/", "", main, flags=re.S)
+    assert "itts_lora_shrink_mix" in re.findall(r"\b(itts_[a-z0-9_]+)\s*\(", txt) and "itts_lora_shrink_mix" in nat.EXPORTED_SYMBOLS
+    assert hasattr(ctypes.CDLL(nat.LIB_PATH), "itts_lora_shrink_mix")
     assert L.itts_lora_shrink_mix.argtypes is not None and callable(nat.lora_shrink_mix)
-    others = set(nat.EXPORTED_SYMBOLS) | set(nat.ROW_SYMBOLS) | set(nat.W8_SYMBOLS) | set(nat.KV8_SYMBOLS) | set(nat.PROMPT_SYMBOLS)
-    assert not set(syms) & others
-    # the existing structs are what they were (LP64); the new argument struct is itts_lora_shrink_args with one pointer renamed
-    assert ctypes.sizeof(nat.LoraShrinkArgs) == ctypes.sizeof(nat.LoraShrinkMixArgs) == 88
-    assert [(n, t) for n, t in nat.LoraShrinkMixArgs._fields_ if n != "mix"] == [(n, t) for n, t in nat.LoraShrinkArgs._fields_ if n != "ids"]
-    assert nat.LoraShrinkMixArgs.mix.offset == nat.LoraShrinkArgs.ids.offset
-    assert ctypes.sizeof(nat.SkinnyArgs) == 184 and ctypes.sizeof(nat.ConvArgs) == 160 and ctypes.sizeof(nat.SampleRowsArgs) == 128
+    # one argument struct for the id launch and the mix launch (LP64): the header's field order, ids where it was, mix last
+    decl = txt[txt.index("typedef struct itts_lora_shrink_args {"):txt.index("} itts_lora_shrink_args;")]
+    order = [n for line in decl.split("{", 1)[1].split(";") for n in re.findall(r"(\w+)\s*(?:,|$)", line.strip())]
+    assert order == [n for n, _ in nat.LoraShrinkArgs._fields_]
+    assert (nat.LoraShrinkArgs.ids.offset, nat.LoraShrinkArgs.mix.offset) == (32, 88)
+    assert "const itts_lora_shrink_args* a" in txt[txt.index("int itts_lora_shrink_mix("):]
 
 
 def test_record_layout():
@@ -40,7 +37,7 @@ def test_record_layout():
     from indextts import _native as nat
     assert ctypes.sizeof(nat.LoraMixRow) == nat.LORA_MIX_ROW_BYTES == 32 and nat.LORA_MIX_ENTRIES == 4
     assert (nat.LoraMixEntry.id.offset, nat.LoraMixEntry.weight.offset, ctypes.sizeof(nat.LoraMixEntry)) == (0, 4, 8)
-    hdr = open(os.path.join(ROOT, "include", "indextts_hip_mix.h")).read()
+    hdr = open(os.path.join(ROOT, "include", "indextts_hip.h")).read()
     assert re.search(r"#define ITTS_LORA_MIX_ENTRIES 4\b", hdr) and "aligned(16)" in hdr
     rows = nat.pack_lora_mix([(), ((2, 1.0),), ((0, 0.7), (1, 0.3)), ((0, 0.5), (1, -0.25), (2, 1.25), (3, 2.0))])
     assert rows.shape == (4, 32) and rows.dtype.name == "uint8"
@@ -56,7 +53,7 @@ def test_record_layout():
 
 
 def args(nat, **kw):
-    a = nat.LoraShrinkMixArgs()
+    a = nat.LoraShrinkArgs()
     a.dtype, a.M, a.K = nat.BF16, 4, 64
     a.x = a.mix = a.a_bank = a.u = 0x1000          # never dereferenced: every call below fails its checks
     a.n, a.rp, a.Kx, a.ldu = 3, 16, 64, 128
@@ -69,7 +66,7 @@ def test_bad_calls_are_reported_without_launching():
     """The limits and refusals of itts_lora_shrink (tests/test_lora_bank_cpu.py), and the record table's alignment."""
     from indextts import _native as nat
     L = nat.lib()
-    assert L.itts_lora_shrink_mix(ctypes.byref(nat.LoraShrinkMixArgs()), None) == 1 and b"null" in L.itts_last_error()
+    assert L.itts_lora_shrink_mix(ctypes.byref(nat.LoraShrinkArgs()), None) == 1 and b"null" in L.itts_last_error()
     for kw, word in ((dict(n=0, Kx=0), b"adapters"), (dict(rp=80, Kx=256), b"rank"), (dict(rp=24, Kx=96), b"rp"),
                      (dict(n=9, rp=64, Kx=576), b"Kx"), (dict(Kx=96), b"Kx"), (dict(K=48), b"K %"), (dict(dtype=7), b"dtype"),
                      (dict(ldu=32), b"ldu"), (dict(u=0x1004), b"aligned"), (dict(mix=0x1008), b"aligned"), (dict(x_mtp=1), b"x_mtp"),

@@ -1,4 +1,4 @@
-"""itts_lora_shrink_mix (include/indextts_hip_mix.h): the adapter bank's shrink launch over weighted mixes of up to four voices per
+"""itts_lora_shrink_mix (include/indextts_hip.h): the adapter bank's shrink launch over weighted mixes of up to four voices per
 row, at the shapes of test_lora_bank_gpu.py::test_shrink_kernel_against_fp64_on_the_rounded_operands (the smallest that take every
 path: rp = 48 -> Kx = 160 with padding to 32, one / several / many pieces per lane, a partial tile and three tiles).
 

@@ -22,7 +22,7 @@ def test_library_abi_and_exported_symbols():
         __graft_entry__.build()
     lib = ctypes.CDLL(_native.LIB_PATH)
     syms = header_symbols()
-    assert len(syms) >= 13
+    assert len(syms) == 47            # the whole ABI: one header, one table
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/indextts_hip.h but not exported"
     assert set(syms) == set(_native.EXPORTED_SYMBOLS)
@@ -33,9 +33,13 @@ def test_library_abi_and_exported_symbols():
     for s in dsyms:
         assert not hasattr(lib, s), f"{s} (diagnostic build only) is exported by the product library"
     lib.itts_abi_version.restype = ctypes.c_int
-    assert lib.itts_abi_version() == 9
+    assert lib.itts_abi_version() == 10
     hdr = open(os.path.join(ROOT, "include", "indextts_hip.h")).read()
-    assert re.search(r"#define ITTS_ABI_VERSION (\d+)", hdr).group(1) == "9"
+    assert re.search(r"#define ITTS_ABI_VERSION (\d+)", hdr).group(1) == "10"
+    assert "#include \"indextts" not in hdr          # no side headers: everything is declared here
+    # the argument structs by size (LP64), pinned once: the three that serve two entry points each grew by one pointer at ABI 10
+    assert ctypes.sizeof(_native.ConvArgs) == 160
+    assert (ctypes.sizeof(_native.SkinnyArgs), ctypes.sizeof(_native.SampleArgs), ctypes.sizeof(_native.LoraShrinkArgs)) == (192, 160, 96)
     lib.itts_packed_bytes.restype = ctypes.c_int64
     assert lib.itts_packed_bytes(1, 1280, 3840, 1) == 1280 * 3840 * 2
     assert lib.itts_packed_bytes(7, 24, 1, 0) == 7 * 1 * 2 * 1024

@@ -1,4 +1,4 @@
-"""The segmented forms of the three sequence-mixing front-end kernels (include/indextts_hip_prompts.h) against the single-prompt
+"""The segmented forms of the three sequence-mixing front-end kernels (include/indextts_hip.h) against the single-prompt
 entry points they share their bodies with: every segment's output is BIT-identical to the single-prompt call on that segment
 alone.  The single-prompt forms are pinned to fp64 by test_frontend_kernels_gpu.py, so no tolerance appears here.
 

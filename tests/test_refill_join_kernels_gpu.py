@@ -1,4 +1,4 @@
-"""itts_refill_join alone, through the C ABI (include/indextts_hip_refill.h): the one launch that takes staged rows into a running
+"""itts_refill_join alone, through the C ABI (include/indextts_hip.h): the one launch that takes staged rows into a running
 decode loop equals, bit for bit, the torch scatters and indexed writes it replaces -- on sentinel-filled caches and state, so that an
 element written where none should be shows.  M = 58 staged positions over k = 3 rows of 1, 17 and 40 positions, L = 2, bs = 16: a
 row inside one block, a row crossing a block boundary, a row over three blocks with non-contiguous block ids."""

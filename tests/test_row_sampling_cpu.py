@@ -1,5 +1,5 @@
-"""Per-row sampling settings on the host side (itts_sample_rows, gpt.model.row_sampling_params): the symbol is exported beside the
-unchanged argument structs, a list of settings is checked before anything touches the device, seed and draw stream resolve as
+"""Per-row sampling settings on the host side (itts_sample_rows, gpt.model.row_sampling_params): the symbol is declared, exported and
+bound, a list of settings is checked before anything touches the device, seed and draw stream resolve as
 documented, and a record packs as include/indextts_hip.h lays it out (no GPU needed: validation comes first)."""
 import ctypes
 import os
@@ -15,17 +15,16 @@ GEN = dict(do_sample=True, top_p=0.8, top_k=30, temperature=1.0, repetition_pena
 def test_symbol_is_exported_and_reports_bad_calls_without_launching():
     from indextts import _native as nat
     L = nat.lib()
-    assert L.itts_abi_version() == 9
-    # the registry rule of indextts_hip.h, for the header that declares this entry point: every prototype of indextts_hip_rows.h is
-    # exported by the library and bound by the Python side, and indextts_hip.h pulls that header in
-    main = open(os.path.join(ROOT, "include", "indextts_hip.h")).read()
-    assert '#include "indextts_hip_rows.h"' in main
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "indextts_hip_rows.h")).read(), flags=re.S)
-    syms = sorted(set(re.findall(r"\b(itts_[a-z0-9_]+)\s*\(", txt)))
-    assert syms == sorted(nat.ROW_SYMBOLS) == ["itts_sample_rows"]
-    plain = ctypes.CDLL(nat.LIB_PATH)
-    assert all(hasattr(plain, s_) for s_ in syms) and not set(syms) & set(nat.EXPORTED_SYMBOLS)
-    a = nat.SampleRowsArgs()
+    assert L.itts_abi_version() == 10
+    # the registry rule of indextts_hip.h: the prototype is declared there, exported by the library and bound by the Python side
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "indextts_hip.h")).read(), flags=re.S)
+    assert "itts_sample_rows" in re.findall(r"\b(itts_[a-z0-9_]+)\s*\(", txt) and "itts_sample_rows" in nat.EXPORTED_SYMBOLS
+    assert hasattr(ctypes.CDLL(nat.LIB_PATH), "itts_sample_rows")
+    # one argument struct for both entry points: the header's field order, `rows` last
+    decl = txt[txt.index("typedef struct itts_sample_args {"):txt.index("} itts_sample_args;")]
+    order = [n for line in decl.split("{", 1)[1].split(";") for n in re.findall(r"(\w+)\s*(?:,|$)", line.strip())]
+    assert order == [f[0] for f in nat.SampleArgs._fields_] and order[-1] == "rows"
+    a = nat.SampleArgs()
     assert L.itts_sample_rows(ctypes.byref(a), None) == 1 and b"itts_sample_rows: null" in L.itts_last_error()
     a.logits = a.tokens = a.history = a.finished = a.state = 0x1000     # never dereferenced: every call below fails its checks
     a.B, a.V, a.ldl = 2, 9000, 9000
@@ -34,9 +33,11 @@ def test_symbol_is_exported_and_reports_bad_calls_without_launching():
     assert L.itts_sample_rows(ctypes.byref(a), None) == 1 and b"rows" in L.itts_last_error()          # no table
     a.rows = 0x1008
     assert L.itts_sample_rows(ctypes.byref(a), None) == 1 and b"16-byte aligned" in L.itts_last_error()
-    # the scalar form's refusals are what they were
+    # the scalar form's refusals are what they were, and it refuses a table (per-row settings are never silently dropped)
     s = nat.SampleArgs()
     assert L.itts_sample(ctypes.byref(s), None) == 1 and b"itts_sample: null pointer" in L.itts_last_error()
+    a.rows = 0x1000
+    assert L.itts_sample(ctypes.byref(a), None) == 1 and L.itts_last_error().startswith(b"itts_sample: rows")
 
 
 def test_record_packs_as_the_header_documents_it():

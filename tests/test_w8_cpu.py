@@ -1,4 +1,4 @@
-"""FP8 (E4M3) decoder weights on the host side: the quantiser (indextts/utils/quant.py), the C ABI of include/indextts_hip_w8.h
+"""FP8 (E4M3) decoder weights on the host side: the quantiser (indextts/utils/quant.py), the FP8 GEMM entry points of the C ABI
 (symbols, sizes, planner, refusals -- no GPU needed: validation comes first) and the precision resolution of the public surface.
 
 Quantiser bounds.  scale[n] is fp32(max_k |W[k, n]| / 448); the codes are the round-to-nearest-even E4M3 encoding of W / scale,
@@ -108,21 +108,19 @@ def test_rounding_is_torchs_e4m3fn_cast():
 def test_abi_symbols_sizes_plan_and_refusals():
     from indextts import _native as nat
     L = nat.lib()
-    assert L.itts_abi_version() == 9
+    assert L.itts_abi_version() == 10
     main = open(os.path.join(ROOT, "include", "indextts_hip.h")).read()
-    assert '#include "indextts_hip_w8.h"' in main and re.search(r"#define ITTS_ABI_VERSION (\d+)", main).group(1) == "9"
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "indextts_hip_w8.h")).read(), flags=re.S)
-    syms = sorted(set(re.findall(r"\b(itts_[a-z0-9_]+)\s*\(", txt)))
-    assert syms == sorted(nat.W8_SYMBOLS) == ["itts_gemm_skinny_w8", "itts_pack_weight_w8", "itts_packed_bytes_w8", "itts_skinny_plan_w8"]
+    assert re.search(r"#define ITTS_ABI_VERSION (\d+)", main).group(1) == "10"
+    txt = re.sub(r"/\*.*?\*/", "", main, flags=re.S)
+    syms = ["itts_gemm_skinny_w8", "itts_pack_weight_w8", "itts_packed_bytes_w8", "itts_skinny_plan_w8"]
+    declared = set(re.findall(r"\b(itts_[a-z0-9_]+)\s*\(", txt))
     plain = ctypes.CDLL(nat.LIB_PATH)
-    assert all(hasattr(plain, s_) for s_ in syms) and not set(syms) & (set(nat.EXPORTED_SYMBOLS) | set(nat.ROW_SYMBOLS))
-    # the existing structs are what they were (LP64)
-    assert ctypes.sizeof(nat.SkinnyArgs) == 184 and ctypes.sizeof(nat.ConvArgs) == 160 and ctypes.sizeof(nat.SampleRowsArgs) == 128
-    assert ctypes.sizeof(nat.LoraShrinkArgs) == 88 and ctypes.sizeof(nat.SampleArgs) == 152
-    # the new struct's fields, in the header's order
-    decl = txt[txt.index("typedef struct itts_skinny_w8_args {"):txt.index("} itts_skinny_w8_args;")]
+    assert all(s_ in declared and hasattr(plain, s_) and s_ in nat.EXPORTED_SYMBOLS for s_ in syms)
+    # the struct both GEMM entry points take: its fields, in the header's order
+    decl = txt[txt.index("typedef struct itts_skinny_args {"):txt.index("} itts_skinny_args;")]
     order = [n for line in decl.split("{", 1)[1].split(";") for n in re.findall(r"(\w+)\s*(?:,|$)", line.strip())]
-    assert order == [f[0] for f in nat.SkinnyW8Args._fields_]
+    assert order == [f[0] for f in nat.SkinnyArgs._fields_] and order[-1] == "w_scale"
+    assert "const itts_skinny_args* a" in txt[txt.index("int itts_gemm_skinny_w8("):]
     # packed bytes: ceil(N / 16) * ceil(K / 64) KiB
     for K in (64, 96, 1280):
         for N in (16, 20, 8194):
@@ -141,13 +139,13 @@ def test_abi_symbols_sizes_plan_and_refusals():
                 assert gx * p["tiles_per_wg"] >= -(-N // 16) and p["waves"] * p["ksteps_per_wave"] >= -(-K // 64)
                 assert p["lds"] <= 160 * 1024
     # refusals name the entry point and launch nothing
-    a = nat.SkinnyW8Args()
+    a = nat.SkinnyArgs()
     assert L.itts_gemm_skinny_w8(ctypes.byref(a), None) == 1 and b"itts_gemm_skinny_w8: null" in L.itts_last_error()
     a.wp = a.x = a.y = a.w_scale = 0x1000        # never dereferenced: every call below fails its checks
     a.dtype, a.M, a.N, a.K, a.epi = nat.BF16, 4, 64, 64, nat.EPI_STORE
 
     def refused(word, **kw):
-        b = nat.SkinnyW8Args.from_buffer_copy(a)
+        b = nat.SkinnyArgs.from_buffer_copy(a)
         for k, v in kw.items():
             setattr(b, k, v)
         assert L.itts_gemm_skinny_w8(ctypes.byref(b), None) == 1
@@ -161,6 +159,8 @@ def test_abi_symbols_sizes_plan_and_refusals():
     refused(b"epilogue", epi=nat.EPI_SLAB_F32)
     refused(b"epilogue", epi=nat.EPI_SILU_STORE)
     refused(b"K % 32", K=48)
+    # ... and the 16-bit entry point never reads an FP8 image as 16-bit weights
+    assert L.itts_gemm_skinny(ctypes.byref(a), None) == 1 and L.itts_last_error().startswith(b"itts_gemm_skinny: w_scale")
     out = (ctypes.c_int * 8)()
     assert L.itts_skinny_plan_w8(nat.F32, 4, 64, 64, 0, 0, out) == 1 and b"itts_skinny_plan_w8" in L.itts_last_error()
 

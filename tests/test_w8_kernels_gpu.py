@@ -1,4 +1,4 @@
-"""fp64 parity of the FP8 (E4M3 weight-only) skinny-GEMM forms, itts_gemm_skinny_w8 (include/indextts_hip_w8.h), element by
+"""fp64 parity of the FP8 (E4M3 weight-only) skinny-GEMM forms, itts_gemm_skinny_w8 (include/indextts_hip.h), element by
 element, with the bound model of test_decode_kernels_gpu.py.
 
 The operands are exact: x is rounded to the activation type, the weights are E4M3 codes (every finite one is a bf16 and an f16
