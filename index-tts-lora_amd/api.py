@@ -6,6 +6,7 @@ Same routes, request fields, defaults and status codes as the reference server, 
 working:
     GET  /models          {"models": [{name, filename, type}], "current_model": ...}          (api.py:97-116)
     POST /model/reload    {"model_filename": ...} -> hot-swaps tts.gpt (404 when the file is missing)  (api.py:118-175)
+    POST /tts/stream      /tts's request (not in the reference) -> chunked audio/L16; rate=24000 while the token loop runs, header X-Seed
     POST /tts             text + prompt_audio (upload) | prompt_audio_path, infer_mode fast|normal, speaker_id, seed and the
                           generation knobs -> audio/wav, header X-Seed; 400 without a prompt, 404 for a missing prompt path,
                           503 before the engine is up, 500 with the error text otherwise                (api.py:177-300)
@@ -18,6 +19,7 @@ from __future__ import annotations
 import argparse
 import json
 import os
+import queue
 import random
 import tempfile
 import threading
@@ -27,7 +29,8 @@ from email.parser import BytesParser
 from typing import Optional
 
 from fastapi import FastAPI, HTTPException, Request
-from fastapi.responses import Response
+from fastapi.concurrency import run_in_threadpool
+from fastapi.responses import Response, StreamingResponse
 from pydantic import BaseModel
 
 
@@ -134,8 +137,8 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
         except Exception as e:  # noqa: BLE001
             raise HTTPException(status_code=500, detail=str(e))
 
-    @app.post("/tts")
-    async def text_to_speech(request: Request):
+    async def read_request(request: Request):
+        """The /tts body in any of its three encodings -> (TTSRequest, uploaded prompt (filename, bytes) | None); 422 when malformed."""
         ctype = request.headers.get("content-type", "")
         body = await request.body()
         upload = None
@@ -151,11 +154,15 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
                 fields = {k: v[-1] for k, v in urllib.parse.parse_qs(body.decode("utf-8")).items()}
             fields = {k: (None if isinstance(v, str) and v == "" and k in ("seed", "speaker_id", "prompt_audio_path") else v)
                       for k, v in fields.items()}
-            req = TTSRequest(**fields)
+            return TTSRequest(**fields), upload
         except HTTPException:
             raise
         except Exception as e:  # noqa: BLE001  (validation: FastAPI answers 422 for a malformed form)
             raise HTTPException(status_code=422, detail=str(e))
+
+    @app.post("/tts")
+    async def text_to_speech(request: Request):
+        req, upload = await read_request(request)
         if state["tts"] is None and not os.path.exists(model_dir):
             raise HTTPException(status_code=503, detail="the TTS engine is not initialised")
         if upload is None and not req.prompt_audio_path:
@@ -203,6 +210,70 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
         finally:
             if tmp_path and os.path.exists(tmp_path):
                 os.remove(tmp_path)
+
+    @app.post("/tts/stream")
+    async def text_to_speech_stream(request: Request):
+        """/tts's request, answered chunk by chunk while the token loop runs (IndexTTS.infer_stream): a chunked body of
+        little-endian 16-bit mono PCM, audio/L16; rate=24000, header X-Seed.  Sampling runs with num_beams = 1 (a beam
+        search has no final code before it ends); infer_mode, speaker_id and the bucket size do not apply.
+        A worker thread takes the engine lock, runs the generation to its end and queues the chunks; the response drains the
+        queue.  The lock is therefore held for the generation only -- never while progress waits for the client or the event
+        loop -- and the uploaded prompt's file is removed when the worker ends, whether or not the body was read.  A request
+        (of either route) that arrives during a stream waits for the lock until that generation has ended, as two /tts
+        requests wait for one another; a client that reads slowly delays nobody, its chunks wait in the queue.
+        The first chunk is awaited before the response starts, so what fails before it -- an unreadable prompt, a refused
+        setting -- answers with /tts's status codes (500 with the error text); an error after it ends the body early."""
+        req, upload = await read_request(request)
+        if state["tts"] is None and not os.path.exists(model_dir):
+            raise HTTPException(status_code=503, detail="the TTS engine is not initialised")
+        if upload is None and not req.prompt_audio_path:
+            raise HTTPException(status_code=400, detail="a reference audio is required (upload a file or give a path)")
+        actual_seed = random.randint(0, 2 ** 32 - 1) if req.seed is None or req.seed == -1 else int(req.seed)
+        tmp_path = None
+        if upload is not None:
+            suffix = os.path.splitext(upload[0] or "")[1] or ".wav"
+            with tempfile.NamedTemporaryFile(delete=False, suffix=suffix) as tmp:
+                tmp.write(upload[1])
+                tmp_path = prompt = tmp.name
+        else:
+            if not os.path.exists(req.prompt_audio_path):
+                raise HTTPException(status_code=404, detail=f"reference audio {req.prompt_audio_path} does not exist")
+            if not _inside(req.prompt_audio_path, prompt_roots):
+                raise HTTPException(status_code=403, detail="server-side prompts are only read from the prompt directory")
+            prompt = req.prompt_audio_path
+        kwargs = dict(do_sample=req.do_sample, top_p=req.top_p, top_k=req.top_k if req.top_k > 0 else 30,
+                      temperature=req.temperature, repetition_penalty=req.repetition_penalty,
+                      length_penalty=req.length_penalty, num_beams=1, max_mel_tokens=req.max_mel_tokens, seed=actual_seed)
+
+        chunks: "queue.Queue" = queue.Queue()     # bytes, then None (the end) or the exception that ended the generation
+
+        def work():
+            import torch
+            try:
+                with lock, torch.no_grad():
+                    for _, pcm in engine().infer_stream(prompt, req.text, req.max_text_tokens_per_sentence, **kwargs):
+                        chunks.put(pcm.float().cpu().numpy().astype("<i2").tobytes())
+                chunks.put(None)
+            except BaseException as e:  # noqa: BLE001  (handed to the response, which answers or ends the body)
+                chunks.put(e)
+            finally:
+                if tmp_path and os.path.exists(tmp_path):
+                    os.remove(tmp_path)
+
+        threading.Thread(target=work, name="tts-stream", daemon=True).start()
+        first = await run_in_threadpool(chunks.get)
+        if isinstance(first, HTTPException):
+            raise first
+        if isinstance(first, BaseException):
+            raise HTTPException(status_code=500, detail=str(first))
+
+        def body():
+            item = first
+            while item is not None and not isinstance(item, BaseException):
+                yield item
+                item = chunks.get()
+
+        return StreamingResponse(body(), media_type="audio/L16; rate=24000", headers={"X-Seed": str(actual_seed)})
 
     return app
 

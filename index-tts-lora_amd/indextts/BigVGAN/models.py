@@ -302,3 +302,60 @@ class BigVGAN:
         return wav, None
 
     __call__ = forward
+
+    # ---- windows of a long utterance ----------------------------------------------------------------------------
+    def receptive_halo(self):
+        """(left, right) in latent frames: every output sample of frame t is a function of the latent frames
+        [t - left, t + right] only.  From the configuration alone.
+
+        Place sample n of a tensor at rate R (samples per latent frame: the product of the up-sampling rates in front of it) at
+        x = n / R.  A layer whose output at x reads its input within [x - l / R, x + r / R] widens the interval by l / R to the
+        left and r / R to the right; layers in a chain add, parallel branches take the widest:
+          conv_pre (models.py:151, :226, k = 7, padding 3)                      l = r = 3                         at R = 1
+          ups[i] (models.py:232-233, ConvTranspose1d k, stride u,             l = (k - 1 - p) / u, r = p / u    at R = R_i
+                  p = (k - u) / 2: output t' reads q = (t' + p - s) / u, 0 <= s < k)
+          AMPBlock1 (models.py:65-74), per dilation d: convs1 (k, d) and   l = r = (k - 1) / 2 * (d + 1)     at R = R_i * u
+                  convs2 (k, 1); the blocks of a stage run side by side
+                  and are averaged (models.py:236-245): the widest block counts
+          Activation1d (act.py:10-28): the 12-tap FIR of UpSample1d at    l = r = (6 + 5) / 2               at its input's R
+                  the 2x rate reads 6 samples behind and 5 ahead
+                  (resample.py:29-34), the stride-2 low-pass of
+                  DownSample1d 5 behind and 6 ahead (filter.py:77-95):
+                  11 samples at 2R per side.  Two per dilation of an
+                  AMPBlock1, one in front of conv_post
+          conv_post (models.py:186, :249, k = 7, padding 3)                     l = r = 3                         at R = hop
+        A sample of frame t lies at x in [t, t + 1 - 1 / hop] and reads the frames q (integers) of [x - L, x + Rr] for the sums
+        L, Rr.  The earliest is ceil(t - L) = t - floor(L), the latest floor(t + 1 - 1 / hop + Rr): the sums are rounded once,
+        here, left = floor(L) and right = floor(Rr + 1 - 1 / hop) (= ceil(Rr) unless Rr is a whole number of frames).  The
+        shipped configuration gives L = 35.79, Rr = 34.79: (35, 35)."""
+        from fractions import Fraction as Fr
+        L, Rr = Fr(3), Fr(3)                                    # conv_pre
+        R = 1
+        act = Fr(11, 2)
+        amp = max(sum(Fr(rk - 1, 2) * (d + 1) + 2 * act for d in dils) for rk, dils in zip(self.res_k, self.res_d))
+        for u, k in zip(self.rates, self.ksizes):
+            p = (k - u) // 2
+            L += Fr(k - 1 - p, u * R)
+            Rr += Fr(p, u * R)
+            R *= u
+            L += amp / R
+            Rr += amp / R
+        L += (act + 3) / R                                       # activation_post, conv_post
+        Rr += (act + 3) / R
+        return int(math.floor(L)), int(math.floor(Rr + 1 - Fr(1, R)))
+
+    def vocode_window(self, latents: torch.Tensor, spk: torch.Tensor, t0: int, t1: int) -> torch.Tensor:
+        """The samples of frames [t0, t1) of the utterance whose latents are `latents` [T, gpt_dim] (spk: its speaker embedding
+        [1, 1, 512]): forward() over the frames [max(0, t0 - left), min(T, t1 + right)) of receptive_halo(), cut to
+        [t0 * hop, t1 * hop) -> fp32 [(t1 - t0) * hop] in [-1, 1].  Inside the utterance the window's own edges lie outside what
+        those samples read; where the window is clipped the edge IS the utterance's (T is its true length), and the forward's
+        edge handling -- zero padding of the convolutions, replicate padding of the activations -- applies as in a whole run."""
+        T = int(latents.shape[0])
+        t0, t1 = int(t0), int(t1)
+        if not 0 <= t0 < t1 <= T:
+            raise ValueError(f"vocode_window: frames [{t0}, {t1}) of an utterance of {T}")
+        left, right = self.receptive_halo()
+        lo, hi = max(0, t0 - left), min(T, t1 + right)
+        wav, _ = self.forward(latents[None, lo:hi], speaker_embedding=spk)
+        hop = wav.shape[-1] // (hi - lo)
+        return wav[0, 0, (t0 - lo) * hop: (t1 - lo) * hop]

@@ -13,6 +13,10 @@ def main(argv=None):
     parser.add_argument("--model_dir", type=str, default="checkpoints", help="model directory")
     parser.add_argument("--fp16", action="store_true", default=True, help="half-precision GPT weights when available")
     parser.add_argument("-f", "--force", action="store_true", default=False, help="overwrite the output file")
+    parser.add_argument("--stream", action="store_true", default=False,
+                        help="synthesise chunk by chunk while the token loop runs (IndexTTS.infer_stream) and write the chunks to the same "
+                             "path in the same format; the stream samples with num_beams = 1 (the default path keeps 3 beams), so "
+                             "the samples differ from a run without this flag")
     parser.add_argument("-d", "--device", type=str, default=None, help="device (cuda:N); CPU/MPS are not supported")
     args = parser.parse_args(argv)
 
@@ -43,6 +47,17 @@ def main(argv=None):
         args.device = "cuda:0"
     from indextts.infer import IndexTTS
     tts = IndexTTS(cfg_path=args.config, model_dir=args.model_dir, is_fp16=args.fp16, device=args.device)
+    if args.stream:
+        from indextts.utils.audio import write_pcm16
+        rate, chunks = 24000, []
+        for rate, pcm in tts.infer_stream(audio_prompt=args.voice, text=args.text.strip()):
+            chunks.append(pcm.cpu())
+        if os.path.dirname(args.output_path) != "":
+            os.makedirs(os.path.dirname(args.output_path), exist_ok=True)
+        wav = torch.cat(chunks) if chunks else torch.zeros(0)
+        write_pcm16(args.output_path, wav.to(torch.float32).numpy().astype("int16"), rate)
+        print(f">> [output] saved to: {args.output_path}")
+        return
     tts.infer(audio_prompt=args.voice, text=args.text.strip(), output_path=args.output_path)
 
 

@@ -1257,19 +1257,17 @@ class GPTEngine:
         self.row_sampling.flush()
         return PER_ROW
 
-    def decode(self, max_new: int, sp, force_stop=None, use_graph=True, check_every=16, return_logits=False):
-        """Run the sampling loop after prefill().  Returns codes int64 [B, n] padded with the stop token
-        (HF generate semantics: rows that emitted EOS keep emitting pad = EOS).
-        sp: one dict for the whole batch, or a list of B dicts (check_row_settings) -- every row under its own settings, seed and
-        draw stream (itts_sample_rows); the captured step is the same for every such list."""
+    def _loop_setup(self, who, max_new, sp, force_stop):
+        """What the sampling loop needs after prefill(), for decode() and decode_chunks(): the checks, the cache cover, the
+        force_stop upload.  Returns (B, sp checked, per_row); the caller seeds the state and draws token 1."""
         B = self._B
         per_row = isinstance(sp, (list, tuple))
         if per_row:
             sp = self.check_row_settings(sp, B)
         if self._shared_prefix is not None:
-            raise ValueError("decode(): prefill(beams=n) cached the prompt once per batch element; only decode_beam() can follow it")
+            raise ValueError(f"{who}(): prefill(beams=n) cached the prompt once per batch element; only decode_beam() can follow it")
         if self.kv is None and self._S + max_new + 1 > self._cap_s:
-            raise ValueError("decode(): max_new exceeds the capacity reserved by prefill()")
+            raise ValueError(f"{who}(): max_new exceeds the capacity reserved by prefill()")
         if self.kv is not None:
             for b in range(B):                                   # (no-op when prefill() was given the same max_new)
                 self.kv.cover(b, self._pad_host[b], self._S + max_new + 1)
@@ -1278,6 +1276,14 @@ class GPTEngine:
             self.force_stop[:B] = -1
         else:
             self.force_stop[:B] = torch.as_tensor(force_stop, dtype=torch.int32).to(self.device)
+        return B, sp, per_row
+
+    def decode(self, max_new: int, sp, force_stop=None, use_graph=True, check_every=16, return_logits=False):
+        """Run the sampling loop after prefill().  Returns codes int64 [B, n] padded with the stop token
+        (HF generate semantics: rows that emitted EOS keep emitting pad = EOS).
+        sp: one dict for the whole batch, or a list of B dicts (check_row_settings) -- every row under its own settings, seed and
+        draw stream (itts_sample_rows); the captured step is the same for every such list."""
+        B, sp, per_row = self._loop_setup("decode", max_new, sp, force_stop)
         logits_trace = [self.logits[:B].clone()] if return_logits else None
         sp = self._rows_to_table(sp) if per_row else self._seed_to_state(sp)
         self._sample(B, sp)  # token 1 from the prefill logits
@@ -1286,6 +1292,32 @@ class GPTEngine:
         self._poll()
         codes = self.history[:B, :n].to(torch.int64)
         return (codes, torch.stack(logits_trace, 0)) if return_logits else codes
+
+    def decode_chunks(self, max_new: int, sp, chunk: int, force_stop=None, use_graph=True):
+        """decode() as a generator: the sampling loop after prefill(), run in bursts of `chunk` tokens.  After every burst it polls
+        and yields (codes int64 [B, n] on the host -- the n tokens every row has so far, stop-token padded as decode() pads --,
+        finished flags bool [B] on the host); it ends when every row has finished or n == max_new.  Same set-up, same steps
+        and the same graph key as decode(): one captured step serves both, and the tokens are decode()'s for the same sp.
+        Between two bursts the caller may run latent_mel_rows() / latent() (and anything that is not the engine's) on the same
+        stream: those passes work on buffers of their own (_big_m_layers allocates its operands, slabs included), read the
+        prompt's cache positions only, and touch none of the step's h / hb / xn / a / f / q / slab / logits / state / tokens /
+        history.  Not between bursts: prefill(), decode*() or anything else that writes the loop state."""
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError("decode_chunks(): chunk must be at least one token")
+        B, sp, per_row = self._loop_setup("decode_chunks", max_new, sp, force_stop)
+        sp = self._rows_to_table(sp) if per_row else self._seed_to_state(sp)
+        self._sample(B, sp)  # token 1 from the prefill logits
+        key = self._graph_key("token", B, sp)
+        body = lambda: self._step_kernels(B, sp)   # noqa: E731
+        n = 1
+        while True:
+            # the next multiple of chunk (token 1, drawn from the prefill logits, counts towards the first burst)
+            n = self._token_loop(n, min((n // chunk + 1) * chunk, max_new), body, key, use_graph)
+            done = self._poll() >= B
+            yield self.history[:B, :n].to(torch.int64).cpu(), self.finished[:B].cpu() != 0
+            if done or n >= max_new:
+                return
 
     # ------------------------------------------------------------------------------------------------ slot refill
     def _stage(self, rows, prefixes, stops, n, mixes=None):

@@ -773,6 +773,114 @@ class IndexTTS:
         outs = self._batch_waveforms(st, phase_events, reuse_prefix=True)   # serial: the KV cache still holds this batch's prompt
         return (outs, st["rows"]) if return_codes else outs
 
+    # ------------------------------------------------------------------------------------------------ streaming
+    @staticmethod
+    def _stream_args(generation_kwargs, adapter_ids, adapter_mix):
+        """The checks of stream_utterance that need no device: (gen, one-element adapter_ids | None, adapter_mix | None)."""
+        kw = dict(generation_kwargs)
+        kw.setdefault("num_beams", 1)
+        gen, _ = IndexTTS._gen_kwargs(kw)
+        if kw:
+            raise TypeError(f"stream_utterance: unknown generation settings {sorted(kw)}")
+        if int(gen["num_beams"]) > 1:
+            raise NotImplementedError("stream_utterance: beam search picks its hypothesis when the loop ends, so no code is final "
+                                      "before that; streaming is built for num_beams = 1")
+        for name, v in (("adapter_ids", adapter_ids), ("adapter_mix", adapter_mix)):
+            if v is not None and (isinstance(v, (str, dict)) or not hasattr(v, "__len__") or len(v) != 1):
+                raise ValueError(f"stream_utterance: {name} names the voice of ONE utterance: a one-element list")
+        if adapter_ids is not None and adapter_mix is not None:
+            raise ValueError("stream_utterance: adapter_ids or adapter_mix, one of them")
+        return gen, adapter_ids, adapter_mix
+
+    def stream_utterance(self, cond_mel, text_tokens, chunk_tokens=32, max_mel_tokens=600, seed=1234, force_stop=None,
+                         adapter_ids=None, adapter_mix=None, _trace: dict | None = None, **generation_kwargs):
+        """ONE utterance as a generator of PCM chunks (fp32 tensors on the device, int16 range, like infer_batch's waveforms) that
+        are produced while the token loop is still running; their concatenation is the utterance.
+        Every chunk_tokens tokens the loop pauses (GPTEngine.decode_chunks).  With k codes known and no stop token among them,
+        the teacher-forced pass runs over them (_latents with reuse_prefix: only the mel rows, over the prompt K / V the
+        prefill left in the decode cache; the whole sequence for an FP8 KV cache).  The pass is causal and row i reads the
+        codes < i only, so rows 0 .. k-1 are final.  The vocoder's receptive field is finite (BigVGAN.receptive_halo):
+        the samples of frame t read the latent frames [t - left, t + right], so the frames [emitted, k - right) are vocoded
+        from a window (BigVGAN.vocode_window) and yielded.  At the stop token, or at max_mel_tokens, the rest is flushed against
+        the utterance's true end.  All of it is launched on the loop's stream, between two bursts; the passes work on buffers
+        of their own (see decode_chunks).
+        The latent pass is repeated over all k codes at every boundary: quadratic in the utterance length, at most 600 rows
+        per pass; an incremental pass is not built.
+        Silence: the reference's remove_long_silence is not causal -- it shortens silent runs only when the WHOLE row holds
+        more than 30 silent tokens, which is known when the loop ends.  The stream applies only its cut at the stop token.  For
+        an utterance with at most 30 silent tokens that is all remove_long_silence does, and the stream equals infer_batch.
+        num_beams defaults to 1 here (the whole-utterance calls keep the reference's 3) and a larger value is refused.
+        adapter_ids / adapter_mix: one-element lists, the utterance's voice of an attached bank, as infer_batch takes them.
+        _trace (private: tests, tools): receives "codes" (the utterance's codes, host int64), "frames" (the [t0, t1) of every chunk) and
+        "latent" (per chunk, the rows [t0, t1) its window was vocoded from).
+        The checks run when this is called; the device work starts with the first next()."""
+        gen, adapter_ids, adapter_mix = IndexTTS._stream_args(generation_kwargs, adapter_ids, adapter_mix)
+        if isinstance(cond_mel, (list, tuple)):
+            raise ValueError("stream_utterance: one utterance has one prompt mel")
+        text = torch.as_tensor(text_tokens).reshape(-1).to("cpu", torch.int32)
+        chunk_tokens, max_mel_tokens = int(chunk_tokens), int(max_mel_tokens)
+        if chunk_tokens < 1:
+            raise ValueError("stream_utterance: chunk_tokens must be at least 1")
+        if force_stop is not None:
+            force_stop = [int(v) for v in torch.as_tensor(force_stop).reshape(-1).tolist()]
+            if len(force_stop) != 1:
+                raise ValueError("stream_utterance: force_stop holds one entry")
+        return self._stream(cond_mel, text, chunk_tokens, max_mel_tokens, seed, force_stop, adapter_ids, adapter_mix, _trace, gen)
+
+    @staticmethod
+    def stream_plan(k: int, emitted: int, right: int, final: bool):
+        """The frames a chunk boundary emits: [emitted, hi).  k: the codes known (final: the utterance's length -- the stop token or
+        the token limit has been reached); right: the vocoder's halo towards the future.  Before the end a frame is emitted once
+        the `right` frames behind it exist; the end flushes the rest."""
+        return emitted, (k if final else max(emitted, k - right))
+
+    def _stream(self, cond_mel, text, chunk_tokens, max_mel_tokens, seed, force_stop, adapter_ids, adapter_mix, trace, gen):
+        g, eng = self.gpt, self.gpt.engine
+        if adapter_ids is not None:
+            adapter_ids = eng._row_adapters(adapter_ids, 1)
+        if adapter_mix is not None:
+            adapter_mix = eng._voices(None, adapter_mix, 1)[1]
+        conds, spk = self._prompt_features(cond_mel)
+        emb, pad = g.prefix_rows(conds, text[None])
+        sp = sampling_params(gen, seed)
+        eng.prefill(emb, pad, max_mel_tokens, shared_rows=int(conds.shape[1]), adapter_ids=adapter_ids, adapter_mix=adapter_mix)
+        right = self.bigvgan.receptive_halo()[1]
+        stop, emitted = g.stop_mel_token, 0
+        if trace is not None:
+            trace.update(codes=None, frames=[], latent=[])
+        for codes, _ in eng.decode_chunks(max_mel_tokens, sp, chunk_tokens, force_stop=force_stop):
+            row = codes[0]
+            hit = (row == stop).nonzero()
+            final = bool(hit.numel()) or row.numel() >= max_mel_tokens
+            k = int(hit[0]) if hit.numel() else int(row.numel())       # the cut of remove_long_silence at the stop token
+            t0, t1 = self.stream_plan(k, emitted, right, final)
+            if t1 > t0:
+                lat = self._latents(conds, [text], [row[:k]], reuse_prefix=True, adapter_ids=adapter_ids, adapter_mix=adapter_mix)[0]
+                wav = self.bigvgan.vocode_window(lat, spk, t0, t1)
+                if trace is not None:
+                    trace["frames"].append((t0, t1))
+                    trace["latent"].append(lat[t0:t1].clone())
+                emitted = t1
+                yield torch.clamp(32767 * wav, -32767.0, 32767.0)
+            if final:
+                if not hit.numel():
+                    warnings.warn(f"generation stopped at max_mel_tokens ({max_mel_tokens}); consider shorter sentences",
+                                  category=RuntimeWarning)
+                if trace is not None:
+                    trace["codes"] = row[:k].clone()
+                return
+
+    def infer_stream(self, audio_prompt, text, max_text_tokens_per_sentence=120, **kw):
+        """infer() as a generator of (sampling rate, PCM chunk): the text is split into sentences as infer() splits it and the
+        sentences are streamed one after another (stream_utterance, whose keywords -- chunk_tokens, seed, the generation
+        settings -- pass through).  A chunk is an fp32 device tensor in the int16 range."""
+        cond_mel = self._prompt(audio_prompt)
+        sentences = self.tokenizer.split_sentences(self.tokenizer.tokenize(text), max_text_tokens_per_sentence)
+        for sent in sentences:
+            ids = torch.tensor(self.tokenizer.convert_tokens_to_ids(sent), dtype=torch.int32)
+            for pcm in self.stream_utterance(cond_mel, ids, **kw):
+                yield 24000, pcm
+
     def infer_queue(self, cond_mel: torch.Tensor, text_token_rows: List[torch.Tensor], slots=32, max_mel_tokens=600,
                     force_stop=None, seed=1234, return_codes=False, cache_positions=4096, check_every=16, staged=True,
                     phase_events: dict | None = None, sampling=None, adapter_ids=None, adapter_mix=None, **generation_kwargs):
