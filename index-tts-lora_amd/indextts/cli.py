@@ -17,6 +17,9 @@ def main(argv=None):
                         help="synthesise chunk by chunk while the token loop runs (IndexTTS.infer_stream) and write the chunks to the same "
                              "path in the same format; the stream samples with num_beams = 1 (the default path keeps 3 beams), so "
                              "the samples differ from a run without this flag")
+    parser.add_argument("--stream-parallel", type=int, default=1, metavar="P",
+                        help="with --stream: up to P sentences of the text share one token loop (IndexTTS.infer_stream("
+                             "parallel_sentences=P)); the chunks are still written in text order.  1 streams sentence by sentence")
     parser.add_argument("-d", "--device", type=str, default=None, help="device (cuda:N); CPU/MPS are not supported")
     args = parser.parse_args(argv)
 
@@ -27,6 +30,8 @@ def main(argv=None):
 
     if len(args.text.strip()) == 0:
         fail("text is empty")
+    if args.stream_parallel < 1:
+        fail("--stream-parallel must be at least 1")
     if not os.path.exists(args.voice):
         fail(f"reference audio {args.voice} does not exist")
     if not os.path.exists(args.config):
@@ -50,7 +55,7 @@ def main(argv=None):
     if args.stream:
         from indextts.utils.audio import write_pcm16
         rate, chunks = 24000, []
-        for rate, pcm in tts.infer_stream(audio_prompt=args.voice, text=args.text.strip()):
+        for rate, pcm in tts.infer_stream(audio_prompt=args.voice, text=args.text.strip(), parallel_sentences=args.stream_parallel):
             chunks.append(pcm.cpu())
         if os.path.dirname(args.output_path) != "":
             os.makedirs(os.path.dirname(args.output_path), exist_ok=True)

@@ -1014,8 +1014,10 @@ class GPTEngine:
         with its key tiles cut from sequence position 0 as in latent().  Same bits as latent() on the whole sequence
         (tests/test_engines_gpu.py::test_latent_pass_reuses_the_cached_prompt).
         mel_emb fp32 [sum(m_lens), D]: the mel segments' embeddings, elements in prefill order; cache_rows: the cache row that
-        holds element b's prompt (default b; b * num_beams after a beam prefill that copied rows).
-        adapter_ids: the ids prefill() was given (the default): the cached prompt K / V were computed under them, other ids are refused.
+        holds element b's prompt (default b; b * num_beams after a beam prefill that copied rows; any subset of the prefilled rows,
+        as the batched stream passes the rows that emit at a boundary).
+        adapter_ids: the ids prefill() was given (the default), element b's that of its cache row: the cached prompt K / V were
+        computed under them, other ids are refused.
         adapter_mix: likewise the mixes prefill() was given (the default after such a prefill); other mixes, or ids, are refused.
         Returns final_norm(ln_f(hidden)) fp32 [sum(m_lens), D]."""
         import numpy as np
@@ -1024,17 +1026,27 @@ class GPTEngine:
                                       "(kv_dtype='fp8') run latent() on the whole sequence")
         T, D, H, dev = self.dtype, self.D, self.H, self.device
         B, P = len(m_lens), self._S - 1
+        whole = cache_rows is None                         # the batch as prefilled: as many voices as rows
+        cache_rows = list(range(B)) if whole else [int(r) for r in cache_rows]
+        if len(cache_rows) != B or max(cache_rows) >= len(self._pad_host) or min(cache_rows) < 0:
+            raise ValueError("latent_mel_rows(): the batch differs from the one prefill() cached")
+
+        def cached(voices):      # the voices the prompts in cache_rows were prefilled under (None: none)
+            if voices is None:
+                return None
+            if len(voices) != B if whole else max(cache_rows) >= len(voices):
+                raise ValueError("latent_mel_rows(): the cached prompt was prefilled under other adapter ids" if voices is self._ids_host
+                                 else "latent_mel_rows(): the cached prompt was prefilled under other adapter mixes")
+            return [voices[r] for r in cache_rows]
+        had_ids, had_mix = cached(self._ids_host), cached(self._mix_host)
         if adapter_ids is None and adapter_mix is None:
-            ids, mix = self._ids_host, self._mix_host
+            ids, mix = had_ids, had_mix
         else:
             ids, mix = self._voices(adapter_ids, adapter_mix, B)
-        if mix is not None and mix != self._mix_host:
+        if mix is not None and list(mix) != had_mix:
             raise ValueError("latent_mel_rows(): the cached prompt was prefilled under other adapter mixes")
-        if ids is not None and (self._ids_host is None or list(ids) != list(self._ids_host[:B]) or len(self._ids_host) != B):
+        if ids is not None and list(ids) != had_ids:
             raise ValueError("latent_mel_rows(): the cached prompt was prefilled under other adapter ids")
-        cache_rows = list(range(B)) if cache_rows is None else [int(r) for r in cache_rows]
-        if len(cache_rows) != B or max(cache_rows) >= len(self._pad_host):
-            raise ValueError("latent_mel_rows(): the batch differs from the one prefill() cached")
         pads = [self._pad_host[r] for r in cache_rows]   # (a prefill of expanded beam rows lists the padding per cache row)
         pl = [P - p for p in pads]                        # real prompt rows per element
         m = [int(v) for v in m_lens]

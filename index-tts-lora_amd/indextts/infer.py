@@ -613,37 +613,52 @@ class IndexTTS:
         bucket).  Returns the list of waveforms [T_i * hop], each bit-identical to
         vocoding that utterance alone (BigVGAN.forward(lens=...)): utterances are sorted by length and vocoded in
         buckets of similar length -- one launch sequence per bucket instead of one per distinct length."""
+        return self._vocode_windows(lat, spk, [(0, int(x.shape[0])) for x in lat])
+
+    def _vocode_windows(self, lat, spk, plans):
+        """The samples of the frames [t0_i, t1_i) = plans[i] of utterance i, whose latents so far are lat[i] [T_i, D]; spk as in
+        _vocode_ragged.  Utterance i is vocoded over the window [max(0, t0_i - left), min(T_i, t1_i + right)) of
+        BigVGAN.receptive_halo(), as BigVGAN.vocode_window does it alone: the windows are sorted by length and run in buckets
+        of similar length, zero-padded to the bucket's longest (BigVGAN.forward(lens=...): every element's samples are, bit for
+        bit, those of that window vocoded alone), and each is cut to [t0_i, t1_i).  Returns the list of fp32 waveforms
+        [(t1_i - t0_i) * hop] in the int16 range.  A window clipped at T_i ends at a true edge only when T_i is the utterance's
+        length: the caller plans a frame once the `right` frames behind it exist (stream_plan).  plans (0, T_i) are the whole
+        utterances: _vocode_ragged."""
         outs = [None] * len(lat)
         per_row = spk.shape[0] != 1
         if per_row and spk.shape[0] != len(lat):
             raise ValueError(f"{spk.shape[0]} speaker embeddings for {len(lat)} utterances")
+        if len(plans) != len(lat) or any(not 0 <= t0 <= t1 <= int(x.shape[0]) for x, (t0, t1) in zip(lat, plans)):
+            raise ValueError(f"_vocode_windows: frames {list(plans)} of utterances of {[int(x.shape[0]) for x in lat]}")
+        left, right = self.bigvgan.receptive_halo()
+        win = [(max(0, t0 - left), min(int(x.shape[0]), t1 + right)) if t1 > t0 else (0, 0) for x, (t0, t1) in zip(lat, plans)]
         spk_all = spk
-        order = sorted(range(len(lat)), key=lambda i: int(lat[i].shape[0]))
+        order = sorted(range(len(lat)), key=lambda i: win[i][1] - win[i][0])
         k = 0
         while k < len(order):
-            t_min = int(lat[order[k]].shape[0])
+            t_min = win[order[k]][1] - win[order[k]][0]
             if t_min == 0:
                 outs[order[k]] = torch.zeros(0, device=self.device)
                 k += 1
                 continue
             e = k
-            while e < len(order) and int(lat[order[e]].shape[0]) <= self.VOCODER_BUCKET_RATIO * t_min:
+            while e < len(order) and win[order[e]][1] - win[order[e]][0] <= self.VOCODER_BUCKET_RATIO * t_min:
                 e += 1
             idx = order[k:e]
-            lens = [int(lat[i].shape[0]) for i in idx]
+            lens = [win[i][1] - win[i][0] for i in idx]
             t_max = lens[-1]
             if per_row:
                 spk = spk_all[torch.tensor(idx, device=spk_all.device)]
             if lens[0] == t_max:
-                wav = self._vocode(torch.stack([lat[i] for i in idx], 0), spk)
+                wav = self._vocode(torch.stack([lat[i][win[i][0]: win[i][1]] for i in idx], 0), spk)
             else:
                 x = torch.zeros(len(idx), t_max, lat[idx[0]].shape[1], dtype=lat[idx[0]].dtype, device=lat[idx[0]].device)
                 for j, i in enumerate(idx):
-                    x[j, : lens[j]] = lat[i]
+                    x[j, : lens[j]] = lat[i][win[i][0]: win[i][1]]
                 wav = self._vocode(x, spk, lens=lens)
             hop = wav.shape[1] // t_max
             for j, i in enumerate(idx):
-                outs[i] = wav[j, : lens[j] * hop]
+                outs[i] = wav[j, (plans[i][0] - win[i][0]) * hop: (plans[i][1] - win[i][0]) * hop]
             k = e
         return outs
 
@@ -870,16 +885,179 @@ class IndexTTS:
                     trace["codes"] = row[:k].clone()
                 return
 
-    def infer_stream(self, audio_prompt, text, max_text_tokens_per_sentence=120, **kw):
+    # ------------------------------------------------------------------------------------------------ batched streaming
+    @staticmethod
+    def _stream_batch_args(n_rows, chunk_tokens, max_mel_tokens, force_stop, adapter_ids, adapter_mix, sampling, generation_kwargs):
+        """The checks of stream_batch that need neither a model nor a device: (gen, chunk_tokens, max_mel_tokens, force_stop as
+        n_rows host ints | None)."""
+        kw = dict(generation_kwargs)
+        kw.setdefault("num_beams", 1)
+        gen, _ = IndexTTS._gen_kwargs(kw)
+        if kw:
+            raise TypeError(f"stream_batch: unknown generation settings {sorted(kw)}")
+        if int(gen["num_beams"]) > 1:
+            raise NotImplementedError("stream_batch: beam search picks its hypothesis when the loop ends, so no code is final "
+                                      "before that; streaming is built for num_beams = 1")
+        if adapter_ids is not None and adapter_mix is not None:
+            raise ValueError("stream_batch: adapter_ids or adapter_mix, one of them")
+        for name, v in (("adapter_ids", adapter_ids), ("adapter_mix", adapter_mix), ("sampling", sampling)):
+            if v is not None and (isinstance(v, (str, dict)) or not hasattr(v, "__len__") or len(v) != n_rows):
+                raise ValueError(f"stream_batch: {name} is a list with one entry per utterance ({n_rows})")
+        chunk_tokens, max_mel_tokens = int(chunk_tokens), int(max_mel_tokens)
+        if chunk_tokens < 1:
+            raise ValueError("stream_batch: chunk_tokens must be at least 1")
+        if force_stop is not None:
+            force_stop = force_stop.reshape(-1).tolist() if torch.is_tensor(force_stop) else list(force_stop)
+            if len(force_stop) != n_rows:
+                raise ValueError(f"stream_batch: force_stop holds one entry per utterance ({n_rows}; None or -1: no forced stop)")
+            force_stop = [-1 if v is None else int(v) for v in force_stop]
+        return gen, chunk_tokens, max_mel_tokens, force_stop
+
+    def stream_batch(self, cond_mel, text_token_rows, chunk_tokens=32, max_mel_tokens=600, seed=1234, force_stop=None,
+                     adapter_ids=None, adapter_mix=None, sampling=None, _trace: dict | None = None, **generation_kwargs):
+        """stream_utterance for N utterances in ONE token loop: a generator of events (row, pcm, last) -- row: the index into
+        text_token_rows; pcm: an fp32 device tensor in the int16 range, the next samples of that utterance; last: this is the
+        row's final event (exactly one per row; its pcm is empty when nothing was left to flush).  The concatenation of a row's
+        pcm is that utterance, hop * T_row samples; the events of one boundary come in ascending row order.
+        One prefill and one decode_chunks(chunk_tokens) over all rows, as infer_batch prefills and decodes them (same graph key as
+        decode() at this B: no new capture).  At every boundary, each row that has not ended is planned on its own (stream_batch_plan:
+        its codes up to its first stop token, its own emitted count, stream_plan unchanged); the rows that emit share ONE latent
+        pass (_latents with reuse_prefix over those cache rows; the whole-sequence pass on an FP8 KV cache) and one ragged
+        vocoder call per bucket of similar window lengths (_vocode_windows), so a row's chunk is bit for bit
+        BigVGAN.vocode_window of the same latents.  Rows end at different tokens; a row that has ended costs nothing further.
+        cond_mel (one mel, or a list with one per row), adapter_ids, adapter_mix, sampling: as infer_batch takes and checks them;
+        force_stop: one entry per row (None / -1: none).  num_beams defaults to 1 and a larger value is refused, the silence rule is
+        the cut at the stop token and the latent pass is repeated per boundary, all as in stream_utterance; the max_mel_tokens
+        warning is given once per row that reaches the limit.
+        Closing the generator early abandons the loop; the next prefill() starts from a clean state as after any decode.
+        _trace (private: tests, tools) receives, per row, "codes" (host int64), "frames" ([(t0, t1)]), "latent" (per chunk, the rows
+        [t0, t1) its window was cut from), "window" (per chunk, (lo, the latent rows [lo, hi) the vocoder ran over)) and "boundaries"
+        (the n of every poll the row was planned at).
+        The checks run when this is called; the device work starts with the first next()."""
+        N = len(text_token_rows)
+        gen, chunk_tokens, max_mel_tokens, force_stop = IndexTTS._stream_batch_args(
+            N, chunk_tokens, max_mel_tokens, force_stop, adapter_ids, adapter_mix, sampling, generation_kwargs)
+        if sampling is not None:
+            sampling = row_sampling_params(sampling, N, gen, seed)
+        cond_mel = IndexTTS._check_prompts(self, cond_mel, N, gen, "stream_batch")
+        texts = [torch.as_tensor(t).reshape(-1).to("cpu", torch.int32) for t in text_token_rows]
+        if N == 0:
+            return iter(())
+        adapter_ids, adapter_mix = self.gpt.engine._voices(adapter_ids, adapter_mix, N)    # (no bank: None, None)
+        return self._stream_rows(cond_mel, texts, chunk_tokens, max_mel_tokens, seed, force_stop, adapter_ids, adapter_mix, sampling,
+                                 _trace, gen)
+
+    @staticmethod
+    def stream_batch_plan(codes, emitted, ended, right, max_mel_tokens, stop):
+        """One boundary of stream_batch on the host.  codes: int [B, n], what decode_chunks yields; emitted[b]: the frames row b
+        has given out; ended[b]: row b has had its last event.  Returns [(b, k, t0, t1, final)] in ascending b for the rows that
+        emit now: k = the position of the row's first stop token (the cut of remove_long_silence) or n; final = a stop token is
+        there or n has reached max_mel_tokens; (t0, t1) = stream_plan(k, emitted[b], right, final).  A row with nothing to emit that
+        is not final is left out; a final row is always there, with t1 == t0 when nothing is left."""
+        n = int(codes.shape[1])
+        is_stop = (codes == stop)
+        out = []
+        for b in range(int(codes.shape[0])):
+            if ended[b]:
+                continue
+            hit = is_stop[b].nonzero()
+            final = bool(hit.numel()) or n >= max_mel_tokens
+            k = int(hit[0]) if hit.numel() else n
+            t0, t1 = IndexTTS.stream_plan(k, emitted[b], right, final)
+            if t1 > t0 or final:
+                out.append((b, k, t0, t1, final))
+        return out
+
+    def _stream_rows(self, cond_mel, texts, chunk_tokens, max_mel_tokens, seed, force_stop, adapter_ids, adapter_mix, sampling, trace, gen):
+        g, eng = self.gpt, self.gpt.engine
+        N = len(texts)
+        per_row = isinstance(cond_mel, list)      # conds / spk hold a row per utterance: every boundary gathers its rows'
+        conds, spk = self._prompt_features(cond_mel)
+        batch_h = torch.full((N, max(int(t.numel()) for t in texts)), self.cfg.gpt.stop_text_token, dtype=torch.int32)
+        for i, t in enumerate(texts):
+            batch_h[i, : t.numel()] = t
+        emb, pad = g.prefix_rows(conds, batch_h)
+        sp = sampling_params(gen, seed) if sampling is None else sampling
+        shared = 0 if per_row or conds.shape[0] != 1 else int(conds.shape[1])    # one prompt: every row starts with the same latents
+        eng.prefill(emb, pad, max_mel_tokens, shared_rows=shared, adapter_ids=adapter_ids, adapter_mix=adapter_mix)
+        left, right = self.bigvgan.receptive_halo()
+        stop, emitted, ended = g.stop_mel_token, [0] * N, [False] * N
+        if trace is not None:
+            trace.update(codes=[None] * N, frames=[[] for _ in range(N)], latent=[[] for _ in range(N)],
+                         window=[[] for _ in range(N)], boundaries=[[] for _ in range(N)])
+        chunks = eng.decode_chunks(max_mel_tokens, sp, chunk_tokens, force_stop=force_stop)
+        try:
+            for codes, _ in chunks:
+                plan = self.stream_batch_plan(codes, emitted, ended, right, max_mel_tokens, stop)
+                if trace is not None:
+                    for b in range(N):
+                        if not ended[b]:
+                            trace["boundaries"][b].append(int(codes.shape[1]))
+                rows = [b for b, _, t0, t1, _ in plan if t1 > t0]
+                wavs = {}
+                if rows:
+                    sel = torch.tensor(rows, device=conds.device) if per_row else None
+                    lats = self._latents(conds[sel] if per_row else conds, [texts[b] for b in rows],
+                                         [codes[b, :k] for b, k, t0, t1, _ in plan if t1 > t0], reuse_prefix=True, cache_rows=rows,
+                                         adapter_ids=None if adapter_ids is None else [adapter_ids[b] for b in rows],
+                                         adapter_mix=None if adapter_mix is None else [adapter_mix[b] for b in rows])
+                    spans = [(t0, t1) for _, _, t0, t1, _ in plan if t1 > t0]
+                    wavs = dict(zip(rows, self._vocode_windows(lats, spk[sel] if per_row else spk, spans)))
+                    if trace is not None:
+                        for b, lat, (t0, t1) in zip(rows, lats, spans):
+                            lo = max(0, t0 - left)
+                            trace["frames"][b].append((t0, t1))
+                            trace["latent"][b].append(lat[t0:t1].clone())
+                            trace["window"][b].append((lo, lat[lo: min(int(lat.shape[0]), t1 + right)].clone()))
+                for b, k, t0, t1, final in plan:
+                    emitted[b], ended[b] = t1, final
+                    if final:
+                        if not bool((codes[b] == stop).any()):
+                            warnings.warn(f"generation stopped at max_mel_tokens ({max_mel_tokens}) in utterance {b}; consider shorter "
+                                          f"sentences", category=RuntimeWarning)
+                        if trace is not None:
+                            trace["codes"][b] = codes[b, :k].clone()
+                    yield b, (wavs[b] if t1 > t0 else torch.zeros(0, device=self.device)), final
+                if all(ended):
+                    return
+        finally:
+            chunks.close()       # an early close of this generator abandons the loop, as the end of it does
+
+    def infer_stream(self, audio_prompt, text, max_text_tokens_per_sentence=120, parallel_sentences=1, **kw):
         """infer() as a generator of (sampling rate, PCM chunk): the text is split into sentences as infer() splits it and the
         sentences are streamed one after another (stream_utterance, whose keywords -- chunk_tokens, seed, the generation
-        settings -- pass through).  A chunk is an fp32 device tensor in the int16 range."""
+        settings -- pass through).  A chunk is an fp32 device tensor in the int16 range.
+        parallel_sentences = P > 1: the sentences go through stream_batch in groups of up to P, one token loop per group, and the
+        chunks are still handed out in text order -- what sentence i + 1 produces before sentence i has ended is held back (by
+        reference) until then.  One-element force_stop / adapter_ids / adapter_mix stand for every sentence, as they do with P = 1;
+        a group is sampled as one batch, so its samples are not those of P = 1."""
+        P = int(parallel_sentences)
+        if P < 1:
+            raise ValueError("infer_stream: parallel_sentences must be at least 1")
         cond_mel = self._prompt(audio_prompt)
         sentences = self.tokenizer.split_sentences(self.tokenizer.tokenize(text), max_text_tokens_per_sentence)
-        for sent in sentences:
-            ids = torch.tensor(self.tokenizer.convert_tokens_to_ids(sent), dtype=torch.int32)
-            for pcm in self.stream_utterance(cond_mel, ids, **kw):
-                yield 24000, pcm
+        rows = [torch.tensor(self.tokenizer.convert_tokens_to_ids(sent), dtype=torch.int32) for sent in sentences]
+        if P == 1:
+            for ids in rows:
+                for pcm in self.stream_utterance(cond_mel, ids, **kw):
+                    yield 24000, pcm
+            return
+        for s in range(0, len(rows), P):
+            group = rows[s: s + P]
+            per_row = {k: list(kw[k]) * len(group) for k in ("force_stop", "adapter_ids", "adapter_mix")
+                       if kw.get(k) is not None and not isinstance(kw[k], (str, dict)) and hasattr(kw[k], "__len__") and len(kw[k]) == 1}
+            head, held, over = 0, [[] for _ in group], [False] * len(group)     # head: the sentence whose chunks leave as they come
+            for row, pcm, last in self.stream_batch(cond_mel, group, **{**kw, **per_row}):
+                if pcm.numel():
+                    held[row].append(pcm)
+                over[row] = over[row] or last
+                while head < len(group):
+                    for c in held[head]:
+                        yield 24000, c
+                    held[head] = []
+                    if not over[head]:
+                        break
+                    head += 1
 
     def infer_queue(self, cond_mel: torch.Tensor, text_token_rows: List[torch.Tensor], slots=32, max_mel_tokens=600,
                     force_stop=None, seed=1234, return_codes=False, cache_positions=4096, check_every=16, staged=True,

@@ -4,7 +4,11 @@ IndexTTS.stream_utterance in chunks of 16 / 32 / 64 tokens against IndexTTS.infe
 Host clock around work that ends in a device synchronise: a chunk counts as delivered when its samples are on the host.  Each
 variant is warmed twice (graph capture, prompt features), then the median (min) of `reps` runs is reported.
 profiles/stream_latency.txt is this tool's output.
-usage: bench_stream.py [reps] [layers]"""
+--rows N: N utterances (texts of 40 tokens, stops spread from 140 down to 100 codes) through ONE IndexTTS.stream_batch against N
+sequential stream_utterance calls and against one infer_batch of the N rows, alternating in one process, at --chunk tokens:
+the time to the first chunk of row 0 and to the last chunk of the last row.  profiles/stream_batch_latency.txt is that output.
+usage: bench_stream.py [reps] [layers] [--rows N] [--chunk C]"""
+import argparse
 import os
 import sys
 import time
@@ -20,8 +24,13 @@ import weights  # noqa: E402
 from indextts.infer import IndexTTS  # noqa: E402
 
 torch.set_grad_enabled(False)
-reps = int(sys.argv[1]) if len(sys.argv) > 1 else 9
-layers = int(sys.argv[2]) if len(sys.argv) > 2 else 24
+ap = argparse.ArgumentParser()
+ap.add_argument("reps", nargs="?", type=int, default=9)
+ap.add_argument("layers", nargs="?", type=int, default=24)
+ap.add_argument("--rows", type=int, default=0, help="N utterances through one stream_batch (0: the one-utterance table)")
+ap.add_argument("--chunk", type=int, default=32, help="chunk_tokens of the --rows table")
+args = ap.parse_args()
+reps, layers = args.reps, args.layers
 STOP, LIMIT, CHUNKS = 140, 192, (16, 32, 64)
 GEN = dict(do_sample=True, top_k=30, top_p=0.8, temperature=1.0, repetition_penalty=10.0, num_beams=1)
 
@@ -57,6 +66,72 @@ def stat(v):
     v = sorted(v)
     return f"{v[len(v) // 2]:8.2f} ms ({v[0]:.2f})"
 
+
+def rows_table(N, chunk):
+    """N utterances: one stream_batch | N sequential stream_utterance | one infer_batch, alternating."""
+    rng = np.random.default_rng(12)
+    texts = [torch.from_numpy(rng.integers(2, 12000, size=40)).to(torch.int32) for _ in range(N)]
+    stops = [STOP - (40 * i) // max(N - 1, 1) for i in range(N)]
+
+    def batch_whole():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        wavs = [w.cpu() for w in tts.infer_batch(cond_mel, texts, max_mel_tokens=LIMIT, force_stop=stops, seed=5, **GEN)]
+        return 1e3 * (time.perf_counter() - t0), wavs
+
+    def batch_streamed():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        first0, n_ev, out = None, 0, [[] for _ in range(N)]
+        for row, pcm, _ in tts.stream_batch(cond_mel, texts, chunk_tokens=chunk, max_mel_tokens=LIMIT, seed=5, force_stop=stops, **GEN):
+            out[row].append(pcm.cpu())
+            n_ev += 1
+            if row == 0 and first0 is None:
+                first0 = 1e3 * (time.perf_counter() - t0)
+        return first0, 1e3 * (time.perf_counter() - t0), n_ev, [torch.cat(o) for o in out]
+
+    def one_by_one():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        first0 = None
+        for i in range(N):
+            for pcm in tts.stream_utterance(cond_mel, texts[i], chunk_tokens=chunk, max_mel_tokens=LIMIT, seed=5, force_stop=[stops[i]], **GEN):
+                pcm.cpu()
+                if first0 is None:
+                    first0 = 1e3 * (time.perf_counter() - t0)
+        return first0, 1e3 * (time.perf_counter() - t0)
+
+    for _ in range(2):
+        batch_whole(), batch_streamed(), one_by_one()
+    t_w, b_first, b_last, s_first, s_last = [], [], [], [], []
+    for _ in range(reps):                 # the three paths alternate, so a drift of the machine touches all alike
+        ms, ref = batch_whole()
+        t_w.append(ms)
+        f, l, n_ev, wavs = batch_streamed()
+        b_first.append(f)
+        b_last.append(l)
+        f, l = one_by_one()
+        s_first.append(f)
+        s_last.append(l)
+    rms = max(((a - b) / 32767.0).pow(2).mean().sqrt().item() if a.shape == b.shape else float("nan") for a, b in zip(wavs, ref))
+    audio = sum(stops) * 1024 / 24000
+    med = lambda v: sorted(v)[len(v) // 2]   # noqa: E731
+    tag = f"stream batch latency | {N} rows, chunks of {chunk}"
+    print(f"stream batch latency | {layers} layers, bf16 GPT, fp16 vocoder, {N} utterances of {stops} codes ({audio:.2f} s of audio), texts of 40 "
+          f"tokens, chunks of {chunk} tokens, halo (left, right) = ({left}, {right}) frames; median (min) of {reps}, host clock to samples on the host")
+    print(f"{tag} | infer_batch, whole utterances (first audio = all audio)  | {stat(t_w)}  {audio / med(t_w) * 1e3:7.1f} audio-s/s")
+    print(f"{tag} | stream_batch, one token loop                             | first chunk of row 0 {stat(b_first)}  last chunk of the last row "
+          f"{stat(b_last)}  {audio / med(b_last) * 1e3:7.1f} audio-s/s  events = {n_ev}  worst row rms vs infer_batch = {rms:.2e}")
+    print(f"{tag} | {N} x stream_utterance, one after another{' ' * (21 - len(str(N)))}| first chunk of row 0 {stat(s_first)}  last chunk of the last row "
+          f"{stat(s_last)}  {audio / med(s_last) * 1e3:7.1f} audio-s/s")
+    print(f"{tag} | last chunk: stream_batch / sequential = {med(b_last) / med(s_last):.3f}, stream_batch / infer_batch = {med(b_last) / med(t_w):.3f}; "
+          f"first chunk of row 0: stream_batch / sequential = {med(b_first) / med(s_first):.3f}")
+
+
+if args.rows > 0:
+    rows_table(args.rows, args.chunk)
+    torch.cuda.synchronize()
+    sys.exit(0)
 
 for _ in range(2):
     whole()
