@@ -7,6 +7,7 @@ working:
     GET  /models          {"models": [{name, filename, type}], "current_model": ...}          (api.py:97-116)
     POST /model/reload    {"model_filename": ...} -> hot-swaps tts.gpt (404 when the file is missing)  (api.py:118-175)
     POST /tts/stream      /tts's request (not in the reference) -> chunked audio/L16; rate=24000 while the token loop runs, header X-Seed
+                          (--stream-slots S / create_app(stream_slots=S): all such requests share one refilled loop of S slots)
     POST /tts             text + prompt_audio (upload) | prompt_audio_path, infer_mode fast|normal, speaker_id, seed and the
                           generation knobs -> audio/wav, header X-Seed; 400 without a prompt, 404 for a missing prompt path,
                           503 before the engine is up, 500 with the error text otherwise                (api.py:177-300)
@@ -82,8 +83,11 @@ def _inside(path: str, roots) -> bool:
 
 def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/config.yaml", device=None, use_fp16=True,
                finetune_dir=os.path.join("finetune_models", "checkpoints"), output_dir=os.path.join("outputs", "api"),
-               prompt_dir="prompts"):
+               prompt_dir="prompts", stream_slots=None):
     """`tts`: a ready IndexTTS (tests, embedding) or None to build one from model_dir / config_path on first use.
+    stream_slots = S (off by default): /tts/stream requests are served by ONE worker that owns a refilled streaming loop of S
+    decode slots (IndexTTS.serve_stream_queue): a request that arrives while the loop runs enters it, a request that finds no
+    loop starts one.  None: every /tts/stream request runs its own generation under the engine lock, as before.
     Server-side paths a client may name are confined (the reference opens whatever it is given, api.py:125-134, :218-226):
     /model/reload only loads files inside model_dir / finetune_dir, /tts prompt_audio_path only reads files inside
     prompt_dir / model_dir; anything else answers 403."""
@@ -136,6 +140,60 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
             raise
         except Exception as e:  # noqa: BLE001
             raise HTTPException(status_code=500, detail=str(e))
+
+    class SharedStreamLoop:
+        """The worker of stream_slots: requests wait in `inbox`; one thread at a time holds the engine lock and runs a
+        serve_stream_queue loop, whose more() empties the inbox at every boundary.  The loop ends when it has fallen idle; a
+        request that arrives after that starts the next thread.  The lock is held for the loop only, never while anything waits
+        for a client: the chunks go to each request's own queue."""
+
+        def __init__(self):
+            self.mutex, self.inbox, self.running, self.jobs, self.count = threading.Lock(), [], False, {}, 0
+
+        def submit(self, request, chunks, done):
+            with self.mutex:
+                self.count += 1
+                self.inbox.append(dict(request, handle=self.count))
+                self.jobs[self.count] = (chunks, done)
+                start, self.running = not self.running, True
+            if start:
+                threading.Thread(target=self.work, name="tts-stream-queue", daemon=True).start()
+
+        def take(self):
+            with self.mutex:
+                new, self.inbox = self.inbox, []
+            return new
+
+        def finish(self, handle, end):
+            chunks, done = self.jobs.pop(handle)
+            chunks.put(end)
+            done()
+
+        def work(self):
+            import torch
+            while True:
+                try:
+                    with lock, torch.no_grad():
+                        for handle, pcm, last in engine().serve_stream_queue(self.take, slots=int(stream_slots)):
+                            if isinstance(pcm, BaseException):
+                                self.finish(handle, pcm)
+                                continue
+                            if pcm.numel():
+                                self.jobs[handle][0].put(pcm.float().cpu().numpy().astype("<i2").tobytes())
+                            if last:
+                                self.finish(handle, None)
+                except Exception as e:  # noqa: BLE001  (the loop itself failed: every request it had taken is told)
+                    with self.mutex:
+                        waiting = {r["handle"] for r in self.inbox}
+                    for handle in list(self.jobs):
+                        if handle not in waiting:
+                            self.finish(handle, e)
+                with self.mutex:
+                    if not self.inbox:
+                        self.running = False
+                        return
+
+    shared_loop = SharedStreamLoop()
 
     async def read_request(request: Request):
         """The /tts body in any of its three encodings -> (TTSRequest, uploaded prompt (filename, bytes) | None); 422 when malformed."""
@@ -247,6 +305,15 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
 
         chunks: "queue.Queue" = queue.Queue()     # bytes, then None (the end) or the exception that ended the generation
 
+        def clean_up():
+            if tmp_path and os.path.exists(tmp_path):
+                os.remove(tmp_path)
+
+        if stream_slots is not None:
+            shared_loop.submit(dict(kwargs, audio_prompt=prompt, text=req.text,
+                                    max_text_tokens_per_sentence=req.max_text_tokens_per_sentence), chunks, clean_up)
+            return await respond(chunks, actual_seed)
+
         def work():
             import torch
             try:
@@ -261,6 +328,10 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
                     os.remove(tmp_path)
 
         threading.Thread(target=work, name="tts-stream", daemon=True).start()
+        return await respond(chunks, actual_seed)
+
+    async def respond(chunks, actual_seed):
+        """The chunked answer over a queue of bytes that ends with None or an exception; the first item is awaited first."""
         first = await run_in_threadpool(chunks.get)
         if isinstance(first, HTTPException):
             raise first
@@ -288,6 +359,9 @@ if __name__ == "__main__":
     ap.add_argument("--device", type=str, default=None)
     ap.add_argument("--no-fp16", action="store_true")
     ap.add_argument("--prompt_dir", type=str, default="prompts", help="directory /tts prompt_audio_path may read from")
+    ap.add_argument("--stream-slots", type=int, default=None, metavar="S",
+                    help="serve /tts/stream from one shared refilled loop of S decode slots (IndexTTS.stream_queue): concurrent "
+                         "requests share a token loop instead of waiting for one another.  Off by default")
     a = ap.parse_args()
     import uvicorn
-    uvicorn.run(create_app(None, a.model_dir, a.config, a.device, not a.no_fp16, prompt_dir=a.prompt_dir), host=a.host, port=a.port)
+    uvicorn.run(create_app(None, a.model_dir, a.config, a.device, not a.no_fp16, prompt_dir=a.prompt_dir, stream_slots=a.stream_slots), host=a.host, port=a.port)

@@ -20,6 +20,10 @@ def main(argv=None):
     parser.add_argument("--stream-parallel", type=int, default=1, metavar="P",
                         help="with --stream: up to P sentences of the text share one token loop (IndexTTS.infer_stream("
                              "parallel_sentences=P)); the chunks are still written in text order.  1 streams sentence by sentence")
+    parser.add_argument("--stream-slots", type=int, default=None, metavar="S",
+                        help="with --stream: ALL sentences of the text go through one refilled loop of S decode slots "
+                             "(IndexTTS.infer_stream(slots=S)): a sentence that ends hands its slot to the next one.  The chunks are "
+                             "still written in text order; --stream-parallel does not apply then")
     parser.add_argument("-d", "--device", type=str, default=None, help="device (cuda:N); CPU/MPS are not supported")
     args = parser.parse_args(argv)
 
@@ -32,6 +36,8 @@ def main(argv=None):
         fail("text is empty")
     if args.stream_parallel < 1:
         fail("--stream-parallel must be at least 1")
+    if args.stream_slots is not None and args.stream_slots < 1:
+        fail("--stream-slots must be at least 1")
     if not os.path.exists(args.voice):
         fail(f"reference audio {args.voice} does not exist")
     if not os.path.exists(args.config):
@@ -55,7 +61,8 @@ def main(argv=None):
     if args.stream:
         from indextts.utils.audio import write_pcm16
         rate, chunks = 24000, []
-        for rate, pcm in tts.infer_stream(audio_prompt=args.voice, text=args.text.strip(), parallel_sentences=args.stream_parallel):
+        for rate, pcm in tts.infer_stream(audio_prompt=args.voice, text=args.text.strip(), parallel_sentences=args.stream_parallel,
+                                            **({} if args.stream_slots is None else {"slots": args.stream_slots})):
             chunks.append(pcm.cpu())
         if os.path.dirname(args.output_path) != "":
             os.makedirs(os.path.dirname(args.output_path), exist_ok=True)

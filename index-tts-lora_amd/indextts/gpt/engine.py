@@ -1471,27 +1471,36 @@ class GPTEngine:
         check_adapter_mix takes for one row.  The 2- and 3-tuples name none: the base voice."""
         return item[3] if len(item) > 3 else None
 
-    def _collect_stopped(self, owner, start, n):
-        """The refill loop's poll after n steps: {utterance id: codes ending with the stop token} of the rows that have stopped;
-        their slots become free and their blocks go back to the pool (the slot's later formal appends land in the scratch block)."""
+    def _poll_rows(self, owner, start, where, n, stopped_only=False):
+        """The refill loop's poll after n steps, ONE record per slot that owns an utterance: {"utt": utterance id, "slot", "k": the
+        row's own token count n - start[slot], "codes": history[slot, :k] (host int64; stop-token padded behind the row's stop),
+        "stopped", "prompt": (cache row, first position, length) of the prompt's keys}.  One device-to-host copy of history[:B]
+        (as wide as the longest live row) plus the flags.  The slots of the rows that have stopped become free and their blocks
+        go back to the pool (the slot's later formal appends land in the scratch block).  stopped_only: only the rows that have
+        stopped are copied and reported (a gather of those rows: what decode_refill has always read at a poll)."""
         self._poll()
         fin = self.finished[: len(owner)].tolist()
-        newly = [r for r, o in enumerate(owner) if fin[r] and o is not None and o >= 0]
-        out = {}
-        if newly:
-            width = max(n - start[r] for r in newly)
-            hist = self.history[torch.tensor(newly, device=self.device), :width].cpu()
-            for j, r in enumerate(newly):
-                row = hist[j, : n - start[r]].to(torch.int64)
-                hit = (row == self.stop_mel).nonzero()
-                out[owner[r]] = row[: int(hit[0]) + 1] if hit.numel() else row
+        live = [r for r, o in enumerate(owner) if o is not None and o >= 0 and (fin[r] or not stopped_only)]
+        if not live:
+            return []
+        width = max(n - start[r] for r in live)
+        if stopped_only:
+            hist = dict(zip(live, self.history[torch.tensor(live, device=self.device), :width].cpu()))
+        else:
+            hist = self.history[: len(owner), :width].cpu()
+        out = []
+        for r in live:
+            k = n - start[r]
+            out.append({"utt": owner[r], "slot": r, "k": k, "codes": hist[r][:k].to(torch.int64), "stopped": bool(fin[r]),
+                        "prompt": where[r]})
+            if fin[r]:
                 owner[r] = None
                 if self.kv is not None:
                     self.kv.release(r)
         return out
 
     def decode_refill(self, max_new: int, sp, feed, force_stop=None, use_graph=True, check_every=16, positions=None,
-                      staged=True, sp_default=None, voices=None, join=None):
+                      staged=True, sp_default=None, voices=None, join=None, closed=None):
         """Continuous batching: the sampling loop after prefill(), with every slot whose row has emitted its stop token
         refilled from a queue (the mitigation for mixed output lengths).  num_beams = 1 only.
         feed(k) -> up to k items (prefix_emb fp32 [P, D] = cond | text without padding, stop step or -1); fewer than k means
@@ -1521,7 +1530,47 @@ class GPTEngine:
         queue, whatever voices pass through a slot.  A row's record is written into self.adapter_mix[slot] when it joins; a freed
         slot gets the empty record at the poll that frees it.  join: "kernel" = the join is one launch behind the first-token
         sample (itts_refill_join), "torch" = the indexed writes it replaces, kept as its oracle; None = the engine's
-        refill_join.  Loops without voices always run the torch form."""
+        refill_join.  Loops without voices always run the torch form.
+        closed: see decode_refill_chunks.  This call is that generator drained: one loop body serves both."""
+        codes = {}
+        for rec in self.decode_refill_chunks(max_new, sp, feed, force_stop=force_stop, use_graph=use_graph, check_every=check_every,
+                                             positions=positions, staged=staged, sp_default=sp_default, voices=voices, join=join,
+                                             closed=closed, records="stopped"):
+            for row in rec["rows"]:
+                if row["stopped"]:
+                    c = row["codes"]
+                    hit = (c == self.stop_mel).nonzero()
+                    codes[row["utt"]] = c[: int(hit[0]) + 1] if hit.numel() else c
+        return [codes[i] for i in range(len(codes))], self.refill_leftover
+
+    def decode_refill_chunks(self, max_new: int, sp, feed, force_stop=None, use_graph=True, check_every=16, positions=None,
+                             staged=True, sp_default=None, voices=None, join=None, closed=None, records="all"):
+        """decode_refill() as a generator: the same arguments, checks, graph key ("token", B, sp), stages, join and refill_stats.
+        At every poll -- the loop's one host synchronisation, every check_every steps: check_every is the chunk length -- it
+        yields {"n": the loop's step count, "rows": one record per slot that owns an utterance (_poll_rows)}: the utterance id
+        (entry order, as decode_refill numbers them), the slot, the row's own token count k = n - start[slot], its codes
+        history[slot, :k] (host int64), whether it has stopped (a stopped row is reported once, at the poll that finds it; its
+        slot is free from then on), and "prompt" = (cache row, first position, length): where the keys of its prompt (cond |
+        text, without the start token) lie in the cache -- a caller may reuse them, or ignore them.  When the generator ends,
+        self.refill_leftover holds what decode_refill returns as leftover.
+        records = "stopped": a poll copies and reports only the rows that have stopped -- the gather decode_refill has always done
+        at a poll, and what it (and infer_queue) drains this generator with: that path moves no more bytes than before.
+        closed (a callable, or None): the explicit "no more will come" signal of an OPEN queue.  Without it (None) a feed that
+        returns fewer than k items has said that the queue is empty, as ever.  With it, feed may return fewer than k items --
+        none at all -- and is asked again at every later poll that finds a free slot, until closed() returns True behind such a
+        short answer.  Either way the loop ends once no slot holds an utterance and the feed gave none at that poll: an idle
+        loop is not kept spinning, the caller starts a new one when the next utterance arrives.
+        Between two yields the caller may run latent() / latent_mel_rows() / the vocoder on the loop's stream, under the rule of
+        decode_chunks.  A staged prefill (_stage_beside) may be running on the side stream at that time: it shares no buffer
+        with those passes -- _stage and _big_m_layers allocate every operand per call (xn, qkv, att, ff, slabs, the bank's
+        operands, kst / vst, the head's xn_t / lg_t), the passes read weights and, in latent_mel_rows, cache positions of
+        prompts that have joined; the staged keys enter the cache only in _join, on the loop's stream, inside next().
+        Closing the generator early abandons the loop: rows that were staged and have not joined are dropped (the loop's stream
+        waits for the side stream's pass, so nothing of it is in flight when the next prefill() starts), the slots' blocks go
+        back to the pool, and prefill() starts from a clean state as after any decode.
+        The checks run, and the device work starts, with the first next()."""
+        if records not in ("all", "stopped"):
+            raise ValueError(f"decode_refill_chunks(): records must be 'all' or 'stopped' (got {records!r})")
         per_row = isinstance(sp, (list, tuple))
         if per_row:
             sp = self.check_row_settings(sp, self._B)
@@ -1572,7 +1621,9 @@ class GPTEngine:
             idle = self._mix_records([()])
         self.kv_share.zero_()                                # a refilled row 0 no longer holds the shared block where the others expect it
         owner, start = list(range(B)), [0] * B              # owner: utterance id | None (free) | -1 (reserved for staged rows)
-        ids, codes, leftover, fed_out, pending, row_sp = itertools.count(B), {}, [], False, None, None
+        where = [(b, self._pad_host[b], S - 1 - self._pad_host[b]) for b in range(B)]   # the prompts' keys: (cache row, first position, length)
+        ids, leftover, fed_out, pending, row_sp = itertools.count(B), [], False, None, None
+        self.refill_leftover = leftover
         stats = self.refill_stats = {"steps": 0, "polls": 0, "refill_calls": 0, "rows_refilled": 0, "staged": bool(staged)}
         main = torch.cuda.current_stream(dev)
         side = torch.cuda.Stream(device=dev) if staged else None
@@ -1583,81 +1634,92 @@ class GPTEngine:
         step, key = (lambda: self._step_kernels(B, sp)), self._graph_key("token", B, sp)
         self._sample(B, sp)
         n = 1
-        while True:
-            # ---- A: rows staged during the last steps join here
-            if pending is not None:
-                st, ev, rows, row_sp = pending
-                self._join(st, sp, ev, row_sp, kernel=join == "kernel")
-                for r in rows:
-                    owner[r], start[r] = next(ids), n - 1
-                pending = None
-            # ---- B: utterances for the slots that are free now
-            free = [r for r in range(B) if owner[r] is None]
-            items = []
-            if free and not fed_out and n > 1:
-                items = list(feed(len(free)))
-                if len(items) > len(free):
-                    raise ValueError(f"decode_refill(): feed({len(free)}) returned {len(items)} items")
-                fed_items = items    # (prefix, stop step[, settings[, voice]]) -> the old pairs + the rows' checked settings and voices
-                if per_row:
-                    fed_sp = [self._fed_settings(it, sp_default) for it in items]
-                elif any(len(it) > 2 and it[2] is not None for it in items):
-                    raise ValueError("decode_refill(): a fed item carries sampling settings but the loop runs under one dict "
-                                     "(pass sp as a list)")
-                if voiced:
-                    fed_mix = self.check_adapter_mix([self._fed_voice(it) for it in items], len(items))
-                elif any(self._fed_voice(it) is not None for it in items):
-                    raise ValueError("decode_refill(): a fed item names a voice but the loop runs without voices "
-                                     "(attach_lora_bank, voices=[...])")
-                items = [tuple(it)[:2] for it in items]
-                fed_out = len(items) < len(free)
-                n_join = n + ce if staged else n
-                if limit - (S + n_join + 1) < max_new + ce:     # steps the loop could still take
-                    items, leftover = [], items
-                elif kv is not None:
-                    k = admit(kv, free, items, S + n_join - 1, max_new, ce)
-                    items, leftover = items[:k], items[k:]
-                if leftover:
-                    leftover = fed_items[len(fed_items) - len(leftover):]   # as they were fed, settings and voice included
-                fed_out = fed_out or bool(leftover)
-            if items:
-                rows, prefixes = free[: len(items)], [p for p, _ in items]
-                row_sp = fed_sp[: len(items)] if per_row else None
-                row_mix = fed_mix[: len(items)] if voiced else None
-                stops = [max_new - 1 if int(v) < 0 else min(int(v), max_new - 1) for _, v in items]
-                stats["refill_calls"] += 1
-                stats["rows_refilled"] += len(rows)
-                if not staged:
-                    self._join(self._stage(rows, prefixes, stops, n, row_mix), sp, row_sp=row_sp, kernel=join == "kernel")
+        try:
+            while True:
+                # ---- A: rows staged during the last steps join here
+                if pending is not None:
+                    st, ev, rows, row_sp = pending
+                    self._join(st, sp, ev, row_sp, kernel=join == "kernel")
                     for r in rows:
                         owner[r], start[r] = next(ids), n - 1
-                    items = []
-                else:
-                    fed = torch.cuda.Event()
-                    fed.record(main)                        # the prefix embeddings are complete on the loop's stream
-            if fed_out and pending is None and not items and all(o is None for o in owner):
-                break
-            # ---- C: check_every steps of the loop
-            if kv is not None:
-                kv.flush()
-                stats["peak_blocks"] = max(stats["peak_blocks"], kv.used_blocks())
-            if per_row:
-                self.row_sampling.flush()
-            n = self._token_loop(n, n + ce, step, key, use_graph)
-            # ---- D: the new rows' prompts, enqueued behind the steps on the host and run beside them on the GPU
-            if items:
-                st, ev = self._stage_beside(side, fed, rows, prefixes, stops, n_join, row_mix)
-                pending = (st, ev, rows, row_sp)
-                for r in rows:
-                    owner[r] = -1
-            # ---- E: one host synchronisation: which rows have stopped
-            stats["steps"], stats["polls"] = n, stats["polls"] + 1
-            live = [r for r in range(B) if owner[r] is not None and owner[r] >= 0]
-            codes.update(self._collect_stopped(owner, start, n))
-            freed = [r for r in live if owner[r] is None]
-            if voiced and freed:                            # an idle slot is the base voice (nothing reads what it computes)
-                self.adapter_mix[torch.tensor(freed, device=dev)] = idle
-        return [codes[i] for i in range(len(codes))], leftover
+                    pending = None
+                # ---- B: utterances for the slots that are free now
+                free = [r for r in range(B) if owner[r] is None]
+                items = []
+                if free and not fed_out and n > 1:
+                    items = list(feed(len(free)))
+                    if len(items) > len(free):
+                        raise ValueError(f"decode_refill(): feed({len(free)}) returned {len(items)} items")
+                    fed_items = items    # (prefix, stop step[, settings[, voice]]) -> the old pairs + the rows' checked settings and voices
+                    if per_row:
+                        fed_sp = [self._fed_settings(it, sp_default) for it in items]
+                    elif any(len(it) > 2 and it[2] is not None for it in items):
+                        raise ValueError("decode_refill(): a fed item carries sampling settings but the loop runs under one dict "
+                                         "(pass sp as a list)")
+                    if voiced:
+                        fed_mix = self.check_adapter_mix([self._fed_voice(it) for it in items], len(items))
+                    elif any(self._fed_voice(it) is not None for it in items):
+                        raise ValueError("decode_refill(): a fed item names a voice but the loop runs without voices "
+                                         "(attach_lora_bank, voices=[...])")
+                    items = [tuple(it)[:2] for it in items]
+                    # fewer than asked for: the queue is empty -- or, an open queue, only when closed() says so behind it
+                    fed_out = len(items) < len(free) and (closed is None or bool(closed()))
+                    n_join = n + ce if staged else n
+                    if limit - (S + n_join + 1) < max_new + ce:     # steps the loop could still take
+                        items, leftover[:] = [], items
+                    elif kv is not None:
+                        k = admit(kv, free, items, S + n_join - 1, max_new, ce)
+                        items, leftover[:] = items[:k], items[k:]
+                    if leftover:
+                        leftover[:] = fed_items[len(fed_items) - len(leftover):]   # as they were fed, settings and voice included
+                    fed_out = fed_out or bool(leftover)
+                if items:
+                    rows, prefixes = free[: len(items)], [p for p, _ in items]
+                    row_sp = fed_sp[: len(items)] if per_row else None
+                    row_mix = fed_mix[: len(items)] if voiced else None
+                    stops = [max_new - 1 if int(v) < 0 else min(int(v), max_new - 1) for _, v in items]
+                    stats["refill_calls"] += 1
+                    stats["rows_refilled"] += len(rows)
+                    for r, pfx in zip(rows, prefixes):              # _stage lays the prompt + start token out in front of the join
+                        where[r] = (r, S + n_join - 2 - int(pfx.shape[0]), int(pfx.shape[0]))
+                    if not staged:
+                        self._join(self._stage(rows, prefixes, stops, n, row_mix), sp, row_sp=row_sp, kernel=join == "kernel")
+                        for r in rows:
+                            owner[r], start[r] = next(ids), n - 1
+                        items = []
+                    else:
+                        fed = torch.cuda.Event()
+                        fed.record(main)                        # the prefix embeddings are complete on the loop's stream
+                # no utterance in any slot and none fed: the end -- of a closed queue, and of an open one that has fallen idle
+                if (fed_out or closed is not None) and pending is None and not items and all(o is None for o in owner):
+                    break
+                # ---- C: check_every steps of the loop
+                if kv is not None:
+                    kv.flush()
+                    stats["peak_blocks"] = max(stats["peak_blocks"], kv.used_blocks())
+                if per_row:
+                    self.row_sampling.flush()
+                n = self._token_loop(n, n + ce, step, key, use_graph)
+                # ---- D: the new rows' prompts, enqueued behind the steps on the host and run beside them on the GPU
+                if items:
+                    st, ev = self._stage_beside(side, fed, rows, prefixes, stops, n_join, row_mix)
+                    pending = (st, ev, rows, row_sp)
+                    for r in rows:
+                        owner[r] = -1
+                # ---- E: one host synchronisation: which rows have stopped -- and what every row has so far
+                stats["steps"], stats["polls"] = n, stats["polls"] + 1
+                record = self._poll_rows(owner, start, where, n, stopped_only=records == "stopped")
+                freed = [row["slot"] for row in record if row["stopped"]]
+                if voiced and freed:                            # an idle slot is the base voice (nothing reads what it computes)
+                    self.adapter_mix[torch.tensor(freed, device=dev)] = idle
+                yield {"n": n, "rows": record}
+        finally:
+            if pending is not None:      # closed early: the staged rows never join; their pass ends before this stream goes on
+                main.wait_event(pending[1])
+                pending = None
+            if kv is not None:           # (all free already when the loop ran to its end)
+                for r in range(B):
+                    kv.release(r)
 
     # ------------------------------------------------------------------------------------------------ beam search
     def _ensure_beam(self, B: int, nb: int):

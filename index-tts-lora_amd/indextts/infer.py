@@ -89,6 +89,30 @@ def _resolve_kv_cache(name):
     raise ValueError(f"precision_config: kv_cache must be 'auto' or 'fp8' (got {name!r})")
 
 
+class _TextOrder:
+    """Chunks of n rows that are produced interleaved, handed out in row order: what row i + 1 produces before row i has ended is
+    held back (by reference) until then.  push(row, pcm, last) returns the chunks that may leave now."""
+
+    def __init__(self, n):
+        self.head, self.held, self.ended = 0, [[] for _ in range(n)], [False] * n
+
+    def push(self, row, pcm, last):
+        if pcm.numel():
+            self.held[row].append(pcm)
+        self.ended[row] = self.ended[row] or last
+        out = []
+        while self.head < len(self.held):       # head: the row whose chunks leave as they come
+            out.extend(self.held[self.head])
+            self.held[self.head] = []
+            if not self.ended[self.head]:
+                break
+            self.head += 1
+        return out
+
+    def over(self):
+        return self.head == len(self.held)
+
+
 class IndexTTS:
     def __init__(self, cfg_path="checkpoints/config.yaml", model_dir="checkpoints", is_fp16=True, device=None,
                  use_cuda_kernel=None, speaker_info_path=None, precision_config=None, gpt_path=None,
@@ -887,29 +911,30 @@ class IndexTTS:
 
     # ------------------------------------------------------------------------------------------------ batched streaming
     @staticmethod
-    def _stream_batch_args(n_rows, chunk_tokens, max_mel_tokens, force_stop, adapter_ids, adapter_mix, sampling, generation_kwargs):
-        """The checks of stream_batch that need neither a model nor a device: (gen, chunk_tokens, max_mel_tokens, force_stop as
-        n_rows host ints | None)."""
+    def _stream_batch_args(n_rows, chunk_tokens, max_mel_tokens, force_stop, adapter_ids, adapter_mix, sampling, generation_kwargs,
+                           who="stream_batch"):
+        """The checks of stream_batch (and stream_queue: `who`) that need neither a model nor a device: (gen, chunk_tokens,
+        max_mel_tokens, force_stop as n_rows host ints | None)."""
         kw = dict(generation_kwargs)
         kw.setdefault("num_beams", 1)
         gen, _ = IndexTTS._gen_kwargs(kw)
         if kw:
-            raise TypeError(f"stream_batch: unknown generation settings {sorted(kw)}")
+            raise TypeError(f"{who}: unknown generation settings {sorted(kw)}")
         if int(gen["num_beams"]) > 1:
-            raise NotImplementedError("stream_batch: beam search picks its hypothesis when the loop ends, so no code is final "
+            raise NotImplementedError(f"{who}: beam search picks its hypothesis when the loop ends, so no code is final "
                                       "before that; streaming is built for num_beams = 1")
         if adapter_ids is not None and adapter_mix is not None:
-            raise ValueError("stream_batch: adapter_ids or adapter_mix, one of them")
+            raise ValueError(f"{who}: adapter_ids or adapter_mix, one of them")
         for name, v in (("adapter_ids", adapter_ids), ("adapter_mix", adapter_mix), ("sampling", sampling)):
             if v is not None and (isinstance(v, (str, dict)) or not hasattr(v, "__len__") or len(v) != n_rows):
-                raise ValueError(f"stream_batch: {name} is a list with one entry per utterance ({n_rows})")
+                raise ValueError(f"{who}: {name} is a list with one entry per utterance ({n_rows})")
         chunk_tokens, max_mel_tokens = int(chunk_tokens), int(max_mel_tokens)
         if chunk_tokens < 1:
-            raise ValueError("stream_batch: chunk_tokens must be at least 1")
+            raise ValueError(f"{who}: chunk_tokens must be at least 1")
         if force_stop is not None:
             force_stop = force_stop.reshape(-1).tolist() if torch.is_tensor(force_stop) else list(force_stop)
             if len(force_stop) != n_rows:
-                raise ValueError(f"stream_batch: force_stop holds one entry per utterance ({n_rows}; None or -1: no forced stop)")
+                raise ValueError(f"{who}: force_stop holds one entry per utterance ({n_rows}; None or -1: no forced stop)")
             force_stop = [-1 if v is None else int(v) for v in force_stop]
         return gen, chunk_tokens, max_mel_tokens, force_stop
 
@@ -1023,41 +1048,417 @@ class IndexTTS:
         finally:
             chunks.close()       # an early close of this generator abandons the loop, as the end of it does
 
-    def infer_stream(self, audio_prompt, text, max_text_tokens_per_sentence=120, parallel_sentences=1, **kw):
+    # ------------------------------------------------------------------------------------------------ streaming queue
+    def stream_queue(self, cond_mel, text_token_rows, slots=32, chunk_tokens=32, max_mel_tokens=600, seed=1234, force_stop=None,
+                     adapter_ids=None, adapter_mix=None, sampling=None, more=None, _trace: dict | None = None, _refused=None,
+                     **generation_kwargs):
+        """stream_batch over the REFILLED loop of infer_queue: any number of utterances through `slots` decode slots, each
+        streamed as PCM while the loop runs, and utterances that arrive after the loop has started enter it.  A generator of
+        events (utt, pcm, last) -- the events of stream_batch; utt: the index into text_token_rows, or the handle `more` gave.
+        The loop is infer_queue's: the longest texts are prefilled into the slots, then GPTEngine.decode_refill_chunks(
+        check_every=chunk_tokens, staged=True) -- same prefill, same feed, same polls and joins, so an utterance's codes are
+        infer_queue(slots=slots, check_every=chunk_tokens)'s bit for bit, and no graph is captured that infer_queue would not
+        capture.  What could not be placed (the cache budget of a loop) starts a new loop.
+        At every poll each row is planned on its OWN token count k (stream_queue_plan: stream_plan per row -- it emits the frames
+        [emitted, k - right), and flushes at its first stop token or at max_mel_tokens, with exactly one `last` event).  The rows
+        that emit at a poll share one latent pass and one ragged vocoder call per bucket of similar window lengths
+        (_vocode_windows), as in stream_batch.  A refilled row's prompt does not lie where latent_mel_rows looks for it, so the
+        latent pass is the whole-sequence one (_latents(reuse_prefix=False), as over an FP8 KV cache).  The events of one poll
+        come in the order the utterances entered the loop.
+        cond_mel (one mel, or a list with one per utterance), adapter_ids / adapter_mix and sampling: taken and checked as
+        infer_queue takes and checks them, before anything is launched; force_stop: one entry per utterance (None / -1: none).
+        num_beams defaults to 1 and a larger value is refused (stream_utterance says why).  A row that reaches max_mel_tokens is
+        stopped there by the loop, as in infer_queue.  Silence: the stream's rule -- the cut at the stop token only (the
+        documented divergence from remove_long_silence, see stream_utterance).
+        more (a callable, or None = the static queue): called at every boundary (before the first prefill, and after every
+        poll).  It returns a list -- usually empty -- of requests that have arrived, or None: no more will come (it is not
+        called again).  A request is a dict: "handle" (what the events name it by), "text" (token ids), and optionally "cond_mel"
+        (a mel tensor, or an index into this call's cond_mel list; default: this call's one prompt / its first), "voice" (what
+        adapter_ids or adapter_mix would hold for it, whichever this call was given), "sampling" (a dict as in `sampling`) and
+        "force_stop".  Arrivals wait behind the queue and are fed to the running loop as slots free up.  With `more` the loop
+        runs under per-row settings (as with sampling=[{}, ...]) so that an arrival keeps its own, and the pool is sized for the
+        longest prompt the model takes (gpt.max_text_tokens) instead of the queue's longest.  An arrival whose prompt is longer
+        than the loop can place -- the pool's window, or the positions the loop has passed -- is held back, for a later poll or
+        the next loop; nothing is raised mid-loop on its account.  When the queue and the slots are empty and `more` has not
+        said None, the generator ENDS (no idle loop spins): the caller calls again when the next request comes.
+        The pool is sized with slots_window for that longest prompt + max_mel_tokens + 2 * chunk_tokens, as infer_queue sizes it:
+        every admitted row's whole window is dealt at admission (GPTEngine.admit), so the pool cannot be over-committed.
+        Closing the generator early abandons the loop (decode_refill_chunks releases the staged rows).
+        _trace (private: tests, tools) receives, per utt, "codes" (host int64), "frames" ([(t0, t1)]), "latent" (per chunk, the
+        rows [t0, t1)), "window" (per chunk, (lo, the latent rows [lo, hi) the vocoder ran over)), "polls" (the loop's n at every
+        poll the utterance was planned at) and "loops" (the number of loops started).
+        A request from more() that does not pass its checks raises from the generator (the caller's error, as a bad argument
+        is); _refused (private: serve_stream_queue) is a list that receives (handle, error) instead, and the loop goes on.
+        The checks run when this is called; the device work starts with the first next()."""
+        N = len(text_token_rows)
+        gen, chunk_tokens, max_mel_tokens, force_stop = IndexTTS._stream_batch_args(
+            N, chunk_tokens, max_mel_tokens, force_stop, adapter_ids, adapter_mix, sampling, generation_kwargs, who="stream_queue")
+        if int(slots) < 1:
+            raise ValueError("stream_queue: slots must be >= 1")
+        if more is not None and not callable(more):
+            raise TypeError("stream_queue: more is a callable that returns the requests that have arrived (or None: no more will come)")
+        if sampling is not None or more is not None:
+            sampling = row_sampling_params([{}] * N if sampling is None else sampling, N, gen, seed)
+        eng = self.gpt.engine
+        voice_kind = None                   # which keyword names a voice: the one this call was given
+        if adapter_ids is not None or adapter_mix is not None:
+            adapter_ids, adapter_mix = eng._voices(adapter_ids, adapter_mix, N)
+            voice_kind = "adapter_ids" if adapter_mix is None else "adapter_mix"
+        elif eng.bank is not None:
+            raise NotImplementedError("stream_queue: an adapter bank is attached and no voices were named: pass adapter_ids=[...] or "
+                                      "adapter_mix=[...], one entry per utterance (adapter_ids=[-1] * N is the base voice)")
+        cond_mel = IndexTTS._check_prompts(self, cond_mel, N, gen, "stream_queue")
+        texts = [torch.as_tensor(t).reshape(-1).to("cpu", torch.int32) for t in text_token_rows]
+        if N == 0 and more is None:
+            return iter(())
+        voices = adapter_ids if adapter_mix is None else adapter_mix
+        reqs = [dict(handle=i, text=texts[i], prompt=i if isinstance(cond_mel, list) else 0,
+                     stop=-1 if force_stop is None else force_stop[i], sp=None if sampling is None else sampling[i],
+                     voice=None if voices is None else voices[i]) for i in range(N)]
+        return self._stream_queue(cond_mel, reqs, int(slots), chunk_tokens, max_mel_tokens, seed, voice_kind, more, _trace, gen, _refused)
+
+    @staticmethod
+    def stream_queue_plan(rows, emitted, right, max_mel_tokens, stop):
+        """One poll of stream_queue on the host.  rows: the records of GPTEngine.decode_refill_chunks ("utt", "k", "codes", "stopped");
+        emitted: {utt: the frames it has given out} (an utterance not in it has given none).  Returns [(utt, k, t0, t1, final)] in
+        the order of `rows` for the utterances that emit now: k = the position of the row's first stop token (the cut of
+        remove_long_silence) or its own token count; final = a stop token is there, the loop says the row has stopped, or k has
+        reached max_mel_tokens; (t0, t1) = stream_plan(k, emitted[utt], right, final).  A row with nothing to emit that is not
+        final is left out; a final row is always there, with t1 == t0 when nothing is left."""
+        out = []
+        for row in rows:
+            codes = row["codes"]
+            hit = (codes == stop).nonzero()
+            k = int(hit[0]) if hit.numel() else int(row["k"])
+            final = bool(hit.numel()) or bool(row["stopped"]) or k >= max_mel_tokens
+            t0, t1 = IndexTTS.stream_plan(k, emitted.get(row["utt"], 0), right, final)
+            if t1 > t0 or final:
+                out.append((row["utt"], k, t0, t1, final))
+        return out
+
+    def _queue_request(self, r, n_seen, cond_mel, feats, seed, gen, voice_kind):
+        """A request `more` returned -> the queue's own form, checked on the host; its prompt's features are computed here when
+        the call has not seen that mel (eagerly: no graph is captured beside a running loop)."""
+        eng = self.gpt.engine
+        if not isinstance(r, dict) or "handle" not in r or "text" not in r:
+            raise ValueError("stream_queue: a request from more() is a dict with a 'handle' and a 'text'")
+        unknown = sorted(set(r) - {"handle", "text", "cond_mel", "voice", "sampling", "force_stop"})
+        if unknown:
+            raise ValueError(f"stream_queue: a request from more() holds unknown keys {unknown}")
+        m = r.get("cond_mel")
+        if m is None:
+            m = 0
+        if torch.is_tensor(m):
+            if id(m) not in feats:
+                feats[id(m)] = (m, self.gpt.get_conditioning(m, None), self.bigvgan.speaker_embedding(m.transpose(1, 2)))
+            prompt = id(m)
+        else:
+            prompt = int(m)
+            if not 0 <= prompt < (len(cond_mel) if isinstance(cond_mel, list) else 0 if cond_mel is None else 1):
+                raise ValueError(f"stream_queue: a request from more() names prompt {prompt}, which this call was not given")
+        voice = r.get("voice")
+        if voice_kind is None:
+            if voice is not None:
+                raise ValueError("stream_queue: a request from more() names a voice, but this call was given neither adapter_ids nor adapter_mix")
+        elif voice_kind == "adapter_ids":
+            voice = eng._row_adapters([-1 if voice is None else voice], 1)[0]
+        else:
+            voice = eng.check_adapter_mix([voice], 1)[0]
+        sp = dict(r.get("sampling") or {})
+        sp.setdefault("stream", 0 if "seed" in sp else n_seen)      # the call's seed is shared: arrivals must not draw alike
+        stop = r.get("force_stop")
+        return dict(handle=r["handle"], text=torch.as_tensor(r["text"]).reshape(-1).to("cpu", torch.int32), prompt=prompt,
+                    stop=-1 if stop is None else int(stop), sp=row_sampling_params([sp], 1, gen, seed)[0], voice=voice)
+
+    def _refill_loops(self, waiting, feats, slots, ce, max_mel_tokens, sp_scalar, per_row, voice_kind, one_prompt, staged=True,
+                      cache_positions=4096, text_cap=0, closed=None, drain=False, idle=None):
+        """The refilled loops of infer_queue and stream_queue, ONE set-up for both: a generator of (loop number, entered, record).
+        waiting: the queue, a list of requests the caller may append to between two records -- dicts with "text" (host int32),
+        "prompt" (key into feats: (mel, conds [1, nc, D], spk)), "stop", "sp" (checked settings | None) and "voice".  The first
+        `slots` of it are prefilled, the others fed as slots free up (GPTEngine.decode_refill_chunks; `closed`: its argument);
+        what a loop could not place starts the next one.  entered[u] is the request the record's "utt" u names.  drain: every
+        loop runs to its end inside GPTEngine.decode_refill and is yielded ONCE, as (loop number, the requests it placed, their
+        codes in that order) -- infer_queue's form: a poll then reads only the rows that have stopped.
+        one_prompt: every request speaks from ONE prompt, whose rows the prefill shares (a prompt list never does).  text_cap: size
+        the pool for prompts with texts of up to that many tokens (an open queue) instead of the first batch's longest; a request longer
+        than the loop can place -- the pool's window, the positions the loop has passed -- stays in `waiting` (an open queue only:
+        a static one is fed from its head, longest first).  idle(): called
+        when a loop has ended with nothing waiting, the caller's last chance to append.  per_row: the loops run under per-row
+        settings (every request's "sp"), else under sp_scalar."""
+        g, eng = self.gpt, self.gpt.engine
+        stop_text = self.cfg.gpt.stop_text_token
+
+        def conds_of(rs):
+            if one_prompt:
+                return feats[rs[0]["prompt"]][1]
+            return torch.cat([feats[r["prompt"]][1] for r in rs], 0)
+
+        def prefixes(rs):
+            """(left-padded prefix batch, pad) of the requests `rs` -- one itts_prefix_rows launch"""
+            L = max(int(r["text"].numel()) for r in rs)
+            bh = torch.full((len(rs), L), stop_text, dtype=torch.int32)
+            for j, r in enumerate(rs):
+                bh[j, : r["text"].numel()] = r["text"]
+            return g.prefix_rows(conds_of(rs), bh)
+
+        def voiced(rs):
+            return {} if voice_kind is None else {voice_kind: [r["voice"] for r in rs]}
+
+        number = 0
+        while waiting:
+            first = waiting[:slots]
+            del waiting[:slots]
+            emb, pad = prefixes(first)
+            nc = int(feats[first[0]["prompt"]][1].shape[1])
+            p_max = max(int(emb.shape[1]), nc + int(text_cap) + 2 if text_cap else 0)     # the longest prompt this loop can place
+            shared = nc if one_prompt else 0
+            if eng.paged:
+                # paged cache: one loop serves the whole queue -- a slot's blocks go back to the pool when its row stops.  The pool
+                # holds `slots` windows of (longest prompt + start token + max_mel_tokens + the steps up to the second next poll)
+                eng.prefill(emb, pad, max_mel_tokens + ce + 1, shared_rows=shared,
+                            slots_window=p_max + 1 + max_mel_tokens + 2 * ce + 2, **voiced(first))
+            else:
+                # contiguous strips: the loop runs whole blocks of check_every steps, the cache has to hold that many positions
+                # past max_mel_tokens; cache positions only grow, so a loop ends when `cache_positions` are used up
+                eng.prefill(emb, pad, max(max_mel_tokens + ce + 1, int(cache_positions) - emb.shape[1] - 2),
+                            shared_rows=shared, paged=False, **voiced(first))
+            number += 1
+            entered, cur_n, S = list(first), 1, int(emb.shape[1]) + 1
+
+            def fits(r):
+                """the loop can place r at the next join: its window fits the pool's, its prompt the positions the loop has passed"""
+                P = nc + int(r["text"].numel()) + 2
+                return P <= p_max and P + 1 <= S + cur_n + (ce if staged else 0) - 1
+
+            def feed(k):
+                take = [r for r in waiting if closed is None or fits(r)][:k]
+                if not take:
+                    return []
+                for r in take:
+                    waiting.remove(r)
+                e, p = prefixes(take)
+                p = p.tolist()
+                entered.extend(take)
+                if voice_kind is not None:
+                    return [(e[j, p[j]:], r["stop"], r["sp"], r["voice"]) for j, r in enumerate(take)]
+                if per_row:
+                    return [(e[j, p[j]:], r["stop"], r["sp"]) for j, r in enumerate(take)]
+                return [(e[j, p[j]:], r["stop"]) for j, r in enumerate(take)]
+
+            args = (max_mel_tokens, [r["sp"] for r in first] if per_row else sp_scalar, feed)
+            kw = dict(force_stop=[r["stop"] for r in first], check_every=ce, staged=bool(staged),
+                      positions=None if eng.kv is not None else max(int(cache_positions), eng._S + max_mel_tokens + ce + 1),
+                      **({} if voice_kind is None else {"voices": [r["voice"] for r in first]}))
+            if drain:
+                codes, leftover = eng.decode_refill(*args, **kw)
+                back = len(leftover)
+                yield number, entered[: len(entered) - back], codes
+            else:
+                loop = eng.decode_refill_chunks(*args, closed=closed, **kw)
+                try:
+                    for rec in loop:
+                        cur_n = rec["n"]
+                        yield number, entered, rec
+                finally:
+                    loop.close()       # an early close of this generator abandons the loop, as the end of it does
+                back = len(eng.refill_leftover)
+            if back:               # fed but not placed: back to the head of the queue
+                waiting[:0] = entered[len(entered) - back:]
+            if not waiting and idle is not None:
+                idle()
+
+    def _stream_queue(self, cond_mel, reqs, slots, chunk_tokens, max_mel_tokens, seed, voice_kind, more, trace, gen, refused=None):
+        g = self.gpt
+        waiting = sorted(reqs, key=lambda r: -int(r["text"].numel()))      # longest first, as infer_queue: every later prompt fits
+        n_seen, open_ = len(reqs), more is not None
+        per_row = more is not None or any(r["sp"] is not None for r in reqs)
+        feats = {}                                      # prompt key -> (mel, conds [1, nc, D], spk [1, 1, 512])
+        left, right = self.bigvgan.receptive_halo()
+        stop = g.stop_mel_token
+        emitted = {}
+        if trace is not None:
+            trace.update(codes={}, frames={}, latent={}, window={}, polls={}, loops=0)
+
+        def arrivals():
+            """one call of more(): the new requests go to the back of the queue.  refused (a list; the service form): a request
+            that does not pass its checks is put there with its error and disturbs no other; without it the error is the caller's"""
+            nonlocal open_, n_seen
+            if not open_:
+                return
+            new = more()
+            if new is None:
+                open_ = False
+                return
+            for r in new:
+                try:
+                    waiting.append(self._queue_request(r, n_seen, cond_mel, feats, seed, gen, voice_kind))
+                except Exception as e:  # noqa: BLE001
+                    if refused is None:
+                        raise
+                    refused.append((r.get("handle") if isinstance(r, dict) else None, e))
+                n_seen += 1
+
+        arrivals()
+        if cond_mel is not None:                        # the call's own prompts: conditioned once, as infer_queue conditions them
+            conds, spk = self._prompt_features(cond_mel)
+            if isinstance(cond_mel, list):
+                for i, m in enumerate(cond_mel):
+                    feats[i] = (m, conds[i: i + 1], spk[i: i + 1])
+            else:
+                feats[0] = (cond_mel, conds, spk)
+        one_prompt = more is None and not isinstance(cond_mel, list)       # (an arrival may bring a prompt of its own)
+        text_cap = int(getattr(g, "max_text_tokens", 0)) if more is not None else 0   # an open queue: the longest text the model takes
+        loops = self._refill_loops(waiting, feats, slots, chunk_tokens, max_mel_tokens, sampling_params(gen, seed), per_row, voice_kind,
+                                   one_prompt, text_cap=text_cap, closed=(lambda: not open_) if more is not None else None, idle=arrivals)
+        try:
+            for number, entered, rec in loops:
+                if trace is not None:
+                    trace["loops"] = number
+                plan = self.stream_queue_plan([dict(row, utt=(number, row["utt"])) for row in rec["rows"]], emitted, right,
+                                              max_mel_tokens, stop)
+                codes = {(number, row["utt"]): row["codes"] for row in rec["rows"]}
+                if trace is not None:
+                    for row in rec["rows"]:
+                        trace["polls"].setdefault(entered[row["utt"]]["handle"], []).append(rec["n"])
+                emit = [(u, k, t0, t1) for u, k, t0, t1, _ in plan if t1 > t0]
+                wavs = {}
+                if emit:
+                    rs = [entered[u[1]] for u, _, _, _ in emit]
+                    same = all(feats[r["prompt"]][1] is feats[rs[0]["prompt"]][1] for r in rs)
+                    conds = feats[rs[0]["prompt"]][1] if same else torch.cat([feats[r["prompt"]][1] for r in rs], 0)
+                    lats = self._latents(conds, [r["text"] for r in rs], [codes[u][:k] for u, k, _, _ in emit], reuse_prefix=False,
+                                         **({} if voice_kind is None else {voice_kind: [r["voice"] for r in rs]}))
+                    spans = [(t0, t1) for _, _, t0, t1 in emit]
+                    spks = feats[rs[0]["prompt"]][2] if same else torch.cat([feats[r["prompt"]][2] for r in rs], 0)
+                    wavs = dict(zip([u for u, _, _, _ in emit], self._vocode_windows(lats, spks, spans)))
+                    if trace is not None:
+                        for r, lat, (t0, t1) in zip(rs, lats, spans):
+                            lo, h = max(0, t0 - left), r["handle"]
+                            trace["frames"].setdefault(h, []).append((t0, t1))
+                            trace["latent"].setdefault(h, []).append(lat[t0:t1].clone())
+                            trace["window"].setdefault(h, []).append((lo, lat[lo: min(int(lat.shape[0]), t1 + right)].clone()))
+                for u, k, t0, t1, final in plan:
+                    emitted[u] = t1
+                    if final:
+                        del emitted[u]
+                        if trace is not None:
+                            trace["codes"][entered[u[1]]["handle"]] = codes[u][:k].clone()
+                    yield entered[u[1]]["handle"], (wavs[u] if t1 > t0 else torch.zeros(0, device=self.device)), final
+                arrivals()
+        finally:
+            loops.close()          # an early close of this generator abandons the loop
+
+    def infer_stream(self, audio_prompt, text, max_text_tokens_per_sentence=120, parallel_sentences=1, slots=None, **kw):
         """infer() as a generator of (sampling rate, PCM chunk): the text is split into sentences as infer() splits it and the
         sentences are streamed one after another (stream_utterance, whose keywords -- chunk_tokens, seed, the generation
         settings -- pass through).  A chunk is an fp32 device tensor in the int16 range.
         parallel_sentences = P > 1: the sentences go through stream_batch in groups of up to P, one token loop per group, and the
         chunks are still handed out in text order -- what sentence i + 1 produces before sentence i has ended is held back (by
         reference) until then.  One-element force_stop / adapter_ids / adapter_mix stand for every sentence, as they do with P = 1;
-        a group is sampled as one batch, so its samples are not those of P = 1."""
+        a group is sampled as one batch, so its samples are not those of P = 1.
+        slots = S (not None): ALL sentences go through ONE stream_queue(slots=S) -- the refilled loop: a sentence that ends hands
+        its slot to the next one instead of idling to the end of its group -- and the chunks are handed out in text order in the
+        same way.  parallel_sentences does not apply then.  Without `slots` the call is what it was."""
         P = int(parallel_sentences)
         if P < 1:
             raise ValueError("infer_stream: parallel_sentences must be at least 1")
+        if slots is not None and int(slots) < 1:
+            raise ValueError("infer_stream: slots must be at least 1")
         cond_mel = self._prompt(audio_prompt)
         sentences = self.tokenizer.split_sentences(self.tokenizer.tokenize(text), max_text_tokens_per_sentence)
         rows = [torch.tensor(self.tokenizer.convert_tokens_to_ids(sent), dtype=torch.int32) for sent in sentences]
-        if P == 1:
+        if P == 1 and slots is None:
             for ids in rows:
                 for pcm in self.stream_utterance(cond_mel, ids, **kw):
                     yield 24000, pcm
             return
-        for s in range(0, len(rows), P):
-            group = rows[s: s + P]
+
+        def for_each(group):
+            """the keywords with the one-element lists repeated for every sentence of `group`"""
             per_row = {k: list(kw[k]) * len(group) for k in ("force_stop", "adapter_ids", "adapter_mix")
                        if kw.get(k) is not None and not isinstance(kw[k], (str, dict)) and hasattr(kw[k], "__len__") and len(kw[k]) == 1}
-            head, held, over = 0, [[] for _ in group], [False] * len(group)     # head: the sentence whose chunks leave as they come
-            for row, pcm, last in self.stream_batch(cond_mel, group, **{**kw, **per_row}):
-                if pcm.numel():
-                    held[row].append(pcm)
-                over[row] = over[row] or last
-                while head < len(group):
-                    for c in held[head]:
-                        yield 24000, c
-                    held[head] = []
-                    if not over[head]:
-                        break
-                    head += 1
+            return {**kw, **per_row}
+
+        def in_text_order(events, n):
+            order = _TextOrder(n)
+            for row, pcm, last in events:
+                for c in order.push(row, pcm, last):
+                    yield 24000, c
+
+        if slots is not None:
+            if rows:
+                yield from in_text_order(self.stream_queue(cond_mel, rows, slots=int(slots), **for_each(rows)), len(rows))
+            return
+        for s in range(0, len(rows), P):
+            group = rows[s: s + P]
+            yield from in_text_order(self.stream_batch(cond_mel, group, **for_each(group)), len(group))
+
+    def serve_stream_queue(self, more, slots=32, chunk_tokens=32, max_mel_tokens=600):
+        """The service form of stream_queue: whole REQUESTS (a prompt file and a text of any number of sentences each) through one
+        refilled loop.  more() returns the requests that have arrived (a list, usually empty) or None (no more will come); a
+        request is a dict: "handle", "audio_prompt" (a path), "text", and optionally "max_text_tokens_per_sentence", "seed" and
+        the per-request settings do_sample / temperature / top_k / top_p / repetition_penalty, and "max_mel_tokens" (at most this
+        call's: the request's utterances are stopped there).  A generator of (handle, pcm, last): a request's chunks come in text
+        order (what a later sentence produces early is held back, as in infer_stream), `last` with its final one.  A request
+        that cannot be taken -- an unreadable prompt, a refused setting -- yields (handle, the exception, True) and disturbs no
+        other.  The generator ends when the loop has fallen idle (stream_queue): the caller starts the next one."""
+        book = {}            # handle -> the text order of its sentences (_TextOrder)
+        gen, _ = IndexTTS._gen_kwargs({"num_beams": 1})
+        failed = []          # (handle, error | None = nothing to say, True) from here, ((handle, sentence), error) from the queue
+
+        def sentences_of(r):
+            """the request's utterances, every one checked as the loop will check it -- what is refused is refused here"""
+            mel = self._prompt(r["audio_prompt"])
+            toks = self.tokenizer.split_sentences(self.tokenizer.tokenize(r["text"]), int(r.get("max_text_tokens_per_sentence", 120)))
+            own = {k: r[k] for k in ("do_sample", "temperature", "top_k", "top_p", "repetition_penalty", "seed") if r.get(k) is not None}
+            row_sampling_params([own], 1, gen, 1234)
+            limit = r.get("max_mel_tokens")
+            stop = None if limit is None or int(limit) >= max_mel_tokens else max(int(limit) - 1, 0)
+            return [dict(handle=(r["handle"], i), text=torch.as_tensor(self.tokenizer.convert_tokens_to_ids(sent), dtype=torch.int32),
+                         cond_mel=mel, sampling=dict(own, stream=i), force_stop=stop) for i, sent in enumerate(toks)]
+
+        def utterances():
+            new = more()
+            if new is None:
+                return None
+            out = []
+            for r in new:
+                try:
+                    utts = sentences_of(r)
+                    if utts:
+                        book[r["handle"]] = _TextOrder(len(utts))
+                        out.extend(utts)
+                    else:
+                        failed.append((r["handle"], None, True))
+                except Exception as e:  # noqa: BLE001  (this request's own failure: answered to it alone)
+                    failed.append((r["handle"], e, True))
+            return out
+
+        def drain_failed():
+            while failed:
+                item = failed.pop(0)
+                h, e = (item[0], item[1]) if len(item) == 3 else (item[0][0], item[1])   # (refused inside the queue: named by its sentence)
+                book.pop(h, None)                                # its other sentences, if any run, are dropped
+                if h not in done:
+                    done.add(h)
+                    yield h, (torch.zeros(0, device=self.device) if e is None else e), True
+
+        done = set()         # requests that have had their `last` (a request refused inside the queue may still own rows)
+        events = self.stream_queue(None, [], slots=slots, chunk_tokens=chunk_tokens, max_mel_tokens=max_mel_tokens, more=utterances,
+                                   _refused=failed)
+        yield from drain_failed()
+        for (h, i), pcm, last in events:
+            yield from drain_failed()
+            order = book.get(h)
+            if order is None:                                    # a sentence of a request that has been refused: dropped
+                continue
+            for c in order.push(i, pcm, last):
+                yield h, c, False
+            if order.over():
+                del book[h]
+                done.add(h)
+                yield h, torch.zeros(0, device=self.device), True
+        yield from drain_failed()
 
     def infer_queue(self, cond_mel: torch.Tensor, text_token_rows: List[torch.Tensor], slots=32, max_mel_tokens=600,
                     force_stop=None, seed=1234, return_codes=False, cache_positions=4096, check_every=16, staged=True,
@@ -1097,73 +1498,27 @@ class IndexTTS:
         self._mark(phase_events, "start")
         conds, spk = self._prompt_features(cond_mel)
         per_row = isinstance(cond_mel, list)      # conds / spk hold a row per utterance: every group below gathers its own
-        g, eng = self.gpt, self.gpt.engine
         N = len(text_token_rows)
         texts = [t.reshape(-1).to(torch.int32).cpu() for t in text_token_rows]
         stops = [-1] * N if force_stop is None else [int(v) for v in force_stop]
-        sp = sampling_params(gen, seed)
-        stop_text = self.cfg.gpt.stop_text_token
+        voice_kind = None if voices is None else "adapter_ids" if adapter_mix is None else "adapter_mix"
 
         def voiced(ids):
-            """the keyword that names the voices of the utterances `ids` to prefill() / _latents() (none without voices)"""
-            if voices is None:
-                return {}
-            return {"adapter_ids" if adapter_mix is None else "adapter_mix": [voices[i] for i in ids]}
+            """the keyword that names the voices of the utterances `ids` to _latents() (none without voices)"""
+            return {} if voices is None else {voice_kind: [voices[i] for i in ids]}
 
-        def prefixes(ids):
-            """(left-padded prefix batch, pad) of the utterances `ids` -- one itts_prefix_rows launch"""
-            L = max(int(texts[i].numel()) for i in ids)
-            bh = torch.full((len(ids), L), stop_text, dtype=torch.int32)
-            for j, i in enumerate(ids):
-                bh[j, : texts[i].numel()] = texts[i]
-            return g.prefix_rows(conds[torch.tensor(ids, device=conds.device)] if per_row else conds, bh)
-
-        shared = 0 if per_row else (int(conds.shape[1]) if conds.shape[0] == 1 else 0)
-        queue = sorted(range(N), key=lambda i: -int(texts[i].numel()))     # longest first: every later prompt fits
+        feats = {i: (None, conds[i: i + 1], None) for i in range(N)} if per_row else {0: (None, conds, None)}
+        reqs = [dict(handle=i, text=texts[i], prompt=i if per_row else 0, stop=stops[i], sp=None if sampling is None else sampling[i],
+                     voice=None if voices is None else voices[i]) for i in range(N)]
+        waiting = sorted(reqs, key=lambda r: -int(r["text"].numel()))      # longest first: every later prompt fits
         rows: List[torch.Tensor | None] = [None] * N
         self._mark(phase_events, "conditioned")
-        while queue:
-            first, queue = queue[:slots], queue[slots:]
-            emb, pad = prefixes(first)
-            ce = int(check_every)
-            if eng.paged:
-                # paged cache: one loop serves the whole queue -- a slot's blocks go back to the pool when its row stops.  The pool
-                # holds `slots` windows of (longest prompt + start token + max_mel_tokens + the steps up to the second next poll)
-                eng.prefill(emb, pad, max_mel_tokens + ce + 1, shared_rows=shared,
-                            slots_window=emb.shape[1] + 1 + max_mel_tokens + 2 * ce + 2, **voiced(first))
-            else:
-                # contiguous strips: the loop runs whole blocks of check_every steps, the cache has to hold that many positions
-                # past max_mel_tokens; cache positions only grow, so a loop ends when `cache_positions` are used up
-                eng.prefill(emb, pad, max(max_mel_tokens + ce + 1, int(cache_positions) - emb.shape[1] - 2),
-                            shared_rows=shared, paged=False, **voiced(first))
-            entered = list(first)
-
-            def feed(k):
-                nonlocal queue
-                take, queue = queue[:k], queue[k:]
-                if not take:
-                    return []
-                e, p = prefixes(take)
-                p = p.tolist()
-                entered.extend(take)
-                if voices is not None:
-                    return [(e[j, p[j]:], stops[i], None if sampling is None else sampling[i], voices[i]) for j, i in enumerate(take)]
-                if sampling is not None:
-                    return [(e[j, p[j]:], stops[i], sampling[i]) for j, i in enumerate(take)]
-                return [(e[j, p[j]:], stops[i]) for j, i in enumerate(take)]
-
-            codes, leftover = eng.decode_refill(max_mel_tokens, sp if sampling is None else [sampling[i] for i in first], feed,
-                                                force_stop=[stops[i] for i in first],
-                                                positions=None if eng.kv is not None else
-                                                max(int(cache_positions), eng._S + max_mel_tokens + int(check_every) + 1),
-                                                check_every=int(check_every), staged=bool(staged),
-                                                **({} if voices is None else {"voices": [voices[i] for i in first]}))
-            if leftover:                                               # fed but not placed: back to the head of the queue
-                back = entered[len(entered) - len(leftover):]
-                entered = entered[: len(entered) - len(leftover)]
-                queue = back + queue
-            for i, c in zip(entered, codes):
-                rows[i] = c
+        # the loops of stream_queue (_refill_loops), each drained inside GPTEngine.decode_refill
+        for _, placed, codes in self._refill_loops(waiting, feats, int(slots), int(check_every), max_mel_tokens, sampling_params(gen, seed),
+                                                   sampling is not None, voice_kind, not per_row, staged=staged,
+                                                   cache_positions=cache_positions, drain=True):
+            for r, c in zip(placed, codes):
+                rows[r["handle"]] = c
         self._mark(phase_events, "decoded")
         squeezed = []
         for c in rows:

@@ -7,7 +7,11 @@ profiles/stream_latency.txt is this tool's output.
 --rows N: N utterances (texts of 40 tokens, stops spread from 140 down to 100 codes) through ONE IndexTTS.stream_batch against N
 sequential stream_utterance calls and against one infer_batch of the N rows, alternating in one process, at --chunk tokens:
 the time to the first chunk of row 0 and to the last chunk of the last row.  profiles/stream_batch_latency.txt is that output.
-usage: bench_stream.py [reps] [layers] [--rows N] [--chunk C]"""
+--queue N --slots S: N utterances of mixed lengths (BASELINE config 4's: texts of U{8..100} tokens, stops after U{40..400} codes, seed 3)
+through IndexTTS.stream_queue with S slots, against stream_batch in ceil(N / S) static batches of S and against infer_queue on
+the same queue, alternating in one process: the time to every utterance's first chunk (median and worst over the utterances)
+and to the last chunk of the queue.  profiles/stream_queue_latency.txt is that output.
+usage: bench_stream.py [reps] [layers] [--rows N] [--chunk C] [--queue N --slots S]"""
 import argparse
 import os
 import sys
@@ -29,6 +33,8 @@ ap.add_argument("reps", nargs="?", type=int, default=9)
 ap.add_argument("layers", nargs="?", type=int, default=24)
 ap.add_argument("--rows", type=int, default=0, help="N utterances through one stream_batch (0: the one-utterance table)")
 ap.add_argument("--chunk", type=int, default=32, help="chunk_tokens of the --rows table")
+ap.add_argument("--queue", type=int, default=0, help="N utterances of mixed lengths through stream_queue (0: off)")
+ap.add_argument("--slots", type=int, default=32, help="decode slots of the --queue table")
 args = ap.parse_args()
 reps, layers = args.reps, args.layers
 STOP, LIMIT, CHUNKS = 140, 192, (16, 32, 64)
@@ -127,6 +133,75 @@ def rows_table(N, chunk):
     print(f"{tag} | last chunk: stream_batch / sequential = {med(b_last) / med(s_last):.3f}, stream_batch / infer_batch = {med(b_last) / med(t_w):.3f}; "
           f"first chunk of row 0: stream_batch / sequential = {med(b_first) / med(s_first):.3f}")
 
+
+def queue_table(N, S, chunk):
+    """N utterances of mixed lengths: stream_queue(slots=S) | stream_batch in static batches of S | infer_queue, alternating."""
+    rng = np.random.default_rng(3)
+    texts = [torch.from_numpy(rng.integers(2, 12000, size=int(n))).to(torch.int32) for n in rng.integers(8, 101, size=N)]
+    stops = [int(v) for v in rng.integers(40, 401, size=N)]
+    kw = dict(max_mel_tokens=416, seed=5, **GEN)
+
+    def stamp(events, t0):
+        first, n_ev = {}, 0
+        for utt, pcm, _ in events:
+            pcm.cpu()
+            n_ev += 1
+            first.setdefault(utt, 1e3 * (time.perf_counter() - t0))
+        return first, 1e3 * (time.perf_counter() - t0), n_ev
+
+    def queued():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        return stamp(tts.stream_queue(cond_mel, texts, slots=S, chunk_tokens=chunk, force_stop=stops, **kw), t0)
+
+    def static():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        first, n_ev = {}, 0
+        for s0 in range(0, N, S):
+            f, last, n = stamp(((s0 + r, p, l) for r, p, l in tts.stream_batch(cond_mel, texts[s0: s0 + S], chunk_tokens=chunk,
+                                                                              force_stop=stops[s0: s0 + S], **kw)), t0)
+            first.update(f)
+            n_ev += n
+        return first, last, n_ev
+
+    def whole():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for w in tts.infer_queue(cond_mel, texts, slots=S, check_every=chunk, force_stop=stops, **kw):
+            w.cpu()
+        return 1e3 * (time.perf_counter() - t0)
+
+    for _ in range(2):
+        queued(), static(), whole()
+    res = {"queue": [], "static": []}
+    t_whole = []
+    for _ in range(reps):                 # the three paths alternate, so a drift of the machine touches all alike
+        res["queue"].append(queued())
+        res["static"].append(static())
+        t_whole.append(whole())
+    audio = sum(stops) * 1024 / 24000
+    med = lambda v: sorted(v)[len(v) // 2]   # noqa: E731
+    tag = f"stream queue latency | {N} utterances, {S} slots, chunks of {chunk}"
+    print(f"stream queue latency | {layers} layers, bf16 GPT, fp16 vocoder, {N} utterances of 40 .. 400 codes ({audio:.2f} s of audio, {sum(stops)} "
+          f"codes), texts of 8 .. 100 tokens, {S} slots, chunks of {chunk} tokens, halo (left, right) = ({left}, {right}) frames; median (min) of {reps}, "
+          f"host clock to samples on the host")
+    print(f"{tag} | infer_queue, whole utterances (first audio = all audio) | {stat(t_whole)}  {audio / med(t_whole) * 1e3:7.1f} audio-s/s")
+    for name, label in (("queue", "stream_queue, one refilled loop          "), ("static", f"stream_batch, static batches of {S:<9d}")):
+        runs = res[name]
+        f_med = [med(list(f.values())) for f, _, _ in runs]
+        f_max = [max(f.values()) for f, _, _ in runs]
+        last = [l for _, l, _ in runs]
+        print(f"{tag} | {label} | first chunk of an utterance: median {stat(f_med)}  worst {stat(f_max)}  last chunk of the queue {stat(last)}  "
+              f"{audio / med(last) * 1e3:7.1f} audio-s/s  events = {runs[-1][2]}")
+    ql, sl = med([l for _, l, _ in res["queue"]]), med([l for _, l, _ in res["static"]])
+    print(f"{tag} | last chunk: stream_queue / static stream_batch = {ql / sl:.3f}, stream_queue / infer_queue = {ql / med(t_whole):.3f}")
+
+
+if args.queue > 0:
+    queue_table(args.queue, args.slots, args.chunk)
+    torch.cuda.synchronize()
+    sys.exit(0)
 
 if args.rows > 0:
     rows_table(args.rows, args.chunk)
