@@ -513,7 +513,21 @@ int itts_attn_prefill_prefix(const void* qkv, void* out, const void* kcache, con
  * (k / v thirds of those rows)  |  its own rows.  pre_len[e] = 0 for the shared block itself.  Same key tiling from sequence
  * position 0 as itts_attn_prefill_packed over the un-shared layout: same bits per row.  With caches (T [rows][H][smax][64]),
  * element e's OWN rows are appended to cache row w_row[e] at positions w_pos0[e] + local row (the caller copies the shared
- * block's cache rows to the other elements' cache rows). */
+ * block's cache rows to the other elements' cache rows).
+ *
+ * pre_row0 == NULL selects the CACHED-PREFIX APPEND form (the incremental latent pass of a stream, which keeps the keys and
+ * values of every row it has computed): element e's sequence is  pre_len[e] keys / values read from cache row w_row[e],
+ * positions [w_pos0[e] - pre_len[e], w_pos0[e])  |  its own rows [row_off[e], row_off[e+1]) of qkv.  Only the qkv rows are
+ * queries (query i sits at sequence position pre_len[e] + i and sees every key up to itself), and the k / v thirds of the own
+ * rows are appended to cache row w_row[e] at positions w_pos0[e] + i.  The caches are required (kcache, vcache, w_row, w_pos0
+ * non-NULL) and contiguous, T [rows][H][smax][64]; kv_tab != NULL is refused.  What a launch reads from the caches (< w_pos0[e])
+ * and what it writes (>= w_pos0[e]) never overlap; the keys of the new rows are taken from qkv, never read back.  The caller
+ * guarantees 0 <= w_pos0[e] - pre_len[e], w_pos0[e] + rows of e <= smax and distinct w_row (device data: not checked).
+ * Key tiles are cut from sequence position 0 in steps of 64 and one query row's arithmetic is that of the other forms, so every
+ * output row equals, bit for bit, the row itts_attn_prefill_packed produces for the same sequence with the prefix rows inside
+ * qkv.  Two kernel forms, chosen from Smax, with the same bits per row: Smax <= 128 runs a 16-query tile per workgroup
+ * (itts_last_kernel() = "attn_append<16>"), anything longer the 64-query tile of the other forms ("attn_append<64>"); Smax may
+ * exceed the longest element (workgroups past an element's rows return at once). */
 int itts_attn_prefill_shared(const void* qkv, void* out, void* kcache, void* vcache, const int32_t* row_off,
                              const int32_t* pre_len, const int32_t* pre_row0, const int32_t* w_row, const int32_t* w_pos0,
                              int E, int Smax, int H, int smax, int dtype, const int32_t* kv_tab, int kv_bs, void* stream);

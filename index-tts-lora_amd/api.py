@@ -83,11 +83,13 @@ def _inside(path: str, roots) -> bool:
 
 def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/config.yaml", device=None, use_fp16=True,
                finetune_dir=os.path.join("finetune_models", "checkpoints"), output_dir=os.path.join("outputs", "api"),
-               prompt_dir="prompts", stream_slots=None):
+               prompt_dir="prompts", stream_slots=None, stream_latent_cache=False):
     """`tts`: a ready IndexTTS (tests, embedding) or None to build one from model_dir / config_path on first use.
     stream_slots = S (off by default): /tts/stream requests are served by ONE worker that owns a refilled streaming loop of S
     decode slots (IndexTTS.serve_stream_queue): a request that arrives while the loop runs enters it, a request that finds no
     loop starts one.  None: every /tts/stream request runs its own generation under the engine lock, as before.
+    stream_latent_cache (off by default): /tts/stream runs the incremental latent pass (latent_cache=True of
+    IndexTTS.infer_stream / serve_stream_queue) on either route.
     Server-side paths a client may name are confined (the reference opens whatever it is given, api.py:125-134, :218-226):
     /model/reload only loads files inside model_dir / finetune_dir, /tts prompt_audio_path only reads files inside
     prompt_dir / model_dir; anything else answers 403."""
@@ -96,6 +98,7 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
     app = FastAPI(title="IndexTTS API (MI355X build)", version="1.0.0")
     state = {"tts": tts}
     lock = threading.Lock()
+    latent_kw = {"latent_cache": True} if stream_latent_cache else {}
     model_roots = [model_dir, finetune_dir]
     prompt_roots = [prompt_dir, model_dir]
 
@@ -174,7 +177,7 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
             while True:
                 try:
                     with lock, torch.no_grad():
-                        for handle, pcm, last in engine().serve_stream_queue(self.take, slots=int(stream_slots)):
+                        for handle, pcm, last in engine().serve_stream_queue(self.take, slots=int(stream_slots), **latent_kw):
                             if isinstance(pcm, BaseException):
                                 self.finish(handle, pcm)
                                 continue
@@ -318,7 +321,7 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
             import torch
             try:
                 with lock, torch.no_grad():
-                    for _, pcm in engine().infer_stream(prompt, req.text, req.max_text_tokens_per_sentence, **kwargs):
+                    for _, pcm in engine().infer_stream(prompt, req.text, req.max_text_tokens_per_sentence, **kwargs, **latent_kw):
                         chunks.put(pcm.float().cpu().numpy().astype("<i2").tobytes())
                 chunks.put(None)
             except BaseException as e:  # noqa: BLE001  (handed to the response, which answers or ends the body)
@@ -362,6 +365,10 @@ if __name__ == "__main__":
     ap.add_argument("--stream-slots", type=int, default=None, metavar="S",
                     help="serve /tts/stream from one shared refilled loop of S decode slots (IndexTTS.stream_queue): concurrent "
                          "requests share a token loop instead of waiting for one another.  Off by default")
+    ap.add_argument("--stream-latent-cache", action="store_true", default=False,
+                    help="/tts/stream keeps the latent pass's keys and values between chunks (IndexTTS.infer_stream(latent_cache=True)): "
+                         "a chunk boundary then costs its new rows only.  Off by default")
     a = ap.parse_args()
     import uvicorn
-    uvicorn.run(create_app(None, a.model_dir, a.config, a.device, not a.no_fp16, prompt_dir=a.prompt_dir, stream_slots=a.stream_slots), host=a.host, port=a.port)
+    uvicorn.run(create_app(None, a.model_dir, a.config, a.device, not a.no_fp16, prompt_dir=a.prompt_dir, stream_slots=a.stream_slots,
+                           stream_latent_cache=a.stream_latent_cache), host=a.host, port=a.port)

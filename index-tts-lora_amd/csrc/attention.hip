@@ -382,13 +382,18 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const T* __restrict__
   // position pre_pos0[b] + j.  Key tiles are cut from sequence position 0, exactly as if the prefix rows were part of qkv.
   // pre_qkv != 0: the prefix keys are ROWS OF qkv instead (rows pre_pos0[b] .. of the packed buffer: a block that several
   // elements share, computed once in this very pass); pkc / pvc then point at the k / v thirds of qkv.
+  // pre_qkv == 2 (append form, contiguous caches only): the prefix is the end of the very cache row this element appends to --
+  // row w_row[b], positions [w_pos0[b] - pl, w_pos0[b]); pre_row / pre_pos0 are not read.  The appended positions start at
+  // w_pos0[b]: what a launch reads and what it writes never overlap.
   const int pl = pkc != nullptr ? pre_len[b] : 0;
-  const int64_t pstr = pre_qkv ? (int64_t)3 * D : HD;
-  const int64_t pbase = pkc == nullptr ? 0
-                        : pre_qkv      ? (int64_t)pre_pos0[b] * 3 * D + h * HD
-                                       : (((int64_t)pre_row[b] * H + h) * smax + pre_pos0[b]) * HD;
+  const bool in_qkv = pre_qkv == 1, cached = pkc != nullptr && !in_qkv;
   // (paged cache: a cached prefix key is addressed through the block table, see kv_elem_off)
-  const int p_row = (pkc != nullptr && !pre_qkv) ? pre_row[b] : 0, p_pos0 = (pkc != nullptr && !pre_qkv) ? pre_pos0[b] : 0;
+  const int p_row = !cached ? 0 : pre_qkv == 2 ? w_row[b] : pre_row[b];
+  const int p_pos0 = !cached ? 0 : pre_qkv == 2 ? w_pos0[b] - pl : pre_pos0[b];
+  const int64_t pstr = in_qkv ? (int64_t)3 * D : HD;
+  const int64_t pbase = pkc == nullptr ? 0
+                        : in_qkv       ? (int64_t)pre_pos0[b] * 3 * D + h * HD
+                                       : (((int64_t)p_row * H + h) * smax + p_pos0) * HD;
   const int Stot = pl + S;
   // cache append of the prefix form: this workgroup's own 64 rows go to cache row w_row[b], positions w_pos0[b] + local row
   if (wkc != nullptr) {
@@ -428,7 +433,7 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const T* __restrict__
       const int key = jt + kk;
       frag kv = zero_frag<frag>(), vv = zero_frag<frag>();
       if (key < pl) {
-        const int64_t po = (kv_tab != nullptr && !pre_qkv) ? kv_elem_off(kv_tab, bs_log2, p_row, p_pos0 + key, H, h, smax) + dc * E
+        const int64_t po = (kv_tab != nullptr && !in_qkv) ? kv_elem_off(kv_tab, bs_log2, p_row, p_pos0 + key, H, h, smax) + dc * E
                                                            : pbase + (int64_t)key * pstr + dc * E;
         kv = ld16<frag>(pkc + po);
         vv = ld16<frag>(pvc + po);
@@ -524,6 +529,192 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const T* __restrict__
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Append form, narrow query tile (the incremental latent pass of a stream: 1-64 new rows behind several hundred cached keys).
+// Workgroup = 16 consecutive queries of one (element, head) -- ONE MFMA row block -- and still 4 waves: at a chunk of 16 the
+// 64-query tile above has three of its four waves multiplying zero queries, and only H x E workgroups exist.  Here the waves
+// share one query block and split the COLUMNS of both products: wave w computes the score block of keys 16w .. 16w+15 of the
+// tile (sacc[w] of the kernel above) and the output block of head dims 16w .. 16w+15 (O[w] above).  The raw score blocks are
+// exchanged through LDS (Ss), after which every wave holds all four and runs the SAME online softmax the kernel above runs --
+// four times redundantly, 16 exps per lane per tile, which is cheaper than a second exchange.  Every chain of a query row (the
+// ks order inside sacc[n] and O[n], the n order of the row sum, the 16-lane shuffles, the scale 0.125, the tile order from
+// sequence position 0) is the one of attn_prefill_kernel, so a row's bits do not depend on the form.  A tile whose keys are all
+// behind a query leaves that row's state untouched (corr = 1, p = 0), so the tiles the 64-query form walks past a row's own
+// position, and this form does not, change nothing either.
+// Staging: all 256 threads stage the 64-key tile (K rows, V transposed); the NEXT tile's 16-byte requests are issued into
+// registers right after the current tile is in LDS and land while the MFMAs and the softmax run (the barrier of the score
+// exchange waits for LDS only, not for those requests).
+// Contiguous caches only: the prefix of element e is cache row w_row[e], positions [w_pos0[e] - pre_len[e], w_pos0[e]); the own
+// rows' k / v are stored at w_pos0[e] + local row, and as keys they are taken from qkv, never read back.
+// ---------------------------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void attn_append16_kernel(const T* __restrict__ qkv, T* __restrict__ out, T* kc, T* vc,
+                                                             const int32_t* __restrict__ row_off,
+                                                             const int32_t* __restrict__ pre_len,
+                                                             const int32_t* __restrict__ w_row,
+                                                             const int32_t* __restrict__ w_pos0, int H, int smax) {
+  typedef Elem<T> EL;
+  typedef typename EL::frag frag;
+  constexpr int E = EL::E, KS = EL::KS, NKS = HD / KS;
+  constexpr int ES = (int)sizeof(T);
+  constexpr int RS = HD * ES + 16;        // LDS row stride in bytes (64 elements + 16 B pad), as above
+  constexpr int CPR = HD / E;             // 16-byte chunks per row
+  constexpr int NCH = 64 * CPR / 256;     // chunks of a 64-key tile per thread: 2 (16-bit) / 4 (fp32)
+  constexpr int SS = 68;                  // floats per Ss row: the four row groups of a lane quad land 16 banks apart
+  __shared__ __attribute__((aligned(16))) unsigned char Ks[64 * RS];
+  __shared__ __attribute__((aligned(16))) unsigned char Vt[64 * RS];
+  __shared__ __attribute__((aligned(16))) unsigned char Ps[4][16 * RS];
+  __shared__ float Ss[16 * SS];
+  const int q0 = blockIdx.x * 16, h = blockIdx.y, b = blockIdx.z;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = lane >> 4, c = lane & 15;
+  const int D = H * HD;
+  const int rbeg = row_off[b];
+  const int S = row_off[b + 1] - rbeg;
+  if (q0 >= S) return;  // workgroup-uniform
+  const int pl = pre_len[b], wr = w_row[b], wp0 = w_pos0[b];
+  const int Stot = pl + S;
+  const T* base = qkv + (int64_t)rbeg * 3 * D;
+  const int64_t crow = ((int64_t)wr * H + h) * smax * HD;   // this (cache row, head)
+  const int64_t pbase = crow + (int64_t)(wp0 - pl) * HD;    // prefix key j sits at pbase + j * 64
+
+  // ---- append this workgroup's own 16 rows
+  if (tid < 16 * CPR) {
+    const int kk = tid / CPR, dc = tid - kk * CPR;
+    const int q = q0 + kk;
+    if (q < S) {
+      const T* src = base + (int64_t)q * 3 * D + D + h * HD + dc * E;
+      const int64_t o = crow + (int64_t)(wp0 + q) * HD + dc * E;
+      st16(kc + o, ld16<frag>(src));
+      st16(vc + o, ld16<frag>(src + D));
+    }
+  }
+
+  frag qf[NKS];
+  {
+    const int row = q0 + c;
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks)
+      qf[ks] = (row < S) ? ld16<frag>(base + (int64_t)row * 3 * D + h * HD + ks * KS + g * E) : zero_frag<frag>();
+  }
+  f32x4 O = f32x4{0.f, 0.f, 0.f, 0.f};   // rows 4g+j, head dim 16*wave + c
+  float m[4], l[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { m[j] = -INFINITY; l[j] = 0.f; }
+
+  frag kr[NCH], vr[NCH];
+  auto request_tile = [&](const int jt) {
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      const int ch = tid + i * 256;
+      const int kk = ch / CPR, dc = ch - kk * CPR;
+      const int key = jt + kk;
+      kr[i] = zero_frag<frag>();
+      vr[i] = zero_frag<frag>();
+      if (key < pl) {
+        const int64_t po = pbase + (int64_t)key * HD + dc * E;
+        kr[i] = ld16<frag>(kc + po);
+        vr[i] = ld16<frag>(vc + po);
+      } else if (key < Stot) {
+        const T* src = base + (int64_t)(key - pl) * 3 * D + D + h * HD + dc * E;
+        kr[i] = ld16<frag>(src);
+        vr[i] = ld16<frag>(src + D);
+      }
+    }
+  };
+
+  const int jend = min(Stot, pl + q0 + 16);
+  request_tile(0);
+  for (int jt = 0; jt < jend; jt += 64) {
+    __syncthreads();   // the last tile's readers are done (and the requested fragments have landed)
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      const int ch = tid + i * 256;
+      const int kk = ch / CPR, dc = ch - kk * CPR;
+      st16(Ks + kk * RS + dc * E * ES, kr[i]);
+#pragma unroll
+      for (int e = 0; e < E; ++e) *reinterpret_cast<T*>(Vt + (dc * E + e) * RS + kk * ES) = vr[i][e];
+    }
+    __syncthreads();
+    if (jt + 64 < jend) request_tile(jt + 64);   // workgroup-uniform; in flight until the next iteration's first barrier
+    // ---- this wave's block of S = Q K^T: 16 queries x keys 16*wave .. 16*wave + 15
+    {
+      f32x4 sw = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < NKS; ++ks) {
+        frag bf = ld16<frag>(Ks + (16 * wave + c) * RS + (ks * KS + g * E) * ES);
+        sw = EL::mma(qf[ks], bf, sw);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) Ss[(4 * g + j) * SS + 16 * wave + c] = sw[j];
+    }
+    // LDS-only wait + raw barrier: __syncthreads() would also wait for the next tile's requests
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    f32x4 sacc[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) sacc[n][j] = Ss[(4 * g + j) * SS + 16 * n + c];
+    // ---- online softmax, as in attn_prefill_kernel; this lane holds rows 4g+j (j<4), columns 16n+c (n<4)
+    float rmax[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int q = pl + q0 + 4 * g + j;   // sequence position of the query
+      float mx = -INFINITY;
+#pragma unroll
+      for (int n = 0; n < 4; ++n) {
+        const int key = jt + 16 * n + c;
+        const bool vis = (key <= q) && (key < Stot);
+        const float v = vis ? sacc[n][j] * 0.125f : -INFINITY;
+        sacc[n][j] = v;
+        mx = fmaxf(mx, v);
+      }
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+      rmax[j] = mx;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float mn = fmaxf(m[j], rmax[j]);
+      const float corr = (m[j] == -INFINITY) ? 0.f : __expf(m[j] - mn);
+      float rs = 0.f;
+#pragma unroll
+      for (int n = 0; n < 4; ++n) {
+        const float pv = (sacc[n][j] == -INFINITY) ? 0.f : __expf(sacc[n][j] - mn);
+        sacc[n][j] = pv;
+        rs += pv;
+      }
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) rs += __shfl_xor(rs, o, 64);
+      l[j] = l[j] * corr + rs;
+      m[j] = mn;
+      O[j] *= corr;
+    }
+    // ---- P: accumulator layout -> A-operand layout through the wave's own LDS scratch (same wave writes and reads)
+    unsigned char* ps = Ps[wave];
+#pragma unroll
+    for (int n = 0; n < 4; ++n)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) *reinterpret_cast<T*>(ps + (4 * g + j) * RS + (16 * n + c) * ES) = EL::from_f(sacc[n][j]);
+    // ---- this wave's block of O += P V: head dims 16*wave .. 16*wave + 15
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) {
+      frag af = ld16<frag>(ps + c * RS + (ks * KS + g * E) * ES);
+      frag bf = ld16<frag>(Vt + (16 * wave + c) * RS + (ks * KS + g * E) * ES);
+      O = EL::mma(af, bf, O);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int q = q0 + 4 * g + j;
+    if (q >= S) continue;
+    const float inv = l[j] > 0.f ? 1.0f / l[j] : 0.f;
+    out[((int64_t)rbeg + q) * D + h * HD + 16 * wave + c] = EL::from_f(O[j] * inv);
+  }
+}
+
 }  // namespace itts
 
 using namespace itts;
@@ -600,10 +791,41 @@ extern "C" int itts_attn_prefill_prefix(const void* qkv, void* out, const void* 
                            pre_len, pre_row, pre_pos0, 0, nullptr, nullptr, nullptr, nullptr, kv_tab, kv_bs);
 }
 
+// itts_attn_prefill_shared with pre_row0 == NULL: the cached-prefix append form (include/indextts_hip.h).  Two kernel forms, the
+// same bits per row: chunks (Smax <= ATTN_APPEND_NARROW_MAX) take the 16-query tile, longer passes -- a stream's first one carries
+// the prompt -- the 64-query tile of attn_prefill_kernel, which stages every key tile once per 64 queries instead of once per 16.
+constexpr int ATTN_APPEND_NARROW_MAX = 128;
+
+static int attn_append_impl(const void* qkv, void* out, void* kcache, void* vcache, const int32_t* row_off, const int32_t* pre_len,
+                            const int32_t* w_row, const int32_t* w_pos0, int E, int Smax, int H, int smax, int dtype,
+                            const int32_t* kv_tab, void* stream) {
+  ITTS_REQUIRE(qkv && out && row_off && pre_len && kcache && vcache && w_row && w_pos0,
+               "itts_attn_prefill_shared (append form): null pointer (qkv, out, row_off, pre_len, both caches, w_row and w_pos0 are required)");
+  ITTS_REQUIRE(kv_tab == nullptr, "itts_attn_prefill_shared (append form): a paged cache (kv_tab) is not supported, pass contiguous caches");
+  ITTS_REQUIRE(E > 0 && E <= 65535 && H > 0 && H <= 65535 && Smax >= 1 && smax >= 1 && Smax <= smax,
+               "itts_attn_prefill_shared (append form): bad shape E=%d Smax=%d H=%d smax=%d", E, Smax, H, smax);
+  if (Smax > ATTN_APPEND_NARROW_MAX) {
+    const int rc = attn_prefill_impl(qkv, out, nullptr, nullptr, nullptr, E, Smax, H, smax, dtype, row_off, nullptr, stream, kcache, vcache,
+                                     pre_len, pre_len /* unused */, pre_len /* unused */, 2, kcache, vcache, w_row, w_pos0, nullptr, 0);
+    if (rc == ITTS_OK) set_last_kernel("attn_append<64>");
+    return rc;
+  }
+  dim3 grid((Smax + 15) / 16, H, E), block(256);
+  return by_dtype(dtype, "itts_attn_prefill_shared", [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(attn_append16_kernel<T>, grid, block, 0, (hipStream_t)stream, (const T*)qkv, (T*)out, (T*)kcache, (T*)vcache,
+                       row_off, pre_len, w_row, w_pos0, H, smax);
+    set_last_kernel("attn_append<16>");
+    return check_launch("itts_attn_prefill_shared");
+  });
+}
+
 extern "C" int itts_attn_prefill_shared(const void* qkv, void* out, void* kcache, void* vcache, const int32_t* row_off,
                                         const int32_t* pre_len, const int32_t* pre_row0, const int32_t* w_row,
                                         const int32_t* w_pos0, int E, int Smax, int H, int smax, int dtype, const int32_t* kv_tab,
                                         int kv_bs, void* stream) {
+  if (pre_row0 == nullptr) return attn_append_impl(qkv, out, kcache, vcache, row_off, pre_len, w_row, w_pos0, E, Smax, H, smax, dtype,
+                                                   kv_tab, stream);
   ITTS_REQUIRE(qkv && row_off && pre_len && pre_row0 && (kcache == nullptr) == (vcache == nullptr) &&
                    (kcache == nullptr || (w_row && w_pos0)), "itts_attn_prefill_shared: null pointer");
   const int D = H * 64;

@@ -773,6 +773,31 @@ def attn_prefill_shared(qkv, out, kcache, vcache, row_off, pre_len, pre_row0, w_
            "itts_attn_prefill_shared")
 
 
+def attn_prefill_append(qkv, out, kcache, vcache, row_off, pre_len, w_row, w_pos0, E, Smax, H, smax, kv_tab=None, kv_bs=0):
+    """The cached-prefix append form of itts_attn_prefill_shared (pre_row0 = NULL, see include/indextts_hip.h): element e =
+    pre_len[e] keys of cache row w_row[e] in front of position w_pos0[e], then its rows of qkv, whose k / v are appended there.
+    Checked here, before anything is launched: no paged cache, both caches and w_row / w_pos0 present, contiguous
+    [rows][H][smax][64] views of qkv's dtype, Smax >= 1."""
+    who = "itts_attn_prefill_shared (append form)"
+    if kv_tab is not None:
+        raise NativeError(f"{who}: a paged cache (kv_tab) is not supported, pass contiguous caches")
+    if kcache is None or vcache is None or w_row is None or w_pos0 is None:
+        raise NativeError(f"{who}: the caches, w_row and w_pos0 are required")
+    if not (kcache.is_contiguous() and vcache.is_contiguous()):
+        raise NativeError(f"{who}: the caches must be contiguous [rows][H][smax][64] views")
+    if not (kcache.dtype == vcache.dtype == qkv.dtype == out.dtype):
+        raise NativeError(f"{who}: qkv, out and the caches must share one dtype (got {qkv.dtype}, {out.dtype}, {kcache.dtype}, "
+                          f"{vcache.dtype})")
+    if tuple(kcache.shape[-3:]) != (H, smax, 64) or kcache.shape != vcache.shape:
+        raise NativeError(f"{who}: the caches must be [rows][{H}][{smax}][64] (got {tuple(kcache.shape)}, {tuple(vcache.shape)})")
+    if int(Smax) < 1:
+        raise NativeError(f"{who}: Smax must be at least 1 (got {Smax})")
+    _dev(qkv, out, kcache, vcache, row_off, pre_len, w_row, w_pos0)
+    _check(lib().itts_attn_prefill_shared(_p(qkv), _p(out), _p(kcache), _p(vcache), _p(row_off), _p(pre_len), None,
+                                          _p(w_row), _p(w_pos0), E, Smax, H, smax, dt(qkv.dtype), None, 0, _stream()),
+           "itts_attn_prefill_shared")
+
+
 def kv_share_rows(kc, vc, B, H, Cn, p0, pad, smax, kv_tab=None, kv_bs=0):
     """kc / vc: the whole caches [L, ...] (all layers in one launch): row 0's positions [p0, p0 + Cn) -> [pad[b], pad[b] + Cn) of
     rows 1 .. B-1 (itts_kv_share_rows)."""

@@ -24,6 +24,9 @@ def main(argv=None):
                         help="with --stream: ALL sentences of the text go through one refilled loop of S decode slots "
                              "(IndexTTS.infer_stream(slots=S)): a sentence that ends hands its slot to the next one.  The chunks are "
                              "still written in text order; --stream-parallel does not apply then")
+    parser.add_argument("--stream-latent-cache", action="store_true", default=False,
+                        help="with --stream: keep the latent pass's keys and values between chunks (IndexTTS.infer_stream("
+                             "latent_cache=True)): a chunk boundary then costs its new rows only")
     parser.add_argument("-d", "--device", type=str, default=None, help="device (cuda:N); CPU/MPS are not supported")
     args = parser.parse_args(argv)
 
@@ -62,7 +65,8 @@ def main(argv=None):
         from indextts.utils.audio import write_pcm16
         rate, chunks = 24000, []
         for rate, pcm in tts.infer_stream(audio_prompt=args.voice, text=args.text.strip(), parallel_sentences=args.stream_parallel,
-                                            **({} if args.stream_slots is None else {"slots": args.stream_slots})):
+                                            **({} if args.stream_slots is None else {"slots": args.stream_slots}),
+                                            **({"latent_cache": True} if args.stream_latent_cache else {})):
             chunks.append(pcm.cpu())
         if os.path.dirname(args.output_path) != "":
             os.makedirs(os.path.dirname(args.output_path), exist_ok=True)

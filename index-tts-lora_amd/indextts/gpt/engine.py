@@ -149,6 +149,29 @@ def admit(kv: PagedKV, rows, items, end, max_new, check_every) -> int:
     return len(items)
 
 
+class LatentCache:
+    """The K / V cache of the incremental latent pass (GPTEngine.latent_cache / latent_append): kc / vc of shape
+    T [L][rows][H][cap][64], contiguous per layer, and on the host have[row] = the positions row holds and voice[row] = the
+    voice they were computed under.  Positions >= have[row] are never read, so reset() clears nothing on the device."""
+
+    @staticmethod
+    def nbytes(L, D, rows, cap, dtype):
+        return L * 2 * D * cap * rows * torch.empty(0, dtype=dtype).element_size()
+
+    def __init__(self, L, H, rows, cap, dtype, device):
+        import numpy as np
+        self.rows, self.cap = rows, cap
+        self.kc = torch.zeros(L, rows, H, cap, 64, dtype=dtype, device=device)
+        self.vc = torch.zeros(L, rows, H, cap, 64, dtype=dtype, device=device)
+        self.have = np.zeros(rows, dtype=np.int64)
+        self.voice = [None] * rows
+
+    def reset(self, row: int):
+        """Row `row` starts a new sequence."""
+        self.have[int(row)] = 0
+        self.voice[int(row)] = None
+
+
 class GPTEngine:
     def __init__(self, W: dict, layers: int, model_dim: int, heads: int, dtype=torch.bfloat16, device="cuda",
                  start_mel_token=8192, stop_mel_token=8193, weight_dtype=None, kv_dtype=None):
@@ -1064,6 +1087,83 @@ class GPTEngine:
             **self._row_voices(ids, mix, m))
         out = torch.empty_like(h)
         nat.layernorm(h, self.ln_f[0], self.ln_f[1], out, self.final_norm[0], self.final_norm[1])
+        return out
+
+    # ------------------------------------------------------------------------------------------------ incremental latent pass
+    LATENT_CACHE_BUDGET = 8 << 30      # bytes a latent_cache() may ask for (32 rows of 1 344 positions at 24 x 1280, 16-bit: 5.3 GB)
+
+    def latent_cache(self, rows: int, cap: int) -> "LatentCache":
+        """A K / V cache of the teacher-forced pass itself, for latent_append(): per layer the keys and values of every row
+        the pass has computed, kc[l] / vc[l] of shape T [rows][H][cap][64] (T = the engine's dtype, also over an FP8 decode
+        cache or FP8 weights), and the host array have[rows] -- the positions each row holds -- all zero.  cap is rounded up
+        to a multiple of 64.  It belongs to a stream, not to the decode loop: nothing of the engine points at it.
+        Size: layers x 2 x D x cap x itemsize per row (126 MB per row at 24 layers, D = 1280, cap = 1024, 16-bit).  A request
+        above GPTEngine.LATENT_CACHE_BUDGET (8 GiB) is refused with ValueError before anything is allocated."""
+        rows, cap = int(rows), int(cap)
+        if rows < 1 or cap < 1:
+            raise ValueError(f"latent_cache(): rows and cap must be at least 1 (got {rows}, {cap})")
+        cap = (cap + 63) // 64 * 64
+        need = LatentCache.nbytes(self.L, self.D, rows, cap, self.dtype)
+        if need > self.LATENT_CACHE_BUDGET:
+            raise ValueError(f"latent_cache(): {rows} rows of {cap} positions need {need} bytes, more than the budget of "
+                             f"{self.LATENT_CACHE_BUDGET} (GPTEngine.LATENT_CACHE_BUDGET)")
+        return LatentCache(self.L, self.H, rows, cap, self.dtype, self.device)
+
+    def latent_append(self, cache: "LatentCache", emb: torch.Tensor, n_lens, cache_rows, adapter_ids=None, adapter_mix=None) -> torch.Tensor:
+        """The teacher-forced pass (latent()) over the NEW rows of sequences whose earlier rows are in `cache`.
+        emb fp32 [sum(n_lens), D]: element b's next n_lens[b] rows, which continue the sequence in cache row cache_rows[b] at
+        position cache.have[cache_rows[b]].  The first call for a row carries its whole prompt cond | text followed by start |
+        codes ...; later calls carry only the further mel rows.  The pass is causal, so what it returns for a row is final:
+        final_norm(ln_f(hidden)) fp32 [sum(n_lens), D], the rows latent() gives for the same positions of the whole sequence
+        (fp32: the same bits; 16-bit: the split-K factor of the projections follows the row count, see _proj_ksplit).
+        Only the new rows go through the GEMMs, the LayerNorms and the attention queries; their keys and values are appended to
+        the cache (itts_attn_prefill_shared, append form) and have advances.
+        Refused with ValueError before anything is launched: have + n > cap, a cache row named twice, a cache of another engine
+        shape, and voices (adapter_ids / adapter_mix, as latent() takes them) that differ from those the row's earlier rows were
+        computed under -- the cache remembers them per row until reset().
+        It allocates its operands, reads only weights and the latent cache and writes only the latent cache: none of the step's
+        buffers, the decode cache or the refill staging buffers -- so it may run between two bursts of decode_chunks() /
+        decode_refill_chunks() on the loop's stream, under the rule of decode_chunks."""
+        import numpy as np
+        B = len(n_lens)
+        n = [int(v) for v in n_lens]
+        rows = [int(r) for r in cache_rows]
+        if B < 1 or len(rows) != B or min(n) < 1:
+            raise ValueError("latent_append(): one cache row and at least one new row per element")
+        if (cache.kc.shape[0], cache.kc.shape[2], cache.kc.dtype) != (self.L, self.H, self.dtype) or cache.kc.device != torch.device(self.device):
+            raise ValueError("latent_append(): the cache was made for another engine (layers, heads, dtype or device differ)")
+        if min(rows) < 0 or max(rows) >= cache.rows:
+            raise ValueError(f"latent_append(): cache_rows must lie in [0, {cache.rows}): {rows}")
+        if len(set(rows)) != B:
+            raise ValueError(f"latent_append(): a cache row is named twice in one call: {rows}")
+        have = [int(cache.have[r]) for r in rows]
+        for r, h0, k in zip(rows, have, n):
+            if h0 + k > cache.cap:
+                raise ValueError(f"latent_append(): cache row {r} holds {h0} positions, {k} more do not fit its {cache.cap}")
+        ids, mix = self._voices(adapter_ids, adapter_mix, B)
+        voices = [("mix", mix[b]) if mix is not None else ("id", None if ids is None else ids[b]) for b in range(B)]
+        for r, h0, v in zip(rows, have, voices):
+            if h0 and cache.voice[r] != v:
+                raise ValueError(f"latent_append(): cache row {r} was computed under another voice ({cache.voice[r]}, now {v})")
+        if emb.dim() != 2 or emb.shape[0] != sum(n) or emb.shape[1] != self.D:
+            raise ValueError("latent_append(): emb does not hold sum(n_lens) rows of D")
+        if self._cap_b == 0:
+            self._ensure(1, 64)
+        dev, H = self.device, self.H
+        off = np.concatenate([[0], np.cumsum(n)])
+        meta = torch.from_numpy(np.concatenate([off, have, rows]).astype(np.int32)).to(dev)   # one upload
+        row_off, pos0, w_row = meta[: B + 1], meta[B + 1:2 * B + 1], meta[2 * B + 1:]
+        h = emb.to(dev, torch.float32).contiguous()
+        if h is emb or h.data_ptr() == emb.data_ptr():
+            h = h.clone()                                   # (the blocks run in place)
+        h = self._big_m_layers(h, lambda i, qkv, att: nat.attn_prefill_append(
+            qkv, att, cache.kc[i], cache.vc[i], row_off, pos0, w_row, pos0, B, max(n), H, cache.cap),
+            **self._row_voices(ids, mix, n))
+        out = torch.empty_like(h)
+        nat.layernorm(h, self.ln_f[0], self.ln_f[1], out, self.final_norm[0], self.final_norm[1])
+        for r, k, v in zip(rows, n, voices):
+            cache.have[r] += k
+            cache.voice[r] = v
         return out
 
     # ------------------------------------------------------------------------------------------------ decode loop

@@ -113,6 +113,21 @@ class _TextOrder:
         return self.head == len(self.held)
 
 
+class _LatentRows:
+    """What a stream with latent_cache=True keeps between two boundaries: the engine's latent cache (GPTEngine.latent_cache:
+    the pass-2 keys / values of every row computed so far), and per cache row the mel rows it has been fed and the latents
+    they gave (fp32 [frames, D], on the device).  A cache row is a stream's batch row, or a queue's decode slot."""
+
+    def __init__(self, eng, rows, cap):
+        self.cache = eng.latent_cache(rows, cap)
+        self.fed, self.lat = [0] * rows, [None] * rows
+
+    def reset(self, row):
+        """The row's utterance has ended: its cache row starts the next one from position 0."""
+        self.cache.reset(row)
+        self.fed[row], self.lat[row] = 0, None
+
+
 class IndexTTS:
     def __init__(self, cfg_path="checkpoints/config.yaml", model_dir="checkpoints", is_fp16=True, device=None,
                  use_cuda_kernel=None, speaker_info_path=None, precision_config=None, gpt_path=None,
@@ -605,6 +620,63 @@ class IndexTTS:
         enc = eng.latent(batch, lengths=[s0 + n + 2 for s0, n in spans], adapter_ids=adapter_ids, adapter_mix=adapter_mix)   # real rows only (cond | text | mel incl. start/stop)
         return [enc[i, s0: s0 + n] for i, (s0, n) in enumerate(spans)]
 
+    def _latents_incremental(self, st: "_LatentRows", rows, conds, text_rows, code_rows, adapter_ids=None, adapter_mix=None):
+        """_latents() for a stream that keeps a latent cache (st: _LatentRows; rows: the cache row of every element).  Only the
+        part of each sequence the cache does not hold yet goes through the engine (GPTEngine.latent_append): on a row's first
+        use its prompt rows cond | start_text text stop_text -- the index gather of _latents -- and then the mel rows start |
+        codes[:k-1] beyond those already cached (the latent of frame t reads start and the codes < t: k rows give k frames).
+        The latents a row has produced stay on the device (st.lat[row], fp32 [frames, D]: the vocoder's window reaches back
+        into frames that were computed at earlier boundaries); returns, per element, its [k, D] latents."""
+        g, eng, dev = self.gpt, self.gpt.engine, self.device
+        if conds.shape[0] not in (1, len(text_rows)):
+            raise ValueError(f"_latents: conds holds {conds.shape[0]} prompts for {len(text_rows)} rows (one for all, or one per row)")
+        nc, D = int(conds.shape[1]), int(conds.shape[2])
+        cl = [int(c.numel()) for c in code_rows]
+        cflat = torch.cat([c.reshape(-1).long() for c in code_rows]).cpu().numpy() if code_rows else np.zeros(0, np.int64)
+        c_dst, c_src, t_dst, t_tok, t_pos, m_dst, m_tok, m_pos = [], [], [], [], [], [], [], []
+        sel, n_lens, mel0 = [], [], []          # the elements with new rows, their row counts, and where their mel rows start
+        o = co = 0
+        for i, (r, t, k) in enumerate(zip(rows, text_rows, cl)):
+            fed, n = st.fed[r], 0
+            codes, co = cflat[co: co + k], co + k
+            if k > fed:
+                if fed == 0:
+                    ti = np.concatenate([[g.start_text_token], t.reshape(-1).numpy().astype(np.int64), [g.stop_text_token]])
+                    c_dst.append(o + np.arange(nc))
+                    c_src.append((i if conds.shape[0] > 1 else 0) * nc + np.arange(nc))
+                    t_dst.append(o + nc + np.arange(ti.size))
+                    t_tok.append(ti)
+                    t_pos.append(np.arange(ti.size))
+                    n = nc + ti.size
+                mi = np.concatenate([[g.start_mel_token], codes[: k - 1]])[fed:k]
+                m_dst.append(o + n + np.arange(mi.size))
+                m_tok.append(mi)
+                m_pos.append(fed + np.arange(mi.size))
+                mel0.append(o + n)
+                n += mi.size
+                sel.append(i)
+                n_lens.append(n)
+                o += n
+        if sel:
+            cat = lambda parts: np.concatenate(parts).astype(np.int64) if parts else np.zeros(0, np.int64)   # noqa: E731
+            parts = [cat(c_dst), cat(c_src), cat(t_dst), cat(t_tok), cat(t_pos), cat(m_dst), cat(m_tok), cat(m_pos)]
+            cut = np.cumsum([p.size for p in parts])
+            idx = torch.from_numpy(np.concatenate(parts)).to(dev)                 # one upload
+            cd, cs, td, tt, tp, md, mt, mp = (idx[a:b] for a, b in zip([0, *cut[:-1]], cut))
+            emb = torch.empty(o, D, dtype=torch.float32, device=dev)
+            if cd.numel():
+                emb[cd] = conds.to(dev, torch.float32).reshape(-1, D)[cs]
+                emb[td] = eng.text_emb[tt] + eng.text_pos[tp]
+            emb[md] = eng.mel_emb[mt] + eng.mel_pos[mp]
+            pick = lambda v: None if v is None else [v[i] for i in sel]           # noqa: E731
+            enc = eng.latent_append(st.cache, emb, n_lens, [rows[i] for i in sel], adapter_ids=pick(adapter_ids),
+                                    adapter_mix=pick(adapter_mix))
+            for i, n, m0, off in zip(sel, n_lens, mel0, np.cumsum([0] + n_lens[:-1])):
+                r, new = rows[i], enc[m0: off + n]
+                st.lat[r] = new if st.lat[r] is None else torch.cat([st.lat[r], new], 0)
+                st.fed[r] = cl[i]
+        return [st.lat[r][:k] for r, k in zip(rows, cl)]
+
     def _finish(self, wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, sampling_rate=24000):
         end_time = time.perf_counter()
         wav = torch.cat(wavs, dim=1)
@@ -832,7 +904,8 @@ class IndexTTS:
         return gen, adapter_ids, adapter_mix
 
     def stream_utterance(self, cond_mel, text_tokens, chunk_tokens=32, max_mel_tokens=600, seed=1234, force_stop=None,
-                         adapter_ids=None, adapter_mix=None, _trace: dict | None = None, **generation_kwargs):
+                         adapter_ids=None, adapter_mix=None, latent_cache: bool = False, _trace: dict | None = None,
+                         **generation_kwargs):
         """ONE utterance as a generator of PCM chunks (fp32 tensors on the device, int16 range, like infer_batch's waveforms) that
         are produced while the token loop is still running; their concatenation is the utterance.
         Every chunk_tokens tokens the loop pauses (GPTEngine.decode_chunks).  With k codes known and no stop token among them,
@@ -844,7 +917,11 @@ class IndexTTS:
         the utterance's true end.  All of it is launched on the loop's stream, between two bursts; the passes work on buffers
         of their own (see decode_chunks).
         The latent pass is repeated over all k codes at every boundary: quadratic in the utterance length, at most 600 rows
-        per pass; an incremental pass is not built.
+        per pass.  latent_cache=True runs the INCREMENTAL pass instead (_latents_incremental / GPTEngine.latent_append): the
+        stream keeps the pass's own keys and values, the prompt rows go through it once and every mel row once, and a boundary
+        costs its new rows only.  The cache holds the prompt + max_mel_tokens + 2 positions (GPTEngine.latent_cache says what
+        that takes and what it refuses).  Same codes; fp32 latents are the same bits, 16-bit ones differ by the projections'
+        split-K factor.
         Silence: the reference's remove_long_silence is not causal -- it shortens silent runs only when the WHOLE row holds
         more than 30 silent tokens, which is known when the loop ends.  The stream applies only its cut at the stop token.  For
         an utterance with at most 30 silent tokens that is all remove_long_silence does, and the stream equals infer_batch.
@@ -864,7 +941,8 @@ class IndexTTS:
             force_stop = [int(v) for v in torch.as_tensor(force_stop).reshape(-1).tolist()]
             if len(force_stop) != 1:
                 raise ValueError("stream_utterance: force_stop holds one entry")
-        return self._stream(cond_mel, text, chunk_tokens, max_mel_tokens, seed, force_stop, adapter_ids, adapter_mix, _trace, gen)
+        return self._stream(cond_mel, text, chunk_tokens, max_mel_tokens, seed, force_stop, adapter_ids, adapter_mix, _trace, gen,
+                            bool(latent_cache))
 
     @staticmethod
     def stream_plan(k: int, emitted: int, right: int, final: bool):
@@ -873,7 +951,8 @@ class IndexTTS:
         the `right` frames behind it exist; the end flushes the rest."""
         return emitted, (k if final else max(emitted, k - right))
 
-    def _stream(self, cond_mel, text, chunk_tokens, max_mel_tokens, seed, force_stop, adapter_ids, adapter_mix, trace, gen):
+    def _stream(self, cond_mel, text, chunk_tokens, max_mel_tokens, seed, force_stop, adapter_ids, adapter_mix, trace, gen,
+                latent_cache=False):
         g, eng = self.gpt, self.gpt.engine
         if adapter_ids is not None:
             adapter_ids = eng._row_adapters(adapter_ids, 1)
@@ -885,6 +964,7 @@ class IndexTTS:
         eng.prefill(emb, pad, max_mel_tokens, shared_rows=int(conds.shape[1]), adapter_ids=adapter_ids, adapter_mix=adapter_mix)
         right = self.bigvgan.receptive_halo()[1]
         stop, emitted = g.stop_mel_token, 0
+        lc = _LatentRows(eng, 1, int(emb.shape[1]) + max_mel_tokens + 2) if latent_cache else None
         if trace is not None:
             trace.update(codes=None, frames=[], latent=[])
         for codes, _ in eng.decode_chunks(max_mel_tokens, sp, chunk_tokens, force_stop=force_stop):
@@ -894,7 +974,10 @@ class IndexTTS:
             k = int(hit[0]) if hit.numel() else int(row.numel())       # the cut of remove_long_silence at the stop token
             t0, t1 = self.stream_plan(k, emitted, right, final)
             if t1 > t0:
-                lat = self._latents(conds, [text], [row[:k]], reuse_prefix=True, adapter_ids=adapter_ids, adapter_mix=adapter_mix)[0]
+                if lc is not None:
+                    lat = self._latents_incremental(lc, [0], conds, [text], [row[:k]], adapter_ids=adapter_ids, adapter_mix=adapter_mix)[0]
+                else:
+                    lat = self._latents(conds, [text], [row[:k]], reuse_prefix=True, adapter_ids=adapter_ids, adapter_mix=adapter_mix)[0]
                 wav = self.bigvgan.vocode_window(lat, spk, t0, t1)
                 if trace is not None:
                     trace["frames"].append((t0, t1))
@@ -939,7 +1022,8 @@ class IndexTTS:
         return gen, chunk_tokens, max_mel_tokens, force_stop
 
     def stream_batch(self, cond_mel, text_token_rows, chunk_tokens=32, max_mel_tokens=600, seed=1234, force_stop=None,
-                     adapter_ids=None, adapter_mix=None, sampling=None, _trace: dict | None = None, **generation_kwargs):
+                     adapter_ids=None, adapter_mix=None, sampling=None, latent_cache: bool = False, _trace: dict | None = None,
+                     **generation_kwargs):
         """stream_utterance for N utterances in ONE token loop: a generator of events (row, pcm, last) -- row: the index into
         text_token_rows; pcm: an fp32 device tensor in the int16 range, the next samples of that utterance; last: this is the
         row's final event (exactly one per row; its pcm is empty when nothing was left to flush).  The concatenation of a row's
@@ -953,7 +1037,8 @@ class IndexTTS:
         cond_mel (one mel, or a list with one per row), adapter_ids, adapter_mix, sampling: as infer_batch takes and checks them;
         force_stop: one entry per row (None / -1: none).  num_beams defaults to 1 and a larger value is refused, the silence rule is
         the cut at the stop token and the latent pass is repeated per boundary, all as in stream_utterance; the max_mel_tokens
-        warning is given once per row that reaches the limit.
+        warning is given once per row that reaches the limit.  latent_cache=True: the incremental latent pass of
+        stream_utterance, one cache row per utterance (also over an FP8 KV cache, whose streams otherwise recompute the prompt).
         Closing the generator early abandons the loop; the next prefill() starts from a clean state as after any decode.
         _trace (private: tests, tools) receives, per row, "codes" (host int64), "frames" ([(t0, t1)]), "latent" (per chunk, the rows
         [t0, t1) its window was cut from), "window" (per chunk, (lo, the latent rows [lo, hi) the vocoder ran over)) and "boundaries"
@@ -970,7 +1055,7 @@ class IndexTTS:
             return iter(())
         adapter_ids, adapter_mix = self.gpt.engine._voices(adapter_ids, adapter_mix, N)    # (no bank: None, None)
         return self._stream_rows(cond_mel, texts, chunk_tokens, max_mel_tokens, seed, force_stop, adapter_ids, adapter_mix, sampling,
-                                 _trace, gen)
+                                 _trace, gen, bool(latent_cache))
 
     @staticmethod
     def stream_batch_plan(codes, emitted, ended, right, max_mel_tokens, stop):
@@ -993,7 +1078,8 @@ class IndexTTS:
                 out.append((b, k, t0, t1, final))
         return out
 
-    def _stream_rows(self, cond_mel, texts, chunk_tokens, max_mel_tokens, seed, force_stop, adapter_ids, adapter_mix, sampling, trace, gen):
+    def _stream_rows(self, cond_mel, texts, chunk_tokens, max_mel_tokens, seed, force_stop, adapter_ids, adapter_mix, sampling, trace, gen,
+                     latent_cache=False):
         g, eng = self.gpt, self.gpt.engine
         N = len(texts)
         per_row = isinstance(cond_mel, list)      # conds / spk hold a row per utterance: every boundary gathers its rows'
@@ -1007,6 +1093,7 @@ class IndexTTS:
         eng.prefill(emb, pad, max_mel_tokens, shared_rows=shared, adapter_ids=adapter_ids, adapter_mix=adapter_mix)
         left, right = self.bigvgan.receptive_halo()
         stop, emitted, ended = g.stop_mel_token, [0] * N, [False] * N
+        lc = _LatentRows(eng, N, int(emb.shape[1]) + max_mel_tokens + 2) if latent_cache else None
         if trace is not None:
             trace.update(codes=[None] * N, frames=[[] for _ in range(N)], latent=[[] for _ in range(N)],
                          window=[[] for _ in range(N)], boundaries=[[] for _ in range(N)])
@@ -1022,10 +1109,13 @@ class IndexTTS:
                 wavs = {}
                 if rows:
                     sel = torch.tensor(rows, device=conds.device) if per_row else None
-                    lats = self._latents(conds[sel] if per_row else conds, [texts[b] for b in rows],
-                                         [codes[b, :k] for b, k, t0, t1, _ in plan if t1 > t0], reuse_prefix=True, cache_rows=rows,
-                                         adapter_ids=None if adapter_ids is None else [adapter_ids[b] for b in rows],
-                                         adapter_mix=None if adapter_mix is None else [adapter_mix[b] for b in rows])
+                    largs = (conds[sel] if per_row else conds, [texts[b] for b in rows], [codes[b, :k] for b, k, t0, t1, _ in plan if t1 > t0])
+                    voiced = dict(adapter_ids=None if adapter_ids is None else [adapter_ids[b] for b in rows],
+                                  adapter_mix=None if adapter_mix is None else [adapter_mix[b] for b in rows])
+                    if lc is not None:
+                        lats = self._latents_incremental(lc, rows, *largs, **voiced)
+                    else:
+                        lats = self._latents(*largs, reuse_prefix=True, cache_rows=rows, **voiced)
                     spans = [(t0, t1) for _, _, t0, t1, _ in plan if t1 > t0]
                     wavs = dict(zip(rows, self._vocode_windows(lats, spk[sel] if per_row else spk, spans)))
                     if trace is not None:
@@ -1050,8 +1140,8 @@ class IndexTTS:
 
     # ------------------------------------------------------------------------------------------------ streaming queue
     def stream_queue(self, cond_mel, text_token_rows, slots=32, chunk_tokens=32, max_mel_tokens=600, seed=1234, force_stop=None,
-                     adapter_ids=None, adapter_mix=None, sampling=None, more=None, _trace: dict | None = None, _refused=None,
-                     **generation_kwargs):
+                     adapter_ids=None, adapter_mix=None, sampling=None, more=None, latent_cache: bool = False,
+                     _trace: dict | None = None, _refused=None, **generation_kwargs):
         """stream_batch over the REFILLED loop of infer_queue: any number of utterances through `slots` decode slots, each
         streamed as PCM while the loop runs, and utterances that arrive after the loop has started enter it.  A generator of
         events (utt, pcm, last) -- the events of stream_batch; utt: the index into text_token_rows, or the handle `more` gave.
@@ -1065,6 +1155,10 @@ class IndexTTS:
         (_vocode_windows), as in stream_batch.  A refilled row's prompt does not lie where latent_mel_rows looks for it, so the
         latent pass is the whole-sequence one (_latents(reuse_prefix=False), as over an FP8 KV cache).  The events of one poll
         come in the order the utterances entered the loop.
+        latent_cache=True: the incremental latent pass of stream_utterance, one cache row per decode slot; a slot's row is reset
+        when its utterance has had its last event, before the next owner's first rows.  The cache is sized for the longest
+        prompt the loop can place (the queue's longest text; with `more`, gpt.max_text_tokens) + max_mel_tokens + 2, and a
+        request from more() whose text is longer than that is refused like any other bad request.
         cond_mel (one mel, or a list with one per utterance), adapter_ids / adapter_mix and sampling: taken and checked as
         infer_queue takes and checks them, before anything is launched; force_stop: one entry per utterance (None / -1: none).
         num_beams defaults to 1 and a larger value is refused (stream_utterance says why).  A row that reaches max_mel_tokens is
@@ -1115,7 +1209,8 @@ class IndexTTS:
         reqs = [dict(handle=i, text=texts[i], prompt=i if isinstance(cond_mel, list) else 0,
                      stop=-1 if force_stop is None else force_stop[i], sp=None if sampling is None else sampling[i],
                      voice=None if voices is None else voices[i]) for i in range(N)]
-        return self._stream_queue(cond_mel, reqs, int(slots), chunk_tokens, max_mel_tokens, seed, voice_kind, more, _trace, gen, _refused)
+        return self._stream_queue(cond_mel, reqs, int(slots), chunk_tokens, max_mel_tokens, seed, voice_kind, more, _trace, gen, _refused,
+                                  bool(latent_cache))
 
     @staticmethod
     def stream_queue_plan(rows, emitted, right, max_mel_tokens, stop):
@@ -1267,8 +1362,11 @@ class IndexTTS:
             if not waiting and idle is not None:
                 idle()
 
-    def _stream_queue(self, cond_mel, reqs, slots, chunk_tokens, max_mel_tokens, seed, voice_kind, more, trace, gen, refused=None):
+    def _stream_queue(self, cond_mel, reqs, slots, chunk_tokens, max_mel_tokens, seed, voice_kind, more, trace, gen, refused=None,
+                      latent_cache=False):
         g = self.gpt
+        lc, lc_loop = None, 0                           # the latent cache (made at the first emission) and the loop it serves
+        lc_text = max([int(getattr(g, "max_text_tokens", 0)) if more is not None else 0] + [int(r["text"].numel()) for r in reqs])
         waiting = sorted(reqs, key=lambda r: -int(r["text"].numel()))      # longest first, as infer_queue: every later prompt fits
         n_seen, open_ = len(reqs), more is not None
         per_row = more is not None or any(r["sp"] is not None for r in reqs)
@@ -1291,7 +1389,11 @@ class IndexTTS:
                 return
             for r in new:
                 try:
-                    waiting.append(self._queue_request(r, n_seen, cond_mel, feats, seed, gen, voice_kind))
+                    q = self._queue_request(r, n_seen, cond_mel, feats, seed, gen, voice_kind)
+                    if latent_cache and int(q["text"].numel()) > lc_text:
+                        raise ValueError(f"stream_queue: a request from more() holds {int(q['text'].numel())} text tokens, the latent "
+                                         f"cache of this call is sized for {lc_text}")
+                    waiting.append(q)
                 except Exception as e:  # noqa: BLE001
                     if refused is None:
                         raise
@@ -1317,6 +1419,7 @@ class IndexTTS:
                 plan = self.stream_queue_plan([dict(row, utt=(number, row["utt"])) for row in rec["rows"]], emitted, right,
                                               max_mel_tokens, stop)
                 codes = {(number, row["utt"]): row["codes"] for row in rec["rows"]}
+                slot_of = {(number, row["utt"]): row["slot"] for row in rec["rows"]}
                 if trace is not None:
                     for row in rec["rows"]:
                         trace["polls"].setdefault(entered[row["utt"]]["handle"], []).append(rec["n"])
@@ -1326,8 +1429,18 @@ class IndexTTS:
                     rs = [entered[u[1]] for u, _, _, _ in emit]
                     same = all(feats[r["prompt"]][1] is feats[rs[0]["prompt"]][1] for r in rs)
                     conds = feats[rs[0]["prompt"]][1] if same else torch.cat([feats[r["prompt"]][1] for r in rs], 0)
-                    lats = self._latents(conds, [r["text"] for r in rs], [codes[u][:k] for u, k, _, _ in emit], reuse_prefix=False,
-                                         **({} if voice_kind is None else {voice_kind: [r["voice"] for r in rs]}))
+                    largs = (conds, [r["text"] for r in rs], [codes[u][:k] for u, k, _, _ in emit])
+                    voiced = {} if voice_kind is None else {voice_kind: [r["voice"] for r in rs]}
+                    if latent_cache:
+                        if lc is None:
+                            lc = _LatentRows(self.gpt.engine, slots, int(conds.shape[1]) + lc_text + 2 + max_mel_tokens + 2)
+                        if lc_loop != number:           # a new loop has prefilled every slot anew
+                            for s in range(slots):
+                                lc.reset(s)
+                            lc_loop = number
+                        lats = self._latents_incremental(lc, [slot_of[u] for u, _, _, _ in emit], *largs, **voiced)
+                    else:
+                        lats = self._latents(*largs, reuse_prefix=False, **voiced)
                     spans = [(t0, t1) for _, _, t0, t1 in emit]
                     spks = feats[rs[0]["prompt"]][2] if same else torch.cat([feats[r["prompt"]][2] for r in rs], 0)
                     wavs = dict(zip([u for u, _, _, _ in emit], self._vocode_windows(lats, spks, spans)))
@@ -1341,6 +1454,8 @@ class IndexTTS:
                     emitted[u] = t1
                     if final:
                         del emitted[u]
+                        if lc is not None and lc_loop == number:
+                            lc.reset(slot_of[u])          # the slot goes to the next utterance
                         if trace is not None:
                             trace["codes"][entered[u[1]]["handle"]] = codes[u][:k].clone()
                     yield entered[u[1]]["handle"], (wavs[u] if t1 > t0 else torch.zeros(0, device=self.device)), final
@@ -1348,7 +1463,8 @@ class IndexTTS:
         finally:
             loops.close()          # an early close of this generator abandons the loop
 
-    def infer_stream(self, audio_prompt, text, max_text_tokens_per_sentence=120, parallel_sentences=1, slots=None, **kw):
+    def infer_stream(self, audio_prompt, text, max_text_tokens_per_sentence=120, parallel_sentences=1, slots=None,
+                     latent_cache: bool = False, **kw):
         """infer() as a generator of (sampling rate, PCM chunk): the text is split into sentences as infer() splits it and the
         sentences are streamed one after another (stream_utterance, whose keywords -- chunk_tokens, seed, the generation
         settings -- pass through).  A chunk is an fp32 device tensor in the int16 range.
@@ -1358,7 +1474,10 @@ class IndexTTS:
         a group is sampled as one batch, so its samples are not those of P = 1.
         slots = S (not None): ALL sentences go through ONE stream_queue(slots=S) -- the refilled loop: a sentence that ends hands
         its slot to the next one instead of idling to the end of its group -- and the chunks are handed out in text order in the
-        same way.  parallel_sentences does not apply then.  Without `slots` the call is what it was."""
+        same way.  parallel_sentences does not apply then.  Without `slots` the call is what it was.
+        latent_cache=True: every one of these streams runs the incremental latent pass (stream_utterance says what that is)."""
+        if latent_cache:
+            kw = dict(kw, latent_cache=True)
         P = int(parallel_sentences)
         if P < 1:
             raise ValueError("infer_stream: parallel_sentences must be at least 1")
@@ -1393,7 +1512,7 @@ class IndexTTS:
             group = rows[s: s + P]
             yield from in_text_order(self.stream_batch(cond_mel, group, **for_each(group)), len(group))
 
-    def serve_stream_queue(self, more, slots=32, chunk_tokens=32, max_mel_tokens=600):
+    def serve_stream_queue(self, more, slots=32, chunk_tokens=32, max_mel_tokens=600, latent_cache: bool = False):
         """The service form of stream_queue: whole REQUESTS (a prompt file and a text of any number of sentences each) through one
         refilled loop.  more() returns the requests that have arrived (a list, usually empty) or None (no more will come); a
         request is a dict: "handle", "audio_prompt" (a path), "text", and optionally "max_text_tokens_per_sentence", "seed" and
@@ -1401,7 +1520,8 @@ class IndexTTS:
         call's: the request's utterances are stopped there).  A generator of (handle, pcm, last): a request's chunks come in text
         order (what a later sentence produces early is held back, as in infer_stream), `last` with its final one.  A request
         that cannot be taken -- an unreadable prompt, a refused setting -- yields (handle, the exception, True) and disturbs no
-        other.  The generator ends when the loop has fallen idle (stream_queue): the caller starts the next one."""
+        other.  The generator ends when the loop has fallen idle (stream_queue): the caller starts the next one.
+        latent_cache: stream_queue's."""
         book = {}            # handle -> the text order of its sentences (_TextOrder)
         gen, _ = IndexTTS._gen_kwargs({"num_beams": 1})
         failed = []          # (handle, error | None = nothing to say, True) from here, ((handle, sentence), error) from the queue
@@ -1445,7 +1565,7 @@ class IndexTTS:
 
         done = set()         # requests that have had their `last` (a request refused inside the queue may still own rows)
         events = self.stream_queue(None, [], slots=slots, chunk_tokens=chunk_tokens, max_mel_tokens=max_mel_tokens, more=utterances,
-                                   _refused=failed)
+                                   _refused=failed, **({"latent_cache": True} if latent_cache else {}))
         yield from drain_failed()
         for (h, i), pcm, last in events:
             yield from drain_failed()

@@ -11,7 +11,12 @@ the time to the first chunk of row 0 and to the last chunk of the last row.  pro
 through IndexTTS.stream_queue with S slots, against stream_batch in ceil(N / S) static batches of S and against infer_queue on
 the same queue, alternating in one process: the time to every utterance's first chunk (median and worst over the utterances)
 and to the last chunk of the queue.  profiles/stream_queue_latency.txt is that output.
-usage: bench_stream.py [reps] [layers] [--rows N] [--chunk C] [--queue N --slots S]"""
+--latent-cache: latent_cache=False (the latent pass repeated over all k codes per boundary) against latent_cache=True (the incremental
+pass, GPTEngine.latent_append), alternating in one process: first and last chunk of the one-utterance table (chunks of 16 / 32 / 64), of
+stream_batch with --rows N (stops spread from --stop down to --stop - 40) or of stream_queue with --queue N --slots S; then one run of
+each with the latent pass timed per boundary (synchronised around it, so those runs are not the ones the chunk times come from).
+profiles/stream_latent_cache.txt is that output.
+usage: bench_stream.py [reps] [layers] [--rows N] [--chunk C] [--queue N --slots S] [--latent-cache [--stop T]]"""
 import argparse
 import os
 import sys
@@ -35,6 +40,8 @@ ap.add_argument("--rows", type=int, default=0, help="N utterances through one st
 ap.add_argument("--chunk", type=int, default=32, help="chunk_tokens of the --rows table")
 ap.add_argument("--queue", type=int, default=0, help="N utterances of mixed lengths through stream_queue (0: off)")
 ap.add_argument("--slots", type=int, default=32, help="decode slots of the --queue table")
+ap.add_argument("--latent-cache", action="store_true", help="latent_cache=False against latent_cache=True on the chosen table")
+ap.add_argument("--stop", type=int, default=140, help="codes of the longest utterance of the --latent-cache tables")
 args = ap.parse_args()
 reps, layers = args.reps, args.layers
 STOP, LIMIT, CHUNKS = 140, 192, (16, 32, 64)
@@ -197,6 +204,84 @@ def queue_table(N, S, chunk):
     ql, sl = med([l for _, l, _ in res["queue"]]), med([l for _, l, _ in res["static"]])
     print(f"{tag} | last chunk: stream_queue / static stream_batch = {ql / sl:.3f}, stream_queue / infer_queue = {ql / med(t_whole):.3f}")
 
+
+def latent_cache_table():
+    """latent_cache False | True, alternating: (first, last) chunk times per form, then the latent pass per boundary."""
+    rng = np.random.default_rng(12)
+    stop, limit = args.stop, args.stop + 52
+    if args.queue > 0:
+        r3 = np.random.default_rng(3)
+        texts = [torch.from_numpy(r3.integers(2, 12000, size=int(n))).to(torch.int32) for n in r3.integers(8, 101, size=args.queue)]
+        stops = [int(v) for v in r3.integers(40, 401, size=args.queue)]
+        forms = [(f"stream_queue, {args.queue} utterances of 40 .. 400 codes, {args.slots} slots, chunks of {args.chunk}",
+                  lambda lc: tts.stream_queue(cond_mel, texts, slots=args.slots, chunk_tokens=args.chunk, force_stop=stops, max_mel_tokens=416,
+                                              seed=5, latent_cache=lc, **GEN))]
+    elif args.rows > 0:
+        N = args.rows
+        texts = [torch.from_numpy(rng.integers(2, 12000, size=40)).to(torch.int32) for _ in range(N)]
+        stops = [stop - (40 * i) // max(N - 1, 1) for i in range(N)]
+        forms = [(f"stream_batch, {N} rows of {stops[0]} .. {stops[-1]} codes, chunks of {args.chunk}",
+                  lambda lc: tts.stream_batch(cond_mel, texts, chunk_tokens=args.chunk, max_mel_tokens=limit, seed=5, force_stop=stops,
+                                              latent_cache=lc, **GEN))]
+    else:
+        forms = [(f"stream_utterance, {stop} codes, chunks of {c:2d}",
+                  lambda lc, c=c: ((0, p, False) for p in tts.stream_utterance(cond_mel, text, chunk_tokens=c, max_mel_tokens=limit, seed=5,
+                                                                              force_stop=[stop], latent_cache=lc, **GEN))) for c in CHUNKS]
+
+    def run(form, lc):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        at = []
+        for _, pcm, _ in form(lc):
+            if pcm.numel():
+                pcm.cpu()
+                at.append(1e3 * (time.perf_counter() - t0))
+        return at[0], at[-1]
+
+    def timed(form, lc):
+        """one run with the latent pass wrapped: [(rows the pass was asked for, ms)] per boundary"""
+        name, out = ("_latents_incremental", []) if lc else ("_latents", [])
+        real = getattr(tts, name)
+
+        def wrapped(*a, **k):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = real(*a, **k)
+            torch.cuda.synchronize()
+            out.append((sum(int(x.shape[0]) for x in r), 1e3 * (time.perf_counter() - t0)))
+            return r
+        setattr(tts, name, wrapped)
+        try:
+            run(form, lc)
+        finally:
+            delattr(tts, name)
+        return out
+
+    print(f"stream latent cache | {layers} layers, bf16 GPT, fp16 vocoder, text(s) of 40 tokens unless said, halo (left, right) = ({left}, {right}) "
+          f"frames; median (min) of {reps}, host clock to samples on the host; latent_cache False and True alternate in one process")
+    for label, form in forms:
+        for _ in range(2):
+            run(form, False), run(form, True)
+        res = {False: [], True: []}
+        for _ in range(reps):
+            for lc in (False, True):
+                res[lc].append(run(form, lc))
+        med = lambda v: sorted(v)[len(v) // 2]   # noqa: E731
+        for lc in (False, True):
+            print(f"stream latent cache | {label} | latent_cache={lc!s:5} | first chunk {stat([f for f, _ in res[lc]])}  last chunk "
+                  f"{stat([l for _, l in res[lc]])}")
+        print(f"stream latent cache | {label} | last chunk True / False = {med([l for _, l in res[True]]) / med([l for _, l in res[False]]):.3f}  "
+              f"first chunk True / False = {med([f for f, _ in res[True]]) / med([f for f, _ in res[False]]):.3f}")
+        for lc in (False, True):
+            per = timed(form, lc)
+            print(f"stream latent cache | {label} | latent_cache={lc!s:5} | latent pass per boundary, (frames held by the emitting rows: ms) = "
+                  + "  ".join(f"{k}: {ms:.2f}" for k, ms in per[:24]) + f"  | sum = {sum(ms for _, ms in per):.1f} ms over {len(per)} passes")
+
+
+if args.latent_cache:
+    latent_cache_table()
+    torch.cuda.synchronize()
+    sys.exit(0)
 
 if args.queue > 0:
     queue_table(args.queue, args.slots, args.chunk)
