@@ -9,6 +9,7 @@ a prompt are computed once per call instead of once per sentence (same values).
 """
 from __future__ import annotations
 
+import collections
 import json
 import os
 import queue
@@ -126,6 +127,20 @@ class _LatentRows:
         """The row's utterance has ended: its cache row starts the next one from position 0."""
         self.cache.reset(row)
         self.fed[row], self.lat[row] = 0, None
+
+
+class _StreamState:
+    """What a stream keeps between two boundaries, for IndexTTS._emit_boundary.  emitted: {utterance key: the frames it has given
+    out} (an utterance not in it has given none, or has had its last event); left / right: the vocoder's halo; stop /
+    max_mel_tokens: where a row ends; voice_kind: the keyword that names a voice to the latent pass (None: no voices); trace: the
+    stream's _trace (or None), its "frames" / "latent" / "window" / "codes" indexed by an utterance's handle; latent: which pass
+    a boundary runs -- "reuse" (repeated, over the prompt K / V the prefill left in the decode cache: _latents(reuse_prefix=True,
+    cache_rows=...)), "whole" (repeated, the whole sequence) or a _LatentRows (incremental); warn: the words for a row that
+    reaches max_mel_tokens, `{}` = its handle (None: nothing is said)."""
+
+    def __init__(self, halo, stop, max_mel_tokens, voice_kind, trace, latent, warn=None):
+        self.emitted, (self.left, self.right), self.stop, self.max_mel_tokens = {}, halo, stop, max_mel_tokens
+        self.voice_kind, self.trace, self.latent, self.warn = voice_kind, trace, latent, warn
 
 
 class IndexTTS:
@@ -885,24 +900,6 @@ class IndexTTS:
         return (outs, st["rows"]) if return_codes else outs
 
     # ------------------------------------------------------------------------------------------------ streaming
-    @staticmethod
-    def _stream_args(generation_kwargs, adapter_ids, adapter_mix):
-        """The checks of stream_utterance that need no device: (gen, one-element adapter_ids | None, adapter_mix | None)."""
-        kw = dict(generation_kwargs)
-        kw.setdefault("num_beams", 1)
-        gen, _ = IndexTTS._gen_kwargs(kw)
-        if kw:
-            raise TypeError(f"stream_utterance: unknown generation settings {sorted(kw)}")
-        if int(gen["num_beams"]) > 1:
-            raise NotImplementedError("stream_utterance: beam search picks its hypothesis when the loop ends, so no code is final "
-                                      "before that; streaming is built for num_beams = 1")
-        for name, v in (("adapter_ids", adapter_ids), ("adapter_mix", adapter_mix)):
-            if v is not None and (isinstance(v, (str, dict)) or not hasattr(v, "__len__") or len(v) != 1):
-                raise ValueError(f"stream_utterance: {name} names the voice of ONE utterance: a one-element list")
-        if adapter_ids is not None and adapter_mix is not None:
-            raise ValueError("stream_utterance: adapter_ids or adapter_mix, one of them")
-        return gen, adapter_ids, adapter_mix
-
     def stream_utterance(self, cond_mel, text_tokens, chunk_tokens=32, max_mel_tokens=600, seed=1234, force_stop=None,
                          adapter_ids=None, adapter_mix=None, latent_cache: bool = False, _trace: dict | None = None,
                          **generation_kwargs):
@@ -913,9 +910,10 @@ class IndexTTS:
         prefill left in the decode cache; the whole sequence for an FP8 KV cache).  The pass is causal and row i reads the
         codes < i only, so rows 0 .. k-1 are final.  The vocoder's receptive field is finite (BigVGAN.receptive_halo):
         the samples of frame t read the latent frames [t - left, t + right], so the frames [emitted, k - right) are vocoded
-        from a window (BigVGAN.vocode_window) and yielded.  At the stop token, or at max_mel_tokens, the rest is flushed against
-        the utterance's true end.  All of it is launched on the loop's stream, between two bursts; the passes work on buffers
-        of their own (see decode_chunks).
+        from a window (_vocode_windows: BigVGAN.vocode_window's forward, clamped and cut) and yielded.  At the stop token, or at
+        max_mel_tokens, the rest is flushed against the utterance's true end.  All of it is launched on the loop's stream,
+        between two bursts; the passes work on buffers of their own (see decode_chunks).  The stream IS stream_batch's with one
+        row (_stream_rows, _emit_boundary), its events unwrapped.
         The latent pass is repeated over all k codes at every boundary: quadratic in the utterance length, at most 600 rows
         per pass.  latent_cache=True runs the INCREMENTAL pass instead (_latents_incremental / GPTEngine.latent_append): the
         stream keeps the pass's own keys and values, the prompt rows go through it once and every mel row once, and a boundary
@@ -930,19 +928,31 @@ class IndexTTS:
         _trace (private: tests, tools): receives "codes" (the utterance's codes, host int64), "frames" (the [t0, t1) of every chunk) and
         "latent" (per chunk, the rows [t0, t1) its window was vocoded from).
         The checks run when this is called; the device work starts with the first next()."""
-        gen, adapter_ids, adapter_mix = IndexTTS._stream_args(generation_kwargs, adapter_ids, adapter_mix)
+        gen, chunk_tokens, max_mel_tokens, _ = IndexTTS._stream_batch_args(
+            1, chunk_tokens, max_mel_tokens, None, adapter_ids, adapter_mix, None, generation_kwargs, who="stream_utterance")
         if isinstance(cond_mel, (list, tuple)):
             raise ValueError("stream_utterance: one utterance has one prompt mel")
         text = torch.as_tensor(text_tokens).reshape(-1).to("cpu", torch.int32)
-        chunk_tokens, max_mel_tokens = int(chunk_tokens), int(max_mel_tokens)
-        if chunk_tokens < 1:
-            raise ValueError("stream_utterance: chunk_tokens must be at least 1")
         if force_stop is not None:
             force_stop = [int(v) for v in torch.as_tensor(force_stop).reshape(-1).tolist()]
             if len(force_stop) != 1:
                 raise ValueError("stream_utterance: force_stop holds one entry")
-        return self._stream(cond_mel, text, chunk_tokens, max_mel_tokens, seed, force_stop, adapter_ids, adapter_mix, _trace, gen,
-                            bool(latent_cache))
+
+        def chunks():
+            eng, rows = self.gpt.engine, (None if _trace is None else {})
+            ids = None if adapter_ids is None else eng._row_adapters(adapter_ids, 1)
+            mix = None if adapter_mix is None else eng._voices(None, adapter_mix, 1)[1]
+            events = self._stream_rows(cond_mel, [text], chunk_tokens, max_mel_tokens, seed, force_stop, ids, mix, None, rows, gen,
+                                       bool(latent_cache), who="stream_utterance")
+            try:
+                for _, pcm, _ in events:
+                    if _trace is not None:        # the one row's trace, flat
+                        _trace.update(codes=rows["codes"][0], frames=rows["frames"][0], latent=rows["latent"][0])
+                    if pcm.numel():
+                        yield pcm
+            finally:
+                events.close()
+        return chunks()
 
     @staticmethod
     def stream_plan(k: int, emitted: int, right: int, final: bool):
@@ -951,53 +961,91 @@ class IndexTTS:
         the `right` frames behind it exist; the end flushes the rest."""
         return emitted, (k if final else max(emitted, k - right))
 
-    def _stream(self, cond_mel, text, chunk_tokens, max_mel_tokens, seed, force_stop, adapter_ids, adapter_mix, trace, gen,
-                latent_cache=False):
-        g, eng = self.gpt, self.gpt.engine
-        if adapter_ids is not None:
-            adapter_ids = eng._row_adapters(adapter_ids, 1)
-        if adapter_mix is not None:
-            adapter_mix = eng._voices(None, adapter_mix, 1)[1]
-        conds, spk = self._prompt_features(cond_mel)
-        emb, pad = g.prefix_rows(conds, text[None])
-        sp = sampling_params(gen, seed)
-        eng.prefill(emb, pad, max_mel_tokens, shared_rows=int(conds.shape[1]), adapter_ids=adapter_ids, adapter_mix=adapter_mix)
-        right = self.bigvgan.receptive_halo()[1]
-        stop, emitted = g.stop_mel_token, 0
-        lc = _LatentRows(eng, 1, int(emb.shape[1]) + max_mel_tokens + 2) if latent_cache else None
-        if trace is not None:
-            trace.update(codes=None, frames=[], latent=[])
-        for codes, _ in eng.decode_chunks(max_mel_tokens, sp, chunk_tokens, force_stop=force_stop):
-            row = codes[0]
-            hit = (row == stop).nonzero()
-            final = bool(hit.numel()) or row.numel() >= max_mel_tokens
-            k = int(hit[0]) if hit.numel() else int(row.numel())       # the cut of remove_long_silence at the stop token
-            t0, t1 = self.stream_plan(k, emitted, right, final)
-            if t1 > t0:
-                if lc is not None:
-                    lat = self._latents_incremental(lc, [0], conds, [text], [row[:k]], adapter_ids=adapter_ids, adapter_mix=adapter_mix)[0]
-                else:
-                    lat = self._latents(conds, [text], [row[:k]], reuse_prefix=True, adapter_ids=adapter_ids, adapter_mix=adapter_mix)[0]
-                wav = self.bigvgan.vocode_window(lat, spk, t0, t1)
-                if trace is not None:
-                    trace["frames"].append((t0, t1))
-                    trace["latent"].append(lat[t0:t1].clone())
-                emitted = t1
-                yield torch.clamp(32767 * wav, -32767.0, 32767.0)
+    @staticmethod
+    def stream_queue_plan(rows, emitted, right, max_mel_tokens, stop):
+        """One boundary of a stream on the host: THE per-row rule of stream_utterance, stream_batch and stream_queue.  rows: records
+        with "utt", "k", "codes" and "stopped" (what GPTEngine.decode_refill_chunks reports; stream_batch_plan makes them of a
+        decode_chunks poll); emitted: {utt: the frames it has given out} (an utterance not in it has given none).  Returns
+        [(utt, k, t0, t1, final)] in the order of `rows` for the utterances that emit now: k = the position of the row's first stop
+        token (the cut of remove_long_silence) or its own token count; final = a stop token is there, the loop says the row has
+        stopped, or k has reached max_mel_tokens; (t0, t1) = stream_plan(k, emitted[utt], right, final).  A row with nothing to emit
+        that is not final is left out; a final row is always there, with t1 == t0 when nothing is left."""
+        out = []
+        for row in rows:
+            hit = np.flatnonzero(row["codes"].numpy() == stop)       # (host codes: numpy is the cheaper of the two here)
+            k = int(hit[0]) if hit.size else int(row["k"])
+            final = bool(hit.size) or bool(row["stopped"]) or k >= max_mel_tokens
+            t0, t1 = IndexTTS.stream_plan(k, emitted.get(row["utt"], 0), right, final)
+            if t1 > t0 or final:
+                out.append((row["utt"], k, t0, t1, final))
+        return out
+
+    @staticmethod
+    def stream_batch_plan(codes, emitted, ended, right, max_mel_tokens, stop):
+        """stream_queue_plan for one poll of decode_chunks.  codes: int [B, n]; emitted[b]: the frames row b has given out; ended[b]:
+        row b has had its last event and is not planned again.  Every other row is a record with k = n that the loop has not
+        stopped (a row ends at its stop token, or at n == max_mel_tokens): [(b, k, t0, t1, final)] in ascending b."""
+        n, live = int(codes.shape[1]), [b for b in range(int(codes.shape[0])) if not ended[b]]
+        return IndexTTS.stream_queue_plan([dict(utt=b, k=n, codes=codes[b], stopped=False) for b in live],
+                                          {b: emitted[b] for b in live}, right, max_mel_tokens, stop)
+
+    def _emit_boundary(self, st: "_StreamState", recs):
+        """One boundary of ANY stream (stream_utterance, stream_batch, stream_queue): the events [(handle, pcm, last)] of the
+        utterances `recs`, in their order.  A record is stream_queue_plan's ("utt": the key st.emitted knows the utterance by, "k",
+        "codes" on the host, "stopped") and carries what the passes need: "handle" (what its events and the trace name it by),
+        "text", its prompt's "conds" [1, nc, D] and "spk" [1, 1, 512], "voice", "cache_row" (the decode-cache row its prompt lies
+        in: st.latent == "reuse") and "lc_row" (its row of a _LatentRows).  The rows are planned (stream_queue_plan); those that
+        emit share ONE latent pass (st.latent) and one ragged vocoder call per bucket of similar window lengths
+        (_vocode_windows); one prompt for all of them is passed as that tensor, different ones are concatenated.  A final row
+        leaves st.emitted, gives its cache row back (a _LatentRows), is warned about when it ran into max_mel_tokens (st.warn)
+        and has an empty pcm when nothing was left to flush.  The sources call it through the class, as stream_queue calls
+        _check_prompts: of `self` it needs _latents, _latents_incremental, _vocode_windows and device only."""
+        plan = IndexTTS.stream_queue_plan(recs, st.emitted, st.right, st.max_mel_tokens, st.stop)
+        by = {r["utt"]: r for r in recs}
+        emit = [(by[u], k, t0, t1) for u, k, t0, t1, _ in plan if t1 > t0]
+        wavs = {}
+        if emit:
+            rs = [r for r, _, _, _ in emit]
+            same = all(r["conds"] is rs[0]["conds"] for r in rs)
+            conds = rs[0]["conds"] if same else torch.cat([r["conds"] for r in rs], 0)
+            largs = (conds, [r["text"] for r in rs], [r["codes"][:k] for r, k, _, _ in emit])
+            voiced = {} if st.voice_kind is None else {st.voice_kind: [r["voice"] for r in rs]}
+            if isinstance(st.latent, _LatentRows):
+                lats = self._latents_incremental(st.latent, [r["lc_row"] for r in rs], *largs, **voiced)
+            elif st.latent == "reuse":
+                lats = self._latents(*largs, reuse_prefix=True, cache_rows=[r["cache_row"] for r in rs], **voiced)
+            else:
+                lats = self._latents(*largs, reuse_prefix=False, **voiced)
+            spans = [(t0, t1) for _, _, t0, t1 in emit]
+            spk = rs[0]["spk"] if same else torch.cat([r["spk"] for r in rs], 0)
+            wavs = dict(zip([r["utt"] for r in rs], self._vocode_windows(lats, spk, spans)))
+            if st.trace is not None:
+                for r, lat, (t0, t1) in zip(rs, lats, spans):
+                    lo, h = max(0, t0 - st.left), r["handle"]
+                    st.trace["frames"][h].append((t0, t1))
+                    st.trace["latent"][h].append(lat[t0:t1].clone())
+                    st.trace["window"][h].append((lo, lat[lo: min(int(lat.shape[0]), t1 + st.right)].clone()))
+        events = []
+        for u, k, t0, t1, final in plan:
+            r = by[u]
+            st.emitted[u] = t1
             if final:
-                if not hit.numel():
-                    warnings.warn(f"generation stopped at max_mel_tokens ({max_mel_tokens}); consider shorter sentences",
-                                  category=RuntimeWarning)
-                if trace is not None:
-                    trace["codes"] = row[:k].clone()
-                return
+                del st.emitted[u]                         # (a stream_queue runs for as long as requests come)
+                if isinstance(st.latent, _LatentRows):
+                    st.latent.reset(r["lc_row"])          # the row goes to the next utterance
+                if st.warn is not None and not bool((r["codes"] == st.stop).any()):
+                    warnings.warn(st.warn.format(r["handle"]), category=RuntimeWarning)
+                if st.trace is not None:
+                    st.trace["codes"][r["handle"]] = r["codes"][:k].clone()
+            events.append((r["handle"], wavs[u] if t1 > t0 else torch.zeros(0, device=self.device), final))
+        return events
 
     # ------------------------------------------------------------------------------------------------ batched streaming
     @staticmethod
     def _stream_batch_args(n_rows, chunk_tokens, max_mel_tokens, force_stop, adapter_ids, adapter_mix, sampling, generation_kwargs,
                            who="stream_batch"):
-        """The checks of stream_batch (and stream_queue: `who`) that need neither a model nor a device: (gen, chunk_tokens,
-        max_mel_tokens, force_stop as n_rows host ints | None)."""
+        """The checks of stream_utterance (n_rows = 1), stream_batch and stream_queue (`who`) that need neither a model nor a
+        device: (gen, chunk_tokens, max_mel_tokens, force_stop as n_rows host ints | None)."""
         kw = dict(generation_kwargs)
         kw.setdefault("num_beams", 1)
         gen, _ = IndexTTS._gen_kwargs(kw)
@@ -1029,10 +1077,10 @@ class IndexTTS:
         row's final event (exactly one per row; its pcm is empty when nothing was left to flush).  The concatenation of a row's
         pcm is that utterance, hop * T_row samples; the events of one boundary come in ascending row order.
         One prefill and one decode_chunks(chunk_tokens) over all rows, as infer_batch prefills and decodes them (same graph key as
-        decode() at this B: no new capture).  At every boundary, each row that has not ended is planned on its own (stream_batch_plan:
-        its codes up to its first stop token, its own emitted count, stream_plan unchanged); the rows that emit share ONE latent
-        pass (_latents with reuse_prefix over those cache rows; the whole-sequence pass on an FP8 KV cache) and one ragged
-        vocoder call per bucket of similar window lengths (_vocode_windows), so a row's chunk is bit for bit
+        decode() at this B: no new capture).  At every boundary (_emit_boundary), each row that has not ended is planned on its own
+        (stream_batch_plan: its codes up to its first stop token, its own emitted count, stream_plan unchanged); the rows that emit
+        share ONE latent pass (_latents with reuse_prefix over those cache rows; the whole-sequence pass on an FP8 KV cache) and
+        one ragged vocoder call per bucket of similar window lengths (_vocode_windows), so a row's chunk is bit for bit
         BigVGAN.vocode_window of the same latents.  Rows end at different tokens; a row that has ended costs nothing further.
         cond_mel (one mel, or a list with one per row), adapter_ids, adapter_mix, sampling: as infer_batch takes and checks them;
         force_stop: one entry per row (None / -1: none).  num_beams defaults to 1 and a larger value is refused, the silence rule is
@@ -1057,32 +1105,13 @@ class IndexTTS:
         return self._stream_rows(cond_mel, texts, chunk_tokens, max_mel_tokens, seed, force_stop, adapter_ids, adapter_mix, sampling,
                                  _trace, gen, bool(latent_cache))
 
-    @staticmethod
-    def stream_batch_plan(codes, emitted, ended, right, max_mel_tokens, stop):
-        """One boundary of stream_batch on the host.  codes: int [B, n], what decode_chunks yields; emitted[b]: the frames row b
-        has given out; ended[b]: row b has had its last event.  Returns [(b, k, t0, t1, final)] in ascending b for the rows that
-        emit now: k = the position of the row's first stop token (the cut of remove_long_silence) or n; final = a stop token is
-        there or n has reached max_mel_tokens; (t0, t1) = stream_plan(k, emitted[b], right, final).  A row with nothing to emit that
-        is not final is left out; a final row is always there, with t1 == t0 when nothing is left."""
-        n = int(codes.shape[1])
-        is_stop = (codes == stop)
-        out = []
-        for b in range(int(codes.shape[0])):
-            if ended[b]:
-                continue
-            hit = is_stop[b].nonzero()
-            final = bool(hit.numel()) or n >= max_mel_tokens
-            k = int(hit[0]) if hit.numel() else n
-            t0, t1 = IndexTTS.stream_plan(k, emitted[b], right, final)
-            if t1 > t0 or final:
-                out.append((b, k, t0, t1, final))
-        return out
-
     def _stream_rows(self, cond_mel, texts, chunk_tokens, max_mel_tokens, seed, force_stop, adapter_ids, adapter_mix, sampling, trace, gen,
-                     latent_cache=False):
+                     latent_cache=False, who="stream_batch"):
+        """stream_batch's generator (and, with one row and who="stream_utterance", stream_utterance's): one prefill, then every poll
+        of decode_chunks becomes the records of the rows that have not ended and goes through _emit_boundary."""
         g, eng = self.gpt, self.gpt.engine
         N = len(texts)
-        per_row = isinstance(cond_mel, list)      # conds / spk hold a row per utterance: every boundary gathers its rows'
+        per_row = isinstance(cond_mel, list)      # conds / spk hold a row per utterance: a record carries its own row's
         conds, spk = self._prompt_features(cond_mel)
         batch_h = torch.full((N, max(int(t.numel()) for t in texts)), self.cfg.gpt.stop_text_token, dtype=torch.int32)
         for i, t in enumerate(texts):
@@ -1091,49 +1120,31 @@ class IndexTTS:
         sp = sampling_params(gen, seed) if sampling is None else sampling
         shared = 0 if per_row or conds.shape[0] != 1 else int(conds.shape[1])    # one prompt: every row starts with the same latents
         eng.prefill(emb, pad, max_mel_tokens, shared_rows=shared, adapter_ids=adapter_ids, adapter_mix=adapter_mix)
-        left, right = self.bigvgan.receptive_halo()
-        stop, emitted, ended = g.stop_mel_token, [0] * N, [False] * N
-        lc = _LatentRows(eng, N, int(emb.shape[1]) + max_mel_tokens + 2) if latent_cache else None
+        voices = adapter_ids if adapter_mix is None else adapter_mix
+        where = "" if who == "stream_utterance" else " in utterance {}"
+        st = _StreamState(self.bigvgan.receptive_halo(), g.stop_mel_token, max_mel_tokens,
+                          None if voices is None else "adapter_ids" if adapter_mix is None else "adapter_mix", trace,
+                          _LatentRows(eng, N, int(emb.shape[1]) + max_mel_tokens + 2) if latent_cache else "reuse",
+                          warn=f"generation stopped at max_mel_tokens ({max_mel_tokens}){where}; consider shorter sentences")
         if trace is not None:
             trace.update(codes=[None] * N, frames=[[] for _ in range(N)], latent=[[] for _ in range(N)],
                          window=[[] for _ in range(N)], boundaries=[[] for _ in range(N)])
+        rows = [dict(utt=b, handle=b, stopped=False, text=texts[b], conds=conds[b: b + 1] if per_row else conds,
+                     spk=spk[b: b + 1] if per_row else spk, voice=None if voices is None else voices[b], cache_row=b, lc_row=b)
+                for b in range(N)]
+        live = list(range(N))                     # the rows that have not had their last event
         chunks = eng.decode_chunks(max_mel_tokens, sp, chunk_tokens, force_stop=force_stop)
         try:
             for codes, _ in chunks:
-                plan = self.stream_batch_plan(codes, emitted, ended, right, max_mel_tokens, stop)
+                n, codes = int(codes.shape[1]), codes.unbind(0)
                 if trace is not None:
-                    for b in range(N):
-                        if not ended[b]:
-                            trace["boundaries"][b].append(int(codes.shape[1]))
-                rows = [b for b, _, t0, t1, _ in plan if t1 > t0]
-                wavs = {}
-                if rows:
-                    sel = torch.tensor(rows, device=conds.device) if per_row else None
-                    largs = (conds[sel] if per_row else conds, [texts[b] for b in rows], [codes[b, :k] for b, k, t0, t1, _ in plan if t1 > t0])
-                    voiced = dict(adapter_ids=None if adapter_ids is None else [adapter_ids[b] for b in rows],
-                                  adapter_mix=None if adapter_mix is None else [adapter_mix[b] for b in rows])
-                    if lc is not None:
-                        lats = self._latents_incremental(lc, rows, *largs, **voiced)
-                    else:
-                        lats = self._latents(*largs, reuse_prefix=True, cache_rows=rows, **voiced)
-                    spans = [(t0, t1) for _, _, t0, t1, _ in plan if t1 > t0]
-                    wavs = dict(zip(rows, self._vocode_windows(lats, spk[sel] if per_row else spk, spans)))
-                    if trace is not None:
-                        for b, lat, (t0, t1) in zip(rows, lats, spans):
-                            lo = max(0, t0 - left)
-                            trace["frames"][b].append((t0, t1))
-                            trace["latent"][b].append(lat[t0:t1].clone())
-                            trace["window"][b].append((lo, lat[lo: min(int(lat.shape[0]), t1 + right)].clone()))
-                for b, k, t0, t1, final in plan:
-                    emitted[b], ended[b] = t1, final
-                    if final:
-                        if not bool((codes[b] == stop).any()):
-                            warnings.warn(f"generation stopped at max_mel_tokens ({max_mel_tokens}) in utterance {b}; consider shorter "
-                                          f"sentences", category=RuntimeWarning)
-                        if trace is not None:
-                            trace["codes"][b] = codes[b, :k].clone()
-                    yield b, (wavs[b] if t1 > t0 else torch.zeros(0, device=self.device)), final
-                if all(ended):
+                    for b in live:
+                        trace["boundaries"][b].append(n)
+                events = IndexTTS._emit_boundary(self, st, [dict(rows[b], k=n, codes=codes[b]) for b in live])
+                over = {b for b, _, last in events if last}
+                live = [b for b in live if b not in over]
+                yield from events
+                if not live:
                     return
         finally:
             chunks.close()       # an early close of this generator abandons the loop, as the end of it does
@@ -1193,43 +1204,38 @@ class IndexTTS:
             raise TypeError("stream_queue: more is a callable that returns the requests that have arrived (or None: no more will come)")
         if sampling is not None or more is not None:
             sampling = row_sampling_params([{}] * N if sampling is None else sampling, N, gen, seed)
-        eng = self.gpt.engine
-        voice_kind = None                   # which keyword names a voice: the one this call was given
-        if adapter_ids is not None or adapter_mix is not None:
-            adapter_ids, adapter_mix = eng._voices(adapter_ids, adapter_mix, N)
-            voice_kind = "adapter_ids" if adapter_mix is None else "adapter_mix"
-        elif eng.bank is not None:
-            raise NotImplementedError("stream_queue: an adapter bank is attached and no voices were named: pass adapter_ids=[...] or "
-                                      "adapter_mix=[...], one entry per utterance (adapter_ids=[-1] * N is the base voice)")
-        cond_mel = IndexTTS._check_prompts(self, cond_mel, N, gen, "stream_queue")
-        texts = [torch.as_tensor(t).reshape(-1).to("cpu", torch.int32) for t in text_token_rows]
+        cond_mel, reqs, voice_kind = IndexTTS._queue_requests(self, "stream_queue", cond_mel, text_token_rows, gen, force_stop, sampling,
+                                                              adapter_ids, adapter_mix)
         if N == 0 and more is None:
             return iter(())
-        voices = adapter_ids if adapter_mix is None else adapter_mix
-        reqs = [dict(handle=i, text=texts[i], prompt=i if isinstance(cond_mel, list) else 0,
-                     stop=-1 if force_stop is None else force_stop[i], sp=None if sampling is None else sampling[i],
-                     voice=None if voices is None else voices[i]) for i in range(N)]
         return self._stream_queue(cond_mel, reqs, int(slots), chunk_tokens, max_mel_tokens, seed, voice_kind, more, _trace, gen, _refused,
                                   bool(latent_cache))
 
+    def _queue_requests(self, who, cond_mel, text_token_rows, gen, force_stop, sampling, adapter_ids, adapter_mix):
+        """What infer_queue and stream_queue (`who`) do with their arguments before anything is launched: the voices are checked
+        (named, or no bank is attached), then the prompts (_check_prompts); every utterance becomes a request -- "handle" (its
+        index), "text" (host int32), "prompt" (the key of its prompt's features), "stop", "sp" (its checked settings | None) and
+        "voice".  Returns (cond_mel as _check_prompts leaves it, the requests in the order given, voice_kind: the keyword that
+        names a voice -- the one this call was given -- or None)."""
+        N, eng = len(text_token_rows), self.gpt.engine
+        voices = voice_kind = None
+        if adapter_ids is not None or adapter_mix is not None:
+            adapter_ids, adapter_mix = eng._voices(adapter_ids, adapter_mix, N)
+            voices, voice_kind = (adapter_ids, "adapter_ids") if adapter_mix is None else (adapter_mix, "adapter_mix")
+        elif eng.bank is not None:
+            raise NotImplementedError(f"{who}: an adapter bank is attached and no voices were named: pass adapter_ids=[...] or "
+                                      "adapter_mix=[...], one entry per utterance (adapter_ids=[-1] * N is the base voice)")
+        cond_mel = IndexTTS._check_prompts(self, cond_mel, N, gen, who)
+        per_row = isinstance(cond_mel, list)
+        reqs = [dict(handle=i, text=torch.as_tensor(t).reshape(-1).to("cpu", torch.int32), prompt=i if per_row else 0,
+                     stop=-1 if force_stop is None else int(force_stop[i]), sp=None if sampling is None else sampling[i],
+                     voice=None if voices is None else voices[i]) for i, t in enumerate(text_token_rows)]
+        return cond_mel, reqs, voice_kind
+
     @staticmethod
-    def stream_queue_plan(rows, emitted, right, max_mel_tokens, stop):
-        """One poll of stream_queue on the host.  rows: the records of GPTEngine.decode_refill_chunks ("utt", "k", "codes", "stopped");
-        emitted: {utt: the frames it has given out} (an utterance not in it has given none).  Returns [(utt, k, t0, t1, final)] in
-        the order of `rows` for the utterances that emit now: k = the position of the row's first stop token (the cut of
-        remove_long_silence) or its own token count; final = a stop token is there, the loop says the row has stopped, or k has
-        reached max_mel_tokens; (t0, t1) = stream_plan(k, emitted[utt], right, final).  A row with nothing to emit that is not
-        final is left out; a final row is always there, with t1 == t0 when nothing is left."""
-        out = []
-        for row in rows:
-            codes = row["codes"]
-            hit = (codes == stop).nonzero()
-            k = int(hit[0]) if hit.numel() else int(row["k"])
-            final = bool(hit.numel()) or bool(row["stopped"]) or k >= max_mel_tokens
-            t0, t1 = IndexTTS.stream_plan(k, emitted.get(row["utt"], 0), right, final)
-            if t1 > t0 or final:
-                out.append((row["utt"], k, t0, t1, final))
-        return out
+    def _longest_first(reqs):
+        """The order a queue is served in: the longest texts start, so that every later prompt fits the positions a loop has passed."""
+        return sorted(reqs, key=lambda r: -int(r["text"].numel()))
 
     def _queue_request(self, r, n_seen, cond_mel, feats, seed, gen, voice_kind):
         """A request `more` returned -> the queue's own form, checked on the host; its prompt's features are computed here when
@@ -1364,18 +1370,20 @@ class IndexTTS:
 
     def _stream_queue(self, cond_mel, reqs, slots, chunk_tokens, max_mel_tokens, seed, voice_kind, more, trace, gen, refused=None,
                       latent_cache=False):
+        """stream_queue's generator: every poll of the refilled loops (_refill_loops) becomes the records of the slots' utterances,
+        keyed (loop number, utt), and goes through _emit_boundary; between two polls the arrivals are taken in."""
         g = self.gpt
-        lc, lc_loop = None, 0                           # the latent cache (made at the first emission) and the loop it serves
+        lc_loop = 0                                     # the loop the latent cache (made at the first poll) serves
         lc_text = max([int(getattr(g, "max_text_tokens", 0)) if more is not None else 0] + [int(r["text"].numel()) for r in reqs])
-        waiting = sorted(reqs, key=lambda r: -int(r["text"].numel()))      # longest first, as infer_queue: every later prompt fits
+        waiting = IndexTTS._longest_first(reqs)
         n_seen, open_ = len(reqs), more is not None
         per_row = more is not None or any(r["sp"] is not None for r in reqs)
         feats = {}                                      # prompt key -> (mel, conds [1, nc, D], spk [1, 1, 512])
-        left, right = self.bigvgan.receptive_halo()
-        stop = g.stop_mel_token
-        emitted = {}
+        # a refilled row's prompt does not lie where latent_mel_rows looks for it: the repeated pass is the whole-sequence one
+        st = _StreamState(self.bigvgan.receptive_halo(), g.stop_mel_token, max_mel_tokens, voice_kind, trace, "whole")
         if trace is not None:
-            trace.update(codes={}, frames={}, latent={}, window={}, polls={}, loops=0)
+            per_utt = lambda: collections.defaultdict(list)   # noqa: E731
+            trace.update(codes={}, frames=per_utt(), latent=per_utt(), window=per_utt(), polls=per_utt(), loops=0)
 
         def arrivals():
             """one call of more(): the new requests go to the back of the queue.  refused (a list; the service form): a request
@@ -1416,49 +1424,22 @@ class IndexTTS:
             for number, entered, rec in loops:
                 if trace is not None:
                     trace["loops"] = number
-                plan = self.stream_queue_plan([dict(row, utt=(number, row["utt"])) for row in rec["rows"]], emitted, right,
-                                              max_mel_tokens, stop)
-                codes = {(number, row["utt"]): row["codes"] for row in rec["rows"]}
-                slot_of = {(number, row["utt"]): row["slot"] for row in rec["rows"]}
-                if trace is not None:
-                    for row in rec["rows"]:
-                        trace["polls"].setdefault(entered[row["utt"]]["handle"], []).append(rec["n"])
-                emit = [(u, k, t0, t1) for u, k, t0, t1, _ in plan if t1 > t0]
-                wavs = {}
-                if emit:
-                    rs = [entered[u[1]] for u, _, _, _ in emit]
-                    same = all(feats[r["prompt"]][1] is feats[rs[0]["prompt"]][1] for r in rs)
-                    conds = feats[rs[0]["prompt"]][1] if same else torch.cat([feats[r["prompt"]][1] for r in rs], 0)
-                    largs = (conds, [r["text"] for r in rs], [codes[u][:k] for u, k, _, _ in emit])
-                    voiced = {} if voice_kind is None else {voice_kind: [r["voice"] for r in rs]}
-                    if latent_cache:
-                        if lc is None:
-                            lc = _LatentRows(self.gpt.engine, slots, int(conds.shape[1]) + lc_text + 2 + max_mel_tokens + 2)
-                        if lc_loop != number:           # a new loop has prefilled every slot anew
-                            for s in range(slots):
-                                lc.reset(s)
-                            lc_loop = number
-                        lats = self._latents_incremental(lc, [slot_of[u] for u, _, _, _ in emit], *largs, **voiced)
-                    else:
-                        lats = self._latents(*largs, reuse_prefix=False, **voiced)
-                    spans = [(t0, t1) for _, _, t0, t1 in emit]
-                    spks = feats[rs[0]["prompt"]][2] if same else torch.cat([feats[r["prompt"]][2] for r in rs], 0)
-                    wavs = dict(zip([u for u, _, _, _ in emit], self._vocode_windows(lats, spks, spans)))
+                recs = []
+                for row in rec["rows"]:
+                    r = entered[row["utt"]]
+                    _, conds, spk = feats[r["prompt"]]
+                    recs.append(dict(utt=(number, row["utt"]), handle=r["handle"], k=row["k"], codes=row["codes"], stopped=row["stopped"],
+                                     text=r["text"], conds=conds, spk=spk, voice=r["voice"], cache_row=None, lc_row=row["slot"]))
                     if trace is not None:
-                        for r, lat, (t0, t1) in zip(rs, lats, spans):
-                            lo, h = max(0, t0 - left), r["handle"]
-                            trace["frames"].setdefault(h, []).append((t0, t1))
-                            trace["latent"].setdefault(h, []).append(lat[t0:t1].clone())
-                            trace["window"].setdefault(h, []).append((lo, lat[lo: min(int(lat.shape[0]), t1 + right)].clone()))
-                for u, k, t0, t1, final in plan:
-                    emitted[u] = t1
-                    if final:
-                        del emitted[u]
-                        if lc is not None and lc_loop == number:
-                            lc.reset(slot_of[u])          # the slot goes to the next utterance
-                        if trace is not None:
-                            trace["codes"][entered[u[1]]["handle"]] = codes[u][:k].clone()
-                    yield entered[u[1]]["handle"], (wavs[u] if t1 > t0 else torch.zeros(0, device=self.device)), final
+                        trace["polls"][r["handle"]].append(rec["n"])
+                if latent_cache and recs and lc_loop != number:
+                    if lc_loop == 0:
+                        st.latent = _LatentRows(g.engine, slots, int(recs[0]["conds"].shape[1]) + lc_text + 2 + max_mel_tokens + 2)
+                    else:                               # a new loop has prefilled every slot anew
+                        for s in range(slots):
+                            st.latent.reset(s)
+                    lc_loop = number
+                yield from IndexTTS._emit_boundary(self, st, recs)
                 arrivals()
         finally:
             loops.close()          # an early close of this generator abandons the loop
@@ -1603,14 +1584,8 @@ class IndexTTS:
             raise NotImplementedError("infer_queue: num_beams = 1 only (beam rows cannot be refilled one at a time)")
         if sampling is not None:        # checked before anything is launched
             sampling = row_sampling_params(sampling, len(text_token_rows), gen, seed)
-        voices = None                   # likewise: one voice per utterance, host ints or normalised mixes
-        if adapter_ids is not None or adapter_mix is not None:
-            adapter_ids, adapter_mix = self.gpt.engine._voices(adapter_ids, adapter_mix, len(text_token_rows))
-            voices = adapter_ids if adapter_mix is None else adapter_mix
-        elif self.gpt.engine.bank is not None:
-            raise NotImplementedError("infer_queue: an adapter bank is attached and no voices were named: pass adapter_ids=[...] or "
-                                      "adapter_mix=[...], one entry per utterance (adapter_ids=[-1] * N is the base voice)")
-        cond_mel = self._check_prompts(cond_mel, len(text_token_rows), gen, "infer_queue")
+        cond_mel, reqs, voice_kind = self._queue_requests("infer_queue", cond_mel, text_token_rows, gen, force_stop, sampling,
+                                                          adapter_ids, adapter_mix)       # likewise: voices, prompts
         if not text_token_rows:
             return ([], []) if return_codes else []
         if int(slots) < 1:
@@ -1618,19 +1593,15 @@ class IndexTTS:
         self._mark(phase_events, "start")
         conds, spk = self._prompt_features(cond_mel)
         per_row = isinstance(cond_mel, list)      # conds / spk hold a row per utterance: every group below gathers its own
-        N = len(text_token_rows)
-        texts = [t.reshape(-1).to(torch.int32).cpu() for t in text_token_rows]
-        stops = [-1] * N if force_stop is None else [int(v) for v in force_stop]
-        voice_kind = None if voices is None else "adapter_ids" if adapter_mix is None else "adapter_mix"
+        N = len(reqs)
+        texts = [r["text"] for r in reqs]
 
         def voiced(ids):
             """the keyword that names the voices of the utterances `ids` to _latents() (none without voices)"""
-            return {} if voices is None else {voice_kind: [voices[i] for i in ids]}
+            return {} if voice_kind is None else {voice_kind: [reqs[i]["voice"] for i in ids]}
 
         feats = {i: (None, conds[i: i + 1], None) for i in range(N)} if per_row else {0: (None, conds, None)}
-        reqs = [dict(handle=i, text=texts[i], prompt=i if per_row else 0, stop=stops[i], sp=None if sampling is None else sampling[i],
-                     voice=None if voices is None else voices[i]) for i in range(N)]
-        waiting = sorted(reqs, key=lambda r: -int(r["text"].numel()))      # longest first: every later prompt fits
+        waiting = self._longest_first(reqs)
         rows: List[torch.Tensor | None] = [None] * N
         self._mark(phase_events, "conditioned")
         # the loops of stream_queue (_refill_loops), each drained inside GPTEngine.decode_refill

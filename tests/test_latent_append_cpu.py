@@ -201,15 +201,15 @@ def test_stream_utterance_sends_every_row_once():
     def make():
         stub = sb.StubTTS(polls)
         stub._prompt_features = lambda cond_mel: (torch.zeros(1, NC, 3), torch.zeros(1, 1, 4))
-        stub.bigvgan.vocode_window = lambda lat, spk, t0, t1: lat[t0:t1, 0].repeat_interleave(sb.HOP)
         stub._latents = lambda conds, texts, codes, **kw: [c.float()[:, None].expand(-1, 3) for c in codes]
+        stub._stream_rows = types.MethodType(IndexTTS._stream_rows, stub)        # stream_utterance is its one-row form
         return stub
     text = torch.tensor([5, 6, 7], dtype=torch.int32)
-    args = (None, text, sb.CHUNK, 96, 7, [70], None, None, None, dict(sb.GEN))
-    off = list(IndexTTS._stream(make(), *args))
+    kw = dict(chunk_tokens=sb.CHUNK, max_mel_tokens=96, seed=7, force_stop=[70], **sb.GEN)
+    off = list(IndexTTS.stream_utterance(make(), None, text, **kw))
     stub = make()
     app = bind(stub, lambda row, first: 0)
-    on = list(IndexTTS._stream(stub, *args, True))
+    on = list(IndexTTS.stream_utterance(stub, None, text, latent_cache=True, **kw))
     assert len(on) == len(off) > 3 and all(torch.equal(a, b) for a, b in zip(on, off))
     (row, u), = per_utterance(app.log)
     assert row == 0 and u["prompt"] == NC + 3 + 2 and u["mel"] == 70 and len(u["spans"]) > 3
@@ -247,6 +247,45 @@ def test_stream_queue_sends_every_row_once_and_resets_a_slot_before_its_next_own
             assert not (ev[2] > 0 and ev[1] in dirty), f"cache row {ev[1]} was handed on without a reset"
             dirty.add(ev[1])
     assert app.cap >= NC + 17 + 2 + 96 + 2                   # sized for the queue's longest prompt + max_mel_tokens + 2
+
+
+def test_stream_queue_resets_a_row_once_between_two_owners_and_every_row_at_a_new_loop():
+    """Where the resets lie, over a fake incremental pass that records (cache row, utterance, codes) and a fake cache that records
+    its resets, each with the number of the loop it happened in.  Two slots, four utterances: 10 (2 codes) and 11 (20 codes) start;
+    17 arrives, takes slot 0 from 10 inside the first loop and stops with 11 at the poll n = 25; 16, whose prompt is longer than
+    the positions that loop has passed, is held back and starts a second loop alone."""
+    from indextts.gpt.model import row_sampling_params
+    from indextts.infer import IndexTTS
+    stub, log = sq.StubQueueTTS(), []
+    stub.gpt.engine.latent_cache = lambda rows, cap: types.SimpleNamespace(reset=lambda row: log.append(("reset", stub.loops, int(row))))
+
+    def incremental(st, rows, conds, text_rows, code_rows, **kw):
+        log.extend(("rows", stub.loops, int(r), int(t[0])) for r, t in zip(rows, text_rows))
+        return [c.float()[:, None].expand(-1, 2) for c in code_rows]
+    stub._latents_incremental = incremental
+    held = dict(handle="held", text=sq.text_of(16, 38), force_stop=40)
+    late = dict(handle="late", text=sq.text_of(17, 4), force_stop=5)
+    more, _ = sq.scripted_more([[held, late]])
+    sp = row_sampling_params([{}] * 2, 2, sq.GEN, 7)
+    reqs = [dict(handle=i, text=sq.text_of(nm, 5), prompt=0, stop=e, sp=sp[i], voice=None) for i, (nm, e) in enumerate([(10, 2), (11, 20)])]
+    events = list(IndexTTS._stream_queue(stub, "mel", reqs, 2, sq.CHUNK, 96, 7, None, more, {}, dict(sq.GEN), None, True))
+    assert stub.loops == 2 and not stub.latent_calls and sorted(str(h) for h, _, last in events if last) == ["0", "1", "held", "late"]
+    served = [ev[1:] for ev in log if ev[0] == "rows"]
+    assert served == [(1, 0, 10), (1, 0, 17), (1, 1, 11), (2, 0, 16)]         # (loop, cache row = slot, utterance)
+    owner, resets = {}, {}                                  # per cache row: (loop, utterance) it last served; resets since then
+    for kind, loop, row, *name in log:
+        if kind == "reset":
+            resets[row] = resets.get(row, 0) + 1
+            continue
+        before = owner.get(row)
+        if before is not None and before != (loop, name[0]):
+            assert resets[row] >= 1, f"cache row {row} was handed on without a reset"
+            if before[0] == loop:
+                assert resets[row] == 1, f"cache row {row}: {resets[row]} resets between two owners of one loop"
+        owner[row], resets[row] = (loop, name[0]), 0
+    # the second loop has prefilled every slot anew: both rows are reset in it, before its first rows are sent
+    first = log.index(("rows", 2, 0, 16))
+    assert {ev[2] for ev in log[:first] if ev[:2] == ("reset", 2)} == {0, 1}
 
 
 def test_a_request_too_long_for_the_cache_is_refused_like_any_other():

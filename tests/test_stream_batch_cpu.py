@@ -148,6 +148,73 @@ def test_plan_of_one_boundary():
     assert plan == [(0, 2, 2, 2, True), (1, 4, 3, 4, True), (2, 0, 0, 0, True), (3, 4, 0, 4, True)]
 
 
+def test_the_batch_plan_is_the_one_planner_over_equivalent_records():
+    """stream_batch_plan holds no rule of its own: over every n, limit, halo, stop position and drawn (ended, emitted) it returns what
+    stream_queue_plan returns for the records of the rows that have not ended (k = n, not stopped) -- and both return what the rule
+    stream_batch_plan held before it became that adapter returns (written out below)."""
+    from indextts.infer import IndexTTS
+
+    def rule(codes, emitted, ended, right, limit):
+        n, out = int(codes.shape[1]), []
+        for b in range(int(codes.shape[0])):
+            if ended[b]:
+                continue
+            hit = (codes[b] == STOP).nonzero()
+            final = bool(hit.numel()) or n >= limit
+            k = int(hit[0]) if hit.numel() else n
+            t1 = k if final else max(emitted[b], k - right)
+            if t1 > emitted[b] or final:
+                out.append((b, k, emitted[b], t1, final))
+        return out
+    rng, B, cases, finals = torch.Generator().manual_seed(5), 3, 0, 0
+    for n in range(1, 13):
+        for limit in (12, 16):
+            for right in (0, 3):
+                for pos in [None] + list(range(n)):
+                    codes = torch.randint(0, 8000, (B, n), generator=rng)
+                    if pos is not None:
+                        codes[int(torch.randint(0, B, (1,), generator=rng)), pos] = STOP
+                    ended = (torch.rand(B, generator=rng) < 0.3).tolist()
+                    emitted = torch.randint(0, n + 1, (B,), generator=rng).tolist()
+                    got = IndexTTS.stream_batch_plan(codes, emitted, ended, right, limit, STOP)
+                    live = [b for b in range(B) if not ended[b]]
+                    want = IndexTTS.stream_queue_plan([dict(utt=b, k=n, codes=codes[b], stopped=False) for b in live],
+                                                      {b: emitted[b] for b in live}, right, limit, STOP)
+                    assert got == want == rule(codes, emitted, ended, right, limit), (n, limit, right, pos, ended, emitted)
+                    cases, finals = cases + 1, finals + sum(f for *_, f in got)
+    assert cases == 12 * 2 * 2 + 2 * 2 * sum(range(1, 13)) and 0 < finals < 3 * cases
+
+
+def stream_one(ends, limit, **kw):
+    """stream_utterance itself over the stub: (chunks, trace, stub, full)."""
+    from indextts.infer import IndexTTS
+    polls, full = recorded_polls(ends, limit)
+    stub, trace = StubTTS(polls), {}
+    stub._stream_rows = types.MethodType(IndexTTS._stream_rows, stub)        # stream_utterance is its one-row form
+    chunks = list(IndexTTS.stream_utterance(stub, None, torch.arange(3, dtype=torch.int32), chunk_tokens=CHUNK, max_mel_tokens=limit,
+                                            seed=7, _trace=trace, **kw, **GEN))
+    return chunks, trace, stub, full
+
+
+@pytest.mark.parametrize("end,limit,frames", [(75, 96, [(0, 5), (5, 13), (13, 21), (21, 29), (29, 37), (37, 75)]),
+                                              (None, 64, [(0, 5), (5, 13), (13, 21), (21, 64)])], ids=["stop-token", "token-limit"])
+def test_one_utterance_is_the_batch_of_one_row_unwrapped(end, limit, frames):
+    with warnings.catch_warnings(record=True) as rec:
+        warnings.simplefilter("always")
+        chunks, trace, stub, full = stream_one([end], limit)
+    T = limit if end is None else end
+    assert all(type(c) is torch.Tensor and c.dim() == 1 and c.numel() > 0 for c in chunks)      # pcm only, and no empty flush
+    assert len(chunks) == len(frames) and torch.equal(torch.cat(chunks), full[0, :T].float().repeat_interleave(HOP))
+    assert trace["frames"] == frames                              # flat: the lists of row 2 in the two tests above
+    assert torch.equal(trace["codes"], full[0, :T]) and torch.equal(torch.cat(trace["latent"])[:, 0], full[0, :T].float())
+    assert stub.latent_calls and all(rows == [0] for rows, _ in stub.latent_calls)
+    assert [n for _, (n,) in stub.latent_calls] == [min(t1 + 35, T) for _, t1 in frames[:-1]] + [T]
+    assert len(stub.vocoder_calls) == len(frames) and all(shape[0] == 1 and lens is None for shape, lens in stub.vocoder_calls)
+    said = [str(w.message) for w in rec if "max_mel_tokens" in str(w.message)]
+    assert len(said) == (end is None) and not any("utterance 0" in s for s in said)
+    assert len(stub.prefills) == 1 and stub.closed
+
+
 def test_an_early_close_abandons_the_loop():
     events, trace, stub, _ = run([3, 40, 75, 88], 96, stop_after=2)
     assert len(events) == 2 and stub.closed and len(stub.latent_calls) == 2

@@ -200,6 +200,24 @@ def test_a_row_streams_as_it_streams_alone(tts32, cond_mel, texts):
     assert rms <= RMS_FP32, rms
 
 
+@pytest.mark.parametrize("latent_cache", [False, True], ids=["repeated", "latent-cache"])
+@pytest.mark.parametrize("which,gen", [("fp32", GREEDY), ("bf16", SAMPLE)], ids=["greedy-fp32", "sampling-bf16"])
+def test_one_utterance_is_the_batch_of_one_row(tts32, tts16, cond_mel, texts, which, gen, latent_cache):
+    """stream_utterance is stream_batch with the one row, unwrapped: the same chunks bit for bit, the same frames and codes.  17 text
+    tokens, a stop after 40 codes of at most 48, chunks of 8: the boundary n = 40 is an interior one and emits (0, 5) from a window
+    clipped on the left only, and the stop token, found at n = 48, flushes the rest."""
+    tts = tts32 if which == "fp32" else tts16
+    kw = dict(chunk_tokens=CHUNK, max_mel_tokens=48, seed=7, latent_cache=latent_cache, **gen)
+    one, rows = {}, {}
+    chunks = list(tts.stream_utterance(cond_mel, texts[2], force_stop=[40], _trace=one, **kw))
+    events = list(tts.stream_batch(cond_mel, [texts[2]], force_stop=[40], _trace=rows, **kw))
+    assert one["frames"] == rows["frames"][0] == [(0, 5), (5, 40)]
+    assert torch.equal(one["codes"], rows["codes"][0]) and one["codes"].numel() == 40
+    assert [(row, last) for row, _, last in events] == [(0, False), (0, True)]
+    assert len(chunks) == 2 and all(torch.equal(c, pcm) for c, (_, pcm, _) in zip(chunks, events))
+    assert torch.cat(chunks).numel() == 40 * hop_of(tts)
+
+
 # ---------------------------------------------------------------------------------------------------------------- 5
 def test_prompt_voice_and_settings_per_row(state, texts):
     tts = make_tts(state)
