@@ -21,6 +21,7 @@ from types import SimpleNamespace
 import torch
 
 from .. import _native as nat
+from . import voice_pool
 from ..utils import quant
 
 
@@ -423,16 +424,7 @@ class GPTEngine:
         k-step innermost: extending K is a re-pack, i.e. a second copy of the block weights).  A target no adapter names keeps
         its base weight and gets no shrink launch.  The decode step runs in "launch" form (the folded GEMMs take their
         LayerNorm statistics over K on the matrix pipe; the shrink needs xn = LN(h) as an operand anyway)."""
-        if self.kv_dtype is not None:
-            raise NotImplementedError("attach_lora_bank(): LoRA with the FP8 KV cache (kv_dtype='fp8') is not built: the bank runs "
-                                      "the 7-launch decode step, whose QKV epilogue appends 16-bit keys")
-        if self.weight_dtype is not None:
-            raise ValueError("attach_lora_bank(): LoRA on an FP8 base is not built (weight_dtype='fp8'): the bank's K-extended "
-                             "weight mixes base rows and adapter rows in one packed operand")
-        if self.lora:
-            raise ValueError("attach_lora_bank(): single adapters are attached (attach_lora(None) first): one or the other")
-        if not self.pa:
-            raise ValueError("attach_lora_bank(): the bank needs the packed activation layout (ITTS_PACKED_ACT=1)")
+        self._bank_refusals("attach_lora_bank")
         bank = [(dict(ad), float(sc)) for ad, sc in bank]
         n = len(bank)
         if n < 1:
@@ -448,41 +440,158 @@ class GPTEngine:
         if max(ranks) > 64:
             raise ValueError("the adapter bank supports rank <= 64")
         rp = (max(ranks) + 15) // 16 * 16
+        names = {wkey: name for name, wkey in self.BANK_TARGETS}
+        targets = [(i, wkey) for i in range(self.L) for _, wkey in self.BANK_TARGETS
+                   if any(f"gpt.h.{i}.{names[wkey]}" in ad for ad, _ in bank)]
+        self._bank_build("attach_lora_bank", n, rp, targets, bank)
+
+    def _bank_refusals(self, who):
+        """What an adapter bank -- fixed (attach_lora_bank) or paged (attach_lora_pool) -- cannot be attached to."""
+        if self.kv_dtype is not None:
+            raise NotImplementedError(f"{who}(): LoRA with the FP8 KV cache (kv_dtype='fp8') is not built: the bank runs "
+                                      "the 7-launch decode step, whose QKV epilogue appends 16-bit keys")
+        if self.weight_dtype is not None:
+            raise ValueError(f"{who}(): LoRA on an FP8 base is not built (weight_dtype='fp8'): the bank's K-extended "
+                             "weight mixes base rows and adapter rows in one packed operand")
+        if self.lora:
+            raise ValueError(f"{who}(): single adapters are attached (attach_lora(None) first): one or the other")
+        if not self.pa:
+            raise ValueError(f"{who}(): the bank needs the packed activation layout (ITTS_PACKED_ACT=1)")
+
+    def _bank_build(self, who, n, rp, targets, bank=()):
+        """The bank's structure for n slots of padded rank rp on `targets` [(layer, weight key)]: per target A_bank T [n, rp, K] and
+        the packed [W ; B_bank^T], filled from `bank` [(adapters, scaling)] -- slot a <- bank[a]; slots beyond it stay zero."""
         Kx = nat.lora_kx(n, rp)
         if Kx > 512:
-            raise ValueError(f"attach_lora_bank(): {n} adapters of padded rank {rp} need {Kx} extra operand columns (limit 512)")
+            raise ValueError(f"{who}(): {n} adapters of padded rank {rp} need {Kx} extra operand columns (limit 512)")
         dev, T, W = self.device, self.dtype, self._W
+        names = {wkey: name for name, wkey in self.BANK_TARGETS}
         self.detach_lora_bank()
-        sig = []
-        for i, l in enumerate(self.layers):
-            for name, wkey in self.BANK_TARGETS:
-                key = f"gpt.h.{i}.{name}"
-                if not any(key in ad for ad, _ in bank):
-                    continue
-                base = W[key + ".weight"].detach().to(dev, torch.float32)              # [K, N]
-                K, N = base.shape
-                a_bank = torch.zeros(n, rp, K, dtype=torch.float32, device=dev)
-                ext = torch.zeros(K + Kx, N, dtype=torch.float32, device=dev)
-                ext[:K] = base
-                for a, (ad, sc) in enumerate(bank):
-                    if key in ad:
-                        A, Bm = (t.detach().to(dev, torch.float32) for t in ad[key])
-                        r = A.shape[0]
-                        if A.shape != (r, K) or Bm.shape != (N, r):
-                            raise ValueError(f"attach_lora_bank(): {key} of adapter {a}: A must be [r, {K}] and B [{N}, r]")
-                        a_bank[a, :r] = A * sc                                           # the scaling rides on A, folded in at fp32
-                        ext[K + a * rp:K + a * rp + r] = Bm.t()
-                l["bank_a_" + wkey] = a_bank.to(T).contiguous()
-                l["bank_" + wkey] = nat.pack_weight(ext.to(T).contiguous())
-                sig.append((i, wkey))
-        self.bank = SimpleNamespace(n=n, rp=rp, Kx=Kx, sig=(n, rp, tuple(sig)))
+        for i, wkey in targets:
+            l, key = self.layers[i], f"gpt.h.{i}.{names[wkey]}"
+            base = W[key + ".weight"].detach().to(dev, torch.float32)              # [K, N]
+            K, N = base.shape
+            a_bank = torch.zeros(n, rp, K, dtype=torch.float32, device=dev)
+            ext = torch.zeros(K + Kx, N, dtype=torch.float32, device=dev)
+            ext[:K] = base
+            for a, (ad, sc) in enumerate(bank):
+                if key in ad:
+                    A, Bm = (t.detach().to(dev, torch.float32) for t in ad[key])
+                    r = A.shape[0]
+                    if A.shape != (r, K) or Bm.shape != (N, r):
+                        raise ValueError(f"{who}(): {key} of adapter {a}: A must be [r, {K}] and B [{N}, r]")
+                    a_bank[a, :r] = A * sc                                           # the scaling rides on A, folded in at fp32
+                    ext[K + a * rp:K + a * rp + r] = Bm.t()
+            l["bank_a_" + wkey] = a_bank.to(T).contiguous()
+            l["bank_" + wkey] = nat.pack_weight(ext.to(T).contiguous())
+        self.bank = SimpleNamespace(n=n, rp=rp, Kx=Kx, sig=(n, rp, tuple((i, k) for i, k in targets)), pool=None)
         self._graphs.clear()
         if hasattr(self, "xn") and self.xn.shape[1] < self.D + Kx:
             self._cap_b = self._cap_s = 0   # xn / a / f need room for the shrink columns: reallocate on the next prefill
 
+    def attach_lora_pool(self, pool, slots: int):
+        """The adapter bank as a CACHE over a voice pool (gpt/voice_pool.py): exactly the structure
+        attach_lora_bank builds for `slots` voices of padded rank pool.rp on pool.targets, with all-zero extension rows and zero
+        bank_a_*; same refusals, exclusive with attach_lora_bank (detach_lora_bank() detaches either).  From here on adapter_ids /
+        adapter_mix name POOL VOICE IDS wherever the engine takes voices: they are checked against the pool, the named voices
+        are made resident (voice_pool.Residency: residents keep their slot, misses take empty slots, then the least recently
+        used unpinned one), every miss is paged in -- per (layer, target) one strided device copy of its B-image into the
+        slot's run of bank_w* and one contiguous copy of its A-image into bank_a_*[slot], on the current stream, i.e. between
+        graph replays like PagedKV.flush, no host synchronisation -- and the ids are rewritten to slot numbers before the
+        device tables are packed.  bank.sig stays (slots, rp, targets): one captured step serves every voice of the pool;
+        pool.add / pool.remove need no re-attach and clear no graph.
+        Pins (counts): prefill() pins its batch's voices until the next prefill() or the detach; the refill loop pins a row's
+        voices from its admission until the loop is resumed behind the poll that reported the row stopped -- so the passes a
+        stream runs for that last poll (latent pass, latent-cache append) find them resident -- and a fed item whose voices do
+        not fit beside the pinned ones waits (voice_pool.admit_voices), its voices guarded against pool.remove meanwhile.  Any other call acquires its voices at once and launches
+        in stream order behind its page-ins, which is all a pin for its own duration would give."""
+        self._bank_refusals("attach_lora_pool")
+        if self.bank is not None:
+            raise ValueError("attach_lora_pool(): an adapter bank or pool is attached (detach_lora_bank() first): one or the other")
+        if (pool.L, pool.D, pool.dtype, pool.device) != (self.L, self.D, self.dtype, self.device):
+            raise ValueError("attach_lora_pool(): the pool was made for another engine (layers, width, dtype or device differ)")
+        slots = int(slots)
+        if slots < 1:
+            raise ValueError("attach_lora_pool(): at least one slot")
+        self._bank_build("attach_lora_pool", slots, pool.rp, list(pool.targets))
+        self._pool_adopt(pool, voice_pool.Residency(slots))
+
+    def _pool_adopt(self, pool, res):
+        """This engine's bank_* tensors page voices of `pool` under the bookkeeping `res`."""
+        self.bank.pool, self.bank.res, self.bank.deferrals = pool, res, 0
+        pool._residencies.add(res)
+
+    def _pool(self):
+        bank = self.bank
+        return None if bank is None else getattr(bank, "pool", None)
+
+    def pool_resident(self):
+        """slot -> the pool voice resident there, or None."""
+        if self._pool() is None:
+            raise ValueError("pool_resident(): no voice pool is attached (attach_lora_pool)")
+        return self.bank.res.resident()
+
+    def pool_stats(self):
+        """Page-ins (loads), acquires that found their voice resident (hits), evictions, and fed items that had to wait for a slot."""
+        if self._pool() is None:
+            raise ValueError("pool_stats(): no voice pool is attached (attach_lora_pool)")
+        r = self.bank.res
+        return {"loads": r.loads, "hits": r.hits, "evictions": r.evictions, "deferrals": self.bank.deferrals}
+
+    def _page_in(self, loads):
+        """[(slot, voice)] -> the voices' images into the slots, on the current stream."""
+        bank, es = self.bank, torch.empty(0, dtype=self.dtype).element_size()
+        for slot, voice in loads:
+            for i, wkey in bank.pool.targets:
+                l = self.layers[i]
+                a_img, b_img = bank.pool.images(voice, (i, wkey))
+                K, N = voice_pool.target_shape(wkey, self.D)
+                NT, stride, off, run = voice_pool.span(K, N, bank.Kx, slot, bank.rp, es)
+                l["bank_" + wkey].view(NT, stride)[:, off:off + run].copy_(b_img)
+                l["bank_a_" + wkey][slot].copy_(a_img)
+
+    def _slots(self, ids, mix, pin=None):
+        """Checked (ids, mix) in pool voice ids -> the same in bank slot numbers, with every named voice resident and paged in
+        (no pool: unchanged).  pin (a list): the voices are pinned and appended to it; the caller unpins them."""
+        if self._pool() is None:
+            return ids, mix
+        res = self.bank.res
+        named = [v for v in ids if v >= 0] if mix is None else [i for row in mix for i, _ in row]
+        named = list(dict.fromkeys(named))
+        self._page_in(res.acquire(named))
+        if pin is not None:
+            res.pin(named)
+            pin.extend(named)
+        at = res.slot_of
+        if mix is None:
+            return [-1 if v < 0 else at[v] for v in ids], None
+        return None, [tuple(sorted((at[i], w) for i, w in row)) for row in mix]
+
+    def batch_fit(self, voices) -> int:
+        """How many leading rows of `voices` (checked ids, or normalised mixes) one batch can hold: with a voice pool, as many as
+        name no more distinct voices than the bank has slots (at least one: a single row always fits); all of them otherwise."""
+        pool = None if self.bank is None else getattr(self.bank, "pool", None)
+        if pool is None:
+            return len(voices)
+        seen = set()
+        for j, v in enumerate(voices):
+            named = {i for i, _ in v} if isinstance(v, tuple) else {int(v)} - {-1}
+            if len(seen | named) > self.bank.n:
+                return j
+            seen |= named
+        return len(voices)
+
+    def _unpin_prefill(self):
+        held, self._prefill_pins = getattr(self, "_prefill_pins", None), None
+        if held and self._pool() is not None:
+            self.bank.res.unpin(held)
+
     def detach_lora_bank(self):
         """Back to the base weights: drops the bank's A factors and extended weights and the graphs captured over them.  Only this
-        engine changes: a fork holds its own layer dicts."""
+        engine changes: a fork holds its own layer dicts.  Detaches a voice pool too (attach_lora_pool): its pins go with it."""
+        if self._pool() is not None:
+            self.bank.pool._residencies.discard(self.bank.res)
+        self._prefill_pins = None
         for l in self.layers:
             for k in [k for k in l if k.startswith("bank_")]:
                 del l[k]
@@ -495,9 +604,10 @@ class GPTEngine:
             self.adapter_mix.copy_(self._mix_records([()] * self.adapter_mix.shape[0]))
         self._graphs.clear()
 
-    def _row_adapters(self, adapter_ids, B):
+    def _row_adapters(self, adapter_ids, B, queue=False):
         """The batch's adapter ids as host ints, checked before anything is launched (None without a bank; all -1 when a bank is
-        attached and the caller names none)."""
+        attached and the caller names none).  With a voice pool the ids are pool voice ids: each must be alive, and -- unless the
+        rows are a queue's (queue=True), which need not be resident together -- the distinct ones at most the slots."""
         if adapter_ids is None:
             return None if self.bank is None else [-1] * B
         if self.bank is None:
@@ -505,16 +615,26 @@ class GPTEngine:
         ids = [int(v) for v in (adapter_ids.tolist() if torch.is_tensor(adapter_ids) else adapter_ids)]
         if len(ids) != B:
             raise ValueError(f"adapter_ids holds {len(ids)} ids for a batch of {B}")
-        if any(v < -1 or v >= self.bank.n for v in ids):
+        pool = getattr(self.bank, "pool", None)   # (read off the bank: these checks also run over engines that hold nothing else)
+        if pool is not None:
+            gone = [v for v in ids if v != -1 and not pool.alive(v)]
+            if gone:
+                raise ValueError(f"adapter_ids must be -1 or voices of the pool: {gone} are not (never added, or removed)")
+            if not queue and len({v for v in ids if v >= 0}) > self.bank.n:
+                raise ValueError(f"adapter_ids name {len({v for v in ids if v >= 0})} distinct voices, the pool is attached with "
+                                 f"{self.bank.n} slots")
+        elif any(v < -1 or v >= self.bank.n for v in ids):
             raise ValueError(f"adapter_ids must lie in [-1, {self.bank.n}): {ids}")
         return ids
 
-    def check_adapter_mix(self, mix, B):
+    def check_adapter_mix(self, mix, B, queue=False):
         """The batch's adapter mixes, normalised and checked on the host before anything is launched: one tuple of up to four
         (id, weight) per row, sorted by id (the order of a record's entries moves no bit of the result).  Every element of `mix` is
         None or -1 (the base voice), an int id (that adapter at weight 1), a {id: weight} dict or a sequence of (id, weight).
         ValueError: no bank attached, a wrong number of rows, an id outside [0, n), a repeated id within a row, more than four
-        entries, a weight that is not finite."""
+        entries, a weight that is not finite.  With a voice pool the ids are pool voice ids: each must be alive, a mix holds at
+        most as many entries as the pool has slots, and with queue=False (the rows of one batch) all rows together name at most
+        that many distinct voices."""
         import math
         import numbers
         if self.bank is None:
@@ -522,6 +642,7 @@ class GPTEngine:
         mix = mix.tolist() if torch.is_tensor(mix) else list(mix)
         if len(mix) != B:
             raise ValueError(f"adapter_mix holds {len(mix)} mixes for a batch of {B}")
+        pool = getattr(self.bank, "pool", None)
         out = []
         for b, el in enumerate(mix):
             if el is None or (isinstance(el, numbers.Integral) and int(el) == -1):
@@ -539,9 +660,14 @@ class GPTEngine:
                                      f"(got {el!r})") from None
             if len(pairs) > nat.LORA_MIX_ENTRIES:
                 raise ValueError(f"adapter_mix[{b}]: a mix holds at most {nat.LORA_MIX_ENTRIES} entries (got {len(pairs)})")
+            if pool is not None and len(pairs) > self.bank.n:
+                raise ValueError(f"adapter_mix[{b}]: a mix of {len(pairs)} voices cannot be resident in the pool's {self.bank.n} slots")
             row = []
             for i, w in pairs:
-                if not isinstance(i, numbers.Integral) or not 0 <= int(i) < self.bank.n:
+                if pool is not None:
+                    if not isinstance(i, numbers.Integral) or not pool.alive(int(i)):
+                        raise ValueError(f"adapter_mix[{b}]: ids must be voices of the pool (got {i!r}: never added, or removed)")
+                elif not isinstance(i, numbers.Integral) or not 0 <= int(i) < self.bank.n:
                     raise ValueError(f"adapter_mix[{b}]: ids must lie in [0, {self.bank.n}) (got {i!r})")
                 if not isinstance(w, numbers.Real) or not math.isfinite(w):
                     raise ValueError(f"adapter_mix[{b}]: the weight of adapter {int(i)} must be a finite number (got {w!r})")
@@ -549,16 +675,21 @@ class GPTEngine:
             if len({i for i, _ in row}) != len(row):
                 raise ValueError(f"adapter_mix[{b}]: adapter ids repeat within the row: {[i for i, _ in row]}")
             out.append(tuple(sorted(row)))
+        if pool is not None and not queue:
+            distinct = {i for row in out for i, _ in row}
+            if len(distinct) > self.bank.n:
+                raise ValueError(f"adapter_mix names {len(distinct)} distinct voices, the pool is attached with {self.bank.n} slots")
         return out
 
-    def _voices(self, adapter_ids, adapter_mix, B):
-        """(ids, mix) of a batch, checked: adapter ids (_row_adapters) or -- exclusive -- adapter mixes (check_adapter_mix)."""
+    def _voices(self, adapter_ids, adapter_mix, B, queue=False):
+        """(ids, mix) of a batch, checked: adapter ids (_row_adapters) or -- exclusive -- adapter mixes (check_adapter_mix).
+        queue: the rows are a queue's utterances, not one batch (a voice pool then places no bound on the distinct voices)."""
         if adapter_mix is None:
-            return self._row_adapters(adapter_ids, B), None
+            return self._row_adapters(adapter_ids, B, queue), None
         if adapter_ids is not None:
             raise ValueError("adapter_ids and adapter_mix are mutually exclusive: a row is an id or a mix (an int in adapter_mix is "
                              "that adapter at weight 1)")
-        return None, self.check_adapter_mix(adapter_mix, B)
+        return None, self.check_adapter_mix(adapter_mix, B, queue)
 
     def _mix_records(self, mixes):
         """uint8 device tensor [len(mixes), 32]: the itts_lora_mix_row records of normalised mixes."""
@@ -583,10 +714,21 @@ class GPTEngine:
     def fork(self) -> "GPTEngine":
         """A second engine over the SAME packed weights (read-only, shared tensors) with its own KV cache, scratch buffers,
         loop state, captured graphs and per-layer dicts: what a concurrent request needs (infer.RequestPool).  A fork keeps
-        the adapter state it was forked with; attach_lora / detach_lora on one engine never changes another."""
+        the adapter state it was forked with; attach_lora / detach_lora on one engine never changes another.
+        A fork of an engine with a voice pool (attach_lora_pool) shares the pool's images, which are read-only, but CLONES the
+        bank_* tensors -- a page-in on one engine must not rewrite another's weights -- and keeps its own Residency: that costs a
+        second copy of the block weights (K-extended) per fork, about 1 GB at 24 layers x 1280, 16-bit."""
         import copy
         e = copy.copy(self)
         e.layers = [dict(l) for l in self.layers]
+        if self._pool() is not None:
+            # page-ins rewrite bank_*: the fork gets its own copies and its own residency (the arrangement it was forked with, no pins)
+            for l in e.layers:
+                for k in [k for k in l if k.startswith("bank_")]:
+                    l[k] = l[k].clone()
+            e.bank = copy.copy(self.bank)
+            e._pool_adopt(self.bank.pool, self.bank.res.copy_unpinned())
+            e._prefill_pins = None
         e._cap_b = e._cap_s = 0
         e.kv = None
         e._kv_pool = None
@@ -921,6 +1063,11 @@ class GPTEngine:
         if beams > 1 and self.beam_kv != "table":
             raise ValueError("prefill(beams>1) needs the KV row table (beam_kv='table')")
         pad_h = [int(v) for v in torch.as_tensor(pad).tolist()]
+        # voice pool: the batch's voices become resident and stay pinned until the next prefill(); the device tables hold slots
+        self._unpin_prefill()
+        held = []
+        s_ids, s_mix = self._slots(ids, mix, pin=held)
+        self._prefill_pins = held
         use_pages = (self.paged if paged is None else bool(paged)) and beams == 1
         if use_pages:
             window = max(S + max_new + 1 - min(pad_h), int(slots_window))
@@ -949,9 +1096,9 @@ class GPTEngine:
         self.kv_share.zero_()
         self._ids_host, self._mix_host = ids, mix
         if ids is not None:
-            self.adapter_ids[:B] = torch.tensor(ids, dtype=torch.int32).to(dev)
+            self.adapter_ids[:B] = torch.tensor(s_ids, dtype=torch.int32).to(dev)
         if mix is not None:
-            self.adapter_mix[:B] = self._mix_records(mix)
+            self.adapter_mix[:B] = self._mix_records(s_mix)
         # (with a bank the conditioning rows' hidden states depend on the row's adapter: nothing is shared)
         # (FP8 KV cache: the shared-prefix path is off in this version -- the un-shared prefill runs and kv_share stays 0)
         if shared_rows and B > 1 and self.share_prefix and ids is None and mix is None and self.kv_dtype is None:
@@ -969,7 +1116,7 @@ class GPTEngine:
             meta = torch.tensor(off + [b_off - 1 for b_off in off[1:]], dtype=torch.int32).to(dev)   # row_off | last rows
             row_off, last_rows = meta[: B + 1], meta[B + 1:].long()
             h = emb.view(B * S, D)[idx.to(dev)]
-            h = self._blocks_full(h, B, S, None, True, row_off=row_off, cache_shift=self.pad[:B], **self._row_voices(ids, mix, lens))
+            h = self._blocks_full(h, B, S, None, True, row_off=row_off, cache_shift=self.pad[:B], **self._row_voices(s_ids, s_mix, lens))
             self._head(h[last_rows].contiguous(), B)
         self.state.zero_()                 # step, cache position, finished rows, arrival counter, seed (lo, hi)
         self.state[1] = S - 1
@@ -1009,7 +1156,7 @@ class GPTEngine:
         src = emb.to(dev, torch.float32).contiguous().view(B * S, D)
         if lengths is None:
             h = src.clone()
-            self._blocks_full(h, B, S, None, False, **self._row_voices(ids, mix, [S] * B))
+            self._blocks_full(h, B, S, None, False, **self._row_voices(*self._slots(ids, mix), [S] * B))
             out = torch.empty_like(h)
             nat.layernorm(h, self.ln_f[0], self.ln_f[1], out, self.final_norm[0], self.final_norm[1])
             return out.view(B, S, D)
@@ -1020,7 +1167,7 @@ class GPTEngine:
         idx = torch.cat([torch.arange(b * S, b * S + lens[b]) for b in range(B)]).to(dev)
         row_off = torch.tensor(off, dtype=torch.int32).to(dev)
         h = src[idx]
-        self._blocks_full(h, B, max(lens), None, False, row_off=row_off, **self._row_voices(ids, mix, lens))
+        self._blocks_full(h, B, max(lens), None, False, row_off=row_off, **self._row_voices(*self._slots(ids, mix), lens))
         packed = torch.empty_like(h)
         nat.layernorm(h, self.ln_f[0], self.ln_f[1], packed, self.final_norm[0], self.final_norm[1])
         out = torch.zeros(B * S, D, dtype=torch.float32, device=dev)
@@ -1084,7 +1231,7 @@ class GPTEngine:
         # the prompt's keys / values straight from the decode cache (itts_attn_prefill_prefix), the mel rows' from qkv
         h = self._big_m_layers(h, lambda i, qkv, att: nat.attn_prefill_prefix(
             qkv, att, self.kc[i], self.vc[i], row_off, pre_len, pre_row, pre_pos0, B, max(m), H, self._cap_s, **kva),
-            **self._row_voices(ids, mix, m))
+            **self._row_voices(*self._slots(ids, mix), m))
         out = torch.empty_like(h)
         nat.layernorm(h, self.ln_f[0], self.ln_f[1], out, self.final_norm[0], self.final_norm[1])
         return out
@@ -1158,7 +1305,7 @@ class GPTEngine:
             h = h.clone()                                   # (the blocks run in place)
         h = self._big_m_layers(h, lambda i, qkv, att: nat.attn_prefill_append(
             qkv, att, cache.kc[i], cache.vc[i], row_off, pos0, w_row, pos0, B, max(n), H, cache.cap),
-            **self._row_voices(ids, mix, n))
+            **self._row_voices(*self._slots(ids, mix), n))
         out = torch.empty_like(h)
         nat.layernorm(h, self.ln_f[0], self.ln_f[1], out, self.final_norm[0], self.final_norm[1])
         for r, k, v in zip(rows, n, voices):
@@ -1692,7 +1839,7 @@ class GPTEngine:
             raise ValueError("decode_refill(): num_beams = 1 only")
         voiced = voices is not None
         if voiced:
-            mix = self.check_adapter_mix(voices, B)
+            mix = self.check_adapter_mix(voices, B, queue=True)    # (resident already: prefill() placed them)
             had = self._mix_host if self._mix_host is not None else [() if i < 0 else ((i, 1.0),) for i in self._ids_host or [-1] * B]
             if mix != list(had):
                 raise ValueError("decode_refill(): voices differ from the voices the rows were prefilled under")
@@ -1715,9 +1862,19 @@ class GPTEngine:
         fs = [max_new - 1 if v < 0 else min(v, max_new - 1) for v in fs]
         self.force_stop[:B] = torch.tensor(fs, dtype=torch.int32).to(dev)
         sp = self._rows_to_table(sp) if per_row else self._seed_to_state(sp)
+        pooled = voiced and self._pool() is not None
+        res = self.bank.res if pooled else None
+        row_pins = [[] for _ in range(B)]      # voice pool: the voices each slot's row holds a pin on
+        unpin_next, held, guarded = [], [], []     # ... pins to drop when the loop is resumed; fed items that wait for a bank slot, their voices
         if voiced:      # from here on the step is the mix launch (graph key "bank-mix"), whichever launch the prefill ran
             self._ids_host, self._mix_host = None, mix
-            self.adapter_mix[:B] = self._mix_records(mix)
+            if pooled:  # the rows take the pins over from prefill(): a row's voices are free again once it has left
+                in_slots = self._slots(None, mix)[1]
+                for b in range(B):
+                    row_pins[b] = voice_pool.mix_voices(mix[b])
+                    res.pin(row_pins[b])
+                self._unpin_prefill()
+            self.adapter_mix[:B] = self._mix_records(in_slots if pooled else mix)
             idle = self._mix_records([()])
         self.kv_share.zero_()                                # a refilled row 0 no longer holds the shared block where the others expect it
         owner, start = list(range(B)), [0] * B              # owner: utterance id | None (free) | -1 (reserved for staged rows)
@@ -1725,7 +1882,7 @@ class GPTEngine:
         ids, leftover, fed_out, pending, row_sp = itertools.count(B), [], False, None, None
         self.refill_leftover = leftover
         stats = self.refill_stats = {"steps": 0, "polls": 0, "refill_calls": 0, "rows_refilled": 0, "staged": bool(staged)}
-        main = torch.cuda.current_stream(dev)
+        main = torch.cuda.current_stream(dev) if staged else None     # (only the staged form orders two streams)
         side = torch.cuda.Stream(device=dev) if staged else None
         if kv is not None:
             for b in range(B):      # the prefilled rows' whole windows, as admit() deals them (prefill(max_new + check_every) has)
@@ -1736,6 +1893,9 @@ class GPTEngine:
         n = 1
         try:
             while True:
+                if unpin_next:       # rows the last poll reported stopped: whatever the caller ran for them is enqueued by now
+                    res.unpin(unpin_next)
+                    unpin_next = []
                 # ---- A: rows staged during the last steps join here
                 if pending is not None:
                     st, ev, rows, row_sp = pending
@@ -1746,10 +1906,13 @@ class GPTEngine:
                 # ---- B: utterances for the slots that are free now
                 free = [r for r in range(B) if owner[r] is None]
                 items = []
-                if free and not fed_out and n > 1:
-                    items = list(feed(len(free)))
-                    if len(items) > len(free):
-                        raise ValueError(f"decode_refill(): feed({len(free)}) returned {len(items)} items")
+                if free and n > 1 and (held or not fed_out):
+                    ask = max(0, len(free) - len(held))    # (items that wait for a bank slot go first: the order they were fed in)
+                    items = list(feed(ask)) if ask and not fed_out else []
+                    if len(items) > ask:
+                        raise ValueError(f"decode_refill(): feed({ask}) returned {len(items)} items")
+                    short = len(items) < ask
+                    waited, items, held = len(held), held + items, []
                     fed_items = items    # (prefix, stop step[, settings[, voice]]) -> the old pairs + the rows' checked settings and voices
                     if per_row:
                         fed_sp = [self._fed_settings(it, sp_default) for it in items]
@@ -1757,26 +1920,43 @@ class GPTEngine:
                         raise ValueError("decode_refill(): a fed item carries sampling settings but the loop runs under one dict "
                                          "(pass sp as a list)")
                     if voiced:
-                        fed_mix = self.check_adapter_mix([self._fed_voice(it) for it in items], len(items))
+                        fed_mix = self.check_adapter_mix([self._fed_voice(it) for it in items], len(items), queue=True)
                     elif any(self._fed_voice(it) is not None for it in items):
                         raise ValueError("decode_refill(): a fed item names a voice but the loop runs without voices "
                                          "(attach_lora_bank, voices=[...])")
                     items = [tuple(it)[:2] for it in items]
                     # fewer than asked for: the queue is empty -- or, an open queue, only when closed() says so behind it
-                    fed_out = len(items) < len(free) and (closed is None or bool(closed()))
+                    fed_out = fed_out or (short and (closed is None or bool(closed())))
+                    if pooled:      # voice-aware admission: the first item whose voices find no slot, and every later one, wait
+                        res.unguard(guarded)
+                        fit = voice_pool.admit_voices(res, [voice_pool.mix_voices(m) for m in fed_mix])
+                        self.bank.deferrals += len(items) - max(fit, waited)
+                        held, items = fed_items[fit:], items[:fit]
                     n_join = n + ce if staged else n
+                    placed = len(items)
                     if limit - (S + n_join + 1) < max_new + ce:     # steps the loop could still take
-                        items, leftover[:] = [], items
+                        items = []
                     elif kv is not None:
-                        k = admit(kv, free, items, S + n_join - 1, max_new, ce)
-                        items, leftover[:] = items[:k], items[k:]
-                    if leftover:
-                        leftover[:] = fed_items[len(fed_items) - len(leftover):]   # as they were fed, settings and voice included
+                        items = items[:admit(kv, free, items, S + n_join - 1, max_new, ce)]
+                    if len(items) < placed or (held and limit - (S + n_join + 1) < max_new + ce):
+                        # not placed: as they were fed, settings and voice included -- and, behind them, those that waited for a voice
+                        # (which this loop, out of positions, could never place either)
+                        leftover[:] = fed_items[len(items):]
+                        held = []
+                    if pooled:      # a waiting item keeps its voices in the pool: remove() refuses them until it is placed or handed back
+                        guarded = [v for m in fed_mix[fit: fit + len(held)] for v in voice_pool.mix_voices(m)]
+                        res.guard(guarded)
                     fed_out = fed_out or bool(leftover)
                 if items:
                     rows, prefixes = free[: len(items)], [p for p, _ in items]
                     row_sp = fed_sp[: len(items)] if per_row else None
                     row_mix = fed_mix[: len(items)] if voiced else None
+                    if pooled:      # the new rows' voices: resident and paged in on this stream before `fed` is recorded, pinned
+                        in_slots = self._slots(None, row_mix)[1]
+                        for r, m in zip(rows, row_mix):
+                            row_pins[r] = voice_pool.mix_voices(m)
+                            res.pin(row_pins[r])
+                        row_mix = in_slots
                     stops = [max_new - 1 if int(v) < 0 else min(int(v), max_new - 1) for _, v in items]
                     stats["refill_calls"] += 1
                     stats["rows_refilled"] += len(rows)
@@ -1791,8 +1971,11 @@ class GPTEngine:
                         fed = torch.cuda.Event()
                         fed.record(main)                        # the prefix embeddings are complete on the loop's stream
                 # no utterance in any slot and none fed: the end -- of a closed queue, and of an open one that has fallen idle
-                if (fed_out or closed is not None) and pending is None and not items and all(o is None for o in owner):
-                    break
+                if pending is None and not items and all(o is None for o in owner):
+                    # no row holds a pin, and an item alone always fits the bank's slots: nothing can be waiting for a voice
+                    assert not held, "decode_refill(): an item waits for a bank slot although no row is active"
+                    if fed_out or closed is not None:
+                        break
                 # ---- C: check_every steps of the loop
                 if kv is not None:
                     kv.flush()
@@ -1812,11 +1995,18 @@ class GPTEngine:
                 freed = [row["slot"] for row in record if row["stopped"]]
                 if voiced and freed:                            # an idle slot is the base voice (nothing reads what it computes)
                     self.adapter_mix[torch.tensor(freed, device=dev)] = idle
+                for r in freed:
+                    unpin_next.extend(row_pins[r])
+                    row_pins[r] = []
                 yield {"n": n, "rows": record}
         finally:
             if pending is not None:      # closed early: the staged rows never join; their pass ends before this stream goes on
                 main.wait_event(pending[1])
                 pending = None
+            if pooled and self.bank is not None and self.bank.res is res:
+                res.unpin(unpin_next + [v for pins in row_pins for v in pins])
+                res.unguard(guarded)
+            leftover.extend(held)        # (none when the loop ran to its end)
             if kv is not None:           # (all free already when the loop ran to its end)
                 for r in range(B):
                     kv.release(r)

@@ -320,6 +320,15 @@ class UnifiedVoice:
         self.engine.attach_lora_bank(bank)
         return self
 
+    def attach_lora_pool(self, pool, slots: int):
+        """The bank's `slots` slots as a cache over a voice pool of any size (gpt/voice_pool.VoicePool): adapter_ids / adapter_mix then
+        name pool voice ids (see GPTEngine.attach_lora_pool).  Exclusive with attach_lora and attach_lora_bank; detach_lora_bank()
+        detaches it."""
+        if self.engine is None:
+            raise RuntimeError("call post_init_gpt2_config() first")
+        self.engine.attach_lora_pool(pool, slots)
+        return self
+
     def detach_lora_bank(self):
         if self.engine is None:
             raise RuntimeError("call post_init_gpt2_config() first")

@@ -549,6 +549,48 @@ class IndexTTS:
         emb, pad = self.gpt.prefix_rows(conds, batch_h)
         return eng.calibrate_kv_scales(emb, pad)
 
+    # ------------------------------------------------------------------------------------------------ voice pool
+    def attach_voice_pool(self, voices=(), slots=32, rank=None):
+        """Any number of LoRA voices behind `slots` bank slots (GPTEngine.attach_lora_pool).  voices:
+        [(adapters, scaling), ...] in the attach_lora format; rank: the largest rank a voice of this pool may have (default: the
+        largest among `voices`, 16 without any), padded to a multiple of 16; slots * padded rank <= 512.  Returns the voices' ids.
+        From here on adapter_ids / adapter_mix of infer_batch, infer_queue, stream_batch, stream_queue and infer_stream name
+        pool voice ids: a batch may name at most `slots` distinct voices (ValueError before anything is launched), a queue any
+        number -- an utterance whose voices find no slot waits for one, and a loop runs as many decode slots as the leading utterances'
+        voices fit the bank (`slots` of the queue calls may exceed the bank's).  Everything refused with a bank stays refused."""
+        from indextts.gpt.voice_pool import VoicePool
+        eng = self.gpt.engine
+        voices = [(dict(ad), float(sc)) for ad, sc in voices]
+        if rank is None:
+            rank = max([int(A.shape[0]) for ad, _ in voices for A, _ in ad.values()] + [1])
+        rank = int(rank)
+        if not 1 <= rank <= 64:
+            raise ValueError(f"attach_voice_pool(): rank must lie in [1, 64] (got {rank})")
+        if eng.bank is not None:
+            raise ValueError("attach_voice_pool(): an adapter bank or pool is attached (detach it first): one or the other")
+        pool = VoicePool(eng, (rank + 15) // 16 * 16)
+        ids = [pool.add(ad, sc) for ad, sc in voices]
+        eng.attach_lora_pool(pool, slots)
+        return ids
+
+    def _voice_pool(self, who):
+        pool = self.gpt.engine._pool()
+        if pool is None:
+            raise ValueError(f"{who}(): no voice pool is attached (attach_voice_pool)")
+        return pool
+
+    def add_voice(self, adapters, scaling) -> int:
+        """One more voice for the attached pool, usable at once: no re-attach, no captured graph is dropped.  Returns its id."""
+        return self._voice_pool("add_voice").add(adapters, scaling)
+
+    def remove_voice(self, voice: int):
+        """The voice leaves the pool (its id is never reused); ValueError while a batch or a queued utterance speaks with it."""
+        self._voice_pool("remove_voice").remove(int(voice))
+
+    def detach_voice_pool(self):
+        self._voice_pool("detach_voice_pool")
+        self.gpt.engine.detach_lora_bank()
+
     @staticmethod
     def _gen_kwargs(kw):
         return dict(do_sample=kw.pop("do_sample", True), top_p=kw.pop("top_p", 0.8), top_k=kw.pop("top_k", 30),
@@ -1220,7 +1262,7 @@ class IndexTTS:
         N, eng = len(text_token_rows), self.gpt.engine
         voices = voice_kind = None
         if adapter_ids is not None or adapter_mix is not None:
-            adapter_ids, adapter_mix = eng._voices(adapter_ids, adapter_mix, N)
+            adapter_ids, adapter_mix = eng._voices(adapter_ids, adapter_mix, N, queue=True)   # (a pool pages a queue's voices)
             voices, voice_kind = (adapter_ids, "adapter_ids") if adapter_mix is None else (adapter_mix, "adapter_mix")
         elif eng.bank is not None:
             raise NotImplementedError(f"{who}: an adapter bank is attached and no voices were named: pass adapter_ids=[...] or "
@@ -1274,6 +1316,8 @@ class IndexTTS:
     def _refill_loops(self, waiting, feats, slots, ce, max_mel_tokens, sp_scalar, per_row, voice_kind, one_prompt, staged=True,
                       cache_positions=4096, text_cap=0, closed=None, drain=False, idle=None):
         """The refilled loops of infer_queue and stream_queue, ONE set-up for both: a generator of (loop number, entered, record).
+        With a voice pool attached a loop starts with as many of the leading requests as name no more distinct voices than the bank
+        has slots (GPTEngine.batch_fit) and runs that many decode slots; the others are fed.
         waiting: the queue, a list of requests the caller may append to between two records -- dicts with "text" (host int32),
         "prompt" (key into feats: (mel, conds [1, nc, D], spk)), "stop", "sp" (checked settings | None) and "voice".  The first
         `slots` of it are prefilled, the others fed as slots free up (GPTEngine.decode_refill_chunks; `closed`: its argument);
@@ -1308,7 +1352,11 @@ class IndexTTS:
         number = 0
         while waiting:
             first = waiting[:slots]
-            del waiting[:slots]
+            if voice_kind is not None:
+                # a voice pool: the prefilled rows speak at once, so only the leading requests whose voices fit the bank's slots
+                # together start the loop -- it then runs that many decode slots -- and the others are fed (and wait for a voice)
+                first = first[: max(1, eng.batch_fit([r["voice"] for r in first]))]
+            del waiting[: len(first)]
             emb, pad = prefixes(first)
             nc = int(feats[first[0]["prompt"]][1].shape[1])
             p_max = max(int(emb.shape[1]), nc + int(text_cap) + 2 if text_cap else 0)     # the longest prompt this loop can place
@@ -1439,6 +1487,10 @@ class IndexTTS:
                         for s in range(slots):
                             st.latent.reset(s)
                     lc_loop = number
+                # Every pass a row of this poll needs -- its latent pass or latent-cache append, its vocoder windows, its `last`
+                # event -- is launched inside _emit_boundary, BEFORE `loops` is resumed: with a voice pool the refill loop keeps a
+                # stopped row's voices pinned until that resumption (GPTEngine.attach_lora_pool) and relies on exactly this order.
+                # Work for a stopped row that moves behind the next next(loops) needs a pin of its own.
                 yield from IndexTTS._emit_boundary(self, st, recs)
                 arrivals()
         finally:
@@ -1617,8 +1669,12 @@ class IndexTTS:
             squeezed.append(cc[0, : int(ln[0])].cpu())
         outs: List[torch.Tensor | None] = [None] * N
         order = sorted(range(N), key=lambda i: int(squeezed[i].numel()))
-        for k in range(0, N, slots):
+        k = 0
+        while k < N:
             ids = order[k: k + slots]
+            if voice_kind is not None:      # a voice pool: a group names no more distinct voices than the bank has slots
+                ids = ids[: max(1, self.gpt.engine.batch_fit([reqs[i]["voice"] for i in ids]))]
+            k += len(ids)
             sel = torch.tensor(ids, device=conds.device) if per_row else None
             lat = self._latents(conds[sel] if per_row else conds, [texts[i] for i in ids], [squeezed[i] for i in ids], **voiced(ids))
             for i, w in zip(ids, self._vocode_ragged(lat, spk[sel] if per_row else spk)):
