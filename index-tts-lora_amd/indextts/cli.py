@@ -3,8 +3,59 @@ import os
 import sys
 
 
+def extract_voice_main(argv):
+    """`indextts --extract-voice CKPT --voice-out FILE [--voice-max-rank R]`: recover the LoRA voice a merged fine-tuned checkpoint
+    holds against this model's base weights (IndexTTS.voice_from_checkpoint) and save it (IndexTTS.save_voice).  A command of its
+    own with its own arguments: the synthesis command line below is what it was."""
+    import argparse
+    parser = argparse.ArgumentParser(prog="indextts --extract-voice", description="IndexTTS: a voice file from a merged fine-tuned checkpoint")
+    parser.add_argument("--extract-voice", type=str, required=True, metavar="CKPT", help="merged fine-tuned checkpoint (gpt_finetuned.pth)")
+    parser.add_argument("--voice-out", type=str, required=True, metavar="FILE", help="the voice file to write (IndexTTS.load_voice reads it)")
+    parser.add_argument("--voice-max-rank", type=int, default=16, metavar="R", help="the largest LoRA rank looked for (1..64)")
+    parser.add_argument("-c", "--config", type=str, default="checkpoints/config.yaml", help="config file")
+    parser.add_argument("--model_dir", type=str, default="checkpoints", help="model directory (holds the base gpt.pth)")
+    parser.add_argument("--fp16", action="store_true", default=True, help="half-precision GPT weights when available")
+    parser.add_argument("-f", "--force", action="store_true", default=False, help="overwrite the voice file")
+    parser.add_argument("-d", "--device", type=str, default=None, help="device (cuda:N); CPU/MPS are not supported")
+    args = parser.parse_args(argv)
+
+    def fail(msg):
+        print(f"[error] {msg}")
+        parser.print_help()
+        sys.exit(1)
+
+    if not os.path.exists(args.extract_voice):
+        fail(f"checkpoint {args.extract_voice} does not exist")
+    if not 1 <= args.voice_max_rank <= 64:
+        fail("--voice-max-rank must lie in [1, 64]")
+    if not os.path.exists(args.config):
+        fail(f"config {args.config} does not exist")
+    if os.path.exists(args.voice_out) and not args.force:
+        fail(f"voice file {args.voice_out} exists; use --force to overwrite")
+    import torch
+    if args.device is None:
+        if not torch.cuda.is_available():
+            print("[error] no GPU visible: this build needs an AMD GPU (no CPU path)")
+            sys.exit(1)
+        args.device = "cuda:0"
+    from indextts.infer import IndexTTS
+    tts = IndexTTS(cfg_path=args.config, model_dir=args.model_dir, is_fp16=args.fp16, device=args.device)
+    try:
+        adapters, scaling, report = tts.voice_from_checkpoint(args.extract_voice, max_rank=args.voice_max_rank, return_report=True)
+    except ValueError as e:
+        print(f"[error] {e}")
+        sys.exit(1)
+    for key, rep in report.items():
+        print(f">> {key}: rank {rep['r']}, sigma_r {rep['sigma_r']:.4g}, sigma_r+1 {rep['sigma_next']:.4g}, ratio {rep['ratio']:.4g}")
+    tts.save_voice(args.voice_out, adapters, scaling)
+    print(f">> [voice] {len(adapters)} targets saved to: {args.voice_out}")
+
+
 def main(argv=None):
     import argparse
+    argv = sys.argv[1:] if argv is None else list(argv)
+    if any(a == "--extract-voice" or a.startswith("--extract-voice=") for a in argv):
+        return extract_voice_main(argv)
     parser = argparse.ArgumentParser(description="IndexTTS command line (MI355X build)")
     parser.add_argument("text", type=str, help="text to synthesise")
     parser.add_argument("-v", "--voice", type=str, required=True, help="reference (prompt) audio file, wav")

@@ -410,6 +410,18 @@ class GPTEngine:
         self.lora = False
         self._graphs.clear()
 
+    def extract_lora(self, tuned_state_dict: dict, max_rank: int = 16, gap: float = 8.0, seed: int = 0, ignore_other: bool = False):
+        """The LoRA a MERGED fine-tuned checkpoint of this engine's base holds (what train.py saves: merge_and_unload(), fp16), as
+        (adapters, 1.0, report): adapters in the attach_lora format -- what attach_lora_bank, VoicePool.add and add_voice take --
+        and per target the rank found, sigma_r, sigma_{r+1} and their ratio.  The base is this engine's own checkpoint; the
+        difference is reached only through ittv_delta_project launches (gpt/voice_extract.py).  ValueError
+        before any launch: a shape mismatch, tensors outside the 4 x layers targets that differ (ignore_other=True overrides); and
+        per target: no singular-value ratio of at least `gap`, or a rank above max_rank -- a full fine-tune, or the wrong base.  A
+        target that did not change names no adapter.  Nothing of the engine changes."""
+        from indextts.gpt import voice_extract
+        return voice_extract.extract(self._W, tuned_state_dict, self.L, voice_extract.DeviceDelta(self.device), max_rank=max_rank,
+                                     gap=gap, seed=seed, ignore_other=ignore_other)
+
     # ------------------------------------------------------------------------------------------------ adapter bank
     BANK_TARGETS = (("attn.c_attn", "w_qkv"), ("attn.c_proj", "w_o"), ("mlp.c_fc", "w_fc"), ("mlp.c_proj", "w_pr"))
 

@@ -587,6 +587,38 @@ class IndexTTS:
         """The voice leaves the pool (its id is never reused); ValueError while a batch or a queued utterance speaks with it."""
         self._voice_pool("remove_voice").remove(int(voice))
 
+    # ------------------------------------------------------------------------------------------------ voices from checkpoints
+    def voice_from_checkpoint(self, path_or_state_dict, return_report: bool = False, **kw):
+        """(adapters, scaling) of the LoRA voice a MERGED fine-tuned checkpoint holds -- the one artifact the reference's train.py
+        produces (gpt_finetuned.pth) -- against this instance's GPT weights as the base: GPTEngine.extract_lora (DESIGN.md section
+        4.21).  A path goes through the checkpoint loader of utils/checkpoint.py; a state dict may be bare or wrapped as
+        {'model': sd}.  kw: max_rank (16), gap (8.0), seed (0), ignore_other (False).  return_report: (adapters, scaling, report)
+        with the rank and singular-value gap found per target.  ValueError for what is not a LoRA of this base."""
+        from indextts.utils.checkpoint import _safe_load
+        sd = _safe_load(path_or_state_dict) if isinstance(path_or_state_dict, (str, os.PathLike)) else path_or_state_dict
+        adapters, scaling, report = self.gpt.engine.extract_lora(sd, **kw)     # (which takes the {'model': sd} wrapper off)
+        return (adapters, scaling, report) if return_report else (adapters, scaling)
+
+    def add_voice_from_checkpoint(self, path, **kw) -> int:
+        """add_voice of voice_from_checkpoint(path, **kw): a merged fine-tuned checkpoint becomes a voice of the attached pool.
+        Returns its id.  kw: max_rank, gap, seed, ignore_other (the report is voice_from_checkpoint's to return)."""
+        self._voice_pool("add_voice_from_checkpoint")
+        if "return_report" in kw:
+            raise TypeError("add_voice_from_checkpoint() returns the pool id: ask voice_from_checkpoint(return_report=True) for the report")
+        return self.add_voice(*self.voice_from_checkpoint(path, **kw))
+
+    @staticmethod
+    def save_voice(path, adapters, scaling):
+        """A voice (adapters in the attach_lora format, scaling) as a file of tensors and a float only."""
+        from indextts.gpt.voice_extract import save_voice
+        save_voice(path, adapters, scaling)
+
+    @staticmethod
+    def load_voice(path):
+        """(adapters, scaling) of a save_voice file, read with the weights-only unpickler."""
+        from indextts.gpt.voice_extract import load_voice
+        return load_voice(path)
+
     def detach_voice_pool(self):
         self._voice_pool("detach_voice_pool")
         self.gpt.engine.detach_lora_bank()
