@@ -83,7 +83,7 @@ def _inside(path: str, roots) -> bool:
 
 def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/config.yaml", device=None, use_fp16=True,
                finetune_dir=os.path.join("finetune_models", "checkpoints"), output_dir=os.path.join("outputs", "api"),
-               prompt_dir="prompts", stream_slots=None, stream_latent_cache=False):
+               prompt_dir="prompts", stream_slots=None, stream_latent_cache=False, prompt_frontend="torch"):
     """`tts`: a ready IndexTTS (tests, embedding) or None to build one from model_dir / config_path on first use.
     stream_slots = S (off by default): /tts/stream requests are served by ONE worker that owns a refilled streaming loop of S
     decode slots (IndexTTS.serve_stream_queue): a request that arrives while the loop runs enters it, a request that finds no
@@ -106,7 +106,8 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
         if state["tts"] is None:
             if not os.path.exists(model_dir):
                 raise HTTPException(status_code=503, detail=f"model directory {model_dir} does not exist")
-            state["tts"] = IndexTTS(model_dir=model_dir, cfg_path=config_path, device=device, is_fp16=use_fp16)
+            state["tts"] = IndexTTS(model_dir=model_dir, cfg_path=config_path, device=device, is_fp16=use_fp16,
+                                    prompt_frontend=prompt_frontend)
         return state["tts"]
 
     app.state.engine = engine
@@ -368,7 +369,10 @@ if __name__ == "__main__":
     ap.add_argument("--stream-latent-cache", action="store_true", default=False,
                     help="/tts/stream keeps the latent pass's keys and values between chunks (IndexTTS.infer_stream(latent_cache=True)): "
                          "a chunk boundary then costs its new rows only.  Off by default")
+    ap.add_argument("--prompt-frontend", choices=("torch", "hip"), default="torch",
+                    help="where a prompt's wav becomes its log-mel: torch (host ops, the default) or hip (the device front-end, "
+                         "IndexTTS(prompt_frontend='hip'))")
     a = ap.parse_args()
     import uvicorn
     uvicorn.run(create_app(None, a.model_dir, a.config, a.device, not a.no_fp16, prompt_dir=a.prompt_dir, stream_slots=a.stream_slots,
-                           stream_latent_cache=a.stream_latent_cache), host=a.host, port=a.port)
+                           stream_latent_cache=a.stream_latent_cache, prompt_frontend=a.prompt_frontend), host=a.host, port=a.port)

@@ -78,6 +78,9 @@ def main(argv=None):
     parser.add_argument("--stream-latent-cache", action="store_true", default=False,
                         help="with --stream: keep the latent pass's keys and values between chunks (IndexTTS.infer_stream("
                              "latent_cache=True)): a chunk boundary then costs its new rows only")
+    parser.add_argument("--prompt-frontend", choices=("torch", "hip"), default="torch",
+                        help="where the prompt's wav becomes its log-mel: torch (host ops, the default) or hip (the device "
+                             "front-end, IndexTTS(prompt_frontend='hip'))")
     parser.add_argument("-d", "--device", type=str, default=None, help="device (cuda:N); CPU/MPS are not supported")
     args = parser.parse_args(argv)
 
@@ -111,7 +114,8 @@ def main(argv=None):
             sys.exit(1)
         args.device = "cuda:0"
     from indextts.infer import IndexTTS
-    tts = IndexTTS(cfg_path=args.config, model_dir=args.model_dir, is_fp16=args.fp16, device=args.device)
+    tts = IndexTTS(cfg_path=args.config, model_dir=args.model_dir, is_fp16=args.fp16, device=args.device,
+                   prompt_frontend=args.prompt_frontend)
     if args.stream:
         from indextts.utils.audio import write_pcm16
         rate, chunks = 24000, []

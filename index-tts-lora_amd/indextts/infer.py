@@ -26,6 +26,7 @@ from indextts import _native as nat
 from indextts.BigVGAN.models import BigVGAN as Generator
 from indextts.gpt.model import UnifiedVoice, row_sampling_params, sampling_params
 from indextts.utils.audio import read_audio, write_pcm16
+from indextts.utils.audio_engine import PromptAudioEngine, as_planar, refusal
 from indextts.utils.checkpoint import load_checkpoint
 from indextts.utils.config import Config, load_config
 from indextts.utils.feature_extractors import MelSpectrogramFeatures, resample
@@ -146,12 +147,14 @@ class _StreamState:
 class IndexTTS:
     def __init__(self, cfg_path="checkpoints/config.yaml", model_dir="checkpoints", is_fp16=True, device=None,
                  use_cuda_kernel=None, speaker_info_path=None, precision_config=None, gpt_path=None,
-                 _weights=None, _cfg=None):
+                 prompt_frontend="torch", _weights=None, _cfg=None):
         if device is None:
             device = "cuda:0" if torch.cuda.is_available() else "cpu"
         if not str(device).startswith("cuda") or not torch.cuda.is_available():
             raise RuntimeError("this build of IndexTTS runs on an AMD GPU through libindextts_hip.so; "
                                f"device={device!r} is not supported (there is no CPU fallback)")
+        if prompt_frontend not in ("torch", "hip"):
+            raise ValueError(f"prompt_frontend must be 'torch' or 'hip' (got {prompt_frontend!r})")
         self.device = device
         self.is_fp16 = is_fp16
         self.use_cuda_kernel = True  # the fused HIP activation kernel is always used
@@ -249,6 +252,10 @@ class IndexTTS:
             except Exception as e:  # noqa: BLE001
                 print(f">> [error] could not read speaker info: {e}")
         self.mel_extractor = MelSpectrogramFeatures()
+        # "hip": wav -> log-mel on the device (utils/audio_engine.py); "torch" (default): the host ops above
+        self.prompt_frontend = prompt_frontend
+        self.audio_engine = PromptAudioEngine(self.device) if prompt_frontend == "hip" else None
+        self._frontend_warned = False
 
     # `tts.gpt` is replaceable, as the reference's callers do when they hot-swap a fine-tuned checkpoint (api.py:118-175,
     # webui.py:107-160: build UnifiedVoice(**tts.cfg.gpt), load_checkpoint, .to / .eval / .half, post_init_gpt2_config, then
@@ -284,10 +291,11 @@ class IndexTTS:
         return info
 
     @classmethod
-    def from_weights(cls, cfg, gpt_state_dict, bigvgan_state_dict, device="cuda:0", is_fp16=True, precision_config=None):
+    def from_weights(cls, cfg, gpt_state_dict, bigvgan_state_dict, device="cuda:0", is_fp16=True, precision_config=None,
+                     prompt_frontend="torch"):
         """Build from in-memory state dicts in the reference checkpoint key format (offline / synthetic weights)."""
         cfg = cfg if isinstance(cfg, Config) else Config(cfg)
-        return cls(model_dir="", is_fp16=is_fp16, device=device, precision_config=precision_config, _cfg=cfg,
+        return cls(model_dir="", is_fp16=is_fp16, device=device, precision_config=precision_config, prompt_frontend=prompt_frontend, _cfg=cfg,
                    _weights={"gpt": gpt_state_dict, "bigvgan": bigvgan_state_dict})
 
     def replica(self) -> "IndexTTS":
@@ -409,14 +417,67 @@ class IndexTTS:
     def _prompt(self, audio_prompt):
         """infer.py:789-800: mono mean -> 24 kHz -> log-mel, cached by path; plus (new) cached conditioner outputs."""
         if self.cache_cond_mel is None or self.cache_audio_prompt != audio_prompt:
-            audio, sr = read_audio(audio_prompt)
-            audio = torch.from_numpy(audio.T if audio.ndim > 1 else audio.reshape(1, -1)).float()
-            audio = torch.mean(audio, dim=0, keepdim=True)
-            audio = resample(audio, sr, 24000)
-            self.cache_cond_mel = self.mel_extractor(audio).to(self.device)
+            self.cache_cond_mel = self._mels([self._decode(audio_prompt)])[0]
             self.cache_audio_prompt = audio_prompt
             self._cache_conds = self._cache_spk = None
         return self.cache_cond_mel
+
+    @staticmethod
+    def _decode(path):
+        """A file -> (planar fp32 [C, N] on the host, its sample rate)."""
+        audio, sr = read_audio(path)
+        return torch.from_numpy(audio.T if audio.ndim > 1 else audio.reshape(1, -1)).float(), sr
+
+    def _mel_torch(self, planar, sr):
+        """The host front-end: mono mean -> 24 kHz -> log-mel in torch ops, then the upload."""
+        audio = torch.mean(planar, dim=0, keepdim=True)
+        audio = resample(audio, sr, 24000)
+        return self.mel_extractor(audio).to(self.device)
+
+    def _mels(self, decoded):
+        """[(planar [C, N], sr), ..] -> their mels [1, 100, T_i] on the device.  prompt_frontend "hip": one pass of the audio
+        engine over all of them; what the engine refuses (a rate whose tap table is too large, more than 8 channels, too few
+        samples to reflect) goes through the torch path, with one warning per instance."""
+        if self.audio_engine is None:
+            return [self._mel_torch(p, sr) for p, sr in decoded]
+        mels, take = [None] * len(decoded), []
+        for i, (p, sr) in enumerate(decoded):
+            why = refusal(tuple(p.shape), sr)
+            if why is None:
+                take.append(i)
+                continue
+            if not self._frontend_warned:
+                self._frontend_warned = True
+                warnings.warn(f"prompt_frontend='hip': {why}; such prompts go through the torch front-end", RuntimeWarning)
+            mels[i] = self._mel_torch(p, sr)
+        if take:
+            for i, m in zip(take, self.audio_engine.mel([decoded[i][0] for i in take], [decoded[i][1] for i in take])):
+                mels[i] = m
+        return mels
+
+    def prompt_mel(self, audio, sr=None):
+        """The prompt mel [1, 100, T] (fp32, on the device) of a reference audio: what infer_batch, infer_queue, stream_batch,
+        stream_queue and `more` take as cond_mel.  audio: a path, or an array / tensor [N] or [C, N] of decoded samples with its
+        sample rate `sr`.  Runs the front-end this instance was built with (prompt_frontend); not cached."""
+        return self.prompt_mels([audio], None if sr is None else [sr])[0]
+
+    def prompt_mels(self, audios, srs=None):
+        """prompt_mel of every entry of a list, in ONE pass of the audio engine under prompt_frontend="hip" (any rates, channel
+        counts and lengths; every mel bit-equal to prompt_mel of that entry alone).  An entry is a path, an (array, sr) pair, or
+        an array / tensor whose rate srs[i] gives."""
+        decoded = []
+        for i, a in enumerate(audios):
+            if isinstance(a, (str, os.PathLike)):
+                decoded.append(self._decode(a))
+                continue
+            if isinstance(a, tuple) and len(a) == 2:
+                a, sr = a
+            else:
+                sr = None if srs is None else srs[i]
+            if sr is None:
+                raise ValueError("prompt_mel: decoded samples need their sample rate (sr)")
+            decoded.append((as_planar(a), int(sr)))
+        return self._mels(decoded)
 
     MAX_FEATURE_GRAPHS = 64     # (network, prompt shape) pairs kept captured: ~30 MB of activations + a graph each
 
