@@ -7,6 +7,8 @@ working:
     GET  /models          {"models": [{name, filename, type}], "current_model": ...}          (api.py:97-116)
     POST /model/reload    {"model_filename": ...} -> hot-swaps tts.gpt (404 when the file is missing)  (api.py:118-175)
     POST /tts/stream      /tts's request (not in the reference) -> chunked audio/L16; rate=24000 while the token loop runs, header X-Seed
+                          (with the form fields sample_rate / encoding: audio/L16 | audio/PCMU | audio/PCMA | audio/L32F; rate=R,
+                          resampled and encoded on the device; /tts takes the same fields and tags its WAV accordingly)
                           (--stream-slots S / create_app(stream_slots=S): all such requests share one refilled loop of S slots)
     POST /tts             text + prompt_audio (upload) | prompt_audio_path, infer_mode fast|normal, speaker_id, seed and the
                           generation knobs -> audio/wav, header X-Seed; 400 without a prompt, 404 for a missing prompt path,
@@ -51,6 +53,24 @@ class TTSRequest(BaseModel):
     repetition_penalty: float = 10.0
     length_penalty: float = 0.0
     max_mel_tokens: int = 600
+    sample_rate: Optional[int] = None      # None: 24000, the vocoder's rate
+    encoding: Optional[str] = None         # None: pcm16; f32 | mulaw | alaw (IndexTTS.output_format)
+
+
+def output_of(req):
+    """The OutputFormat a request names with sample_rate / encoding (None when it names neither: the answer is what it has
+    always been); a value the device back-end does not produce is a 400."""
+    if req.sample_rate is None and req.encoding is None:
+        return None
+    from indextts.utils.pcm_out import OutputFormat
+    try:
+        return OutputFormat(24000 if req.sample_rate is None else req.sample_rate, req.encoding or "pcm16")
+    except ValueError as e:
+        raise HTTPException(status_code=400, detail=str(e))
+
+
+def chunk_bytes(pcm, fmt):
+    return pcm.float().cpu().numpy().astype("<i2").tobytes() if fmt is None else fmt.to_bytes(pcm)
 
 
 class ModelReloadRequest(BaseModel):
@@ -153,12 +173,15 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
 
         def __init__(self):
             self.mutex, self.inbox, self.running, self.jobs, self.count = threading.Lock(), [], False, {}, 0
+            self.outs = {}       # handle -> [its OutputFormat, its PcmOutStream once its first chunk has come]
 
-        def submit(self, request, chunks, done):
+        def submit(self, request, chunks, done, fmt=None):
             with self.mutex:
                 self.count += 1
                 self.inbox.append(dict(request, handle=self.count))
                 self.jobs[self.count] = (chunks, done)
+                if fmt is not None:
+                    self.outs[self.count] = [fmt, None]
                 start, self.running = not self.running, True
             if start:
                 threading.Thread(target=self.work, name="tts-stream-queue", daemon=True).start()
@@ -170,6 +193,7 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
 
         def finish(self, handle, end):
             chunks, done = self.jobs.pop(handle)
+            self.outs.pop(handle, None)
             chunks.put(end)
             done()
 
@@ -182,8 +206,13 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
                             if isinstance(pcm, BaseException):
                                 self.finish(handle, pcm)
                                 continue
+                            out = self.outs.get(handle)
+                            if out is not None:      # this request's own format: its resampler state lives as long as it does
+                                if out[1] is None:
+                                    out[1] = engine()._out_engine().stream(out[0])
+                                pcm = out[1].push(pcm.float(), last)
                             if pcm.numel():
-                                self.jobs[handle][0].put(pcm.float().cpu().numpy().astype("<i2").tobytes())
+                                self.jobs[handle][0].put(chunk_bytes(pcm, None if out is None else out[0]))
                             if last:
                                 self.finish(handle, None)
                 except Exception as e:  # noqa: BLE001  (the loop itself failed: every request it had taken is told)
@@ -214,7 +243,7 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
                     upload = up
             else:
                 fields = {k: v[-1] for k, v in urllib.parse.parse_qs(body.decode("utf-8")).items()}
-            fields = {k: (None if isinstance(v, str) and v == "" and k in ("seed", "speaker_id", "prompt_audio_path") else v)
+            fields = {k: (None if isinstance(v, str) and v == "" and k in ("seed", "speaker_id", "prompt_audio_path", "sample_rate", "encoding") else v)
                       for k, v in fields.items()}
             return TTSRequest(**fields), upload
         except HTTPException:
@@ -229,6 +258,7 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
             raise HTTPException(status_code=503, detail="the TTS engine is not initialised")
         if upload is None and not req.prompt_audio_path:
             raise HTTPException(status_code=400, detail="a reference audio is required (upload a file or give a path)")
+        fmt = output_of(req)
         actual_seed = random.randint(0, 2 ** 32 - 1) if req.seed is None or req.seed == -1 else int(req.seed)
         tmp_path = None
         try:
@@ -249,6 +279,8 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
             kwargs = dict(do_sample=req.do_sample, top_p=req.top_p, top_k=req.top_k if req.top_k > 0 else 30,
                           temperature=req.temperature, repetition_penalty=req.repetition_penalty,
                           length_penalty=req.length_penalty, num_beams=3, max_mel_tokens=req.max_mel_tokens)
+            if fmt is not None:
+                kwargs["output"] = fmt
             with lock:
                 t = engine()
                 set_seed(actual_seed)
@@ -290,6 +322,7 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
             raise HTTPException(status_code=503, detail="the TTS engine is not initialised")
         if upload is None and not req.prompt_audio_path:
             raise HTTPException(status_code=400, detail="a reference audio is required (upload a file or give a path)")
+        fmt = output_of(req)
         actual_seed = random.randint(0, 2 ** 32 - 1) if req.seed is None or req.seed == -1 else int(req.seed)
         tmp_path = None
         if upload is not None:
@@ -315,15 +348,16 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
 
         if stream_slots is not None:
             shared_loop.submit(dict(kwargs, audio_prompt=prompt, text=req.text,
-                                    max_text_tokens_per_sentence=req.max_text_tokens_per_sentence), chunks, clean_up)
-            return await respond(chunks, actual_seed)
+                                    max_text_tokens_per_sentence=req.max_text_tokens_per_sentence), chunks, clean_up, fmt)
+            return await respond(chunks, actual_seed, fmt)
 
         def work():
             import torch
             try:
                 with lock, torch.no_grad():
-                    for _, pcm in engine().infer_stream(prompt, req.text, req.max_text_tokens_per_sentence, **kwargs, **latent_kw):
-                        chunks.put(pcm.float().cpu().numpy().astype("<i2").tobytes())
+                    for _, pcm in engine().infer_stream(prompt, req.text, req.max_text_tokens_per_sentence, **kwargs, **latent_kw,
+                                                        **({} if fmt is None else {"output": fmt})):
+                        chunks.put(chunk_bytes(pcm, fmt))
                 chunks.put(None)
             except BaseException as e:  # noqa: BLE001  (handed to the response, which answers or ends the body)
                 chunks.put(e)
@@ -332,9 +366,9 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
                     os.remove(tmp_path)
 
         threading.Thread(target=work, name="tts-stream", daemon=True).start()
-        return await respond(chunks, actual_seed)
+        return await respond(chunks, actual_seed, fmt)
 
-    async def respond(chunks, actual_seed):
+    async def respond(chunks, actual_seed, fmt=None):
         """The chunked answer over a queue of bytes that ends with None or an exception; the first item is awaited first."""
         first = await run_in_threadpool(chunks.get)
         if isinstance(first, HTTPException):
@@ -348,7 +382,10 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
                 yield item
                 item = chunks.get()
 
-        return StreamingResponse(body(), media_type="audio/L16; rate=24000", headers={"X-Seed": str(actual_seed)})
+        if fmt is None:
+            return StreamingResponse(body(), media_type="audio/L16; rate=24000", headers={"X-Seed": str(actual_seed)})
+        return StreamingResponse(body(), media_type=fmt.content_type, headers={
+            "X-Seed": str(actual_seed), "X-Sample-Rate": str(fmt.sample_rate), "X-Encoding": fmt.encoding})
 
     return app
 

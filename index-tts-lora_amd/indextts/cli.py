@@ -81,6 +81,11 @@ def main(argv=None):
     parser.add_argument("--prompt-frontend", choices=("torch", "hip"), default="torch",
                         help="where the prompt's wav becomes its log-mel: torch (host ops, the default) or hip (the device "
                              "front-end, IndexTTS(prompt_frontend='hip'))")
+    parser.add_argument("--sample-rate", type=int, default=None, metavar="HZ",
+                        help="sample rate of the output file (8000, 16000, 44100, 48000, ...; resampled on the device, "
+                             "IndexTTS.output_format).  Default: 24000, the vocoder's")
+    parser.add_argument("--encoding", choices=("pcm16", "f32", "mulaw", "alaw"), default=None,
+                        help="sample encoding of the output file: 16-bit PCM (the default), IEEE float, or G.711 mu-law / A-law")
     parser.add_argument("-d", "--device", type=str, default=None, help="device (cuda:N); CPU/MPS are not supported")
     args = parser.parse_args(argv)
 
@@ -89,6 +94,13 @@ def main(argv=None):
         parser.print_help()
         sys.exit(1)
 
+    output = None
+    if args.sample_rate is not None or args.encoding is not None:
+        from indextts.utils.pcm_out import OutputFormat
+        try:
+            output = OutputFormat(24000 if args.sample_rate is None else args.sample_rate, args.encoding or "pcm16")
+        except ValueError as e:
+            fail(str(e))
     if len(args.text.strip()) == 0:
         fail("text is empty")
     if args.stream_parallel < 1:
@@ -121,15 +133,22 @@ def main(argv=None):
         rate, chunks = 24000, []
         for rate, pcm in tts.infer_stream(audio_prompt=args.voice, text=args.text.strip(), parallel_sentences=args.stream_parallel,
                                             **({} if args.stream_slots is None else {"slots": args.stream_slots}),
-                                            **({"latent_cache": True} if args.stream_latent_cache else {})):
+                                            **({"latent_cache": True} if args.stream_latent_cache else {}),
+                                            **({} if output is None else {"output": output})):
             chunks.append(pcm.cpu())
         if os.path.dirname(args.output_path) != "":
             os.makedirs(os.path.dirname(args.output_path), exist_ok=True)
+        if output is not None:
+            from indextts.utils.audio import write_wav
+            wav = torch.cat(chunks) if chunks else torch.zeros(0, dtype=output.dtype)
+            write_wav(args.output_path, wav.numpy(), output.sample_rate, output.encoding)
+            print(f">> [output] saved to: {args.output_path}")
+            return
         wav = torch.cat(chunks) if chunks else torch.zeros(0)
         write_pcm16(args.output_path, wav.to(torch.float32).numpy().astype("int16"), rate)
         print(f">> [output] saved to: {args.output_path}")
         return
-    tts.infer(audio_prompt=args.voice, text=args.text.strip(), output_path=args.output_path)
+    tts.infer(audio_prompt=args.voice, text=args.text.strip(), output_path=args.output_path, **({} if output is None else {"output": output}))
 
 
 if __name__ == "__main__":

@@ -25,7 +25,8 @@ import torch
 from indextts import _native as nat
 from indextts.BigVGAN.models import BigVGAN as Generator
 from indextts.gpt.model import UnifiedVoice, row_sampling_params, sampling_params
-from indextts.utils.audio import read_audio, write_pcm16
+from indextts.utils.audio import read_audio, write_pcm16, write_wav
+from indextts.utils.pcm_out import OutputFormat, PcmOutEngine
 from indextts.utils.audio_engine import PromptAudioEngine, as_planar, refusal
 from indextts.utils.checkpoint import load_checkpoint
 from indextts.utils.config import Config, load_config
@@ -137,11 +138,34 @@ class _StreamState:
     stream's _trace (or None), its "frames" / "latent" / "window" / "codes" indexed by an utterance's handle; latent: which pass
     a boundary runs -- "reuse" (repeated, over the prompt K / V the prefill left in the decode cache: _latents(reuse_prefix=True,
     cache_rows=...)), "whole" (repeated, the whole sequence) or a _LatentRows (incremental); warn: the words for a row that
-    reaches max_mel_tokens, `{}` = its handle (None: nothing is said)."""
+    reaches max_mel_tokens, `{}` = its handle (None: nothing is said); out: a _StreamOut (the events carry the samples in its
+    format) or None (fp32 at 24 kHz, as the vocoder leaves them)."""
 
-    def __init__(self, halo, stop, max_mel_tokens, voice_kind, trace, latent, warn=None):
+    def __init__(self, halo, stop, max_mel_tokens, voice_kind, trace, latent, warn=None, out=None):
         self.emitted, (self.left, self.right), self.stop, self.max_mel_tokens = {}, halo, stop, max_mel_tokens
-        self.voice_kind, self.trace, self.latent, self.warn = voice_kind, trace, latent, warn
+        self.voice_kind, self.trace, self.latent, self.warn, self.out = voice_kind, trace, latent, warn, out
+
+
+class _StreamOut:
+    """The output side of a stream whose caller named an OutputFormat: the PcmOutEngine, the format, and a PcmOutStream per
+    utterance that has not had its last event (its carried filter tail, on the device)."""
+
+    def __init__(self, engine, fmt):
+        self.engine, self.fmt, self.streams = engine, fmt, {}
+
+    def encode(self, rows):
+        """rows: [(utterance key, fp32 pcm, last)] of ONE boundary -> their samples in the format, in one launch."""
+        items = []
+        for u, pcm, last in rows:
+            s = self.streams.get(u)
+            if s is None:
+                s = self.streams[u] = self.engine.stream(self.fmt)
+            items.append((s, pcm.to(torch.float32), last))
+        outs = self.engine.push_many(items)
+        for u, _, last in rows:
+            if last:
+                del self.streams[u]
+        return outs
 
 
 class IndexTTS:
@@ -827,7 +851,31 @@ class IndexTTS:
                 st.fed[r] = cl[i]
         return [st.lat[r][:k] for r, k in zip(rows, cl)]
 
-    def _finish(self, wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, sampling_rate=24000):
+    # ------------------------------------------------------------------------------------------------ output formats
+    def output_format(self, sample_rate=24000, encoding="pcm16") -> OutputFormat:
+        """The value the `output=` keyword of the synthesis calls takes: the samples at `sample_rate` (any rate
+        libindextts_out.so has a table for: 8000, 16000, 44100, 48000, ...) as "pcm16", "f32", "mulaw" or "alaw" (G.711), produced
+        on the device (indextts/utils/pcm_out.py).  output=None, the default of every call, is what the calls have always
+        returned: fp32 at 24 kHz in the int16 range (PCM16 in a file)."""
+        return OutputFormat(sample_rate, encoding)
+
+    @staticmethod
+    def _check_output(output, who):
+        if output is not None and not isinstance(output, OutputFormat):
+            raise TypeError(f"{who}: output is an OutputFormat (IndexTTS.output_format(sample_rate, encoding)) or None")
+        return output
+
+    def _out_engine(self) -> PcmOutEngine:
+        eng = getattr(self, "_pcm_out", None)
+        if eng is None:
+            eng = self._pcm_out = PcmOutEngine(self.device)
+        return eng
+
+    def _encode_rows(self, wavs, output):
+        """Whole utterances (fp32 device tensors at 24 kHz) in the format `output`: one launch for all of them."""
+        return self._out_engine().encode([w.reshape(-1).to(torch.float32) for w in wavs], output)
+
+    def _finish(self, wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, sampling_rate=24000, output=None):
         end_time = time.perf_counter()
         wav = torch.cat(wavs, dim=1)
         wav_length = wav.shape[-1] / sampling_rate
@@ -835,6 +883,15 @@ class IndexTTS:
         print(f"   - GPT generation: {gpt_gen_time:.2f}s")
         print(f"   - GPT forward: {gpt_forward_time:.2f}s")
         print(f"   - vocoder: {bigvgan_time:.2f}s")
+        if output is not None:      # the sentences were joined at 24 kHz above: one encode, no filter transient at a join
+            arr = self._encode_rows([wav], output)[0].cpu().numpy()
+            if output_path:
+                if os.path.dirname(output_path) != "":
+                    os.makedirs(os.path.dirname(output_path), exist_ok=True)
+                write_wav(output_path, arr, output.sample_rate, output.encoding)
+                print(f">> [output] saved to: {output_path}")
+                return output_path
+            return (output.sample_rate, arr)
         wav = wav.cpu()
         if output_path:
             if os.path.isfile(output_path):
@@ -910,8 +967,11 @@ class IndexTTS:
 
     # ------------------------------------------------------------------------------------------------ public API
     def infer(self, audio_prompt, text, output_path, verbose=False, max_text_tokens_per_sentence=120, speaker_id=None,
-              **generation_kwargs):
-        """Sentence-by-sentence synthesis (infer.py:779-917)."""
+              *, output=None, **generation_kwargs):
+        """Sentence-by-sentence synthesis (infer.py:779-917).  output (an OutputFormat; None = 24 kHz PCM16 as ever): the
+        sentences are joined at 24 kHz on the device and encoded once; with an output_path the WAV carries the format's tag,
+        without one the call returns (rate, array in the encoding)."""
+        IndexTTS._check_output(output, "infer")
         if speaker_id is not None:
             if not self.speaker_list:
                 raise ValueError("multi-speaker mode is not enabled; load speaker_info_path first")
@@ -948,14 +1008,15 @@ class IndexTTS:
             wav = self._vocode(latent, spk)
             torch.cuda.synchronize()
             bigvgan_time += time.perf_counter() - t0
-            wavs.append(wav.cpu())
+            wavs.append(wav.cpu() if output is None else wav)
         self._set_gr_progress(0.9, "saving audio...")
-        return self._finish(wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time)
+        return self._finish(wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, output=output)
 
     def infer_fast(self, audio_prompt, text, output_path, verbose=False, max_text_tokens_per_sentence=100,
-                   sentences_bucket_max_size=4, **generation_kwargs):
+                   sentences_bucket_max_size=4, *, output=None, **generation_kwargs):
         """Bucketed batch synthesis (infer.py:595-777): sentences of similar length are decoded as one left-padded batch;
-        latents are computed in one batched pass and vocoded in time-concatenated pairs (chunk_size 2)."""
+        latents are computed in one batched pass and vocoded in time-concatenated pairs (chunk_size 2).  output: as in infer."""
+        IndexTTS._check_output(output, "infer_fast")
         print(">> [infer] fast mode")
         self._set_gr_progress(0, "initialising...")
         start_time = time.perf_counter()
@@ -1002,14 +1063,14 @@ class IndexTTS:
             wav = self._vocode(torch.cat(lat[i:i + 2], dim=0)[None], spk)
             torch.cuda.synchronize()
             bigvgan_time += time.perf_counter() - t0
-            wavs.append(wav.cpu())
+            wavs.append(wav.cpu() if output is None else wav)
         self.torch_empty_cache()
         self._set_gr_progress(0.9, "saving audio...")
-        return self._finish(wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time)
+        return self._finish(wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, output=output)
 
     def infer_batch(self, cond_mel: torch.Tensor, text_token_rows: List[torch.Tensor], max_mel_tokens=600, force_stop=None,
                     seed=1234, return_codes=False, phase_events: dict | None = None, adapter_ids=None, sampling=None,
-                    adapter_mix=None, **generation_kwargs):
+                    adapter_mix=None, *, output=None, **generation_kwargs):
         """Utterance-batch data path used by bench.py / the multi-GPU sharder (not in the reference API): one shared
         prompt, N independent texts decoded as ONE left-padded batch, one batched latent pass, and one vocoder call per
         group of equal-length utterances (batching unequal lengths would change the tail of the shorter waveforms).
@@ -1028,16 +1089,21 @@ class IndexTTS:
         own reference audio, as if synthesised alone with that prompt.  Entries that are the same tensor object are one prompt
         and are conditioned once (_prompt_features_rows); nothing is shared between the rows' prefixes in the prefill.  Works
         together with adapter_ids / adapter_mix and sampling; num_beams = 1 only; a list whose length is not the number of utterances is a
-        ValueError.  One tensor is one prompt for all utterances, as before."""
+        ValueError.  One tensor is one prompt for all utterances, as before.
+        output (an OutputFormat; None = the fp32 waveforms above): the waveforms resampled and encoded on the device, all rows in
+        one launch -- a list of uint8 / int16 / float32 device tensors."""
+        IndexTTS._check_output(output, "infer_batch")
         st = self._batch_tokens(cond_mel, text_token_rows, max_mel_tokens, force_stop, seed, phase_events, lazy_spk=True,
                                 adapter_ids=adapter_ids, sampling=sampling, adapter_mix=adapter_mix, **generation_kwargs)
         outs = self._batch_waveforms(st, phase_events, reuse_prefix=True)   # serial: the KV cache still holds this batch's prompt
+        if output is not None:
+            outs = self._encode_rows(outs, output)
         return (outs, st["rows"]) if return_codes else outs
 
     # ------------------------------------------------------------------------------------------------ streaming
     def stream_utterance(self, cond_mel, text_tokens, chunk_tokens=32, max_mel_tokens=600, seed=1234, force_stop=None,
                          adapter_ids=None, adapter_mix=None, latent_cache: bool = False, _trace: dict | None = None,
-                         **generation_kwargs):
+                         *, output=None, **generation_kwargs):
         """ONE utterance as a generator of PCM chunks (fp32 tensors on the device, int16 range, like infer_batch's waveforms) that
         are produced while the token loop is still running; their concatenation is the utterance.
         Every chunk_tokens tokens the loop pauses (GPTEngine.decode_chunks).  With k codes known and no stop token among them,
@@ -1062,7 +1128,11 @@ class IndexTTS:
         adapter_ids / adapter_mix: one-element lists, the utterance's voice of an attached bank, as infer_batch takes them.
         _trace (private: tests, tools): receives "codes" (the utterance's codes, host int64), "frames" (the [t0, t1) of every chunk) and
         "latent" (per chunk, the rows [t0, t1) its window was vocoded from).
+        output (an OutputFormat; None = the fp32 chunks above): the chunks at its rate and in its encoding, produced on the device
+        with the resampler's state carried from chunk to chunk -- their concatenation is, bit for bit, the whole utterance
+        encoded at once (indextts/utils/pcm_out.py); a chunk holds the samples its boundary has determined.
         The checks run when this is called; the device work starts with the first next()."""
+        IndexTTS._check_output(output, "stream_utterance")
         gen, chunk_tokens, max_mel_tokens, _ = IndexTTS._stream_batch_args(
             1, chunk_tokens, max_mel_tokens, None, adapter_ids, adapter_mix, None, generation_kwargs, who="stream_utterance")
         if isinstance(cond_mel, (list, tuple)):
@@ -1078,7 +1148,7 @@ class IndexTTS:
             ids = None if adapter_ids is None else eng._row_adapters(adapter_ids, 1)
             mix = None if adapter_mix is None else eng._voices(None, adapter_mix, 1)[1]
             events = self._stream_rows(cond_mel, [text], chunk_tokens, max_mel_tokens, seed, force_stop, ids, mix, None, rows, gen,
-                                       bool(latent_cache), who="stream_utterance")
+                                       bool(latent_cache), who="stream_utterance", output=output)
             try:
                 for _, pcm, _ in events:
                     if _trace is not None:        # the one row's trace, flat
@@ -1173,6 +1243,9 @@ class IndexTTS:
                 if st.trace is not None:
                     st.trace["codes"][r["handle"]] = r["codes"][:k].clone()
             events.append((r["handle"], wavs[u] if t1 > t0 else torch.zeros(0, device=self.device), final))
+        if st.out is not None and events:     # the boundary's rows through ONE launch; a `last` row flushes its carried tail
+            enc = st.out.encode([(u, pcm, last) for (u, _, _, _, _), (_, pcm, last) in zip(plan, events)])
+            events = [(h, e, last) for (h, _, last), e in zip(events, enc)]
         return events
 
     # ------------------------------------------------------------------------------------------------ batched streaming
@@ -1206,7 +1279,7 @@ class IndexTTS:
 
     def stream_batch(self, cond_mel, text_token_rows, chunk_tokens=32, max_mel_tokens=600, seed=1234, force_stop=None,
                      adapter_ids=None, adapter_mix=None, sampling=None, latent_cache: bool = False, _trace: dict | None = None,
-                     **generation_kwargs):
+                     *, output=None, **generation_kwargs):
         """stream_utterance for N utterances in ONE token loop: a generator of events (row, pcm, last) -- row: the index into
         text_token_rows; pcm: an fp32 device tensor in the int16 range, the next samples of that utterance; last: this is the
         row's final event (exactly one per row; its pcm is empty when nothing was left to flush).  The concatenation of a row's
@@ -1226,7 +1299,10 @@ class IndexTTS:
         _trace (private: tests, tools) receives, per row, "codes" (host int64), "frames" ([(t0, t1)]), "latent" (per chunk, the rows
         [t0, t1) its window was cut from), "window" (per chunk, (lo, the latent rows [lo, hi) the vocoder ran over)) and "boundaries"
         (the n of every poll the row was planned at).
+        output (an OutputFormat): the events' pcm at its rate and in its encoding, as in stream_utterance; the rows of one
+        boundary share one launch, and a row's concatenated pcm is infer_batch(output=...)'s for the same codes.
         The checks run when this is called; the device work starts with the first next()."""
+        IndexTTS._check_output(output, "stream_batch")
         N = len(text_token_rows)
         gen, chunk_tokens, max_mel_tokens, force_stop = IndexTTS._stream_batch_args(
             N, chunk_tokens, max_mel_tokens, force_stop, adapter_ids, adapter_mix, sampling, generation_kwargs)
@@ -1238,10 +1314,10 @@ class IndexTTS:
             return iter(())
         adapter_ids, adapter_mix = self.gpt.engine._voices(adapter_ids, adapter_mix, N)    # (no bank: None, None)
         return self._stream_rows(cond_mel, texts, chunk_tokens, max_mel_tokens, seed, force_stop, adapter_ids, adapter_mix, sampling,
-                                 _trace, gen, bool(latent_cache))
+                                 _trace, gen, bool(latent_cache), output=output)
 
     def _stream_rows(self, cond_mel, texts, chunk_tokens, max_mel_tokens, seed, force_stop, adapter_ids, adapter_mix, sampling, trace, gen,
-                     latent_cache=False, who="stream_batch"):
+                     latent_cache=False, who="stream_batch", output=None):
         """stream_batch's generator (and, with one row and who="stream_utterance", stream_utterance's): one prefill, then every poll
         of decode_chunks becomes the records of the rows that have not ended and goes through _emit_boundary."""
         g, eng = self.gpt, self.gpt.engine
@@ -1260,7 +1336,8 @@ class IndexTTS:
         st = _StreamState(self.bigvgan.receptive_halo(), g.stop_mel_token, max_mel_tokens,
                           None if voices is None else "adapter_ids" if adapter_mix is None else "adapter_mix", trace,
                           _LatentRows(eng, N, int(emb.shape[1]) + max_mel_tokens + 2) if latent_cache else "reuse",
-                          warn=f"generation stopped at max_mel_tokens ({max_mel_tokens}){where}; consider shorter sentences")
+                          warn=f"generation stopped at max_mel_tokens ({max_mel_tokens}){where}; consider shorter sentences",
+                          out=None if output is None else _StreamOut(self._out_engine(), output))
         if trace is not None:
             trace.update(codes=[None] * N, frames=[[] for _ in range(N)], latent=[[] for _ in range(N)],
                          window=[[] for _ in range(N)], boundaries=[[] for _ in range(N)])
@@ -1287,7 +1364,7 @@ class IndexTTS:
     # ------------------------------------------------------------------------------------------------ streaming queue
     def stream_queue(self, cond_mel, text_token_rows, slots=32, chunk_tokens=32, max_mel_tokens=600, seed=1234, force_stop=None,
                      adapter_ids=None, adapter_mix=None, sampling=None, more=None, latent_cache: bool = False,
-                     _trace: dict | None = None, _refused=None, **generation_kwargs):
+                     _trace: dict | None = None, _refused=None, *, output=None, **generation_kwargs):
         """stream_batch over the REFILLED loop of infer_queue: any number of utterances through `slots` decode slots, each
         streamed as PCM while the loop runs, and utterances that arrive after the loop has started enter it.  A generator of
         events (utt, pcm, last) -- the events of stream_batch; utt: the index into text_token_rows, or the handle `more` gave.
@@ -1329,7 +1406,10 @@ class IndexTTS:
         poll the utterance was planned at) and "loops" (the number of loops started).
         A request from more() that does not pass its checks raises from the generator (the caller's error, as a bad argument
         is); _refused (private: serve_stream_queue) is a list that receives (handle, error) instead, and the loop goes on.
+        output (an OutputFormat): the events' pcm at its rate and in its encoding, as in stream_batch; an utterance keeps its
+        resampler state from its first boundary to its last, in whichever slot it runs.
         The checks run when this is called; the device work starts with the first next()."""
+        IndexTTS._check_output(output, "stream_queue")
         N = len(text_token_rows)
         gen, chunk_tokens, max_mel_tokens, force_stop = IndexTTS._stream_batch_args(
             N, chunk_tokens, max_mel_tokens, force_stop, adapter_ids, adapter_mix, sampling, generation_kwargs, who="stream_queue")
@@ -1344,7 +1424,7 @@ class IndexTTS:
         if N == 0 and more is None:
             return iter(())
         return self._stream_queue(cond_mel, reqs, int(slots), chunk_tokens, max_mel_tokens, seed, voice_kind, more, _trace, gen, _refused,
-                                  bool(latent_cache))
+                                  bool(latent_cache), output=output)
 
     def _queue_requests(self, who, cond_mel, text_token_rows, gen, force_stop, sampling, adapter_ids, adapter_mix):
         """What infer_queue and stream_queue (`who`) do with their arguments before anything is launched: the voices are checked
@@ -1510,7 +1590,7 @@ class IndexTTS:
                 idle()
 
     def _stream_queue(self, cond_mel, reqs, slots, chunk_tokens, max_mel_tokens, seed, voice_kind, more, trace, gen, refused=None,
-                      latent_cache=False):
+                      latent_cache=False, output=None):
         """stream_queue's generator: every poll of the refilled loops (_refill_loops) becomes the records of the slots' utterances,
         keyed (loop number, utt), and goes through _emit_boundary; between two polls the arrivals are taken in."""
         g = self.gpt
@@ -1521,7 +1601,8 @@ class IndexTTS:
         per_row = more is not None or any(r["sp"] is not None for r in reqs)
         feats = {}                                      # prompt key -> (mel, conds [1, nc, D], spk [1, 1, 512])
         # a refilled row's prompt does not lie where latent_mel_rows looks for it: the repeated pass is the whole-sequence one
-        st = _StreamState(self.bigvgan.receptive_halo(), g.stop_mel_token, max_mel_tokens, voice_kind, trace, "whole")
+        st = _StreamState(self.bigvgan.receptive_halo(), g.stop_mel_token, max_mel_tokens, voice_kind, trace, "whole",
+                          out=None if output is None else _StreamOut(self._out_engine(), output))
         if trace is not None:
             per_utt = lambda: collections.defaultdict(list)   # noqa: E731
             trace.update(codes={}, frames=per_utt(), latent=per_utt(), window=per_utt(), polls=per_utt(), loops=0)
@@ -1590,7 +1671,7 @@ class IndexTTS:
             loops.close()          # an early close of this generator abandons the loop
 
     def infer_stream(self, audio_prompt, text, max_text_tokens_per_sentence=120, parallel_sentences=1, slots=None,
-                     latent_cache: bool = False, **kw):
+                     latent_cache: bool = False, *, output=None, **kw):
         """infer() as a generator of (sampling rate, PCM chunk): the text is split into sentences as infer() splits it and the
         sentences are streamed one after another (stream_utterance, whose keywords -- chunk_tokens, seed, the generation
         settings -- pass through).  A chunk is an fp32 device tensor in the int16 range.
@@ -1601,7 +1682,13 @@ class IndexTTS:
         slots = S (not None): ALL sentences go through ONE stream_queue(slots=S) -- the refilled loop: a sentence that ends hands
         its slot to the next one instead of idling to the end of its group -- and the chunks are handed out in text order in the
         same way.  parallel_sentences does not apply then.  Without `slots` the call is what it was.
-        latent_cache=True: every one of these streams runs the incremental latent pass (stream_utterance says what that is)."""
+        latent_cache=True: every one of these streams runs the incremental latent pass (stream_utterance says what that is).
+        output (an OutputFormat): the chunks at its rate and in its encoding (each sentence is an utterance of its own, as it is
+        a stream of its own); the rate yielded is the format's."""
+        IndexTTS._check_output(output, "infer_stream")
+        rate = 24000 if output is None else output.sample_rate
+        if output is not None:
+            kw = dict(kw, output=output)
         if latent_cache:
             kw = dict(kw, latent_cache=True)
         P = int(parallel_sentences)
@@ -1615,7 +1702,7 @@ class IndexTTS:
         if P == 1 and slots is None:
             for ids in rows:
                 for pcm in self.stream_utterance(cond_mel, ids, **kw):
-                    yield 24000, pcm
+                    yield rate, pcm
             return
 
         def for_each(group):
@@ -1628,7 +1715,7 @@ class IndexTTS:
             order = _TextOrder(n)
             for row, pcm, last in events:
                 for c in order.push(row, pcm, last):
-                    yield 24000, c
+                    yield rate, c
 
         if slots is not None:
             if rows:
@@ -1638,7 +1725,7 @@ class IndexTTS:
             group = rows[s: s + P]
             yield from in_text_order(self.stream_batch(cond_mel, group, **for_each(group)), len(group))
 
-    def serve_stream_queue(self, more, slots=32, chunk_tokens=32, max_mel_tokens=600, latent_cache: bool = False):
+    def serve_stream_queue(self, more, slots=32, chunk_tokens=32, max_mel_tokens=600, latent_cache: bool = False, *, output=None):
         """The service form of stream_queue: whole REQUESTS (a prompt file and a text of any number of sentences each) through one
         refilled loop.  more() returns the requests that have arrived (a list, usually empty) or None (no more will come); a
         request is a dict: "handle", "audio_prompt" (a path), "text", and optionally "max_text_tokens_per_sentence", "seed" and
@@ -1647,7 +1734,9 @@ class IndexTTS:
         order (what a later sentence produces early is held back, as in infer_stream), `last` with its final one.  A request
         that cannot be taken -- an unreadable prompt, a refused setting -- yields (handle, the exception, True) and disturbs no
         other.  The generator ends when the loop has fallen idle (stream_queue): the caller starts the next one.
-        latent_cache: stream_queue's."""
+        latent_cache: stream_queue's.  output (an OutputFormat): every request's chunks in that format (stream_queue's)."""
+        IndexTTS._check_output(output, "serve_stream_queue")
+        empty = lambda: torch.zeros(0, device=self.device, dtype=torch.float32 if output is None else output.dtype)   # noqa: E731
         book = {}            # handle -> the text order of its sentences (_TextOrder)
         gen, _ = IndexTTS._gen_kwargs({"num_beams": 1})
         failed = []          # (handle, error | None = nothing to say, True) from here, ((handle, sentence), error) from the queue
@@ -1687,11 +1776,12 @@ class IndexTTS:
                 book.pop(h, None)                                # its other sentences, if any run, are dropped
                 if h not in done:
                     done.add(h)
-                    yield h, (torch.zeros(0, device=self.device) if e is None else e), True
+                    yield h, (empty() if e is None else e), True
 
         done = set()         # requests that have had their `last` (a request refused inside the queue may still own rows)
         events = self.stream_queue(None, [], slots=slots, chunk_tokens=chunk_tokens, max_mel_tokens=max_mel_tokens, more=utterances,
-                                   _refused=failed, **({"latent_cache": True} if latent_cache else {}))
+                                   _refused=failed, **({"latent_cache": True} if latent_cache else {}),
+                                   **({} if output is None else {"output": output}))
         yield from drain_failed()
         for (h, i), pcm, last in events:
             yield from drain_failed()
@@ -1703,12 +1793,13 @@ class IndexTTS:
             if order.over():
                 del book[h]
                 done.add(h)
-                yield h, torch.zeros(0, device=self.device), True
+                yield h, empty(), True
         yield from drain_failed()
 
     def infer_queue(self, cond_mel: torch.Tensor, text_token_rows: List[torch.Tensor], slots=32, max_mel_tokens=600,
                     force_stop=None, seed=1234, return_codes=False, cache_positions=4096, check_every=16, staged=True,
-                    phase_events: dict | None = None, sampling=None, adapter_ids=None, adapter_mix=None, **generation_kwargs):
+                    phase_events: dict | None = None, sampling=None, adapter_ids=None, adapter_mix=None, *, output=None,
+                    **generation_kwargs):
         """Continuous batching (not in the reference API; SURVEY.md section 8e's mitigation for mixed output lengths): any
         number of utterances of one prompt through `slots` decode slots.  The longest texts start; whenever a row emits its
         stop token its codes are taken and its slot is refilled with the next utterance (GPTEngine.decode_refill: the new
@@ -1723,7 +1814,9 @@ class IndexTTS:
         utterance as in infer_batch -- an utterance takes its own prompt's latents into whichever slot it enters.
         adapter_ids / adapter_mix (one entry per utterance, exclusive, the rules of infer_batch; needs gpt.attach_lora_bank, and with a
         bank attached one of them is needed: adapter_ids=[-1] * N is the base voice): an utterance takes its voice into whichever
-        slot, and at whichever step, it enters (GPTEngine.decode_refill(voices=...)), and into its latent pass."""
+        slot, and at whichever step, it enters (GPTEngine.decode_refill(voices=...)), and into its latent pass.
+        output (an OutputFormat; None = the fp32 waveforms): as in infer_batch -- all utterances encoded in one launch."""
+        IndexTTS._check_output(output, "infer_queue")
         gen, _ = self._gen_kwargs(generation_kwargs)
         if int(gen.get("num_beams", 1)) != 1:
             raise NotImplementedError("infer_queue: num_beams = 1 only (beam rows cannot be refilled one at a time)")
@@ -1773,6 +1866,8 @@ class IndexTTS:
             for i, w in zip(ids, self._vocode_ragged(lat, spk[sel] if per_row else spk)):
                 outs[i] = w
         self._mark(phase_events, "vocoded")
+        if output is not None:
+            outs = self._encode_rows(outs, output)
         return (outs, squeezed) if return_codes else outs
 
     @staticmethod

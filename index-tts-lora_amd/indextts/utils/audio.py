@@ -68,3 +68,28 @@ def write_pcm16(path: str, samples: np.ndarray, sample_rate: int):
         w.setsampwidth(2)
         w.setframerate(int(sample_rate))
         w.writeframes(s.tobytes())
+
+
+WAV_FORMATS = {"pcm16": (1, "<i2"), "f32": (3, "<f4"), "alaw": (6, "u1"), "mulaw": (7, "u1")}   # encoding -> (format tag, sample type)
+
+
+def write_wav(path: str, samples: np.ndarray, sample_rate: int, encoding: str = "pcm16"):
+    """Mono samples already in `encoding` (int16 / float32 / G.711 code bytes: what the PCM output back-end produces) -> a RIFF
+    file with the matching format tag: 1 PCM, 3 IEEE float, 6 A-law, 7 mu-law.  The non-PCM forms carry the 18-byte fmt chunk
+    and the fact chunk the format asks of them."""
+    if encoding not in WAV_FORMATS:
+        raise ValueError(f"write_wav: encoding {encoding!r} is none of {sorted(WAV_FORMATS)}")
+    tag, kind = WAV_FORMATS[encoding]
+    s = np.ascontiguousarray(samples).reshape(-1)
+    if s.dtype != np.dtype(kind):
+        raise ValueError(f"write_wav: {encoding} samples are {np.dtype(kind)} (got {s.dtype})")
+    data = s.astype(kind, copy=False).tobytes()
+    size = np.dtype(kind).itemsize
+    fmt = struct.pack("<HHIIHH", tag, 1, int(sample_rate), int(sample_rate) * size, size, 8 * size)
+    if tag == 1:
+        chunks = b"fmt " + struct.pack("<I", 16) + fmt
+    else:
+        chunks = b"fmt " + struct.pack("<I", 18) + fmt + struct.pack("<H", 0) + b"fact" + struct.pack("<II", 4, s.size)
+    chunks += b"data" + struct.pack("<I", len(data)) + data + (b"\x00" if len(data) & 1 else b"")
+    with open(path, "wb") as f:
+        f.write(b"RIFF" + struct.pack("<I", 4 + len(chunks)) + b"WAVE" + chunks)
