@@ -13,6 +13,8 @@ working:
     POST /tts             text + prompt_audio (upload) | prompt_audio_path, infer_mode fast|normal, speaker_id, seed and the
                           generation knobs -> audio/wav, header X-Seed; 400 without a prompt, 404 for a missing prompt path,
                           503 before the engine is up, 500 with the error text otherwise                (api.py:177-300)
+                          (with the fields trim_db / max_pause_ms / target_rms_db / peak_db: silence trimmed, pauses capped and the
+                          level set on the device, IndexTTS.post_process; 400 for an out-of-range value, and on /tts/stream)
 /tts accepts the reference's multipart form (parsed with the standard library: python-multipart is optional), a urlencoded
 form, or a JSON body with the same field names (the reference's TTSRequest model, api.py:35-50).  One engine instance per
 process, requests are serialised by a lock (the reference's endpoints are effectively serial as well: one global
@@ -55,6 +57,10 @@ class TTSRequest(BaseModel):
     max_mel_tokens: int = 600
     sample_rate: Optional[int] = None      # None: 24000, the vocoder's rate
     encoding: Optional[str] = None         # None: pcm16; f32 | mulaw | alaw (IndexTTS.output_format)
+    trim_db: Optional[float] = None        # /tts only (IndexTTS.post_process): frames below this level (dBFS) are silence; the ends are trimmed
+    max_pause_ms: Optional[float] = None   # /tts only: an inner pause longer than this is shortened to it (needs trim_db)
+    target_rms_db: Optional[float] = None  # /tts only: the RMS of the speech is brought to this level (dBFS)
+    peak_db: Optional[float] = None        # /tts only: the peak ceiling (dBFS; -1 under a target); alone: peak normalisation
 
 
 def output_of(req):
@@ -65,6 +71,25 @@ def output_of(req):
     from indextts.utils.pcm_out import OutputFormat
     try:
         return OutputFormat(24000 if req.sample_rate is None else req.sample_rate, req.encoding or "pcm16")
+    except ValueError as e:
+        raise HTTPException(status_code=400, detail=str(e))
+
+
+POST_FIELDS = ("trim_db", "max_pause_ms", "target_rms_db", "peak_db")
+
+
+def post_of(req, streaming=False):
+    """The PostProcess a request names with trim_db / max_pause_ms / target_rms_db / peak_db (None when it names none: the answer
+    is what it has always been); an out-of-range value is a 400, and so is any of them on /tts/stream -- the level of a whole
+    utterance is not known at its first chunk."""
+    given = {k: getattr(req, k) for k in POST_FIELDS if getattr(req, k) is not None}
+    if not given:
+        return None
+    if streaming:
+        raise HTTPException(status_code=400, detail=f"{', '.join(given)}: /tts/stream does not finish waveforms (use /tts)")
+    from indextts.utils.post_wave import PostProcess
+    try:
+        return PostProcess(**given)
     except ValueError as e:
         raise HTTPException(status_code=400, detail=str(e))
 
@@ -243,7 +268,7 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
                     upload = up
             else:
                 fields = {k: v[-1] for k, v in urllib.parse.parse_qs(body.decode("utf-8")).items()}
-            fields = {k: (None if isinstance(v, str) and v == "" and k in ("seed", "speaker_id", "prompt_audio_path", "sample_rate", "encoding") else v)
+            fields = {k: (None if isinstance(v, str) and v == "" and k in ("seed", "speaker_id", "prompt_audio_path", "sample_rate", "encoding") + POST_FIELDS else v)
                       for k, v in fields.items()}
             return TTSRequest(**fields), upload
         except HTTPException:
@@ -259,6 +284,7 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
         if upload is None and not req.prompt_audio_path:
             raise HTTPException(status_code=400, detail="a reference audio is required (upload a file or give a path)")
         fmt = output_of(req)
+        post = post_of(req)
         actual_seed = random.randint(0, 2 ** 32 - 1) if req.seed is None or req.seed == -1 else int(req.seed)
         tmp_path = None
         try:
@@ -281,6 +307,8 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
                           length_penalty=req.length_penalty, num_beams=3, max_mel_tokens=req.max_mel_tokens)
             if fmt is not None:
                 kwargs["output"] = fmt
+            if post is not None:
+                kwargs["post"] = post
             with lock:
                 t = engine()
                 set_seed(actual_seed)
@@ -323,6 +351,7 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
         if upload is None and not req.prompt_audio_path:
             raise HTTPException(status_code=400, detail="a reference audio is required (upload a file or give a path)")
         fmt = output_of(req)
+        post_of(req, streaming=True)
         actual_seed = random.randint(0, 2 ** 32 - 1) if req.seed is None or req.seed == -1 else int(req.seed)
         tmp_path = None
         if upload is not None:

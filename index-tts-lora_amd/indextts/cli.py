@@ -86,6 +86,15 @@ def main(argv=None):
                              "IndexTTS.output_format).  Default: 24000, the vocoder's")
     parser.add_argument("--encoding", choices=("pcm16", "f32", "mulaw", "alaw"), default=None,
                         help="sample encoding of the output file: 16-bit PCM (the default), IEEE float, or G.711 mu-law / A-law")
+    parser.add_argument("--trim-db", type=float, default=None, metavar="DB",
+                        help="cut leading and trailing silence: a 10 ms frame below this level (dBFS, e.g. -45) is silent "
+                             "(on the device, IndexTTS.post_process).  Default: nothing is cut")
+    parser.add_argument("--max-pause-ms", type=float, default=None, metavar="MS",
+                        help="shorten an inner pause longer than this to it (needs --trim-db)")
+    parser.add_argument("--target-rms-db", type=float, default=None, metavar="DB",
+                        help="bring the RMS of the speech to this level (dBFS, e.g. -20); the peak stays under --peak-db")
+    parser.add_argument("--peak-db", type=float, default=None, metavar="DB",
+                        help="peak ceiling (dBFS; -1 under --target-rms-db); alone: peak normalisation")
     parser.add_argument("-d", "--device", type=str, default=None, help="device (cuda:N); CPU/MPS are not supported")
     args = parser.parse_args(argv)
 
@@ -99,6 +108,16 @@ def main(argv=None):
         from indextts.utils.pcm_out import OutputFormat
         try:
             output = OutputFormat(24000 if args.sample_rate is None else args.sample_rate, args.encoding or "pcm16")
+        except ValueError as e:
+            fail(str(e))
+    post = None
+    if any(v is not None for v in (args.trim_db, args.max_pause_ms, args.target_rms_db, args.peak_db)):
+        if args.stream:
+            fail("--trim-db, --max-pause-ms, --target-rms-db and --peak-db do not apply to --stream: the level of a whole "
+                 "utterance is not known at its first chunk")
+        from indextts.utils.post_wave import PostProcess
+        try:
+            post = PostProcess(trim_db=args.trim_db, max_pause_ms=args.max_pause_ms, target_rms_db=args.target_rms_db, peak_db=args.peak_db)
         except ValueError as e:
             fail(str(e))
     if len(args.text.strip()) == 0:
@@ -148,7 +167,8 @@ def main(argv=None):
         write_pcm16(args.output_path, wav.to(torch.float32).numpy().astype("int16"), rate)
         print(f">> [output] saved to: {args.output_path}")
         return
-    tts.infer(audio_prompt=args.voice, text=args.text.strip(), output_path=args.output_path, **({} if output is None else {"output": output}))
+    tts.infer(audio_prompt=args.voice, text=args.text.strip(), output_path=args.output_path, **({} if output is None else {"output": output}),
+              **({} if post is None else {"post": post}))
 
 
 if __name__ == "__main__":

@@ -27,6 +27,7 @@ from indextts.BigVGAN.models import BigVGAN as Generator
 from indextts.gpt.model import UnifiedVoice, row_sampling_params, sampling_params
 from indextts.utils.audio import read_audio, write_pcm16, write_wav
 from indextts.utils.pcm_out import OutputFormat, PcmOutEngine
+from indextts.utils.post_wave import PostProcess, PostWaveEngine
 from indextts.utils.audio_engine import PromptAudioEngine, as_planar, refusal
 from indextts.utils.checkpoint import load_checkpoint
 from indextts.utils.config import Config, load_config
@@ -875,9 +876,42 @@ class IndexTTS:
         """Whole utterances (fp32 device tensors at 24 kHz) in the format `output`: one launch for all of them."""
         return self._out_engine().encode([w.reshape(-1).to(torch.float32) for w in wavs], output)
 
-    def _finish(self, wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, sampling_rate=24000, output=None):
+    # --------------------------------------------------------------------------------------------- waveform finishing
+    def post_process(self, **kw) -> PostProcess:
+        """The value the `post=` keyword of infer, infer_fast, infer_batch and infer_queue takes: trim_db, max_pause_ms, keep_ms,
+        target_rms_db, peak_db (indextts/utils/post_wave.PostProcess) -- silence trimmed, pauses capped and the level set on the
+        device, after the vocoder and before `output=`.  post=None, the default of every call, is what the calls have always
+        returned.  The streams do not take it: a gain from whole-utterance statistics is not known at the first chunk."""
+        return PostProcess(**kw)
+
+    @staticmethod
+    def _check_post(post, who):
+        if post is not None and not isinstance(post, PostProcess):
+            raise TypeError(f"{who}: post is a PostProcess (IndexTTS.post_process(trim_db=..., target_rms_db=..., ...)) or None")
+        return post
+
+    @staticmethod
+    def _no_post(kw, who):
+        if "post" in kw:        # (it would otherwise pass for a generation setting and be dropped unseen)
+            raise TypeError(f"{who}: the streams do not take post= -- a gain from whole-utterance statistics is not known at the "
+                            f"first chunk; use infer, infer_fast, infer_batch or infer_queue")
+
+    def _post_engine(self) -> PostWaveEngine:
+        eng = getattr(self, "_post_wave", None)
+        if eng is None:
+            eng = self._post_wave = PostWaveEngine(self.device)
+        return eng
+
+    def _post_rows(self, wavs, post):
+        """Whole utterances (fp32 device tensors at 24 kHz) finished as `post` says: two launches for all of them."""
+        return self._post_engine().process([w.reshape(-1).to(torch.float32) for w in wavs], post)
+
+    def _finish(self, wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, sampling_rate=24000, output=None,
+                post=None):
         end_time = time.perf_counter()
         wav = torch.cat(wavs, dim=1)
+        if post is not None:        # on the joined sentences, so that a pause across a join is one pause and the level one level
+            wav = self._post_rows([wav], post)[0][None]
         wav_length = wav.shape[-1] / sampling_rate
         print(f">> [stats] total: {end_time - start_time:.2f}s (RTF: {(end_time - start_time) / max(wav_length, 1e-9):.4f})")
         print(f"   - GPT generation: {gpt_gen_time:.2f}s")
@@ -967,11 +1001,13 @@ class IndexTTS:
 
     # ------------------------------------------------------------------------------------------------ public API
     def infer(self, audio_prompt, text, output_path, verbose=False, max_text_tokens_per_sentence=120, speaker_id=None,
-              *, output=None, **generation_kwargs):
+              *, output=None, post=None, **generation_kwargs):
         """Sentence-by-sentence synthesis (infer.py:779-917).  output (an OutputFormat; None = 24 kHz PCM16 as ever): the
         sentences are joined at 24 kHz on the device and encoded once; with an output_path the WAV carries the format's tag,
-        without one the call returns (rate, array in the encoding)."""
+        without one the call returns (rate, array in the encoding).  post (a PostProcess, IndexTTS.post_process; None = the
+        samples as ever): silence trimmed, pauses capped and the level set on the joined sentences, before output."""
         IndexTTS._check_output(output, "infer")
+        IndexTTS._check_post(post, "infer")
         if speaker_id is not None:
             if not self.speaker_list:
                 raise ValueError("multi-speaker mode is not enabled; load speaker_info_path first")
@@ -1008,15 +1044,17 @@ class IndexTTS:
             wav = self._vocode(latent, spk)
             torch.cuda.synchronize()
             bigvgan_time += time.perf_counter() - t0
-            wavs.append(wav.cpu() if output is None else wav)
+            wavs.append(wav.cpu() if output is None and post is None else wav)
         self._set_gr_progress(0.9, "saving audio...")
-        return self._finish(wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, output=output)
+        return self._finish(wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, output=output, post=post)
 
     def infer_fast(self, audio_prompt, text, output_path, verbose=False, max_text_tokens_per_sentence=100,
-                   sentences_bucket_max_size=4, *, output=None, **generation_kwargs):
+                   sentences_bucket_max_size=4, *, output=None, post=None, **generation_kwargs):
         """Bucketed batch synthesis (infer.py:595-777): sentences of similar length are decoded as one left-padded batch;
-        latents are computed in one batched pass and vocoded in time-concatenated pairs (chunk_size 2).  output: as in infer."""
+        latents are computed in one batched pass and vocoded in time-concatenated pairs (chunk_size 2).  output, post: as in
+        infer."""
         IndexTTS._check_output(output, "infer_fast")
+        IndexTTS._check_post(post, "infer_fast")
         print(">> [infer] fast mode")
         self._set_gr_progress(0, "initialising...")
         start_time = time.perf_counter()
@@ -1063,14 +1101,14 @@ class IndexTTS:
             wav = self._vocode(torch.cat(lat[i:i + 2], dim=0)[None], spk)
             torch.cuda.synchronize()
             bigvgan_time += time.perf_counter() - t0
-            wavs.append(wav.cpu() if output is None else wav)
+            wavs.append(wav.cpu() if output is None and post is None else wav)
         self.torch_empty_cache()
         self._set_gr_progress(0.9, "saving audio...")
-        return self._finish(wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, output=output)
+        return self._finish(wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, output=output, post=post)
 
     def infer_batch(self, cond_mel: torch.Tensor, text_token_rows: List[torch.Tensor], max_mel_tokens=600, force_stop=None,
                     seed=1234, return_codes=False, phase_events: dict | None = None, adapter_ids=None, sampling=None,
-                    adapter_mix=None, *, output=None, **generation_kwargs):
+                    adapter_mix=None, *, output=None, post=None, **generation_kwargs):
         """Utterance-batch data path used by bench.py / the multi-GPU sharder (not in the reference API): one shared
         prompt, N independent texts decoded as ONE left-padded batch, one batched latent pass, and one vocoder call per
         group of equal-length utterances (batching unequal lengths would change the tail of the shorter waveforms).
@@ -1091,11 +1129,17 @@ class IndexTTS:
         together with adapter_ids / adapter_mix and sampling; num_beams = 1 only; a list whose length is not the number of utterances is a
         ValueError.  One tensor is one prompt for all utterances, as before.
         output (an OutputFormat; None = the fp32 waveforms above): the waveforms resampled and encoded on the device, all rows in
-        one launch -- a list of uint8 / int16 / float32 device tensors."""
+        one launch -- a list of uint8 / int16 / float32 device tensors.
+        post (a PostProcess, IndexTTS.post_process; None = the waveforms as they are): every utterance trimmed, its pauses capped
+        and its level set from its own statistics -- voices recorded at different levels come back at one -- in two launches for
+        all rows (indextts/utils/post_wave.py), before output."""
         IndexTTS._check_output(output, "infer_batch")
+        IndexTTS._check_post(post, "infer_batch")
         st = self._batch_tokens(cond_mel, text_token_rows, max_mel_tokens, force_stop, seed, phase_events, lazy_spk=True,
                                 adapter_ids=adapter_ids, sampling=sampling, adapter_mix=adapter_mix, **generation_kwargs)
         outs = self._batch_waveforms(st, phase_events, reuse_prefix=True)   # serial: the KV cache still holds this batch's prompt
+        if post is not None:
+            outs = self._post_rows(outs, post)
         if output is not None:
             outs = self._encode_rows(outs, output)
         return (outs, st["rows"]) if return_codes else outs
@@ -1133,6 +1177,7 @@ class IndexTTS:
         encoded at once (indextts/utils/pcm_out.py); a chunk holds the samples its boundary has determined.
         The checks run when this is called; the device work starts with the first next()."""
         IndexTTS._check_output(output, "stream_utterance")
+        IndexTTS._no_post(generation_kwargs, "stream_utterance")
         gen, chunk_tokens, max_mel_tokens, _ = IndexTTS._stream_batch_args(
             1, chunk_tokens, max_mel_tokens, None, adapter_ids, adapter_mix, None, generation_kwargs, who="stream_utterance")
         if isinstance(cond_mel, (list, tuple)):
@@ -1303,6 +1348,7 @@ class IndexTTS:
         boundary share one launch, and a row's concatenated pcm is infer_batch(output=...)'s for the same codes.
         The checks run when this is called; the device work starts with the first next()."""
         IndexTTS._check_output(output, "stream_batch")
+        IndexTTS._no_post(generation_kwargs, "stream_batch")
         N = len(text_token_rows)
         gen, chunk_tokens, max_mel_tokens, force_stop = IndexTTS._stream_batch_args(
             N, chunk_tokens, max_mel_tokens, force_stop, adapter_ids, adapter_mix, sampling, generation_kwargs)
@@ -1410,6 +1456,7 @@ class IndexTTS:
         resampler state from its first boundary to its last, in whichever slot it runs.
         The checks run when this is called; the device work starts with the first next()."""
         IndexTTS._check_output(output, "stream_queue")
+        IndexTTS._no_post(generation_kwargs, "stream_queue")
         N = len(text_token_rows)
         gen, chunk_tokens, max_mel_tokens, force_stop = IndexTTS._stream_batch_args(
             N, chunk_tokens, max_mel_tokens, force_stop, adapter_ids, adapter_mix, sampling, generation_kwargs, who="stream_queue")
@@ -1686,6 +1733,7 @@ class IndexTTS:
         output (an OutputFormat): the chunks at its rate and in its encoding (each sentence is an utterance of its own, as it is
         a stream of its own); the rate yielded is the format's."""
         IndexTTS._check_output(output, "infer_stream")
+        IndexTTS._no_post(kw, "infer_stream")
         rate = 24000 if output is None else output.sample_rate
         if output is not None:
             kw = dict(kw, output=output)
@@ -1799,7 +1847,7 @@ class IndexTTS:
     def infer_queue(self, cond_mel: torch.Tensor, text_token_rows: List[torch.Tensor], slots=32, max_mel_tokens=600,
                     force_stop=None, seed=1234, return_codes=False, cache_positions=4096, check_every=16, staged=True,
                     phase_events: dict | None = None, sampling=None, adapter_ids=None, adapter_mix=None, *, output=None,
-                    **generation_kwargs):
+                    post=None, **generation_kwargs):
         """Continuous batching (not in the reference API; SURVEY.md section 8e's mitigation for mixed output lengths): any
         number of utterances of one prompt through `slots` decode slots.  The longest texts start; whenever a row emits its
         stop token its codes are taken and its slot is refilled with the next utterance (GPTEngine.decode_refill: the new
@@ -1815,8 +1863,10 @@ class IndexTTS:
         adapter_ids / adapter_mix (one entry per utterance, exclusive, the rules of infer_batch; needs gpt.attach_lora_bank, and with a
         bank attached one of them is needed: adapter_ids=[-1] * N is the base voice): an utterance takes its voice into whichever
         slot, and at whichever step, it enters (GPTEngine.decode_refill(voices=...)), and into its latent pass.
-        output (an OutputFormat; None = the fp32 waveforms): as in infer_batch -- all utterances encoded in one launch."""
+        output (an OutputFormat; None = the fp32 waveforms): as in infer_batch -- all utterances encoded in one launch.
+        post (a PostProcess; None = the waveforms as they are): as in infer_batch -- all utterances finished in two launches."""
         IndexTTS._check_output(output, "infer_queue")
+        IndexTTS._check_post(post, "infer_queue")
         gen, _ = self._gen_kwargs(generation_kwargs)
         if int(gen.get("num_beams", 1)) != 1:
             raise NotImplementedError("infer_queue: num_beams = 1 only (beam rows cannot be refilled one at a time)")
@@ -1866,6 +1916,8 @@ class IndexTTS:
             for i, w in zip(ids, self._vocode_ragged(lat, spk[sel] if per_row else spk)):
                 outs[i] = w
         self._mark(phase_events, "vocoded")
+        if post is not None:
+            outs = self._post_rows(outs, post)
         if output is not None:
             outs = self._encode_rows(outs, output)
         return (outs, squeezed) if return_codes else outs
