@@ -15,6 +15,8 @@ working:
                           503 before the engine is up, 500 with the error text otherwise                (api.py:177-300)
                           (with the fields trim_db / max_pause_ms / target_rms_db / peak_db: silence trimmed, pauses capped and the
                           level set on the device, IndexTTS.post_process; 400 for an out-of-range value, and on /tts/stream)
+                          (with the field speed, 0.5 .. 2.0: the speaking rate at the same pitch, on the device before the
+                          finishing, IndexTTS.infer(speed=...); 400 for an out-of-range value, and on /tts/stream)
 /tts accepts the reference's multipart form (parsed with the standard library: python-multipart is optional), a urlencoded
 form, or a JSON body with the same field names (the reference's TTSRequest model, api.py:35-50).  One engine instance per
 process, requests are serialised by a lock (the reference's endpoints are effectively serial as well: one global
@@ -61,6 +63,7 @@ class TTSRequest(BaseModel):
     max_pause_ms: Optional[float] = None   # /tts only: an inner pause longer than this is shortened to it (needs trim_db)
     target_rms_db: Optional[float] = None  # /tts only: the RMS of the speech is brought to this level (dBFS)
     peak_db: Optional[float] = None        # /tts only: the peak ceiling (dBFS; -1 under a target); alone: peak normalisation
+    speed: Optional[float] = None          # /tts only: the speaking rate, 0.5 .. 2.0 (1.25 a quarter faster), at the same pitch
 
 
 def output_of(req):
@@ -73,6 +76,21 @@ def output_of(req):
         return OutputFormat(24000 if req.sample_rate is None else req.sample_rate, req.encoding or "pcm16")
     except ValueError as e:
         raise HTTPException(status_code=400, detail=str(e))
+
+
+def speed_of(req, streaming=False):
+    """The speaking rate a request names with speed (None when it names none: the answer is what it has always been); a value
+    outside [0.5, 2.0] is a 400, and so is the field on /tts/stream -- the chain of lags is not carried across chunks."""
+    if req.speed is None:
+        return None
+    if streaming:
+        raise HTTPException(status_code=400, detail="speed: /tts/stream does not change the speaking rate (use /tts)")
+    from indextts.utils.tempo import fixed_speed
+    try:
+        fixed_speed(req.speed)
+    except ValueError as e:
+        raise HTTPException(status_code=400, detail=str(e))
+    return float(req.speed)
 
 
 POST_FIELDS = ("trim_db", "max_pause_ms", "target_rms_db", "peak_db")
@@ -285,6 +303,7 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
             raise HTTPException(status_code=400, detail="a reference audio is required (upload a file or give a path)")
         fmt = output_of(req)
         post = post_of(req)
+        speed = speed_of(req)
         actual_seed = random.randint(0, 2 ** 32 - 1) if req.seed is None or req.seed == -1 else int(req.seed)
         tmp_path = None
         try:
@@ -309,6 +328,8 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
                 kwargs["output"] = fmt
             if post is not None:
                 kwargs["post"] = post
+            if speed is not None:
+                kwargs["speed"] = speed
             with lock:
                 t = engine()
                 set_seed(actual_seed)
@@ -352,6 +373,7 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
             raise HTTPException(status_code=400, detail="a reference audio is required (upload a file or give a path)")
         fmt = output_of(req)
         post_of(req, streaming=True)
+        speed_of(req, streaming=True)
         actual_seed = random.randint(0, 2 ** 32 - 1) if req.seed is None or req.seed == -1 else int(req.seed)
         tmp_path = None
         if upload is not None:

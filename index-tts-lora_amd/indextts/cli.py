@@ -95,6 +95,9 @@ def main(argv=None):
                         help="bring the RMS of the speech to this level (dBFS, e.g. -20); the peak stays under --peak-db")
     parser.add_argument("--peak-db", type=float, default=None, metavar="DB",
                         help="peak ceiling (dBFS; -1 under --target-rms-db); alone: peak normalisation")
+    parser.add_argument("--speed", type=float, default=None, metavar="X",
+                        help="speaking rate, 0.5 to 2.0: 0.8 is a fifth slower, 1.25 a quarter faster, at the same pitch (WSOLA on "
+                             "the device, IndexTTS.infer(speed=...)).  Default: the voice as it is")
     parser.add_argument("-d", "--device", type=str, default=None, help="device (cuda:N); CPU/MPS are not supported")
     args = parser.parse_args(argv)
 
@@ -120,6 +123,14 @@ def main(argv=None):
             post = PostProcess(trim_db=args.trim_db, max_pause_ms=args.max_pause_ms, target_rms_db=args.target_rms_db, peak_db=args.peak_db)
         except ValueError as e:
             fail(str(e))
+    if args.speed is not None:
+        if args.stream:
+            fail("--speed does not apply to --stream: the chain of lags is not carried across chunk boundaries")
+        from indextts.utils.tempo import fixed_speed
+        try:
+            fixed_speed(args.speed)
+        except ValueError as e:
+            fail(f"--speed: {e}")
     if len(args.text.strip()) == 0:
         fail("text is empty")
     if args.stream_parallel < 1:
@@ -168,7 +179,7 @@ def main(argv=None):
         print(f">> [output] saved to: {args.output_path}")
         return
     tts.infer(audio_prompt=args.voice, text=args.text.strip(), output_path=args.output_path, **({} if output is None else {"output": output}),
-              **({} if post is None else {"post": post}))
+              **({} if post is None else {"post": post}), **({} if args.speed is None else {"speed": args.speed}))
 
 
 if __name__ == "__main__":

@@ -28,6 +28,7 @@ from indextts.gpt.model import UnifiedVoice, row_sampling_params, sampling_param
 from indextts.utils.audio import read_audio, write_pcm16, write_wav
 from indextts.utils.pcm_out import OutputFormat, PcmOutEngine
 from indextts.utils.post_wave import PostProcess, PostWaveEngine
+from indextts.utils.tempo import SPEED_ONE, TempoEngine, fixed_speed
 from indextts.utils.audio_engine import PromptAudioEngine, as_planar, refusal
 from indextts.utils.checkpoint import load_checkpoint
 from indextts.utils.config import Config, load_config
@@ -906,10 +907,54 @@ class IndexTTS:
         """Whole utterances (fp32 device tensors at 24 kHz) finished as `post` says: two launches for all of them."""
         return self._post_engine().process([w.reshape(-1).to(torch.float32) for w in wavs], post)
 
+    # -------------------------------------------------------------------------------------------------- speaking rate
+    @staticmethod
+    def _check_speed(speed, who, n=None):
+        """What the `speed=` keyword of infer, infer_fast, infer_batch and infer_queue asks for: None when nothing of the feature
+        runs (speed None or 1.0, or every entry of a list one of the two), otherwise S = fixed_speed(speed) -- for a call of
+        n utterances a list of n entries, S or None.  A bool, a value that is not finite or outside [0.5, 2.0], a list where one
+        number is expected or a list of another length than n is a ValueError, raised before anything is launched."""
+        if speed is None:
+            return None
+        try:
+            if isinstance(speed, (list, tuple)):
+                if n is None:
+                    raise ValueError(f"speed = {speed!r}: one number for the call")
+                if len(speed) != n:
+                    raise ValueError(f"{len(speed)} speeds for {n} utterances")
+                rows = [None if v is None else fixed_speed(v) for v in speed]
+            else:
+                rows = [fixed_speed(speed)] * (1 if n is None else n)
+        except ValueError as e:
+            raise ValueError(f"{who}: {e}") from None
+        if all(S is None or S == SPEED_ONE for S in rows):
+            return None
+        return rows[0] if n is None else rows
+
+    @staticmethod
+    def _no_speed(kw, who):
+        if "speed" in kw:       # (it would otherwise pass for a generation setting and be dropped unseen)
+            raise TypeError(f"{who}: the streams do not take speed= -- the chain of lags is not carried across chunk boundaries; "
+                            f"use infer, infer_fast, infer_batch or infer_queue")
+
+    def _tempo_engine(self) -> TempoEngine:
+        eng = getattr(self, "_tempo", None)
+        if eng is None:
+            eng = self._tempo = TempoEngine(self.device)
+        return eng
+
+    def _speed_rows(self, wavs, speeds):
+        """Whole utterances (fp32 device tensors at 24 kHz) at the speeds S_i / 1024 (None: as it is): two launches for all of
+        them; a row at None or 1024 comes back as the same tensor."""
+        wavs = [w if w.dim() == 1 and w.dtype == torch.float32 else w.reshape(-1).to(torch.float32) for w in wavs]
+        return self._tempo_engine().process(wavs, speeds)
+
     def _finish(self, wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, sampling_rate=24000, output=None,
-                post=None):
+                post=None, speed=None):
         end_time = time.perf_counter()
         wav = torch.cat(wavs, dim=1)
+        if speed is not None:       # (S, not 1024) on the joined sentences: one chain of lags, no seam at a join; before post
+            wav = self._speed_rows([wav.reshape(-1)], [speed])[0][None]
         if post is not None:        # on the joined sentences, so that a pause across a join is one pause and the level one level
             wav = self._post_rows([wav], post)[0][None]
         wav_length = wav.shape[-1] / sampling_rate
@@ -1001,13 +1046,16 @@ class IndexTTS:
 
     # ------------------------------------------------------------------------------------------------ public API
     def infer(self, audio_prompt, text, output_path, verbose=False, max_text_tokens_per_sentence=120, speaker_id=None,
-              *, output=None, post=None, **generation_kwargs):
+              *, output=None, post=None, speed=None, **generation_kwargs):
         """Sentence-by-sentence synthesis (infer.py:779-917).  output (an OutputFormat; None = 24 kHz PCM16 as ever): the
         sentences are joined at 24 kHz on the device and encoded once; with an output_path the WAV carries the format's tag,
         without one the call returns (rate, array in the encoding).  post (a PostProcess, IndexTTS.post_process; None = the
-        samples as ever): silence trimmed, pauses capped and the level set on the joined sentences, before output."""
+        samples as ever): silence trimmed, pauses capped and the level set on the joined sentences, before output.  speed (a number
+        in [0.5, 2.0]; None and 1.0 = the samples as ever): the speaking rate -- 0.8 a fifth slower, 1.25 a quarter faster, at
+        the same pitch (WSOLA on the device, indextts/utils/tempo.py) -- on the joined sentences, before post."""
         IndexTTS._check_output(output, "infer")
         IndexTTS._check_post(post, "infer")
+        speed = IndexTTS._check_speed(speed, "infer")
         if speaker_id is not None:
             if not self.speaker_list:
                 raise ValueError("multi-speaker mode is not enabled; load speaker_info_path first")
@@ -1044,17 +1092,19 @@ class IndexTTS:
             wav = self._vocode(latent, spk)
             torch.cuda.synchronize()
             bigvgan_time += time.perf_counter() - t0
-            wavs.append(wav.cpu() if output is None and post is None else wav)
+            wavs.append(wav.cpu() if output is None and post is None and speed is None else wav)
         self._set_gr_progress(0.9, "saving audio...")
-        return self._finish(wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, output=output, post=post)
+        return self._finish(wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, output=output, post=post,
+                            speed=speed)
 
     def infer_fast(self, audio_prompt, text, output_path, verbose=False, max_text_tokens_per_sentence=100,
-                   sentences_bucket_max_size=4, *, output=None, post=None, **generation_kwargs):
+                   sentences_bucket_max_size=4, *, output=None, post=None, speed=None, **generation_kwargs):
         """Bucketed batch synthesis (infer.py:595-777): sentences of similar length are decoded as one left-padded batch;
-        latents are computed in one batched pass and vocoded in time-concatenated pairs (chunk_size 2).  output, post: as in
-        infer."""
+        latents are computed in one batched pass and vocoded in time-concatenated pairs (chunk_size 2).  output, post, speed: as
+        in infer."""
         IndexTTS._check_output(output, "infer_fast")
         IndexTTS._check_post(post, "infer_fast")
+        speed = IndexTTS._check_speed(speed, "infer_fast")
         print(">> [infer] fast mode")
         self._set_gr_progress(0, "initialising...")
         start_time = time.perf_counter()
@@ -1101,14 +1151,15 @@ class IndexTTS:
             wav = self._vocode(torch.cat(lat[i:i + 2], dim=0)[None], spk)
             torch.cuda.synchronize()
             bigvgan_time += time.perf_counter() - t0
-            wavs.append(wav.cpu() if output is None and post is None else wav)
+            wavs.append(wav.cpu() if output is None and post is None and speed is None else wav)
         self.torch_empty_cache()
         self._set_gr_progress(0.9, "saving audio...")
-        return self._finish(wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, output=output, post=post)
+        return self._finish(wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, output=output, post=post,
+                            speed=speed)
 
     def infer_batch(self, cond_mel: torch.Tensor, text_token_rows: List[torch.Tensor], max_mel_tokens=600, force_stop=None,
                     seed=1234, return_codes=False, phase_events: dict | None = None, adapter_ids=None, sampling=None,
-                    adapter_mix=None, *, output=None, post=None, **generation_kwargs):
+                    adapter_mix=None, *, output=None, post=None, speed=None, **generation_kwargs):
         """Utterance-batch data path used by bench.py / the multi-GPU sharder (not in the reference API): one shared
         prompt, N independent texts decoded as ONE left-padded batch, one batched latent pass, and one vocoder call per
         group of equal-length utterances (batching unequal lengths would change the tail of the shorter waveforms).
@@ -1132,12 +1183,19 @@ class IndexTTS:
         one launch -- a list of uint8 / int16 / float32 device tensors.
         post (a PostProcess, IndexTTS.post_process; None = the waveforms as they are): every utterance trimmed, its pauses capped
         and its level set from its own statistics -- voices recorded at different levels come back at one -- in two launches for
-        all rows (indextts/utils/post_wave.py), before output."""
+        all rows (indextts/utils/post_wave.py), before output.
+        speed (a number in [0.5, 2.0], or a list with one entry per utterance, None entries allowed; None and 1.0 = the waveforms
+        as they are): the speaking rate of every utterance at the same pitch -- WSOLA on the device, two launches for all rows
+        (indextts/utils/tempo.py) -- before post: pauses and levels are judged on what the listener hears.  The codes, and what
+        return_codes returns, are those of the plain call."""
         IndexTTS._check_output(output, "infer_batch")
         IndexTTS._check_post(post, "infer_batch")
+        speed = IndexTTS._check_speed(speed, "infer_batch", len(text_token_rows))
         st = self._batch_tokens(cond_mel, text_token_rows, max_mel_tokens, force_stop, seed, phase_events, lazy_spk=True,
                                 adapter_ids=adapter_ids, sampling=sampling, adapter_mix=adapter_mix, **generation_kwargs)
         outs = self._batch_waveforms(st, phase_events, reuse_prefix=True)   # serial: the KV cache still holds this batch's prompt
+        if speed is not None:
+            outs = self._speed_rows(outs, speed)
         if post is not None:
             outs = self._post_rows(outs, post)
         if output is not None:
@@ -1178,6 +1236,7 @@ class IndexTTS:
         The checks run when this is called; the device work starts with the first next()."""
         IndexTTS._check_output(output, "stream_utterance")
         IndexTTS._no_post(generation_kwargs, "stream_utterance")
+        IndexTTS._no_speed(generation_kwargs, "stream_utterance")
         gen, chunk_tokens, max_mel_tokens, _ = IndexTTS._stream_batch_args(
             1, chunk_tokens, max_mel_tokens, None, adapter_ids, adapter_mix, None, generation_kwargs, who="stream_utterance")
         if isinstance(cond_mel, (list, tuple)):
@@ -1349,6 +1408,7 @@ class IndexTTS:
         The checks run when this is called; the device work starts with the first next()."""
         IndexTTS._check_output(output, "stream_batch")
         IndexTTS._no_post(generation_kwargs, "stream_batch")
+        IndexTTS._no_speed(generation_kwargs, "stream_batch")
         N = len(text_token_rows)
         gen, chunk_tokens, max_mel_tokens, force_stop = IndexTTS._stream_batch_args(
             N, chunk_tokens, max_mel_tokens, force_stop, adapter_ids, adapter_mix, sampling, generation_kwargs)
@@ -1457,6 +1517,7 @@ class IndexTTS:
         The checks run when this is called; the device work starts with the first next()."""
         IndexTTS._check_output(output, "stream_queue")
         IndexTTS._no_post(generation_kwargs, "stream_queue")
+        IndexTTS._no_speed(generation_kwargs, "stream_queue")
         N = len(text_token_rows)
         gen, chunk_tokens, max_mel_tokens, force_stop = IndexTTS._stream_batch_args(
             N, chunk_tokens, max_mel_tokens, force_stop, adapter_ids, adapter_mix, sampling, generation_kwargs, who="stream_queue")
@@ -1734,6 +1795,7 @@ class IndexTTS:
         a stream of its own); the rate yielded is the format's."""
         IndexTTS._check_output(output, "infer_stream")
         IndexTTS._no_post(kw, "infer_stream")
+        IndexTTS._no_speed(kw, "infer_stream")
         rate = 24000 if output is None else output.sample_rate
         if output is not None:
             kw = dict(kw, output=output)
@@ -1791,6 +1853,7 @@ class IndexTTS:
 
         def sentences_of(r):
             """the request's utterances, every one checked as the loop will check it -- what is refused is refused here"""
+            IndexTTS._no_speed(r, "serve_stream_queue")      # (a request's own failure, like any refused setting)
             mel = self._prompt(r["audio_prompt"])
             toks = self.tokenizer.split_sentences(self.tokenizer.tokenize(r["text"]), int(r.get("max_text_tokens_per_sentence", 120)))
             own = {k: r[k] for k in ("do_sample", "temperature", "top_k", "top_p", "repetition_penalty", "seed") if r.get(k) is not None}
@@ -1847,7 +1910,7 @@ class IndexTTS:
     def infer_queue(self, cond_mel: torch.Tensor, text_token_rows: List[torch.Tensor], slots=32, max_mel_tokens=600,
                     force_stop=None, seed=1234, return_codes=False, cache_positions=4096, check_every=16, staged=True,
                     phase_events: dict | None = None, sampling=None, adapter_ids=None, adapter_mix=None, *, output=None,
-                    post=None, **generation_kwargs):
+                    post=None, speed=None, **generation_kwargs):
         """Continuous batching (not in the reference API; SURVEY.md section 8e's mitigation for mixed output lengths): any
         number of utterances of one prompt through `slots` decode slots.  The longest texts start; whenever a row emits its
         stop token its codes are taken and its slot is refilled with the next utterance (GPTEngine.decode_refill: the new
@@ -1864,9 +1927,11 @@ class IndexTTS:
         bank attached one of them is needed: adapter_ids=[-1] * N is the base voice): an utterance takes its voice into whichever
         slot, and at whichever step, it enters (GPTEngine.decode_refill(voices=...)), and into its latent pass.
         output (an OutputFormat; None = the fp32 waveforms): as in infer_batch -- all utterances encoded in one launch.
-        post (a PostProcess; None = the waveforms as they are): as in infer_batch -- all utterances finished in two launches."""
+        post (a PostProcess; None = the waveforms as they are): as in infer_batch -- all utterances finished in two launches.
+        speed (a number or one entry per utterance; None and 1.0 = as they are): as in infer_batch -- before post."""
         IndexTTS._check_output(output, "infer_queue")
         IndexTTS._check_post(post, "infer_queue")
+        speed = IndexTTS._check_speed(speed, "infer_queue", len(text_token_rows))
         gen, _ = self._gen_kwargs(generation_kwargs)
         if int(gen.get("num_beams", 1)) != 1:
             raise NotImplementedError("infer_queue: num_beams = 1 only (beam rows cannot be refilled one at a time)")
@@ -1916,6 +1981,8 @@ class IndexTTS:
             for i, w in zip(ids, self._vocode_ragged(lat, spk[sel] if per_row else spk)):
                 outs[i] = w
         self._mark(phase_events, "vocoded")
+        if speed is not None:
+            outs = self._speed_rows(outs, speed)
         if post is not None:
             outs = self._post_rows(outs, post)
         if output is not None:
