@@ -51,11 +51,57 @@ def extract_voice_main(argv):
     print(f">> [voice] {len(adapters)} targets saved to: {args.voice_out}")
 
 
+def extract_codes_main(argv):
+    """`indextts --extract-codes LIST --out DIR`: the mel codes and mels of every clip of an audio list (`path<TAB>transcript` per
+    line), the first step of the fine-tuning workflow (IndexTTS.extract_codes).  A command of its own with its own arguments."""
+    import argparse
+    parser = argparse.ArgumentParser(prog="indextts --extract-codes", description="IndexTTS: mel codes and mels of an audio list")
+    parser.add_argument("--extract-codes", type=str, required=True, metavar="LIST", help="audio list: path<TAB>transcript per line")
+    parser.add_argument("--out", type=str, required=True, metavar="DIR", help="directory for codes/, mels/ and metadata.jsonl")
+    parser.add_argument("--dvae", type=str, default=None, metavar="CKPT", help="DVAE checkpoint (default: the config's dvae_checkpoint)")
+    parser.add_argument("--batch-clips", type=int, default=16, metavar="N", help="clips per ragged batch")
+    parser.add_argument("-c", "--config", type=str, default="checkpoints/config.yaml", help="config file")
+    parser.add_argument("--model_dir", type=str, default="checkpoints", help="model directory")
+    parser.add_argument("--fp16", action="store_true", default=True, help="half-precision GPT weights when available")
+    parser.add_argument("--prompt-frontend", choices=("torch", "hip"), default="hip", help="where the log-mel is computed")
+    parser.add_argument("-d", "--device", type=str, default=None, help="device (cuda:N); CPU/MPS are not supported")
+    args = parser.parse_args(argv)
+
+    def fail(msg):
+        print(f"[error] {msg}")
+        parser.print_help()
+        sys.exit(1)
+
+    if not os.path.exists(args.extract_codes):
+        fail(f"audio list {args.extract_codes} does not exist")
+    if args.batch_clips < 1:
+        fail("--batch-clips must be at least 1")
+    if not os.path.exists(args.config):
+        fail(f"config {args.config} does not exist")
+    import torch
+    if args.device is None:
+        if not torch.cuda.is_available():
+            print("[error] no GPU visible: this build needs an AMD GPU (no CPU path)")
+            sys.exit(1)
+        args.device = "cuda:0"
+    from indextts.infer import IndexTTS
+    tts = IndexTTS(cfg_path=args.config, model_dir=args.model_dir, is_fp16=args.fp16, device=args.device, prompt_frontend=args.prompt_frontend)
+    try:
+        tts.load_tokenizer(args.dvae)
+        records = tts.extract_codes(args.extract_codes, args.out, batch_clips=args.batch_clips)
+    except (ValueError, OSError, RuntimeError) as e:
+        print(f"[error] {e}")
+        sys.exit(1)
+    print(f">> [codes] {len(records)} clips, {sum(r['duration'] for r in records):.1f} s of audio -> {args.out}")
+
+
 def main(argv=None):
     import argparse
     argv = sys.argv[1:] if argv is None else list(argv)
     if any(a == "--extract-voice" or a.startswith("--extract-voice=") for a in argv):
         return extract_voice_main(argv)
+    if any(a == "--extract-codes" or a.startswith("--extract-codes=") for a in argv):
+        return extract_codes_main(argv)
     parser = argparse.ArgumentParser(description="IndexTTS command line (MI355X build)")
     parser.add_argument("text", type=str, help="text to synthesise")
     parser.add_argument("-v", "--voice", type=str, required=True, help="reference (prompt) audio file, wav")

@@ -949,6 +949,89 @@ class IndexTTS:
         wavs = [w if w.dim() == 1 and w.dtype == torch.float32 else w.reshape(-1).to(torch.float32) for w in wavs]
         return self._tempo_engine().process(wavs, speeds)
 
+    # ------------------------------------------------------------------------------------------------ audio -> codes
+    def load_tokenizer(self, path=None, state_dict=None):
+        """The acoustic tokenizer (indextts/vqvae/dvae.py): the DVAE's encoder and codebook from `path`, or
+        from the config's dvae_checkpoint under model_dir, checked against the config's vqvae block -- or from a state dict
+        in the reference's key format.  Nothing of it is loaded or imported until this is called (audio_codes and
+        extract_codes call it).  Returns the CodecEngine."""
+        from indextts.utils.checkpoint import check_dvae, load_dvae
+        from indextts.vqvae.dvae import CodecEngine
+        if state_dict is None:
+            state_dict = load_dvae(self.cfg, self.model_dir, path)
+        elif "vqvae" in self.cfg:
+            check_dvae(state_dict, self.cfg["vqvae"])
+        self._codec = CodecEngine(state_dict, self.device)
+        return self._codec
+
+    def _codec_engine(self):
+        eng = getattr(self, "_codec", None)
+        return eng if eng is not None else self.load_tokenizer()
+
+    def audio_codes(self, audios, srs=None):
+        """The mel codes of recordings: every entry (a path, an (array, sr) pair, or an array / tensor whose rate srs[i] gives, as
+        prompt_mels takes them) through this instance's prompt front-end and the tokenizer, all clips in one ragged batch.
+        Returns (codes, mels): int64 device tensors [code_count(T_i)] and the mels [1, 100, T_i] they were taken from."""
+        eng = self._codec_engine()
+        mels = self.prompt_mels(audios, srs)
+        return eng.encode([m[0].to(torch.float32).contiguous() for m in mels]), mels
+
+    def synthesize_codes(self, cond_mel, text_token_rows: List[torch.Tensor], code_rows: List[torch.Tensor], adapter_ids=None,
+                         adapter_mix=None):
+        """Copy synthesis: given codes -- of a recording (audio_codes), or what infer_batch(return_codes=True) returned -- through
+        the teacher-forced latent pass and the vocoder of infer_batch, in the voice of cond_mel (one prompt, or a list with one
+        per row) and under the rows' adapters.  Returns the fp32 waveforms, like infer_batch.  No token is sampled."""
+        if len(code_rows) != len(text_token_rows):
+            raise ValueError(f"synthesize_codes: {len(code_rows)} code rows for {len(text_token_rows)} texts")
+        eng = self.gpt.engine
+        if adapter_ids is not None:
+            adapter_ids = eng._row_adapters(adapter_ids, len(text_token_rows))
+        if adapter_mix is not None:
+            adapter_mix = eng._voices(adapter_ids, adapter_mix, len(text_token_rows))[1]
+        cond_mel = self._check_prompts(cond_mel, len(text_token_rows), {}, "synthesize_codes")
+        conds, spk = self._prompt_features(cond_mel)
+        rows = [c.reshape(-1).cpu().long() for c in code_rows]
+        st = dict(conds=conds, spk=spk, rows=rows, texts=[t.reshape(-1).cpu() for t in text_token_rows], cache_rows=None,
+                  cond_mel=cond_mel, adapter_ids=adapter_ids, adapter_mix=adapter_mix)
+        return self._batch_waveforms(st, None, reuse_prefix=False)
+
+    def extract_codes(self, audio_list, out_dir, batch_clips=16):
+        """The first step of the fine-tuning workflow: the codes and mels of every clip of an audio list (one
+        `path<TAB>transcript` per line; a relative path is relative to the list), in ragged batches of batch_clips.  Writes per
+        clip <out_dir>/codes/<n>_<stem>.npy (int64 [1, T2]) and <out_dir>/mels/<n>_<stem>.npy (fp32 [1, 100, T]), as the
+        reference's dataset loads them, and <out_dir>/metadata.jsonl with audio, text, codes, mels, duration per clip.
+        Returns the metadata records."""
+        base = os.path.dirname(os.path.abspath(audio_list))
+        items = []
+        with open(audio_list, "r", encoding="utf-8") as f:
+            for n, line in enumerate(f):
+                line = line.rstrip("\r\n")
+                if not line.strip():
+                    continue
+                path, tab, text = line.partition("\t")
+                if not tab or not path.strip():
+                    raise ValueError(f"{audio_list}:{n + 1}: expected `path<TAB>transcript`")
+                path = path.strip()
+                items.append((path if os.path.isabs(path) else os.path.join(base, path), text.strip()))
+        for sub in ("codes", "mels"):
+            os.makedirs(os.path.join(out_dir, sub), exist_ok=True)
+        records = []
+        for at in range(0, len(items), max(1, int(batch_clips))):
+            chunk = items[at: at + max(1, int(batch_clips))]
+            decoded = [self._decode(p) for p, _ in chunk]
+            codes, mels = self.audio_codes([(d[0], d[1]) for d in decoded])
+            for k, ((path, text), (planar, sr), c, m) in enumerate(zip(chunk, decoded, codes, mels)):
+                name = f"{at + k:06d}_{os.path.splitext(os.path.basename(path))[0]}.npy"
+                rec = dict(audio=path, text=text, codes=os.path.join(out_dir, "codes", name), mels=os.path.join(out_dir, "mels", name),
+                           duration=float(planar.shape[-1]) / float(sr))
+                np.save(rec["codes"], c.cpu().numpy().astype(np.int64)[None])
+                np.save(rec["mels"], m.to(torch.float32).cpu().numpy().reshape(1, m.shape[-2], m.shape[-1]))
+                records.append(rec)
+        with open(os.path.join(out_dir, "metadata.jsonl"), "w", encoding="utf-8") as f:
+            for rec in records:
+                f.write(json.dumps(rec, ensure_ascii=False) + "\n")
+        return records
+
     def _finish(self, wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, sampling_rate=24000, output=None,
                 post=None, speed=None):
         end_time = time.perf_counter()

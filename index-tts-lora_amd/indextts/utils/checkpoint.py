@@ -61,3 +61,45 @@ def load_checkpoint(model, model_pth: str) -> dict:
     if isinstance(ckpt, dict) and "speakers" in ckpt:
         cfg["speakers"] = ckpt["speakers"]
     return cfg
+
+
+def check_dvae(sd: dict, vq) -> None:
+    """Hold a DVAE state dict (the reference's DiscreteVAE: encoder.N.*, codebook.embed) against the config's `vqvae:` block;
+    a ValueError names the first disagreement.  Only what the tokenizer reads is looked at (the decoder half is not)."""
+    get = (lambda k, d=None: vq[k] if k in vq else d)
+    if int(get("positional_dims", 1)) != 1 or bool(get("use_transposed_convs", False)) or int(get("num_layers", 2)) != 2:
+        raise ValueError("vqvae: the tokenizer is built for positional_dims 1, num_layers 2, use_transposed_convs false")
+    ch, hid, cd, nt = int(get("channels")), int(get("hidden_dim")), int(get("codebook_dim")), int(get("num_tokens"))
+    ks, nres = int(get("kernel_size", 3)), int(get("num_resnet_blocks", 0))
+    want = {"encoder.0.0.weight": (hid, ch, ks), "encoder.1.0.weight": (2 * hid, hid, ks), "codebook.embed": (cd, nt),
+            f"encoder.{2 + nres}.weight": (cd, 2 * hid, 1)}
+    for i in range(nres):
+        want[f"encoder.{2 + i}.net.0.weight"] = (2 * hid, 2 * hid, 3)
+        want[f"encoder.{2 + i}.net.2.weight"] = (2 * hid, 2 * hid, 3)
+        want[f"encoder.{2 + i}.net.4.weight"] = (2 * hid, 2 * hid, 1)
+    for k, shape in want.items():
+        if k not in sd:
+            raise ValueError(f"dvae checkpoint: {k} is missing (the config's vqvae block asks for it)")
+        if tuple(sd[k].shape) != shape:
+            raise ValueError(f"dvae checkpoint: {k} has the shape {tuple(sd[k].shape)}, the config's vqvae block says {shape}")
+    extra = [k for k in sd if k.startswith("encoder.") and k.endswith(".weight") and k not in want]
+    if extra:
+        raise ValueError(f"dvae checkpoint: {extra[0]} is not a layer of the config's vqvae block")
+
+
+def load_dvae(cfg, model_dir: str, path=None) -> dict:
+    """The DVAE's state dict for the acoustic tokenizer (indextts/vqvae/dvae.py): `path`, or the config's dvae_checkpoint under
+    model_dir; a bare state dict or {'model': sd}; checked against the config's `vqvae:` block."""
+    if path is None:
+        if "dvae_checkpoint" not in cfg:
+            raise ValueError("load_dvae: the config names no dvae_checkpoint and no path was given")
+        path = cfg["dvae_checkpoint"]
+    if not os.path.isabs(path) and model_dir and not os.path.exists(path):
+        path = os.path.join(model_dir, path)
+    if "vqvae" not in cfg:
+        raise ValueError("load_dvae: the config has no vqvae block to hold the checkpoint against")
+    ckpt = _safe_load(path)
+    sd = ckpt["model"] if isinstance(ckpt, dict) and "model" in ckpt and "codebook.embed" not in ckpt else ckpt
+    sd = {k: v for k, v in sd.items() if torch.is_tensor(v) and (k.startswith("encoder.") or k == "codebook.embed")}
+    check_dvae(sd, cfg["vqvae"])
+    return {k: v.float() for k, v in sd.items()}
