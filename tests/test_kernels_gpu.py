@@ -195,6 +195,8 @@ CONV_CASES = [
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16])
 @pytest.mark.parametrize("case", CONV_CASES)
 def test_gemm_conv_conv1d(nat, dtype, case):
+    """One global max-abs figure against torch's own convolution.  The per-element fp64 pins of these forms are
+    tests/test_vocoder_kernels_gpu.py (16-bit) and tests/test_vocoder_fp32_kernels_gpu.py (fp32)."""
     B, T, Cin, Cout, k, dil = case
     x = rnd(B, T, Cin, seed=40).to(dtype)  # channels-last
     w = (rnd(Cout, Cin, k, seed=41) * (1.0 / (Cin * k) ** 0.5)).to(dtype)
@@ -260,6 +262,8 @@ def test_gemm_conv_ragged_batch_equals_single_runs(nat, dtype, case):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
 @pytest.mark.parametrize("C", [24, 48, 96, 128])
 def test_aa_snake_ragged_batch_equals_single_runs(nat, dtype, C):
+    """The activation against itself.  Its fp64 pins, ragged lengths included, are tests/test_vocoder_kernels_gpu.py (16-bit) and
+    tests/test_vocoder_fp32_kernels_gpu.py (fp32)."""
     from indextts.BigVGAN.models import kaiser_sinc_filter
     f = kaiser_sinc_filter()
     lens = [1, 777, 0, 76, 77, 500, 13]
@@ -296,6 +300,8 @@ def convtr_as_conv(w, u):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
 @pytest.mark.parametrize("case", UPS)
 def test_gemm_conv_transposed(nat, dtype, case):
+    """One global max-abs figure against torch's transposed convolution.  The per-element fp64 pins of the six up-samplers are
+    tests/test_vocoder_kernels_gpu.py (16-bit) and tests/test_vocoder_fp32_kernels_gpu.py (fp32)."""
     B, T, Cin, Cout, k, u = case
     x = rnd(B, T, Cin, seed=50).to(dtype)
     w = (rnd(Cin, Cout, k, seed=51) * (1.0 / (Cin * k / u) ** 0.5)).to(dtype)
@@ -489,6 +495,8 @@ def test_sample_finish_and_force(nat):
 
 
 def test_tanh_pcm(nat):
+    """One loose check.  tests/test_vocoder_fp32_kernels_gpu.py pins tanh_pcm to tanh64 in every input type, with the stride loop, the
+    clamp and the PCM truncation."""
     x = rnd(3, 1000, seed=90, scale=2.0)
     wav = torch.empty_like(x)
     pcm = torch.empty(3, 1000, dtype=torch.int16, device=DEV)

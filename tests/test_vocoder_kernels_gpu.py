@@ -36,6 +36,8 @@ import torch
 
 import weights
 from fp64_check import check, excess, must_fail, ulp  # noqa: F401  (shared with test_decode_kernels_gpu.py)
+from vocoder_refs import (EHW, EPI_MATRIX, EPIS, act_bound, act_ref, conv_bound, conv_ref, perturbed_filter, perturbed_tap,  # noqa: F401
+                          shifted_rows, swapped_last, ups_slice)
 
 pytestmark = pytest.mark.gpu
 
@@ -75,44 +77,7 @@ def form(nat, expect=None, pin=True):
 
 
 # ------------------------------------------------------------------------------------------------- convolution
-def conv_ref(x, w, taps, off0, dil, Tout, bias=None, bias2=None, resid=None, yprev=None, scale=1.0, vr=None):
-    """fp64 y[b,t,n] = (sum_j sum_c x[b, t+off0+j*dil, c] W[j,c,n] + bias[n] + bias2[b,n] + resid) * scale + y_prev, zero
-    padding (and rows past vr[b] read as zeros); returns (ref, S) with S the sum of |terms| of the bound."""
-    B, Tin, Cin = x.shape
-    N = w.shape[2]
-    xd = x.double()
-    if vr is not None:
-        xd = xd * (torch.arange(Tin, device=DEV)[None, :] < vr.long()[:, None])[..., None]
-    wd = w.double()
-    acc = torch.zeros(B, Tout, N, dtype=torch.float64, device=DEV)
-    mag = torch.zeros_like(acc)
-    for j in range(taps):
-        s = off0 + j * dil
-        lo, hi = max(0, -s), min(Tout, Tin - s)
-        if hi > lo:
-            xs = xd[:, lo + s:hi + s]
-            acc[:, lo:hi] += xs @ wd[j]
-            mag[:, lo:hi] += xs.abs() @ wd[j].abs()
-    for t in (bias, None if bias2 is None else bias2[:, None, :], resid):
-        if t is not None:
-            acc = acc + t.double()
-            mag = mag + t.double().abs()
-    sc = float(np.float32(scale))
-    acc, mag = acc * sc, mag * abs(sc)
-    if yprev is not None:
-        acc, mag = acc + yprev.double(), mag + yprev.double().abs()
-    return acc, mag
-
-
-def conv_bound(ref, mag, dtype):
-    return ulp(ref, dtype) + 2.0 ** -21 * mag
-
-
-# epilogues: (residual, accumulate into y, scale, per-batch bias2); the vocoder's second convolutions use "resid",
-# "resid_third" (first AMP block of a stage) and "resid_acc_third" (the other two), never with bias2
-EPIS = {"bias": (False, False, 1.0, False), "resid": (True, False, 1.0, False), "resid_third": (True, False, 1.0 / 3.0, False),
-        "resid_acc_third": (True, True, 1.0 / 3.0, False), "bias2_resid_acc": (True, True, 1.0 / 3.0, True)}
-EPI_MATRIX = ("bias", "resid", "resid_acc_third", "bias2_resid_acc")
+# conv_ref, conv_bound, EPIS / EPI_MATRIX and the control builders: tests/vocoder_refs.py
 
 
 def run_conv(nat, dtype, B, T, C, N, k, d, epi, seed, vr=None, controls=False, expect=None, pin=True):
@@ -148,18 +113,12 @@ def run_conv(nat, dtype, B, T, C, N, k, d, epi, seed, vr=None, controls=False, e
     if controls:
         bound = conv_bound(ref, mag, dtype)
         tb = min(T - 2, 128 if T > 200 else T // 2)
-        xs = x.clone()
-        xs[:, tb:-1] = x[:, tb + 1:]
-        r_bad, _ = conv_ref(xs, w, k, off0, d, T, bias=bias, vr=vr, **rk)
+        r_bad, _ = conv_ref(shifted_rows(x, tb), w, k, off0, d, T, bias=bias, vr=vr, **rk)
         must_fail(what, "input shifted by one row at a tile boundary", y, r_bad, bound, valid)
-        wb = w.double().clone()
-        wb[k // 2] *= 1 + 2.0 ** -9
-        r_bad, _ = conv_ref(x, wb, k, off0, d, T, bias=bias, vr=vr, **rk)
+        r_bad, _ = conv_ref(x, perturbed_tap(w, k // 2, 2.0 ** -9), k, off0, d, T, bias=bias, vr=vr, **rk)
         must_fail(what, "one weight tap off by 2^-9 relative", y, r_bad, bound, valid)
         if N > 1:
-            wb = w.clone()
-            wb[..., [0, 1]] = w[..., [1, 0]]
-            r_bad, _ = conv_ref(x, wb, k, off0, d, T, bias=bias, vr=vr, **rk)
+            r_bad, _ = conv_ref(x, swapped_last(w), k, off0, d, T, bias=bias, vr=vr, **rk)
             must_fail(what, "two output channels of a 16-channel block exchanged", y, r_bad, bound, valid)
     return f
 
@@ -248,15 +207,13 @@ def run_upsampler(nat, dtype, B, Tn, cin, c, k, u, seed, expect=None, pin=True, 
 
     def ref_of(tp):
         acc, mag = conv_ref(x, tp, tp.shape[0], off0, 1, rows, bias=bias, bias2=b2)
-        lo = -shift
-        return (acc.reshape(B, -1)[:, lo:lo + Tu * c].reshape(B, Tu, c), mag.reshape(B, -1)[:, lo:lo + Tu * c].reshape(B, Tu, c))
+        return ups_slice(acc, shift, B, Tu, c), ups_slice(mag, shift, B, Tu, c)
 
     ref, mag = ref_of(taps)
     what = f"{f} upsampler B={B} Tn={Tn} {cin}->{c} k={k} u={u}"
     check(what, y, ref, conv_bound(ref, mag, dtype))
     if controls:
-        tb = taps.double().clone()
-        tb[-1] *= 1 + 2.0 ** -9
+        tb = perturbed_tap(taps, taps.shape[0] - 1, 2.0 ** -9)
         must_fail(what, "one weight tap off by 2^-9 relative", y, ref_of(tb)[0], conv_bound(ref, mag, dtype))
     return f
 
@@ -288,83 +245,7 @@ def test_pre_and_post_conv_fp64(nat):
 
 
 # ------------------------------------------------------------------------------------------------- activation
-def act_ref(x, al, be, up, dn, mfma, lens=None, end_pad="replicate"):
-    """fp64 anti-aliased SnakeBeta of x [B,T,C] (storage type), channels last, each element at its own length.
-
-    u[2q] = 2 sum_{d=-3..2} x[q+d] up[5-2d], u[2q+1] = 2 sum_{d=-2..3} x[q+d] up[6-2d] (x index clamped: replicate padding);
-    s = u + sin^2(u e^alpha) / (e^beta + 1e-9);  y[t] = sum_j down[j] s[clamp(2t + j - 5, 0, 2n - 1)].
-    mfma: s is rounded to fp16 before the down filter, as the MFMA form does.  Returns (y_ref, E, ok_len mask) with E the
-    fp32-level error budget of `act_bound`."""
-    B, T, C = x.shape
-    ys, es = torch.zeros(B, T, C, dtype=torch.float64, device=DEV), torch.zeros(B, T, C, dtype=torch.float64, device=DEV)
-    up2 = [2.0 * float(np.float32(v)) for v in up]
-    dn_ = [float(np.float32(v)) for v in dn]
-    ea = torch.exp(al.double())
-    ib = 1.0 / (torch.exp(be.double()) + float(np.float32(1e-9)))
-    groups = [(list(range(B)), T)] if lens is None else [([b], n) for b, n in enumerate(lens) if n > 0]
-    for bs, n in groups:
-        xd = x[bs, :n].double()
-        q = torch.arange(n, device=DEV)
-        if end_pad == "replicate":
-            xat = lambda dd: xd[:, torch.clamp(q + dd, 0, n - 1)]
-        else:     # negative control: zero padding past the end
-            xat = lambda dd: torch.where((q + dd < n)[None, :, None], xd[:, torch.clamp(q + dd, 0, n - 1)], torch.zeros_like(xd))
-        ue = sum(xat(dd) * up2[5 - 2 * dd] for dd in range(-3, 3))
-        uo = sum(xat(dd) * up2[6 - 2 * dd] for dd in range(-2, 4))
-        uae = sum(xat(dd).abs() * abs(up2[5 - 2 * dd]) for dd in range(-3, 3))
-        uao = sum(xat(dd).abs() * abs(up2[6 - 2 * dd]) for dd in range(-2, 4))
-        xae = sum(xat(dd).abs() for dd in range(-3, 3))
-        xao = sum(xat(dd).abs() for dd in range(-2, 4))
-        il = lambda a, b: torch.stack([a, b], 2).reshape(len(bs), 2 * n, C)
-        u, ua, xa = il(ue, uo), il(uae, uao), il(xae, xao)
-        th = u * ea
-        s = u + ib * torch.sin(th) ** 2
-        # fp32-level error of the kernel's s: up-filter sums (+ the hi/lo split of the fp16 tap matrices in the MFMA form)
-        # carried through ds/du = 1 + (ib e^alpha) sin 2θ, the phase (fp32 e^alpha, the products and the 1/2pi scaling:
-        # a few 2^-24 |θ|), the hardware sine (EHW), and the fp32 roundings of s itself
-        du = 2.0 ** -20 * ua + ((2.0 ** -22 * ua + 2.0 ** -25 * xa) if mfma else 0.0)
-        e_s = du * (1 + ib * ea) + ib * (2.0 ** -20 * th.abs() + 2 * EHW) + 2.0 ** -21 * (u.abs() + ib)
-        if mfma:
-            s16 = s.to(F16).double()
-            near = (0.5 * ulp(s, F16) - (s - s16).abs()) <= 2 * e_s     # may round to the neighbour: one fp16 ulp more
-            extra = torch.where(near, ulp(s, F16), torch.zeros_like(s))
-            s = s16
-        else:
-            extra = torch.zeros_like(s)
-        m = torch.arange(n, device=DEV)
-        if end_pad == "replicate":
-            sat = lambda j: s[:, torch.clamp(2 * m + j - 5, 0, 2 * n - 1)]
-        else:
-            sat = lambda j: torch.where((2 * m + j - 5 < 2 * n)[None, :, None], s[:, torch.clamp(2 * m + j - 5, 0, 2 * n - 1)],
-                                        torch.zeros_like(s[:, :n]))
-        at = lambda a, j: a[:, torch.clamp(2 * m + j - 5, 0, 2 * n - 1)]
-        y = sum(dn_[j] * sat(j) for j in range(12))
-        sa = sum(abs(dn_[j]) * at(s, j).abs() for j in range(12))
-        e = 2.0 ** -20 * sa + sum(abs(dn_[j]) * (at(e_s, j) + at(extra, j)) for j in range(12))
-        if mfma:      # the down filter's hi/lo tap split
-            e = e + sum((2.0 ** -22 * abs(dn_[j]) + 2.0 ** -25) * at(s, j).abs() for j in range(12))
-        ys[bs, :n] = y
-        es[bs, :n] = e
-    ok = None
-    if lens is not None:
-        ok = (torch.arange(T, device=DEV)[None, :] < torch.tensor(lens, device=DEV)[:, None])[..., None]
-    return ys, es, ok
-
-
-# absolute error allowance of the hardware sine (v_sin_f32; the MFMA form reduces its argument to [0, 1) revolutions first)
-EHW = 2.0 ** -19
-
-
-def act_bound(ref, e, dtype):
-    """Derivation.  The kernel's value before its last rounding differs from the reference (same operands, float64) by
-    at most E:  the up-filter sums (fp32 fma chains, or MFMAs with fp16 hi + lo tap matrices exact to ~2^-22 relative and
-    2^-25 absolute), carried into s through ds/du = 1 + (ib e^alpha) sin(2θ);  the phase error of θ = u e^alpha (fp32
-    e^alpha, product, 1/2pi scaling: 2^-20 |θ| is ~4x their sum) and the hardware sine;  the fp32 roundings of s;  the
-    down-filter sums (2^-20 sum |down s|: 12 fp32 roundings, or the hi/lo MFMAs).  In the MFMA form s is rounded to fp16
-    in LDS: the reference rounds it too, and where the reference s lies within (2x its fp32 error) of an fp16 rounding
-    midpoint the kernel may round it the other way -- one fp16 ulp of s times |down[j]| more.  The final rounding to the
-    storage type adds half an ulp at the reference value.  Bound = ulp/2 + 2 E (2: slack on the fp32-level constants)."""
-    return 0.5 * ulp(ref, dtype) + 2.0 * e
+# act_ref, act_bound, EHW: tests/vocoder_refs.py
 
 
 def run_act(nat, fir, dtype, B, T, C, seed, expect=None, lens=None, xscale=1.0, al=None, be=None, controls=False, pin=True,
@@ -390,13 +271,9 @@ def run_act(nat, fir, dtype, B, T, C, seed, expect=None, lens=None, xscale=1.0, 
         assert (y[past] == 7.0).all(), f"{what}: rows past a length were written"
     if controls:
         tb = 128 if T > 256 else T // 2
-        xs = x.clone()
-        xs[:, tb:-1] = x[:, tb + 1:]
-        must_fail(what, "input shifted by one row at a tile boundary", y, act_ref(xs, al, be, up, dn, mfma, lens)[0], bound, ok)
+        must_fail(what, "input shifted by one row at a tile boundary", y, act_ref(shifted_rows(x, tb), al, be, up, dn, mfma, lens)[0], bound, ok)
         must_fail(what, "zero padding at the sequence end", y, act_ref(x, al, be, up, dn, mfma, lens, end_pad="zero")[0], bound, ok)
-        j = int(np.argmax(np.abs(dn)))
-        dnb = np.array(dn, dtype=np.float64)
-        dnb[j] *= 1 + 2.0 ** -9
+        dnb = perturbed_filter(dn, 2.0 ** -9)
         must_fail(what, "one down-filter tap off by 2^-9 relative", y, act_ref(x, al, be, up, dnb, mfma, lens)[0], bound, ok)
         if f.endswith("pair>"):     # two batch elements share a 48-channel slice: swap a channel across the pair
             xs = x.clone()
@@ -404,9 +281,7 @@ def run_act(nat, fir, dtype, B, T, C, seed, expect=None, lens=None, xscale=1.0, 
             must_fail(what, "channel 5 of the two paired elements exchanged", y, act_ref(xs, al, be, up, dn, mfma, lens)[0], bound, ok)
         else:
             must_fail(what, "alpha and beta swapped", y, act_ref(x, be, al, up, dn, mfma, lens)[0], bound, ok)
-            xs = x.clone()
-            xs[..., [0, 1]] = x[..., [1, 0]]
-            must_fail(what, "two channels of a 16-channel block exchanged", y, act_ref(xs, al, be, up, dn, mfma, lens)[0], bound, ok)
+            must_fail(what, "two channels of a 16-channel block exchanged", y, act_ref(swapped_last(x), al, be, up, dn, mfma, lens)[0], bound, ok)
     return f
 
 
