@@ -95,6 +95,98 @@ def extract_codes_main(argv):
     print(f">> [codes] {len(records)} clips, {sum(r['duration'] for r in records):.1f} s of audio -> {args.out}")
 
 
+def score_rows(tts, cond_mel, items, voice_ids=(None,), voice_names=(None,), batch_clips=16):
+    """The records of `indextts --score`: for every clip of items [(path, transcript)] and every voice one dict -- audio, text, voice
+    and the fields of IndexTTS.score_codes with the arrays as lists.  The clips' codes are taken once per chunk
+    (IndexTTS.audio_codes) and scored under each voice in turn."""
+    step = max(1, int(batch_clips))
+    for at in range(0, len(items), step):
+        chunk = items[at: at + step]
+        codes, _ = tts.audio_codes([p for p, _ in chunk])
+        rows = [tts.text_token_row(t) for _, t in chunk]
+        for vid, vname in zip(voice_ids, voice_names):
+            recs = tts.score_codes(cond_mel, rows, codes, adapter_ids=None if vid is None else [vid] * len(chunk))
+            for (path, text), r in zip(chunk, recs):
+                yield dict(audio=path, text=text, voice=vname, **{k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in r.items()})
+
+
+def read_audio_list(path):
+    """[(audio path, transcript)] of a `path<TAB>transcript` list; a relative audio path is relative to the list."""
+    base = os.path.dirname(os.path.abspath(path))
+    items = []
+    with open(path, "r", encoding="utf-8") as f:
+        for n, line in enumerate(f):
+            line = line.rstrip("\r\n")
+            if not line.strip():
+                continue
+            audio, tab, text = line.partition("\t")
+            if not tab or not audio.strip():
+                raise ValueError(f"{path}:{n + 1}: expected `path<TAB>transcript`")
+            audio = audio.strip()
+            items.append((audio if os.path.isabs(audio) else os.path.join(base, audio), text.strip()))
+    return items
+
+
+def score_main(argv):
+    """`indextts --score LIST -v PROMPT --out FILE.jsonl [--voices FILE ...]`: how likely is every clip of an audio list
+    (`path<TAB>transcript` per line, the format of --extract-codes) under the model -- and, with --voices, under each voice file
+    (IndexTTS.load_voice) -- in the voice of the prompt: one JSON line per clip and voice (score_rows).  -v is required: the
+    decoder scores codes in the voice of a reference recording, as it synthesises them."""
+    import argparse
+    import json
+    parser = argparse.ArgumentParser(prog="indextts --score", description="IndexTTS: likelihood of recordings' mel codes")
+    parser.add_argument("--score", type=str, required=True, metavar="LIST", help="audio list: path<TAB>transcript per line")
+    parser.add_argument("--out", type=str, required=True, metavar="FILE.jsonl", help="one JSON record per clip and voice")
+    parser.add_argument("-v", "--voice", type=str, required=True, help="reference (prompt) audio file, wav")
+    parser.add_argument("--voices", type=str, nargs="*", default=[], metavar="FILE", help="voice files (--extract-voice); none: the base model")
+    parser.add_argument("--dvae", type=str, default=None, metavar="CKPT", help="DVAE checkpoint (default: the config's dvae_checkpoint)")
+    parser.add_argument("--batch-clips", type=int, default=16, metavar="N", help="clips per ragged batch")
+    parser.add_argument("-c", "--config", type=str, default="checkpoints/config.yaml", help="config file")
+    parser.add_argument("--model_dir", type=str, default="checkpoints", help="model directory")
+    parser.add_argument("--fp32", action="store_true", default=False, help="fp32 GPT weights (default: half precision when available)")
+    parser.add_argument("-d", "--device", type=str, default=None, help="device (cuda:N); CPU/MPS are not supported")
+    args = parser.parse_args(argv)
+    for path, what in ((args.score, "audio list"), (args.voice, "prompt"), (args.config, "config")) + tuple((v, "voice file") for v in args.voices):
+        if not os.path.exists(path):
+            print(f"[error] {what} {path} does not exist")
+            sys.exit(1)
+    if args.batch_clips < 1:
+        print("[error] --batch-clips must be at least 1")
+        sys.exit(1)
+    try:
+        items = read_audio_list(args.score)
+    except ValueError as e:
+        print(f"[error] {e}")
+        sys.exit(1)
+    import torch
+    if args.device is None:
+        if not torch.cuda.is_available():
+            print("[error] no GPU visible: this build needs an AMD GPU (no CPU path)")
+            sys.exit(1)
+        args.device = "cuda:0"
+    from indextts.infer import IndexTTS
+    tts = IndexTTS(cfg_path=args.config, model_dir=args.model_dir, is_fp16=not args.fp32, device=args.device)
+    try:
+        tts.load_tokenizer(args.dvae)
+        cond_mel = tts.prompt_mels([args.voice])[0]
+        ids, names = [None], [None]
+        if args.voices:
+            loaded = [tts.load_voice(v) for v in args.voices]
+            rank = max(int(A.shape[0]) for ad, _ in loaded for A, _ in ad.values())
+            # the pool's limit is slots x (rank padded to 16) <= 512; a batch scores under ONE voice, so few slots do
+            tts.attach_voice_pool(slots=max(1, min(len(loaded), 512 // ((rank + 15) // 16 * 16))), rank=rank)
+            ids, names = [tts.add_voice(ad, sc) for ad, sc in loaded], list(args.voices)
+        n = 0
+        with open(args.out, "w", encoding="utf-8") as f:
+            for rec in score_rows(tts, cond_mel, items, ids, names, args.batch_clips):
+                f.write(json.dumps(rec, ensure_ascii=False) + "\n")
+                n += 1
+    except (ValueError, OSError, RuntimeError) as e:
+        print(f"[error] {e}")
+        sys.exit(1)
+    print(f">> [score] {n} records -> {args.out}")
+
+
 def main(argv=None):
     import argparse
     argv = sys.argv[1:] if argv is None else list(argv)
@@ -102,6 +194,8 @@ def main(argv=None):
         return extract_voice_main(argv)
     if any(a == "--extract-codes" or a.startswith("--extract-codes=") for a in argv):
         return extract_codes_main(argv)
+    if any(a == "--score" or a.startswith("--score=") for a in argv):
+        return score_main(argv)
     parser = argparse.ArgumentParser(description="IndexTTS command line (MI355X build)")
     parser.add_argument("text", type=str, help="text to synthesise")
     parser.add_argument("-v", "--voice", type=str, required=True, help="reference (prompt) audio file, wav")

@@ -385,3 +385,56 @@ class UnifiedVoice:
         return mel_part[:, :-2]
 
     __call__ = forward
+
+    # ---- likelihood of given tokens ------------------------------------------------------------------------------
+    def score_engine(self):
+        """The ScoreEngine (gpt/score.py) over this model's engine and the heads of the checkpoint it was loaded from; built on
+        first use, rebuilt when the engine is."""
+        from .score import ScoreEngine
+        if self.engine is None:
+            raise RuntimeError("call post_init_gpt2_config() first")
+        se = getattr(self, "_score", None)
+        if se is None or se[0] is not self.engine:
+            se = self._score = (self.engine, ScoreEngine(self.engine, self._sd))
+        return se[1]
+
+    def score(self, speech_conditioning_latent, text_inputs, text_lengths, mel_codes, wav_lengths, cond_mel_lengths=None,
+              conds=None, adapter_ids=None, adapter_mix=None):
+        """What model.py:548-604 computes without return_latent, per position and without its logits: the padding and alignment of
+        forward (:565-588), the teacher-forced latent pass, then both heads through the ScoreEngine.
+        -> dict: text_nll / text_rank / text_best / text_lse [B, L + 2] and mel_nll / mel_rank / mel_best / mel_lse [B, T + 2]
+        (position p scores text_targets / mel_targets [:, p], also returned), loss_text and loss_mel: the means over ALL
+        positions, which is what the reference's F.cross_entropy returns."""
+        from .score import aligned_targets
+        eng, dev = self.engine, self.device
+        se = self.score_engine()
+        B = int(text_inputs.shape[0])
+        if adapter_ids is not None:
+            adapter_ids = eng._row_adapters(adapter_ids, B)
+        if adapter_mix is not None:
+            adapter_mix = eng._voices(adapter_ids, adapter_mix, B)[1]
+        if conds is None:
+            conds = self.get_conditioning(speech_conditioning_latent, cond_mel_lengths)
+        text_inputs = text_inputs.to(dev).long()
+        mel_codes = mel_codes.to(dev).long()
+        text_lengths = torch.as_tensor(text_lengths).to(dev).long().reshape(-1)
+        wav_lengths = torch.as_tensor(wav_lengths).to(dev).reshape(-1)
+        mel_len = torch.ceil(wav_lengths.float() / self.mel_length_compression).long() + 1
+        tt = aligned_targets(text_inputs, text_lengths, self.stop_text_token)
+        mt = aligned_targets(mel_codes, mel_len, self.stop_mel_token)
+        ti = F.pad(tt[:, :-1], (1, 0), value=self.start_text_token)
+        mi = F.pad(mt[:, :-1], (1, 0), value=self.start_mel_token)
+        te = eng.text_emb[ti] + eng.text_pos[: ti.shape[1]]
+        me = eng.mel_emb[mi] + eng.mel_pos[: mi.shape[1]]
+        c = conds.to(dev, torch.float32)
+        if c.shape[0] == 1 and B > 1:
+            c = c.expand(B, -1, -1)
+        enc = eng.latent(torch.cat([c, te, me], dim=1), adapter_ids=adapter_ids, adapter_mix=adapter_mix)[:, c.shape[1]:]
+        out = {}
+        for name, rows, tgt in (("text", enc[:, : ti.shape[1]], tt), ("mel", enc[:, -mi.shape[1]:], mt)):
+            r = se.score(rows.reshape(-1, rows.shape[-1]), tgt.reshape(-1), head=name)
+            for k in ("nll", "rank", "best", "lse"):
+                out[f"{name}_{k}"] = r[k].view(B, -1)
+            out[f"{name}_targets"] = tgt
+            out[f"loss_{name}"] = r["nll"].mean()
+        return out

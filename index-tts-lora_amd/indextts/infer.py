@@ -735,7 +735,7 @@ class IndexTTS:
         return g.engine.decode(max_mel_tokens, sp, force_stop=extra.pop("force_stop", None))
 
     def _latents(self, conds, text_rows: List[torch.Tensor], code_rows: List[torch.Tensor], reuse_prefix=False, cache_rows=None,
-                 adapter_ids=None, adapter_mix=None):
+                 adapter_ids=None, adapter_mix=None, whole=False):
         """Teacher-forced pass for several utterances at once (right-padded; causal attention makes padding inert).
         Each row reproduces gpt(cond, text, [L], codes, code_len*1024, return_latent=True) of infer.py:864-874.
         The [cond | text | mel] embedding batch is assembled with two gathers from index arrays built on the host (one
@@ -744,11 +744,13 @@ class IndexTTS:
         has touched its KV cache since -- then only the mel rows are recomputed and the prompt's keys / values come from the
         cache (GPTEngine.latent_mel_rows: same bits, ~40 % fewer GEMM rows).
         adapter_ids: the rows' adapters of an attached bank (with reuse_prefix: the ids the cached prompt was prefilled under).
-        adapter_mix: or the rows' mixes of adapters, under the same rule."""
+        adapter_mix: or the rows' mixes of adapters, under the same rule.
+        whole: return (enc [B, S, D], nc) instead -- every real row of the pass, text rows included (score_codes); row b holds
+        cond at 0 .. nc - 1, start_text | text | stop_text behind it, then start_mel | codes | stop_mel."""
         g, eng, dev = self.gpt, self.gpt.engine, self.device
         if conds.shape[0] not in (1, len(text_rows)):    # a subset of the rows with all rows' conds would speak in the wrong voices
             raise ValueError(f"_latents: conds holds {conds.shape[0]} prompts for {len(text_rows)} rows (one for all, or one per row)")
-        if reuse_prefix and self.reuse_prompt_kv and eng.kv_dtype is None:   # (an FP8 cache holds codes: the prompt rows are recomputed)
+        if reuse_prefix and not whole and self.reuse_prompt_kv and eng.kv_dtype is None:   # (an FP8 cache holds codes: the prompt rows are recomputed)
             cl = [int(c.numel()) for c in code_rows]
             flat = torch.cat([c.reshape(-1).long() for c in code_rows]).cpu().numpy() if code_rows else np.zeros(0, np.int64)
             # start | codes | stop of every row and the position of each token in its row, for all rows at once
@@ -794,6 +796,8 @@ class IndexTTS:
         batch[idx[0, :n_t], idx[1, :n_t]] = eng.text_emb[idx[2, :n_t]] + eng.text_pos[idx[3, :n_t]]
         batch[idx[0, n_t:], idx[1, n_t:]] = eng.mel_emb[idx[2, n_t:]] + eng.mel_pos[idx[3, n_t:]]
         enc = eng.latent(batch, lengths=[s0 + n + 2 for s0, n in spans], adapter_ids=adapter_ids, adapter_mix=adapter_mix)   # real rows only (cond | text | mel incl. start/stop)
+        if whole:
+            return enc, nc
         return [enc[i, s0: s0 + n] for i, (s0, n) in enumerate(spans)]
 
     def _latents_incremental(self, st: "_LatentRows", rows, conds, text_rows, code_rows, adapter_ids=None, adapter_mix=None):
@@ -1031,6 +1035,79 @@ class IndexTTS:
             for rec in records:
                 f.write(json.dumps(rec, ensure_ascii=False) + "\n")
         return records
+
+    # ------------------------------------------------------------------------------------------------ likelihood of given codes
+    def score_codes(self, cond_mel, text_token_rows: List[torch.Tensor], code_rows: List[torch.Tensor], adapter_ids=None,
+                    adapter_mix=None):
+        """How likely are these codes under this voice?    A ragged batch -- utterance i is
+        text_token_rows[i] and code_rows[i] -- through the packed teacher-forced latent pass in the voice of cond_mel (one prompt,
+        or a list with one per row, as in infer_batch) and under the rows' adapters, then both output heads through the
+        ScoreEngine.  One record per utterance over its REAL positions: its n codes and the first stop (mel), its L tokens and the
+        first stop (text): nll_mel (the mean), ppl_mel = exp(nll_mel), acc1 / acc10 / acc20 (the share of mel positions whose
+        target is among the head's top 1 / 10 / 20), nll_text, and the per-token arrays mel_nll, mel_rank, mel_best, mel_lse,
+        text_nll, text_rank (numpy).  No token is sampled and no logit is stored."""
+        if len(code_rows) != len(text_token_rows):
+            raise ValueError(f"score_codes: {len(code_rows)} code rows for {len(text_token_rows)} texts")
+        g, eng = self.gpt, self.gpt.engine
+        B = len(text_token_rows)
+        if adapter_ids is not None:
+            adapter_ids = eng._row_adapters([-1 if v is None else int(v) for v in adapter_ids], B)   # (None: the base model)
+        if adapter_mix is not None:
+            adapter_mix = eng._voices(adapter_ids, adapter_mix, B)[1]
+        cond_mel = self._check_prompts(cond_mel, B, {}, "score_codes")
+        conds, _ = self._prompt_features(cond_mel, spk=False)
+        texts = [t.reshape(-1).cpu().long() for t in text_token_rows]
+        codes = [c.reshape(-1).cpu().long() for c in code_rows]
+        enc, nc = self._latents(conds, texts, codes, adapter_ids=adapter_ids, adapter_mix=adapter_mix, whole=True)
+        # position p of a part predicts its token p; the position behind the last token predicts the first stop
+        ri, ci, tgt = ([], []), ([], []), ([], [])
+        for i, (t, c) in enumerate(zip(texts, codes)):
+            for k, (ids, c0, stop) in enumerate(((t, nc, g.stop_text_token), (c, nc + t.numel() + 2, g.stop_mel_token))):
+                ri[k].append(torch.full((ids.numel() + 1,), i))
+                ci[k].append(c0 + torch.arange(ids.numel() + 1))
+                tgt[k].append(torch.cat([ids, torch.tensor([stop])]))
+        se = g.score_engine()
+        res = []
+        for k, head in enumerate(("text", "mel")):
+            rows = enc[torch.cat(ri[k]).to(self.device), torch.cat(ci[k]).to(self.device)]
+            res.append({key: v.cpu().numpy() for key, v in se.score(rows, torch.cat(tgt[k]), head=head).items()})
+        out, at = [], [0, 0]
+        for t, c in zip(texts, codes):
+            nt, nm = t.numel() + 1, c.numel() + 1
+            tx = {key: v[at[0]: at[0] + nt] for key, v in res[0].items()}
+            ml = {key: v[at[1]: at[1] + nm] for key, v in res[1].items()}
+            at = [at[0] + nt, at[1] + nm]
+            nll = float(ml["nll"].astype(np.float64).mean())
+            out.append(dict(nll_mel=nll, ppl_mel=float(np.exp(nll)), acc1=float((ml["rank"] < 1).mean()), acc10=float((ml["rank"] < 10).mean()),
+                            acc20=float((ml["rank"] < 20).mean()), nll_text=float(tx["nll"].astype(np.float64).mean()), mel_nll=ml["nll"],
+                            mel_rank=ml["rank"], mel_best=ml["best"], mel_lse=ml["lse"], text_nll=tx["nll"], text_rank=tx["rank"]))
+        return out
+
+    def text_token_row(self, text):
+        """A transcript as the token-id row score_codes takes: a string is tokenized as infer() does; a row is passed on."""
+        if isinstance(text, str):
+            return torch.tensor(self.tokenizer.convert_tokens_to_ids(self.tokenizer.tokenize(text)), dtype=torch.long)
+        return text
+
+    def score_audio(self, cond_mel, texts, audios, srs=None, adapter_ids=None, adapter_mix=None):
+        """score_codes of recordings: audio_codes(audios, srs) (the tokenizer: load_tokenizer) against their transcripts `texts`
+        (strings, tokenized as infer() does, or token-id rows)."""
+        rows = [self.text_token_row(t) for t in texts]
+        codes, _ = self.audio_codes(audios, srs)
+        return self.score_codes(cond_mel, rows, codes, adapter_ids=adapter_ids, adapter_mix=adapter_mix)
+
+    def rank_voices(self, cond_mel, text, audio_or_codes, voices):
+        """Which voice explains these codes best?  One batch with a row per entry of `voices` (adapter ids of the attached bank or
+        pool; None or -1: the base model), every row the same text (a string or a token-id row) and the same codes (a code
+        tensor, or a recording for audio_codes).  -> [(voice, record of score_codes)] sorted by nll_mel, best first."""
+        voices = list(voices)
+        if torch.is_tensor(audio_or_codes) and not audio_or_codes.is_floating_point():
+            codes = audio_or_codes
+        else:
+            codes = self.audio_codes([audio_or_codes])[0][0]
+        row = self.text_token_row(text)
+        recs = self.score_codes(cond_mel, [row] * len(voices), [codes] * len(voices), adapter_ids=voices)
+        return sorted(zip(voices, recs), key=lambda vr: vr[1]["nll_mel"])
 
     def _finish(self, wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, sampling_rate=24000, output=None,
                 post=None, speed=None):
