@@ -17,6 +17,9 @@ working:
                           level set on the device, IndexTTS.post_process; 400 for an out-of-range value, and on /tts/stream)
                           (with the field speed, 0.5 .. 2.0: the speaking rate at the same pitch, on the device before the
                           finishing, IndexTTS.infer(speed=...); 400 for an out-of-range value, and on /tts/stream)
+                          (with the field pitch, -12 .. 12 semitones: the voice higher or lower at the duration speed sets, on the
+                          device where speed is applied, IndexTTS.infer(pitch=...); an empty field is none; 400 for a value out
+                          of range or one that takes speed / 2^(pitch / 12) outside 0.5 .. 2.0, and on /tts/stream)
 /tts accepts the reference's multipart form (parsed with the standard library: python-multipart is optional), a urlencoded
 form, or a JSON body with the same field names (the reference's TTSRequest model, api.py:35-50).  One engine instance per
 process, requests are serialised by a lock (the reference's endpoints are effectively serial as well: one global
@@ -64,6 +67,7 @@ class TTSRequest(BaseModel):
     target_rms_db: Optional[float] = None  # /tts only: the RMS of the speech is brought to this level (dBFS)
     peak_db: Optional[float] = None        # /tts only: the peak ceiling (dBFS; -1 under a target); alone: peak normalisation
     speed: Optional[float] = None          # /tts only: the speaking rate, 0.5 .. 2.0 (1.25 a quarter faster), at the same pitch
+    pitch: Optional[float] = None          # /tts only: semitones, -12 .. 12 (the formants move with it), at the duration speed sets
 
 
 def output_of(req):
@@ -76,6 +80,22 @@ def output_of(req):
         return OutputFormat(24000 if req.sample_rate is None else req.sample_rate, req.encoding or "pcm16")
     except ValueError as e:
         raise HTTPException(status_code=400, detail=str(e))
+
+
+def pitch_of(req, streaming=False):
+    """The pitch a request names with pitch, in semitones (None when it names none: the answer is what it has always been); a
+    value outside [-12, 12], or one that with the request's speed takes the time stretch outside [0.5, 2.0], is a 400, and so
+    is the field on /tts/stream -- the chain of lags is not carried across chunks."""
+    if req.pitch is None:
+        return None
+    if streaming:
+        raise HTTPException(status_code=400, detail="pitch: /tts/stream does not change the pitch (use /tts)")
+    from indextts.utils.tempo import pitch_plan
+    try:
+        pitch_plan(req.pitch, req.speed)
+    except ValueError as e:
+        raise HTTPException(status_code=400, detail=str(e))
+    return float(req.pitch)
 
 
 def speed_of(req, streaming=False):
@@ -286,7 +306,7 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
                     upload = up
             else:
                 fields = {k: v[-1] for k, v in urllib.parse.parse_qs(body.decode("utf-8")).items()}
-            fields = {k: (None if isinstance(v, str) and v == "" and k in ("seed", "speaker_id", "prompt_audio_path", "sample_rate", "encoding") + POST_FIELDS else v)
+            fields = {k: (None if isinstance(v, str) and v == "" and k in ("seed", "speaker_id", "prompt_audio_path", "sample_rate", "encoding", "pitch") + POST_FIELDS else v)
                       for k, v in fields.items()}
             return TTSRequest(**fields), upload
         except HTTPException:
@@ -304,6 +324,7 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
         fmt = output_of(req)
         post = post_of(req)
         speed = speed_of(req)
+        pitch = pitch_of(req)
         actual_seed = random.randint(0, 2 ** 32 - 1) if req.seed is None or req.seed == -1 else int(req.seed)
         tmp_path = None
         try:
@@ -330,6 +351,8 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
                 kwargs["post"] = post
             if speed is not None:
                 kwargs["speed"] = speed
+            if pitch is not None:
+                kwargs["pitch"] = pitch
             with lock:
                 t = engine()
                 set_seed(actual_seed)
@@ -374,6 +397,7 @@ def create_app(tts=None, model_dir="checkpoints", config_path="checkpoints/confi
         fmt = output_of(req)
         post_of(req, streaming=True)
         speed_of(req, streaming=True)
+        pitch_of(req, streaming=True)
         actual_seed = random.randint(0, 2 ** 32 - 1) if req.seed is None or req.seed == -1 else int(req.seed)
         tmp_path = None
         if upload is not None:

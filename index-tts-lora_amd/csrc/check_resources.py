@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Build-time resource check: fail if any kernel of the product library -- or of the voice, audio, out, post, tempo, codec and score libraries, whose
+"""Build-time resource check: fail if any kernel of the product library -- or of the voice, audio, out, post, tempo, codec, score and pitch libraries, whose
 objects lie in the same directory -- needs scratch memory or spills registers.
 Reads the AMDGPU metadata (.private_segment_fixed_size, .vgpr_spill_count, .sgpr_spill_count) from the device assembly
 that `hipcc -save-temps=obj` leaves next to each object (build/*-hip-amdgcn-amd-amdhsa-gfx950.s)."""

@@ -238,6 +238,9 @@ def main(argv=None):
     parser.add_argument("--speed", type=float, default=None, metavar="X",
                         help="speaking rate, 0.5 to 2.0: 0.8 is a fifth slower, 1.25 a quarter faster, at the same pitch (WSOLA on "
                              "the device, IndexTTS.infer(speed=...)).  Default: the voice as it is")
+    parser.add_argument("--pitch", type=float, default=None, metavar="SEMITONES",
+                        help="pitch, -12 to 12 semitones: 2 is a whole tone up, at the duration --speed sets (WSOLA and a resampler on "
+                             "the device, IndexTTS.infer(pitch=...)); the formants move with it.  Default: the voice as it is")
     parser.add_argument("-d", "--device", type=str, default=None, help="device (cuda:N); CPU/MPS are not supported")
     args = parser.parse_args(argv)
 
@@ -271,6 +274,14 @@ def main(argv=None):
             fixed_speed(args.speed)
         except ValueError as e:
             fail(f"--speed: {e}")
+    if args.pitch is not None:
+        if args.stream:
+            fail("--pitch does not apply to --stream: the chain of lags is not carried across chunk boundaries")
+        from indextts.utils.tempo import pitch_plan
+        try:
+            pitch_plan(args.pitch, args.speed)
+        except ValueError as e:
+            fail(f"--pitch: {e}")
     if len(args.text.strip()) == 0:
         fail("text is empty")
     if args.stream_parallel < 1:
@@ -319,7 +330,8 @@ def main(argv=None):
         print(f">> [output] saved to: {args.output_path}")
         return
     tts.infer(audio_prompt=args.voice, text=args.text.strip(), output_path=args.output_path, **({} if output is None else {"output": output}),
-              **({} if post is None else {"post": post}), **({} if args.speed is None else {"speed": args.speed}))
+              **({} if post is None else {"post": post}), **({} if args.speed is None else {"speed": args.speed}),
+              **({} if args.pitch is None else {"pitch": args.pitch}))
 
 
 if __name__ == "__main__":

@@ -936,9 +936,39 @@ class IndexTTS:
         return rows[0] if n is None else rows
 
     @staticmethod
+    def _check_pitch(pitch, speed, who, n=None):
+        """What the `pitch=` keyword of infer, infer_fast, infer_batch and infer_queue asks for, beside the call's `speed=` as it
+        was given (and already checked): None when nothing of the feature runs (pitch None or 0, or every entry of a list one of
+        the two) -- the call then takes the speed= path exactly as it always has -- otherwise TempoEngine.plan(pitch, speed), for
+        a call of n utterances a list of n of them (a row without a pitch keeps its speed).  More than 12 semitones either way,
+        a speed / 2^(pitch / 12) outside [0.5, 2.0], a bool, a value that is not finite, a list where one number is expected or
+        a list of another length than n is a ValueError, raised before anything is launched."""
+        if pitch is None:
+            return None
+        try:
+            if isinstance(pitch, (list, tuple)):
+                if n is None:
+                    raise ValueError(f"pitch = {pitch!r}: one number for the call")
+                if len(pitch) != n:
+                    raise ValueError(f"{len(pitch)} pitches for {n} utterances")
+                pitches = list(pitch)
+            else:
+                pitches = [pitch] * (1 if n is None else n)
+            speeds = list(speed) if isinstance(speed, (list, tuple)) else [speed] * len(pitches)
+            plans = [TempoEngine.plan(p, s) for p, s in zip(pitches, speeds)]
+        except ValueError as e:
+            raise ValueError(f"{who}: {e}") from None
+        if all(step is None for _, step in plans):
+            return None
+        return plans[0] if n is None else plans
+
+    @staticmethod
     def _no_speed(kw, who):
         if "speed" in kw:       # (it would otherwise pass for a generation setting and be dropped unseen)
             raise TypeError(f"{who}: the streams do not take speed= -- the chain of lags is not carried across chunk boundaries; "
+                            f"use infer, infer_fast, infer_batch or infer_queue")
+        if "pitch" in kw:       # (pitch is WSOLA and a resampler behind it: the same chain)
+            raise TypeError(f"{who}: the streams do not take pitch= -- the chain of lags is not carried across chunk boundaries; "
                             f"use infer, infer_fast, infer_batch or infer_queue")
 
     def _tempo_engine(self) -> TempoEngine:
@@ -952,6 +982,14 @@ class IndexTTS:
         them; a row at None or 1024 comes back as the same tensor."""
         wavs = [w if w.dim() == 1 and w.dtype == torch.float32 else w.reshape(-1).to(torch.float32) for w in wavs]
         return self._tempo_engine().process(wavs, speeds)
+
+    def _prosody_rows(self, wavs, speeds, plans):
+        """_speed_rows when the call names no pitch (plans None); otherwise the rows at the pitch and speed of their
+        TempoEngine.plan: three launches for all of them."""
+        if plans is None:
+            return self._speed_rows(wavs, speeds)
+        wavs = [w if w.dim() == 1 and w.dtype == torch.float32 else w.reshape(-1).to(torch.float32) for w in wavs]
+        return self._tempo_engine().shift_planned(wavs, plans)
 
     # ------------------------------------------------------------------------------------------------ audio -> codes
     def load_tokenizer(self, path=None, state_dict=None):
@@ -1110,11 +1148,11 @@ class IndexTTS:
         return sorted(zip(voices, recs), key=lambda vr: vr[1]["nll_mel"])
 
     def _finish(self, wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, sampling_rate=24000, output=None,
-                post=None, speed=None):
+                post=None, speed=None, pitch=None):
         end_time = time.perf_counter()
         wav = torch.cat(wavs, dim=1)
-        if speed is not None:       # (S, not 1024) on the joined sentences: one chain of lags, no seam at a join; before post
-            wav = self._speed_rows([wav.reshape(-1)], [speed])[0][None]
+        if speed is not None or pitch is not None:  # on the joined sentences: one chain of lags, no seam at a join; before post
+            wav = self._prosody_rows([wav.reshape(-1)], [speed], None if pitch is None else [pitch])[0][None]
         if post is not None:        # on the joined sentences, so that a pause across a join is one pause and the level one level
             wav = self._post_rows([wav], post)[0][None]
         wav_length = wav.shape[-1] / sampling_rate
@@ -1206,16 +1244,19 @@ class IndexTTS:
 
     # ------------------------------------------------------------------------------------------------ public API
     def infer(self, audio_prompt, text, output_path, verbose=False, max_text_tokens_per_sentence=120, speaker_id=None,
-              *, output=None, post=None, speed=None, **generation_kwargs):
+              *, output=None, post=None, speed=None, pitch=None, **generation_kwargs):
         """Sentence-by-sentence synthesis (infer.py:779-917).  output (an OutputFormat; None = 24 kHz PCM16 as ever): the
         sentences are joined at 24 kHz on the device and encoded once; with an output_path the WAV carries the format's tag,
         without one the call returns (rate, array in the encoding).  post (a PostProcess, IndexTTS.post_process; None = the
         samples as ever): silence trimmed, pauses capped and the level set on the joined sentences, before output.  speed (a number
         in [0.5, 2.0]; None and 1.0 = the samples as ever): the speaking rate -- 0.8 a fifth slower, 1.25 a quarter faster, at
-        the same pitch (WSOLA on the device, indextts/utils/tempo.py) -- on the joined sentences, before post."""
+        the same pitch (WSOLA on the device, indextts/utils/tempo.py) -- on the joined sentences, before post.  pitch (semitones,
+        a number in [-12, 12]; None and 0 = the samples as ever): the voice higher or lower at the duration speed sets -- WSOLA at
+        speed / 2^(pitch / 12), then a resampler by 2^(pitch / 12) on the device; the formants move with the pitch; the two
+        together must keep speed / 2^(pitch / 12) in [0.5, 2.0] -- where speed is applied."""
         IndexTTS._check_output(output, "infer")
         IndexTTS._check_post(post, "infer")
-        speed = IndexTTS._check_speed(speed, "infer")
+        speed, pitch = IndexTTS._check_speed(speed, "infer"), IndexTTS._check_pitch(pitch, speed, "infer")
         if speaker_id is not None:
             if not self.speaker_list:
                 raise ValueError("multi-speaker mode is not enabled; load speaker_info_path first")
@@ -1252,19 +1293,19 @@ class IndexTTS:
             wav = self._vocode(latent, spk)
             torch.cuda.synchronize()
             bigvgan_time += time.perf_counter() - t0
-            wavs.append(wav.cpu() if output is None and post is None and speed is None else wav)
+            wavs.append(wav.cpu() if output is None and post is None and speed is None and pitch is None else wav)
         self._set_gr_progress(0.9, "saving audio...")
         return self._finish(wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, output=output, post=post,
-                            speed=speed)
+                            speed=speed, pitch=pitch)
 
     def infer_fast(self, audio_prompt, text, output_path, verbose=False, max_text_tokens_per_sentence=100,
-                   sentences_bucket_max_size=4, *, output=None, post=None, speed=None, **generation_kwargs):
+                   sentences_bucket_max_size=4, *, output=None, post=None, speed=None, pitch=None, **generation_kwargs):
         """Bucketed batch synthesis (infer.py:595-777): sentences of similar length are decoded as one left-padded batch;
-        latents are computed in one batched pass and vocoded in time-concatenated pairs (chunk_size 2).  output, post, speed: as
-        in infer."""
+        latents are computed in one batched pass and vocoded in time-concatenated pairs (chunk_size 2).  output, post, speed, pitch:
+        as in infer."""
         IndexTTS._check_output(output, "infer_fast")
         IndexTTS._check_post(post, "infer_fast")
-        speed = IndexTTS._check_speed(speed, "infer_fast")
+        speed, pitch = IndexTTS._check_speed(speed, "infer_fast"), IndexTTS._check_pitch(pitch, speed, "infer_fast")
         print(">> [infer] fast mode")
         self._set_gr_progress(0, "initialising...")
         start_time = time.perf_counter()
@@ -1311,15 +1352,15 @@ class IndexTTS:
             wav = self._vocode(torch.cat(lat[i:i + 2], dim=0)[None], spk)
             torch.cuda.synchronize()
             bigvgan_time += time.perf_counter() - t0
-            wavs.append(wav.cpu() if output is None and post is None and speed is None else wav)
+            wavs.append(wav.cpu() if output is None and post is None and speed is None and pitch is None else wav)
         self.torch_empty_cache()
         self._set_gr_progress(0.9, "saving audio...")
         return self._finish(wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, output=output, post=post,
-                            speed=speed)
+                            speed=speed, pitch=pitch)
 
     def infer_batch(self, cond_mel: torch.Tensor, text_token_rows: List[torch.Tensor], max_mel_tokens=600, force_stop=None,
                     seed=1234, return_codes=False, phase_events: dict | None = None, adapter_ids=None, sampling=None,
-                    adapter_mix=None, *, output=None, post=None, speed=None, **generation_kwargs):
+                    adapter_mix=None, *, output=None, post=None, speed=None, pitch=None, **generation_kwargs):
         """Utterance-batch data path used by bench.py / the multi-GPU sharder (not in the reference API): one shared
         prompt, N independent texts decoded as ONE left-padded batch, one batched latent pass, and one vocoder call per
         group of equal-length utterances (batching unequal lengths would change the tail of the shorter waveforms).
@@ -1347,15 +1388,20 @@ class IndexTTS:
         speed (a number in [0.5, 2.0], or a list with one entry per utterance, None entries allowed; None and 1.0 = the waveforms
         as they are): the speaking rate of every utterance at the same pitch -- WSOLA on the device, two launches for all rows
         (indextts/utils/tempo.py) -- before post: pauses and levels are judged on what the listener hears.  The codes, and what
-        return_codes returns, are those of the plain call."""
+        return_codes returns, are those of the plain call.
+        pitch (semitones in [-12, 12], or a list with one entry per utterance, None entries allowed; None and 0 = the waveforms
+        as they are): every utterance higher or lower at the duration its speed sets -- WSOLA at speed / 2^(pitch / 12), then a
+        resampler by 2^(pitch / 12), one more launch for all rows (TempoEngine.shift) -- where speed is applied.  The formants
+        move with the pitch.  A row's speed / 2^(pitch / 12) must lie in [0.5, 2.0]."""
         IndexTTS._check_output(output, "infer_batch")
         IndexTTS._check_post(post, "infer_batch")
-        speed = IndexTTS._check_speed(speed, "infer_batch", len(text_token_rows))
+        n = len(text_token_rows)
+        speed, pitch = IndexTTS._check_speed(speed, "infer_batch", n), IndexTTS._check_pitch(pitch, speed, "infer_batch", n)
         st = self._batch_tokens(cond_mel, text_token_rows, max_mel_tokens, force_stop, seed, phase_events, lazy_spk=True,
                                 adapter_ids=adapter_ids, sampling=sampling, adapter_mix=adapter_mix, **generation_kwargs)
         outs = self._batch_waveforms(st, phase_events, reuse_prefix=True)   # serial: the KV cache still holds this batch's prompt
-        if speed is not None:
-            outs = self._speed_rows(outs, speed)
+        if speed is not None or pitch is not None:
+            outs = self._prosody_rows(outs, speed, pitch)
         if post is not None:
             outs = self._post_rows(outs, post)
         if output is not None:
@@ -2070,7 +2116,7 @@ class IndexTTS:
     def infer_queue(self, cond_mel: torch.Tensor, text_token_rows: List[torch.Tensor], slots=32, max_mel_tokens=600,
                     force_stop=None, seed=1234, return_codes=False, cache_positions=4096, check_every=16, staged=True,
                     phase_events: dict | None = None, sampling=None, adapter_ids=None, adapter_mix=None, *, output=None,
-                    post=None, speed=None, **generation_kwargs):
+                    post=None, speed=None, pitch=None, **generation_kwargs):
         """Continuous batching (not in the reference API; SURVEY.md section 8e's mitigation for mixed output lengths): any
         number of utterances of one prompt through `slots` decode slots.  The longest texts start; whenever a row emits its
         stop token its codes are taken and its slot is refilled with the next utterance (GPTEngine.decode_refill: the new
@@ -2088,10 +2134,12 @@ class IndexTTS:
         slot, and at whichever step, it enters (GPTEngine.decode_refill(voices=...)), and into its latent pass.
         output (an OutputFormat; None = the fp32 waveforms): as in infer_batch -- all utterances encoded in one launch.
         post (a PostProcess; None = the waveforms as they are): as in infer_batch -- all utterances finished in two launches.
-        speed (a number or one entry per utterance; None and 1.0 = as they are): as in infer_batch -- before post."""
+        speed (a number or one entry per utterance; None and 1.0 = as they are): as in infer_batch -- before post.
+        pitch (semitones, a number or one entry per utterance; None and 0 = as they are): as in infer_batch -- where speed is."""
         IndexTTS._check_output(output, "infer_queue")
         IndexTTS._check_post(post, "infer_queue")
-        speed = IndexTTS._check_speed(speed, "infer_queue", len(text_token_rows))
+        n = len(text_token_rows)
+        speed, pitch = IndexTTS._check_speed(speed, "infer_queue", n), IndexTTS._check_pitch(pitch, speed, "infer_queue", n)
         gen, _ = self._gen_kwargs(generation_kwargs)
         if int(gen.get("num_beams", 1)) != 1:
             raise NotImplementedError("infer_queue: num_beams = 1 only (beam rows cannot be refilled one at a time)")
@@ -2141,8 +2189,8 @@ class IndexTTS:
             for i, w in zip(ids, self._vocode_ragged(lat, spk[sel] if per_row else spk)):
                 outs[i] = w
         self._mark(phase_events, "vocoded")
-        if speed is not None:
-            outs = self._speed_rows(outs, speed)
+        if speed is not None or pitch is not None:
+            outs = self._prosody_rows(outs, speed, pitch)
         if post is not None:
             outs = self._post_rows(outs, post)
         if output is not None:
