@@ -187,9 +187,83 @@ def score_main(argv):
     print(f">> [score] {n} records -> {args.out}")
 
 
+def fit_voice_parser():
+    """The argument parser of `indextts --fit-voice` (a function of its own: the parsing is tested without a device)."""
+    import argparse
+    parser = argparse.ArgumentParser(prog="indextts --fit-voice", description="IndexTTS: fit a LoRA voice to a directory of codes")
+    parser.add_argument("--fit-voice", type=str, required=True, metavar="DIR", help="what --extract-codes wrote: metadata.jsonl, codes/")
+    parser.add_argument("-v", "--voice", type=str, required=True, help="reference (prompt) audio file, wav")
+    parser.add_argument("--out", type=str, required=True, metavar="VOICE.pt", help="the voice file to write (IndexTTS.load_voice reads it)")
+    parser.add_argument("--rank", type=int, default=4, metavar="R", help="LoRA rank (1..64)")
+    parser.add_argument("--alpha", type=float, default=8.0, help="LoRA alpha (the scaling is alpha / rank)")
+    parser.add_argument("--steps", type=int, default=100, metavar="N", help="optimizer steps")
+    parser.add_argument("--lr", type=float, default=5.0e-6, help="learning rate of the A factors (B: twice it, LoRA+)")
+    parser.add_argument("--batch-rows", type=int, default=4096, metavar="ROWS", help="rows (utterances x the longest) of one padded batch")
+    parser.add_argument("--text-weight", type=float, default=0.1, help="weight of the text loss (the mel loss: one minus it)")
+    parser.add_argument("--dropout", type=float, default=0.2, help="LoRA dropout")
+    parser.add_argument("--seed", type=int, default=0)
+    parser.add_argument("--save-merged", type=str, default=None, metavar="PATH", help="also write the merged checkpoint (gpt_finetuned.pth format)")
+    parser.add_argument("-c", "--config", type=str, default="checkpoints/config.yaml", help="config file")
+    parser.add_argument("--model_dir", type=str, default="checkpoints", help="model directory")
+    parser.add_argument("--fp32", action="store_true", default=False, help="fp32 GPT weights (default: half precision when available)")
+    parser.add_argument("-f", "--force", action="store_true", default=False, help="overwrite the voice file")
+    parser.add_argument("-d", "--device", type=str, default=None, help="device (cuda:N); CPU/MPS are not supported")
+    return parser
+
+
+def fit_voice_main(argv):
+    """`indextts --fit-voice DIR -v PROMPT --out VOICE.pt [--rank --alpha --steps --lr --batch-rows --text-weight --dropout --seed
+    --save-merged PATH]`: train a LoRA voice on the codes of a directory (IndexTTS.fit_voice_from_dir) and save it."""
+    parser = fit_voice_parser()
+    args = parser.parse_args(argv)
+
+    def fail(msg):
+        print(f"[error] {msg}")
+        parser.print_help()
+        sys.exit(1)
+
+    if not os.path.exists(os.path.join(args.fit_voice, "metadata.jsonl")):
+        fail(f"{args.fit_voice} holds no metadata.jsonl (run --extract-codes first)")
+    for path, what in ((args.voice, "prompt"), (args.config, "config")):
+        if not os.path.exists(path):
+            fail(f"{what} {path} does not exist")
+    if not 1 <= args.rank <= 64:
+        fail("--rank must lie in [1, 64]")
+    if args.steps < 1 or args.batch_rows < 1:
+        fail("--steps and --batch-rows must be at least 1")
+    if os.path.exists(args.out) and not args.force:
+        fail(f"voice file {args.out} exists; use --force to overwrite")
+    import torch
+    if args.device is None:
+        if not torch.cuda.is_available():
+            print("[error] no GPU visible: this build needs an AMD GPU (no CPU path)")
+            sys.exit(1)
+        args.device = "cuda:0"
+    from indextts.infer import IndexTTS
+    tts = IndexTTS(cfg_path=args.config, model_dir=args.model_dir, is_fp16=not args.fp32, device=args.device)
+    try:
+        cond_mel = tts.prompt_mels([args.voice])[0]
+        adapters, scaling, report = tts.fit_voice_from_dir(
+            args.fit_voice, cond_mel, rank=args.rank, alpha=args.alpha, steps=args.steps, lr=args.lr, batch_rows=args.batch_rows,
+            text_weight=args.text_weight, dropout=args.dropout, seed=args.seed, return_report=True)
+    except (ValueError, OSError, RuntimeError) as e:
+        print(f"[error] {e}")
+        sys.exit(1)
+    first, last = report["steps"][0], report["steps"][-1]
+    print(f">> [fit] {len(report['steps'])} steps: loss_mel {first['loss_mel']:.4f} -> {last['loss_mel']:.4f}, "
+          f"loss_text {first['loss_text']:.4f} -> {last['loss_text']:.4f}")
+    tts.save_voice(args.out, adapters, scaling)
+    print(f">> [voice] {len(adapters)} targets saved to: {args.out}")
+    if args.save_merged:
+        tts.save_merged(args.save_merged, adapters, scaling)
+        print(f">> [merged] saved to: {args.save_merged}")
+
+
 def main(argv=None):
     import argparse
     argv = sys.argv[1:] if argv is None else list(argv)
+    if any(a == "--fit-voice" or a.startswith("--fit-voice=") for a in argv):
+        return fit_voice_main(argv)
     if any(a == "--extract-voice" or a.startswith("--extract-voice=") for a in argv):
         return extract_voice_main(argv)
     if any(a == "--extract-codes" or a.startswith("--extract-codes=") for a in argv):

@@ -1147,6 +1147,111 @@ class IndexTTS:
         recs = self.score_codes(cond_mel, [row] * len(voices), [codes] * len(voices), adapter_ids=voices)
         return sorted(zip(voices, recs), key=lambda vr: vr[1]["nll_mel"])
 
+    # ------------------------------------------------------------------------------------------------ voice fitting
+    def fit_voice(self, cond_mel, text_token_rows: List[torch.Tensor], code_rows: List[torch.Tensor], *, rank=4, alpha=8.0, steps=100,
+                  batch_rows=4096, lr=5.0e-6, targets=None, text_weight=0.1, dropout=0.2, loraplus_lr_ratio=2.0, weight_decay=0.01,
+                  max_grad_norm=1.0, warmup_ratio=0.1, accumulate=1, valid=None, eval_every=10, seed=0, return_report=False):
+        """Train the reference's LoRA (train.py:548-605) on this instance's frozen GPT and return (adapters, scaling) in the
+        attach_lora format -- what add_voice, attach_lora_bank, save_voice and score_codes(adapter_ids=...) take (DESIGN.md section
+        4.29).  Utterance i is text_token_rows[i] and code_rows[i] (what extract_codes wrote); cond_mel is one prompt or a list with
+        one per utterance, conditioned once, without gradient.  The utterances are cut, in order, into padded batches of at most
+        batch_rows rows (utterances x the longest); an optimizer step takes `accumulate` of them in turn, `steps` steps in all.
+        valid = (text rows, code rows): the score_codes records of the held-out set every eval_every steps and at the end.
+        return_report: (adapters, scaling, report) with report["steps"] (loss_text, loss_mel, loss, grad_norm, lr per step) and
+        report["valid"].  Every refusal comes before anything is launched.  Nothing of the engine, its bank or its graphs changes -- but
+        for valid= without an attached voice pool, which attaches a one-slot pool for each evaluation and detaches it (every attach
+        drops the captured graphs): attach a pool first to keep them.  With a prompt per utterance, valid=(texts, codes, prompts)."""
+        from indextts.gpt.fit import TARGETS, FitConfig, FitEngine, check_engine, check_rows, plan_batches
+        g, eng = self.gpt, self.gpt.engine
+        cfg = FitConfig(rank=rank, alpha=float(alpha), targets=tuple(TARGETS if targets is None else targets), dropout=float(dropout),
+                        text_weight=float(text_weight), lr=float(lr), loraplus_lr_ratio=float(loraplus_lr_ratio),
+                        weight_decay=float(weight_decay), max_grad_norm=max_grad_norm, total_steps=int(steps), warmup_ratio=float(warmup_ratio),
+                        seed=int(seed), start_text_token=g.start_text_token, stop_text_token=g.stop_text_token,
+                        mel_length_compression=g.mel_length_compression).check()
+        check_engine(eng, "fit_voice")
+        if int(accumulate) < 1 or int(eval_every) < 1:
+            raise ValueError("fit_voice: accumulate and eval_every must be at least 1")
+        B = len(text_token_rows)
+        rows = check_rows(text_token_rows, code_rows, batch_rows, n_cond=int(g.cond_num), who="fit_voice")   # (the perceiver's latents)
+        if valid is not None:
+            check_rows(valid[0], valid[1], None, who="fit_voice(valid=)")
+            if isinstance(cond_mel, (list, tuple)) and len(valid) < 3:
+                raise ValueError("fit_voice(valid=): with a prompt per utterance the held-out set names its own: valid=(texts, codes, prompt "
+                                 "or prompts)")
+        cond_mel = self._check_prompts(cond_mel, B, {}, "fit_voice")
+        with torch.no_grad():
+            conds, _ = self._prompt_features(cond_mel, spk=False)
+        conds = conds.detach()
+        if int(conds.shape[1]) != int(g.cond_num):
+            raise RuntimeError(f"fit_voice: the conditioner gave {int(conds.shape[1])} latents, the model is configured for {int(g.cond_num)}")
+        fit = FitEngine(eng, g._sd, cfg)
+        plan = plan_batches(rows, int(batch_rows))
+        batches = [fit.batch(conds if conds.shape[0] == 1 else conds[torch.tensor(ix, device=conds.device)],
+                             [text_token_rows[i] for i in ix], [code_rows[i] for i in ix]) for ix in plan]
+        report, at = dict(steps=[], valid=[]), 0
+        for k in range(int(steps)):
+            micro = [batches[(at + j) % len(batches)] for j in range(int(accumulate))]
+            at = (at + int(accumulate)) % len(batches)
+            report["steps"].append(fit.step(micro))
+            if valid is not None and ((k + 1) % int(eval_every) == 0 or k + 1 == int(steps)):
+                report["valid"].append(dict(step=k + 1, records=self._score_under(valid[2] if len(valid) > 2 else cond_mel, valid[0], valid[1], fit.voice())))
+        adapters, scaling = fit.voice()
+        return (adapters, scaling, report) if return_report else (adapters, scaling)
+
+    def _score_under(self, cond_mel, text_rows, code_rows, voice):
+        """score_codes of a held-out set under a voice that is in no bank yet: through add_voice / remove_voice when a voice pool is
+        attached (nothing else of it changes), else through a one-slot pool attached for the call and detached after it -- which
+        drops the engine's captured graphs, as every attach does: the one case in which fit_voice touches the engine."""
+        eng = self.gpt.engine
+        n = len(text_rows)
+        prompt = cond_mel                      # (one prompt, or one per held-out utterance: score_codes checks the list)
+        if eng._pool() is not None:
+            vid = self.add_voice(*voice)
+            try:
+                return self.score_codes(prompt, text_rows, code_rows, adapter_ids=[vid] * n)
+            finally:
+                self.remove_voice(vid)
+        if eng.bank is not None:
+            raise ValueError("fit_voice(valid=): a fixed adapter bank is attached: attach a voice pool (attach_voice_pool) or detach it")
+        rank = max(int(A.shape[0]) for A, _ in voice[0].values())
+        self.attach_voice_pool([voice], slots=1, rank=rank)
+        try:
+            return self.score_codes(prompt, text_rows, code_rows, adapter_ids=[0] * n)
+        finally:
+            self.detach_voice_pool()
+
+    def fit_voice_from_dir(self, data_dir, cond_mel, **kw):
+        """fit_voice on what extract_codes wrote into data_dir: metadata.jsonl (text, codes per clip) and codes/*.npy.  The
+        transcripts are tokenized as infer() does.  kw: fit_voice's keywords."""
+        meta = os.path.join(data_dir, "metadata.jsonl")
+        if not os.path.exists(meta):
+            raise ValueError(f"fit_voice_from_dir: {meta} does not exist (extract_codes writes it)")
+        texts, codes = [], []
+        with open(meta, "r", encoding="utf-8") as f:
+            for n, line in enumerate(f):
+                if not line.strip():
+                    continue
+                rec = json.loads(line)
+                if "text" not in rec or "codes" not in rec:
+                    raise ValueError(f"{meta}:{n + 1}: a record needs text and codes")
+                path = rec["codes"] if os.path.isabs(rec["codes"]) or os.path.exists(rec["codes"]) else os.path.join(data_dir, rec["codes"])
+                if not os.path.exists(path):
+                    path = os.path.join(data_dir, "codes", os.path.basename(rec["codes"]))
+                codes.append(torch.from_numpy(np.load(path).astype(np.int64)).reshape(-1))
+                texts.append(self.text_token_row(rec["text"]))
+        return self.fit_voice(cond_mel, texts, codes, **kw)
+
+    def save_merged(self, path, adapters, scaling):
+        """The voice merged into this instance's GPT weights, in the reference's gpt_finetuned.pth format: the checkpoint's own keys
+        and dtypes with W + scaling (B A)^T in the place of every adapted weight.  The reference loads it; voice_from_checkpoint of
+        it gives the voice back."""
+        from indextts.gpt.fit import merged_state_dict
+        sd = merged_state_dict(self.gpt._sd, adapters, scaling, self.gpt.engine.L)
+        if os.path.dirname(path) != "":
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+        torch.save(sd, path)
+        return path
+
     def _finish(self, wavs, output_path, start_time, gpt_gen_time, gpt_forward_time, bigvgan_time, sampling_rate=24000, output=None,
                 post=None, speed=None, pitch=None):
         end_time = time.perf_counter()
