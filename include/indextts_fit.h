@@ -1,6 +1,7 @@
 /*
- * indextts_fit.h -- C ABI of libindextts_fit.so: voice fitting on gfx950 (MI355X / CDNA4): the LoRA-specific gradient reduction
- * and the optimizer of IndexTTS.fit_voice (indextts/gpt/fit.py).
+ * indextts_fit.h -- C ABI of libindextts_fit.so: voice fitting on gfx950 (MI355X / CDNA4): the LoRA-specific gradient reduction,
+ * the optimizer and the ragged causal training attention, forward and backward, of IndexTTS.fit_voice (indextts/gpt/fit.py,
+ * DESIGN.md sections 4.29 and 4.30).
  *
  * A library of its own, beside libindextts_hip.so (include/indextts_hip.h) and the eight others (include/indextts_voice.h,
  * _audio.h, _out.h, _post.h, _tempo.h, _codec.h, _score.h, _pitch.h), whose ABIs it leaves alone: every name here carries the
@@ -36,6 +37,44 @@
  *         p  = p - (lr[G] / bc1) * ( m / (sqrt(v) / bc2_sqrt + eps) )
  *     bc1 = 1 - beta1^t and bc2_sqrt = sqrt(1 - beta2^t) are the host's.  Then t_copy = p rounded ONCE to `dtype` (a copy for
  *     ITTF_F32) where the segment has a t_copy: same element order as p.  Nothing past a segment's n elements is touched.
+ *
+ * THE TRAINING ATTENTION (ittf_attn_fwd, ittf_attn_bwd).  Causal softmax attention over RAGGED rows: fp32 in, fp32 sums
+ * (v_mfma_f32_16x16x4_f32) and fp32 out whatever the engine's dtype, head dimension 64, read in place from the fp32 output of the
+ * attn.c_attn GEMM:  qkv [M][ld], D = 64 H; q of head h at column 64 h + e, k at D + 64 h + e, v at 2 D + 64 h + e.
+ *     s[i][j] = scale * sum_e q[i][e] k[j][e]  (j <= i, rows of one segment),   lse[i] = ln sum_j exp(s[i][j]),
+ *     p[i][j] = exp(s[i][j] - lse[i]),   out[i][d] = sum_j p[i][j] v[j][d]                 out [M][ldo], head h at column 64 h + d
+ *     dP[i][j] = sum_d dout[i][d] v[j][d],   delta[i] = sum_j p[i][j] dP[i][j],   ds[i][j] = p[i][j] (dP[i][j] - delta[i])
+ *     dq[i] = scale sum_j ds[i][j] k[j],   dk[j] = scale sum_i ds[i][j] q[i],   dv[j] = sum_i p[i][j] dout[i]
+ *   dqkv [M][ld] has qkv's layout; lse is [H][M].  The backward recomputes p from qkv and lse tile by tile: nothing of size [n][n]
+ *   is stored anywhere.  delta is sum_d dout[i][d] out[i][d] in exact arithmetic; it is formed as sum_j p dP, from the bits of p
+ *   and dP that ds is then formed from, because ds is a difference of nearly equal numbers wherever one key holds a row's whole
+ *   weight, and rowsum(dout o out) carries the rounding of out into it (dq of such a row missed its bound
+ *   fourfold).  The backward therefore does not read out.
+ *   RAGGED ROWS.  A table of n_seg records ittf_rows (first row, row count) on the device, which the caller built and answers for
+ *   (the host cannot see it): the segments come in rising order, do not overlap, lie inside [0, M), and none is longer than
+ *   max_len, the longest the caller states (at most ITTF_ATTN_MAX_SEG).  A segment is one utterance: its rows attend causally to
+ *   rows of the same segment only, and it may start at any row.  Rows of M that no segment covers are never read and never
+ *   written, in any operand.  (A kernel cuts a record at max_len rows and at row M, so that a wrong table cannot reach outside the
+ *   operands.)
+ *   OWNERSHIP.  Every output tile has one owner and no workgroup waits for another: a wave owns 16 query rows of one (segment,
+ *   head) in the forward (out, lse) and in the dq launch, and 16 key rows in the dk / dv launch; the backward is two launches (dq,
+ *   whose first sweep leaves delta in `ws`; then dk and dv) and computes the scores three times.
+ *   THE ORDER OF THE SUMS.  Rows are counted from the segment's first row; tile t is rows 16 t .. 16 t + 15; rows past the
+ *   segment's end are +0 operands.  Nothing below depends on the segment's place in M, on the other segments, on ld, ldo or on
+ *   the launch.  A "chain" is one accumulator through successive matrix instructions, each adding 4 products to it.
+ *     a score, or sum_d dout[i][d] v[j][d]: a chain of 16 over the 64 columns, instruction 4 a + b taking columns 16 a + b + 4 c,
+ *       c = 0 .. 3; the chain starts from +0.
+ *     forward, per query row, over the key tiles 0 .. its own in rising order (online softmax): s = scale * score rounded once;
+ *       the tile's maximum joins the running maximum m (alpha = exp(m_old - m_new), 0 before the first tile);
+ *       p = exp(s - m_new) (0 above the diagonal); the tile's sum of p is ((p0 + p1) + p2) + p3 over the keys 4 c + 0 .. 3 of each
+ *       c, then (c = 0 with 1) + (c = 2 with 3);  l = fma(l, alpha, that sum);  every out accumulator is multiplied by alpha and
+ *       then takes a chain of 4 over the tile, instruction b taking keys b, 4 + b, 8 + b, 12 + b.  At the end out = acc / l and
+ *       lse = m + ln l.
+ *     backward: s = scale * score rounded once (the forward's bits), p = exp(s - lse[i]).  delta[i]: for each c = 0 .. 3 one
+ *       fma chain from +0 over the key tiles 0 .. i's own in rising order, inside a tile over the keys 4 c + 0 .. 3, of p dP; then
+ *       (c = 0 with 1) + (c = 2 with 3).  ds' = p * (dP - delta[i]).  dv[j] and dk[j] take the query tiles
+ *       from j's own upward, dq[i] the key tiles 0 .. i's own, each a chain of 4 per tile (instruction b: rows b, 4 + b, 8 + b,
+ *       12 + b of the tile) into one accumulator from +0; dq and dk are multiplied by scale once at the end.
  */
 #ifndef INDEXTTS_FIT_H
 #define INDEXTTS_FIT_H
@@ -50,7 +89,7 @@ extern "C" {
 #define ITTF_ERR_INVALID 1 /* bad argument (nothing was launched) */
 #define ITTF_ERR_LAUNCH 2  /* HIP reported an error at launch */
 
-#define ITTF_ABI_VERSION 1
+#define ITTF_ABI_VERSION 2
 
 #define ITTF_F32 0
 #define ITTF_BF16 1
@@ -59,6 +98,9 @@ extern "C" {
 #define ITTF_CHUNK 256   /* rows of one partial sum of ittf_lora_wgrad */
 #define ITTF_MAX_RANK 64 /* the voice pool's own limit */
 #define ITTF_SLICE 4096  /* elements one workgroup of ittf_sqnorm / ittf_adamw_step owns */
+#define ITTF_ATTN_MAX_SEG 4096   /* the longest segment (rows) ittf_attn_fwd / ittf_attn_bwd take */
+#define ITTF_ATTN_MAX_HEADS 256  /* heads of 64 columns */
+#define ITTF_ATTN_MAX_NSEG 65535 /* records of a row table */
 
 int ittf_abi_version(void);
 const char* ittf_last_error(void);
@@ -127,6 +169,47 @@ typedef struct ittf_adamw_args {
 } ittf_adamw_args;
 
 int ittf_adamw_step(const ittf_adamw_args* a, void* stream);
+
+/* one segment of rows (16 bytes): rows first .. first + count - 1 of the [M]-row operands */
+typedef struct ittf_rows {
+  int64_t first;
+  int64_t count;
+} ittf_rows;
+
+/* bytes of workspace ittf_attn_bwd needs for M rows of H heads: 4 H M, the delta of every (head, row) (0 when an argument is out of
+ * range) */
+int64_t ittf_attn_ws_bytes(int64_t M, int H);
+
+/* the training attention, see above.  One struct for both entry points; ittf_attn_fwd ignores dout, dqkv, ws and ws_bytes,
+ * ittf_attn_bwd ignores out (it may be NULL there; ldo is dout's pitch).
+ *   qkv      fp32 [M][ld] (device), 16-byte aligned, ld >= 3 * 64 H and a multiple of 4
+ *   out      fp32 [M][ldo], 16-byte aligned, ldo >= 64 H and a multiple of 4: written by fwd
+ *   lse      fp32 [H][M], 4-byte aligned: written by fwd, read by bwd
+ *   dout     fp32 [M][ldo] (out's pitch), 16-byte aligned;  dqkv  fp32 [M][ld] (qkv's pitch), 16-byte aligned: written by bwd
+ *   ws       ittf_attn_ws_bytes(M, H) bytes, 4-byte aligned (ws_bytes states its size)
+ *   table    ittf_rows [n_seg] on the device, 16-byte aligned; 1 <= n_seg <= ITTF_ATTN_MAX_NSEG
+ *   max_len  the longest segment of the table, 1 .. ITTF_ATTN_MAX_SEG;  M  1 <= M < 2^31;  H  1 .. ITTF_ATTN_MAX_HEADS
+ *   ld, ldo  at most 2^24 + 64;  scale  finite and > 0
+ * What a call writes (fwd: out, lse; bwd: dqkv, ws) may not overlap anything else it is given. */
+typedef struct ittf_attn_args {
+  const float* qkv;
+  float* out;
+  float* lse;
+  const float* dout;
+  float* dqkv;
+  void* ws;
+  int64_t ws_bytes;
+  const ittf_rows* table;
+  int64_t M;
+  int n_seg;
+  int max_len;
+  int H;
+  int ld, ldo;
+  float scale;
+} ittf_attn_args;
+
+int ittf_attn_fwd(const ittf_attn_args* a, void* stream);
+int ittf_attn_bwd(const ittf_attn_args* a, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 // libindextts_fit.so (include/indextts_fit.h): voice fitting for gfx950 -- the LoRA factor gradient and the optimizer of
-// IndexTTS.fit_voice (indextts/gpt/fit.py).  Five kernels; the header states the quantities and the order of
-// every sum.
+// IndexTTS.fit_voice (indextts/gpt/fit.py), and at the end of the file the four kernels of the ragged causal
+// training attention.  The header states the quantities and the order of every sum.
 //
 // wgrad: a tall-skinny reduction over the rows on the matrix pipe.  G^T-tile = s^T z: the A operand is s read down its columns
 //   (row j of the 16 x 16 product is factor row j, k is the batch row m), the B operand z (k = m, column c).  A wave owns 16 columns
@@ -343,4 +343,334 @@ extern "C" int ittf_adamw_step(const ittf_adamw_args* a, void* stream) {
   else if (a->dtype == ITTF_BF16) hipLaunchKernelGGL(adamw<__bf16>, grid, dim3(WG), 0, st, p);
   else hipLaunchKernelGGL(adamw<_Float16>, grid, dim3(WG), 0, st, p);
   return launched("ittf_adamw_step");
+}
+
+// ------------------------------------------------------------------------------------------------ the training attention
+// Ragged causal attention for the fit, forward and backward (the header states the quantities and the order of every sum).  A
+// wave owns one 16-row tile of one (segment, head) and nothing is shared between waves: a workgroup is one wave, there is no LDS
+// and no barrier.  Lane l = 16 g + r.  Every product is a 16 x 16 x 4 fp32 matrix instruction whose operands come from memory as
+// float4s: a reduction index may be permuted freely as long as both operands agree, so
+//   - a product over the 64 head columns reads, per row r, the columns 16 a + 4 g .. + 3 (a = 0 .. 3): instruction (a, b) sums the
+//     columns 16 a + 4 g' + b over g';
+//   - a product over a tile's 16 rows reads row 4 g + b with the columns 4 r .. + 3 (b = 0 .. 3): instruction b sums the rows
+//     4 g' + b, and output tile c holds the columns 4 rho + c of output row index rho -- register e of lane (r, g) is column
+//     16 g + 4 e + c: a lane ends with 16 consecutive columns of row r.
+// The scores are computed with the reduction row of the NEXT product on the accumulator's row index (4 g + b), so that an
+// accumulator is that product's B operand as it stands: keys in the forward and in dq (S^T = K Q^T), queries in dk / dv (S = Q K^T).
+namespace ittf {
+
+struct AttnParams {
+  const float* qkv;
+  float* out;
+  float* lse;
+  const float* dout;
+  float* dqkv;
+  float* delta;                                      // [H][M], the backward's workspace: attn_dq writes it, attn_dkdv reads it
+  const ittf_rows* tab;
+  int64_t M;
+  int max_len, H, ld, ldo;
+  float scale;
+};
+
+// the rows of segment z, cut at max_len rows and at row M: -> the row count (0: nothing to do), `first` its first row
+__device__ inline int attn_segment(const AttnParams& p, int z, int64_t& first) {
+  const ittf_rows s = p.tab[z];
+  first = s.first;
+  if (s.first < 0 || s.first >= p.M || s.count < 1) return 0;
+  int64_t n = s.count < p.max_len ? s.count : p.max_len;
+  if (n > p.M - s.first) n = p.M - s.first;
+  return (int)n;
+}
+
+__device__ inline f32x4 ld4(const float* q, bool live) {   // (a row that is not the segment's is never read)
+  return live ? *reinterpret_cast<const f32x4*>(q) : f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+__device__ inline f32x4 mma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+// acc += sum over the 64 columns of x[row][.] y[row'][.]: the chain of 16
+__device__ inline f32x4 dot64(const f32x4 (&x)[4], const f32x4 (&y)[4], f32x4 acc) {
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc = mma4(x[a][b], y[a][b], acc);
+  return acc;
+}
+
+// a lane's 16 consecutive columns 16 g .. 16 g + 15 of its row, times f
+__device__ inline void store16(float* dst, const f32x4 (&acc)[4], float f) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+    *reinterpret_cast<f32x4*>(dst + 4 * e) =
+        f32x4{__fmul_rn(acc[0][e], f), __fmul_rn(acc[1][e], f), __fmul_rn(acc[2][e], f), __fmul_rn(acc[3][e], f)};
+}
+
+__global__ void __launch_bounds__(64) attn_fwd(AttnParams p) {
+  const int r = threadIdx.x & 15, g = threadIdx.x >> 4, h = blockIdx.y;
+  int64_t first;
+  const int n = attn_segment(p, blockIdx.z, first);
+  const int nt = (n + 15) >> 4;
+  if ((int)blockIdx.x >= nt) return;
+  const int qt = nt - 1 - (int)blockIdx.x;           // the longest sweeps start first
+  const int D = 64 * p.H, qi = qt * 16 + r;
+  const bool qlive = qi < n;
+  const float* base = p.qkv + first * p.ld + 64 * h;
+  f32x4 Q[4], O[4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    Q[a] = ld4(base + (int64_t)qi * p.ld + 16 * a + 4 * g, qlive);
+    O[a] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  float m = -INFINITY, l = 0.f;
+  for (int kt = 0; kt <= qt; ++kt) {
+    const int kj = kt * 16 + r;
+    f32x4 K[4], V[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) K[a] = ld4(base + D + (int64_t)kj * p.ld + 16 * a + 4 * g, kj < n);
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int vj = kt * 16 + 4 * g + b;
+      V[b] = ld4(base + 2 * D + (int64_t)vj * p.ld + 4 * r, vj < n);
+    }
+    const f32x4 S = dot64(K, Q, f32x4{0.f, 0.f, 0.f, 0.f});   // register b: key 4 g + b, query r
+    float s[4], tmax = -INFINITY;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      s[b] = kt * 16 + 4 * g + b <= qi ? __fmul_rn(p.scale, S[b]) : -INFINITY;
+      tmax = fmaxf(tmax, s[b]);
+    }
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 16));
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
+    const float mn = fmaxf(m, tmax);                 // finite from tile 0 on: key 0 is at or below every query
+    const float alpha = expf(__fsub_rn(m, mn));
+    float pr[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) pr[b] = expf(__fsub_rn(s[b], mn));
+    float t = __fadd_rn(__fadd_rn(__fadd_rn(pr[0], pr[1]), pr[2]), pr[3]);
+    t = __fadd_rn(t, __shfl_xor(t, 16));
+    t = __fadd_rn(t, __shfl_xor(t, 32));
+    l = fmaf(l, alpha, t);
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) O[c][e] = __fmul_rn(O[c][e], alpha);
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) O[c] = mma4(V[b][c], pr[b], O[c]);   // O^T = V^T P^T: column 4 rho + c of query r
+    m = mn;
+  }
+  if (!qlive) return;
+  float* o = p.out + (first + qi) * p.ldo + 64 * h + 16 * g;
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+    *reinterpret_cast<f32x4*>(o + 4 * e) =
+        f32x4{__fdiv_rn(O[0][e], l), __fdiv_rn(O[1][e], l), __fdiv_rn(O[2][e], l), __fdiv_rn(O[3][e], l)};
+  if (g == 0) p.lse[(int64_t)h * p.M + first + qi] = __fadd_rn(m, logf(l));
+}
+
+__global__ void __launch_bounds__(64) attn_dkdv(AttnParams p) {
+  const int r = threadIdx.x & 15, g = threadIdx.x >> 4, h = blockIdx.y;
+  int64_t first;
+  const int n = attn_segment(p, blockIdx.z, first);
+  const int nt = (n + 15) >> 4, kt = blockIdx.x;     // (key tile 0 sweeps the most query tiles and starts first)
+  if (kt >= nt) return;
+  const int D = 64 * p.H, kj = kt * 16 + r;
+  const bool klive = kj < n;
+  const float* base = p.qkv + first * p.ld + 64 * h;
+  const float* dob = p.dout + first * p.ldo + 64 * h;
+  const float* lse = p.lse + (int64_t)h * p.M + first;
+  const float* delta = p.delta + (int64_t)h * p.M + first;
+  f32x4 K[4], V[4], dK[4], dV[4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    K[a] = ld4(base + D + (int64_t)kj * p.ld + 16 * a + 4 * g, klive);
+    V[a] = ld4(base + 2 * D + (int64_t)kj * p.ld + 16 * a + 4 * g, klive);
+    dK[a] = dV[a] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  for (int qt = kt; qt < nt; ++qt) {
+    const int qi = qt * 16 + r;
+    f32x4 Qa[4], Oa[4], Qc[4], Oc[4];
+    float ls[4], dl[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      Qa[a] = ld4(base + (int64_t)qi * p.ld + 16 * a + 4 * g, qi < n);
+      Oa[a] = ld4(dob + (int64_t)qi * p.ldo + 16 * a + 4 * g, qi < n);
+    }
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int qb = qt * 16 + 4 * g + b;
+      const bool live = qb < n;
+      Qc[b] = ld4(base + (int64_t)qb * p.ld + 4 * r, live);
+      Oc[b] = ld4(dob + (int64_t)qb * p.ldo + 4 * r, live);
+      ls[b] = live ? lse[qb] : 0.f;
+      dl[b] = live ? delta[qb] : 0.f;
+    }
+    const f32x4 S = dot64(Qa, K, f32x4{0.f, 0.f, 0.f, 0.f});   // register b: query 4 g + b, key r
+    const f32x4 dP = dot64(Oa, V, f32x4{0.f, 0.f, 0.f, 0.f});
+    float pr[4], ds[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int qb = qt * 16 + 4 * g + b;
+      pr[b] = kj <= qb && qb < n ? expf(__fsub_rn(__fmul_rn(p.scale, S[b]), ls[b])) : 0.f;
+      ds[b] = __fmul_rn(pr[b], __fsub_rn(dP[b], dl[b]));
+    }
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        dV[c] = mma4(Oc[b][c], pr[b], dV[c]);        // dV^T = dO^T P
+        dK[c] = mma4(Qc[b][c], ds[b], dK[c]);        // dK^T = Q^T dS
+      }
+  }
+  if (!klive) return;
+  float* dst = p.dqkv + (first + kj) * p.ld + 64 * h + 16 * g;
+  store16(dst + D, dK, p.scale);
+  store16(dst + 2 * D, dV, 1.f);
+}
+
+__global__ void __launch_bounds__(64) attn_dq(AttnParams p) {
+  const int r = threadIdx.x & 15, g = threadIdx.x >> 4, h = blockIdx.y;
+  int64_t first;
+  const int n = attn_segment(p, blockIdx.z, first);
+  const int nt = (n + 15) >> 4;
+  if ((int)blockIdx.x >= nt) return;
+  const int qt = nt - 1 - (int)blockIdx.x;
+  const int D = 64 * p.H, qi = qt * 16 + r;
+  const bool qlive = qi < n;
+  const float* base = p.qkv + first * p.ld + 64 * h;
+  const float* dob = p.dout + first * p.ldo + 64 * h;
+  f32x4 Q[4], dO[4], dQ[4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    Q[a] = ld4(base + (int64_t)qi * p.ld + 16 * a + 4 * g, qlive);
+    dO[a] = ld4(dob + (int64_t)qi * p.ldo + 16 * a + 4 * g, qlive);
+    dQ[a] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  const float ls = qlive ? p.lse[(int64_t)h * p.M + first + qi] : 0.f;
+  // the first sweep: delta = sum over the keys of p dP, with the bits of p and dP that the second sweep (and dk / dv) form again
+  float delta = 0.f;
+  for (int kt = 0; kt <= qt; ++kt) {
+    const int kj = kt * 16 + r;
+    f32x4 Ka[4], Va[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      Ka[a] = ld4(base + D + (int64_t)kj * p.ld + 16 * a + 4 * g, kj < n);
+      Va[a] = ld4(base + 2 * D + (int64_t)kj * p.ld + 16 * a + 4 * g, kj < n);
+    }
+    const f32x4 S = dot64(Ka, Q, f32x4{0.f, 0.f, 0.f, 0.f});
+    const f32x4 dP = dot64(Va, dO, f32x4{0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const float pr = qlive && kt * 16 + 4 * g + b <= qi ? expf(__fsub_rn(__fmul_rn(p.scale, S[b]), ls)) : 0.f;
+      delta = fmaf(pr, dP[b], delta);
+    }
+  }
+  delta = __fadd_rn(delta, __shfl_xor(delta, 16));
+  delta = __fadd_rn(delta, __shfl_xor(delta, 32));
+  if (qlive && g == 0) p.delta[(int64_t)h * p.M + first + qi] = delta;   // for the dk / dv launch behind this one
+  for (int kt = 0; kt <= qt; ++kt) {
+    const int kj = kt * 16 + r;
+    f32x4 Ka[4], Va[4], Kc[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      Ka[a] = ld4(base + D + (int64_t)kj * p.ld + 16 * a + 4 * g, kj < n);
+      Va[a] = ld4(base + 2 * D + (int64_t)kj * p.ld + 16 * a + 4 * g, kj < n);
+    }
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int kb = kt * 16 + 4 * g + b;
+      Kc[b] = ld4(base + D + (int64_t)kb * p.ld + 4 * r, kb < n);
+    }
+    const f32x4 S = dot64(Ka, Q, f32x4{0.f, 0.f, 0.f, 0.f});   // register b: key 4 g + b, query r
+    const f32x4 dP = dot64(Va, dO, f32x4{0.f, 0.f, 0.f, 0.f});
+    float ds[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const float pr = qlive && kt * 16 + 4 * g + b <= qi ? expf(__fsub_rn(__fmul_rn(p.scale, S[b]), ls)) : 0.f;
+      ds[b] = __fmul_rn(pr, __fsub_rn(dP[b], delta));
+    }
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) dQ[c] = mma4(Kc[b][c], ds[b], dQ[c]);   // dQ^T = K^T dS^T
+  }
+  if (!qlive) return;
+  store16(p.dqkv + (first + qi) * p.ld + 64 * h + 16 * g, dQ, p.scale);
+}
+
+}  // namespace ittf
+
+extern "C" int64_t ittf_attn_ws_bytes(int64_t M, int H) {
+  if (M < 1 || M >= ((int64_t)1 << 31) || H < 1 || H > ITTF_ATTN_MAX_HEADS) return 0;
+  return 4 * M * (int64_t)H;
+}
+
+static int attn_check(const char* who, const ittf_attn_args* a, bool bwd) {
+  using namespace ittf;
+  ITTF_REQUIRE(a != nullptr, "%s: null argument struct", who);
+  ITTF_REQUIRE(a->qkv && (bwd || a->out) && a->lse && a->table, "%s: null pointer (qkv, out, lse, table)", who);   // (bwd does not read out)
+  ITTF_REQUIRE(!bwd || (a->dout && a->dqkv && a->ws), "%s: null pointer (dout, dqkv, ws)", who);
+  ITTF_REQUIRE(a->H >= 1 && a->H <= ITTF_ATTN_MAX_HEADS, "%s: H = %d (1 .. %d heads of 64 columns)", who, a->H, ITTF_ATTN_MAX_HEADS);
+  const int D = 64 * a->H;
+  ITTF_REQUIRE(a->M >= 1 && a->M < ((int64_t)1 << 31), "%s: M must be in [1, 2^31) (got %lld)", who, (long long)a->M);
+  ITTF_REQUIRE(a->n_seg >= 1 && a->n_seg <= ITTF_ATTN_MAX_NSEG, "%s: n_seg = %d (1 .. %d)", who, a->n_seg, ITTF_ATTN_MAX_NSEG);
+  ITTF_REQUIRE(a->max_len >= 1 && a->max_len <= ITTF_ATTN_MAX_SEG, "%s: max_len = %d: a segment has 1 .. %d rows", who, a->max_len,
+               ITTF_ATTN_MAX_SEG);
+  ITTF_REQUIRE(a->ld >= 3 * D && a->ld <= MAX_LD && a->ld % 4 == 0, "%s: ld = %d (the pitch of qkv: >= 3 D = %d, a multiple of 4)", who,
+               a->ld, 3 * D);
+  ITTF_REQUIRE(a->ldo >= D && a->ldo <= MAX_LD && a->ldo % 4 == 0, "%s: ldo = %d (the pitch of out: >= D = %d, a multiple of 4)", who,
+               a->ldo, D);
+  ITTF_REQUIRE(a->scale > 0.f && a->scale <= 3.0e38f, "%s: scale = %g (finite and > 0)", who, (double)a->scale);
+  ITTF_REQUIRE(aligned(a->qkv, 16) && (bwd || aligned(a->out, 16)) && aligned(a->lse, 4) && aligned(a->table, 16),
+               "%s: qkv, out and the table must be 16-byte aligned, lse 4-byte aligned", who);
+  ITTF_REQUIRE(!bwd || (aligned(a->dout, 16) && aligned(a->dqkv, 16) && aligned(a->ws, 4)),
+               "%s: dout and dqkv must be 16-byte aligned, ws 4-byte aligned", who);
+  const int64_t qkv_b = 4 * ((a->M - 1) * a->ld + 3 * D), out_b = 4 * ((a->M - 1) * a->ldo + D), lse_b = 4 * a->M * a->H;
+  const int64_t tab_b = 16 * (int64_t)a->n_seg;
+  if (!bwd) {
+    ITTF_REQUIRE(!overlap(a->out, out_b, a->qkv, qkv_b) && !overlap(a->out, out_b, a->table, tab_b) &&
+                     !overlap(a->lse, lse_b, a->qkv, qkv_b) && !overlap(a->lse, lse_b, a->table, tab_b) &&
+                     !overlap(a->out, out_b, a->lse, lse_b),
+                 "%s: out or lse overlaps qkv, the table or the other", who);
+    return ITTF_OK;
+  }
+  const int64_t need = ittf_attn_ws_bytes(a->M, a->H);
+  ITTF_REQUIRE(a->ws_bytes >= need, "%s: ws too small (%lld bytes, %lld rows of %d heads need %lld)", who, (long long)a->ws_bytes,
+               (long long)a->M, a->H, (long long)need);
+  const void* in[4] = {a->qkv, a->lse, a->dout, a->table};
+  const int64_t in_b[4] = {qkv_b, lse_b, out_b, tab_b};
+  for (int i = 0; i < 4; ++i)
+    ITTF_REQUIRE(!overlap(a->dqkv, qkv_b, in[i], in_b[i]) && !overlap(a->ws, need, in[i], in_b[i]),
+                 "%s: dqkv or ws overlaps qkv, lse, dout or the table", who);
+  ITTF_REQUIRE(!overlap(a->dqkv, qkv_b, a->ws, need), "%s: dqkv overlaps ws", who);
+  return ITTF_OK;
+}
+
+static ittf::AttnParams attn_params(const ittf_attn_args* a) {
+  ittf::AttnParams p;
+  p.qkv = a->qkv, p.out = a->out, p.lse = a->lse, p.dout = a->dout, p.dqkv = a->dqkv, p.delta = static_cast<float*>(a->ws);
+  p.tab = a->table, p.M = a->M, p.max_len = a->max_len, p.H = a->H, p.ld = a->ld, p.ldo = a->ldo, p.scale = a->scale;
+  return p;
+}
+
+extern "C" int ittf_attn_fwd(const ittf_attn_args* a, void* stream) {
+  using namespace ittf;
+  if (int rc = attn_check("ittf_attn_fwd", a, false)) return rc;
+  const AttnParams p = attn_params(a);
+  const dim3 grid((unsigned)((a->max_len + 15) / 16), (unsigned)a->H, (unsigned)a->n_seg);
+  hipLaunchKernelGGL(attn_fwd, grid, dim3(64), 0, static_cast<hipStream_t>(stream), p);
+  return launched("ittf_attn_fwd");
+}
+
+extern "C" int ittf_attn_bwd(const ittf_attn_args* a, void* stream) {
+  using namespace ittf;
+  if (int rc = attn_check("ittf_attn_bwd", a, true)) return rc;
+  const AttnParams p = attn_params(a);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)((a->max_len + 15) / 16), (unsigned)a->H, (unsigned)a->n_seg);
+  hipLaunchKernelGGL(attn_dq, grid, dim3(64), 0, st, p);          // (writes delta into ws ...)
+  if (int rc = launched("ittf_attn_bwd")) return rc;
+  hipLaunchKernelGGL(attn_dkdv, grid, dim3(64), 0, st, p);        // (... which this one reads)
+  return launched("ittf_attn_bwd");
 }

@@ -203,6 +203,8 @@ def fit_voice_parser():
     parser.add_argument("--dropout", type=float, default=0.2, help="LoRA dropout")
     parser.add_argument("--seed", type=int, default=0)
     parser.add_argument("--save-merged", type=str, default=None, metavar="PATH", help="also write the merged checkpoint (gpt_finetuned.pth format)")
+    parser.add_argument("--fit-attention", type=str, default="torch", choices=("torch", "hip"),
+                        help="the fit's causal attention: the torch loop, or the ragged HIP kernels (forward and backward)")
     parser.add_argument("-c", "--config", type=str, default="checkpoints/config.yaml", help="config file")
     parser.add_argument("--model_dir", type=str, default="checkpoints", help="model directory")
     parser.add_argument("--fp32", action="store_true", default=False, help="fp32 GPT weights (default: half precision when available)")
@@ -213,7 +215,7 @@ def fit_voice_parser():
 
 def fit_voice_main(argv):
     """`indextts --fit-voice DIR -v PROMPT --out VOICE.pt [--rank --alpha --steps --lr --batch-rows --text-weight --dropout --seed
-    --save-merged PATH]`: train a LoRA voice on the codes of a directory (IndexTTS.fit_voice_from_dir) and save it."""
+    --save-merged PATH --fit-attention torch|hip]`: train a LoRA voice on the codes of a directory (IndexTTS.fit_voice_from_dir) and save it."""
     parser = fit_voice_parser()
     args = parser.parse_args(argv)
 
@@ -245,7 +247,7 @@ def fit_voice_main(argv):
         cond_mel = tts.prompt_mels([args.voice])[0]
         adapters, scaling, report = tts.fit_voice_from_dir(
             args.fit_voice, cond_mel, rank=args.rank, alpha=args.alpha, steps=args.steps, lr=args.lr, batch_rows=args.batch_rows,
-            text_weight=args.text_weight, dropout=args.dropout, seed=args.seed, return_report=True)
+            text_weight=args.text_weight, dropout=args.dropout, seed=args.seed, return_report=True, attention=args.fit_attention)
     except (ValueError, OSError, RuntimeError) as e:
         print(f"[error] {e}")
         sys.exit(1)

@@ -6,7 +6,8 @@ Where the work runs.  The blocks' GEMMs, forward and backward, frozen and low-ra
 packed copy of W made once per fit, du = s dy B, dx += (du A) . mask.  The two factor gradients dB^T = s u^T dy and dA = du^T drop(x)
 are ittf_lora_wgrad, the squared gradient norm ittf_sqnorm and the LoRA+ AdamW update ittf_adamw_step (libindextts_fit.so,
 include/indextts_fit.h).  LayerNorm, GELU, the causal attention, the two heads and their cross-entropy run as torch ops on the
-device and autograd carries their backward: plumbing, named as follow-up kernels in DESIGN.  Nothing here is imported by a default
+device and autograd carries their backward: plumbing, named as follow-up kernels in DESIGN -- but under FitConfig(attention="hip")
+the attention, forward and backward, is ittf_attn_fwd / ittf_attn_bwd (_Attn).  Nothing here is imported by a default
 path, and nothing of the engine changes: the fit reads the engine's packed weights and writes only tensors of its own.
 """
 from __future__ import annotations
@@ -21,6 +22,7 @@ TARGETS = ("attn.c_attn", "attn.c_proj", "mlp.c_fc", "mlp.c_proj")
 _WKEY = {"attn.c_attn": "w_qkv", "attn.c_proj": "w_o", "mlp.c_fc": "w_fc", "mlp.c_proj": "w_pr"}
 _BKEY = {"attn.c_attn": "b_qkv", "attn.c_proj": "b_o", "mlp.c_fc": "b_fc", "mlp.c_proj": "b_pr"}
 MAX_RANK = 64      # the voice pool's own limit (ITTF_MAX_RANK)
+ATTENTIONS = ("torch", "hip")
 
 
 @dataclass
@@ -44,9 +46,12 @@ class FitConfig:
     start_text_token: int = 0
     stop_text_token: int = 1
     mel_length_compression: int = 1024
+    attention: str = "torch"          # "hip": ittf_attn_fwd / ittf_attn_bwd in the place of the per-utterance torch loop (section 4.30)
 
     def check(self):
         """Every refusal of a configuration, before anything is launched."""
+        if self.attention not in ATTENTIONS:
+            raise ValueError(f"fit: attention must be one of {ATTENTIONS} (got {self.attention!r})")
         if not isinstance(self.rank, int) or not 1 <= self.rank <= MAX_RANK:
             raise ValueError(f"fit: rank must be an integer in [1, {MAX_RANK}] (got {self.rank!r})")
         targets = tuple(self.targets)
@@ -206,6 +211,30 @@ class _Gemm(torch.autograd.Function):
         return dx, None, None, None, None
 
 
+class _Attn(torch.autograd.Function):
+    """FitConfig(attention="hip"): the causal attention of every utterance of a batch in one launch over the c_attn GEMM's fp32
+    output qkv [M, 3 D], read in place -> fp32 [M, D], the row-major operand of attn.c_proj (ittf_attn_fwd).  Saved: qkv and
+    lse [H, M]; the backward recomputes the probabilities and needs no out (ittf_attn_bwd).  Rows outside `rows` -- the rectangle's padding -- stay
+    zero in out and in dqkv, as F.pad leaves them in the torch arm."""
+
+    @staticmethod
+    def forward(ctx, qkv, fe, rows):
+        from .. import _native_fit as nf
+        qkv = qkv.detach().contiguous()
+        out, lse = nf.attn_fwd(qkv, rows, fe.H, 0.125)
+        ctx.fe, ctx.rows = fe, rows
+        ctx.save_for_backward(qkv, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from .. import _native_fit as nf
+        qkv, lse = ctx.saved_tensors
+        fe = ctx.fe
+        ws = fe._attn_workspace(nf.attn_ws_bytes(ctx.rows.M, fe.H))
+        return nf.attn_bwd(qkv, lse, dout.contiguous(), ctx.rows, fe.H, 0.125, ws=ws), None, None
+
+
 class FitEngine:
     """The trainer of one voice over a GPTEngine and the checkpoint it was loaded from.  step(batch) is one optimizer step (a list
     of batches: gradient accumulation over them), evaluate(batch) the losses without dropout, voice() the trained (adapters,
@@ -229,7 +258,7 @@ class FitEngine:
         self.L, self.D, self.H = engine.L, engine.D, engine.H
         self.scaling = float(cfg.alpha) / float(cfg.rank)
         self.rp = 128                                    # the small products' K / N, zero-padded: the width at which split-K applies
-        self.step_count, self._accumulate, self._ws = 0, False, None
+        self.step_count, self._accumulate, self._ws, self._attn_ws = 0, False, None, None
         self.probe = None          # a dict here collects, per target and backward, (M, sum |du x|, s sum |u dy|): see _Gemm.backward
         self._hook = torch.zeros((), dtype=torch.float32, device=dev, requires_grad=True)
         self.heads = {}
@@ -286,6 +315,12 @@ class FitEngine:
         if self._ws is None or self._ws.numel() < nbytes:
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return self._ws
+
+    def _attn_workspace(self, nbytes):
+        """ittf_attn_bwd's workspace (its own: a wgrad of the same backward must not grow it away)."""
+        if self._attn_ws is None or self._attn_ws.numel() < nbytes:
+            self._attn_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._attn_ws
 
     def voice(self):
         """(adapters, scaling) in the attach_lora format: {"gpt.h.{i}.{target}": (A [r, in], B [out, r])}, alpha / r."""
@@ -391,6 +426,21 @@ class FitEngine:
                      "mel": (rows_m, mt.reshape(-1), [nm] * B, [int(n) for n in ml.tolist()])}, [S] * B    # (mel_len counts the first stop)
 
     # ---------------------------------------------------------------------------------------------- the pass
+    def _attention(self, qkv, lens, S, causal, rows):
+        """The causal attention of one block over the c_attn GEMM's output qkv [M, 3 D] -> [M, D], the rectangle's padding rows
+        zero.  rows None: the torch loop; otherwise the row table of the batch (attention="hip"): one launch, _Attn."""
+        if rows is not None:
+            return _Attn.apply(qkv, self, rows)
+        H, D = self.H, self.D
+        qkv = qkv.view(len(lens), S, 3, H, 64)
+        att = []
+        for i, n in enumerate(lens):     # per utterance over its own rows: the same shapes -- the same bits -- alone and in any batch
+            q, k, v = qkv[i, :n].permute(1, 2, 0, 3)                                       # each [H, n, 64]
+            sc = (torch.matmul(q, k.transpose(-1, -2)) * 0.125).masked_fill(~causal[:n, :n], float("-inf"))
+            a = torch.matmul(torch.softmax(sc, dim=-1), v).permute(1, 0, 2).reshape(n, D)
+            att.append(F.pad(a, (0, 0, 0, S - n)))
+        return torch.cat(att, 0)
+
     def _forward(self, b, train: bool, gen=None):
         emb, heads, lens = self._inputs(b)
         B, S, D = emb.shape
@@ -398,6 +448,10 @@ class FitEngine:
         dev = self.device
         h = emb.view(M, D)
         causal = torch.ones(S, S, dtype=torch.bool, device=dev).tril()
+        rows = None
+        if self.cfg.attention == "hip":      # the row table, once per batch: utterance i is rows i S .. i S + lens[i] - 1
+            from .. import _native_fit as nf
+            rows = nf.AttnRows([(i * S, n) for i, n in enumerate(lens)], M, dev)
 
         def gemm(x, tg):
             mask = None
@@ -407,14 +461,7 @@ class FitEngine:
 
         for l, tgs in zip(self.engine.layers, self.targets):
             xn = F.layer_norm(h, (D,), l["ln1"][0], l["ln1"][1], 1e-5)
-            qkv = gemm(xn, tgs["attn.c_attn"]).view(B, S, 3, H, 64)
-            att = []
-            for i, n in enumerate(lens):     # per utterance over its own rows: the same shapes -- the same bits -- alone and in any batch
-                q, k, v = qkv[i, :n].permute(1, 2, 0, 3)                                       # each [H, n, 64]
-                sc = (torch.matmul(q, k.transpose(-1, -2)) * 0.125).masked_fill(~causal[:n, :n], float("-inf"))
-                a = torch.matmul(torch.softmax(sc, dim=-1), v).permute(1, 0, 2).reshape(n, D)
-                att.append(F.pad(a, (0, 0, 0, S - n)))
-            att = torch.cat(att, 0)
+            att = self._attention(gemm(xn, tgs["attn.c_attn"]), lens, S, causal, rows)
             h = h + gemm(att, tgs["attn.c_proj"])
             xn = F.layer_norm(h, (D,), l["ln2"][0], l["ln2"][1], 1e-5)
             ff = F.gelu(gemm(xn, tgs["mlp.c_fc"]), approximate="tanh")

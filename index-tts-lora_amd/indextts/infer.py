@@ -1150,7 +1150,8 @@ class IndexTTS:
     # ------------------------------------------------------------------------------------------------ voice fitting
     def fit_voice(self, cond_mel, text_token_rows: List[torch.Tensor], code_rows: List[torch.Tensor], *, rank=4, alpha=8.0, steps=100,
                   batch_rows=4096, lr=5.0e-6, targets=None, text_weight=0.1, dropout=0.2, loraplus_lr_ratio=2.0, weight_decay=0.01,
-                  max_grad_norm=1.0, warmup_ratio=0.1, accumulate=1, valid=None, eval_every=10, seed=0, return_report=False):
+                  max_grad_norm=1.0, warmup_ratio=0.1, accumulate=1, valid=None, eval_every=10, seed=0, return_report=False,
+                  attention="torch"):
         """Train the reference's LoRA (train.py:548-605) on this instance's frozen GPT and return (adapters, scaling) in the
         attach_lora format -- what add_voice, attach_lora_bank, save_voice and score_codes(adapter_ids=...) take (DESIGN.md section
         4.29).  Utterance i is text_token_rows[i] and code_rows[i] (what extract_codes wrote); cond_mel is one prompt or a list with
@@ -1160,14 +1161,16 @@ class IndexTTS:
         return_report: (adapters, scaling, report) with report["steps"] (loss_text, loss_mel, loss, grad_norm, lr per step) and
         report["valid"].  Every refusal comes before anything is launched.  Nothing of the engine, its bank or its graphs changes -- but
         for valid= without an attached voice pool, which attaches a one-slot pool for each evaluation and detaches it (every attach
-        drops the captured graphs): attach a pool first to keep them.  With a prompt per utterance, valid=(texts, codes, prompts)."""
+        drops the captured graphs): attach a pool first to keep them.  With a prompt per utterance, valid=(texts, codes, prompts).
+        attention="hip": the blocks' causal attention, forward and backward, as one ragged HIP launch per block in the place of the
+        per-utterance torch loop; the default "torch" is the loop."""
         from indextts.gpt.fit import TARGETS, FitConfig, FitEngine, check_engine, check_rows, plan_batches
         g, eng = self.gpt, self.gpt.engine
         cfg = FitConfig(rank=rank, alpha=float(alpha), targets=tuple(TARGETS if targets is None else targets), dropout=float(dropout),
                         text_weight=float(text_weight), lr=float(lr), loraplus_lr_ratio=float(loraplus_lr_ratio),
                         weight_decay=float(weight_decay), max_grad_norm=max_grad_norm, total_steps=int(steps), warmup_ratio=float(warmup_ratio),
                         seed=int(seed), start_text_token=g.start_text_token, stop_text_token=g.stop_text_token,
-                        mel_length_compression=g.mel_length_compression).check()
+                        mel_length_compression=g.mel_length_compression, attention=attention).check()
         check_engine(eng, "fit_voice")
         if int(accumulate) < 1 or int(eval_every) < 1:
             raise ValueError("fit_voice: accumulate and eval_every must be at least 1")

@@ -10,8 +10,14 @@ native call: the frozen GEMMs forward and backward (with their slab sums), the s
 (ittf_sqnorm, ittf_adamw_step and the pack_weight launches of _refresh); the two heads with their cross-entropy, forward and
 backward, are timed on their own over the step's row count; what is left of the step is the torch plumbing (LayerNorm, GELU, the
 attention, the residual adds, autograd's own work).  Also reported: the peak bytes a step allocates, and the padding rows computed.
+The blocks' causal attention is a category of its own, forward and backward: device events around FitEngine._attention, and for its
+backward an event when the gradient of its output arrives and one when the gradient of qkv is complete (tensor hooks: the same for
+the torch loop and for the HIP kernels).  --attention torch | hip chooses the arm the step runs (default: torch, the loop);
+--attention both alternates the two arms in the place of (fit) / (linear), at r = 4, with two FitEngines over the one GPTEngine, and
+reports per arm the step, the attention and the peak bytes beside the analytic difference of the saved tensors (DESIGN.md
+section 4.30).
 No speed is promised: the output is the record.  Writes profiles/fit_bench.txt.
-usage: bench_fit.py [--out FILE] [--layers N]"""
+usage: bench_fit.py [--out FILE] [--layers N] [--attention torch|hip|both]"""
 import argparse
 import os
 import statistics
@@ -33,6 +39,7 @@ from indextts.gpt.engine import GPTEngine  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fit_bench.txt"))
 ap.add_argument("--layers", type=int, default=24)
+ap.add_argument("--attention", default="torch", choices=("torch", "hip", "both"))
 args = ap.parse_args()
 if not torch.cuda.is_available():
     sys.exit("bench_fit.py measures on the GPU: none is visible")
@@ -129,6 +136,28 @@ nf.sqnorm = clock.wrap(nf.sqnorm, "optimizer")
 nf.adamw_step = clock.wrap(nf.adamw_step, "optimizer")
 fit.FitEngine._refresh = clock.wrap(fit.FitEngine._refresh, "optimizer")
 
+_attention = fit.FitEngine._attention
+
+
+def attention_timed(self, qkv, lens, S, causal, rows):
+    if not clock.on:
+        return _attention(self, qkv, lens, S, causal, rows)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    ev[0].record()
+    out = _attention(self, qkv, lens, S, causal, rows)
+    ev[1].record()
+    clock.pairs.append(("attention forward", ev[0], ev[1]))
+    if out.requires_grad:
+        out.register_hook(lambda g: ev[2].record())     # the gradient of the attention's output arrives: its backward starts
+        qkv.register_hook(lambda g: ev[3].record())     # the gradient of qkv is complete: it has ended
+        clock.pairs.append(("attention backward", ev[2], ev[3]))
+    return out
+
+
+fit.FitEngine._attention = attention_timed
+BOTH = args.attention == "both"
+ARMS = ("torch", "hip") if BOTH else ("fit", "linear")
+
 say(f"voice fitting: one optimizer step, {args.layers} layers, D = 1280, 8 utterances; ms, median of {REPS} [min .. max]; arms alternating")
 sd = dict(weights.gpt_state_dict(args.layers, with_conditioner=False))
 sd.update({k: torch.from_numpy(v) for k, v in synth.fill_state_dict({"text_head.weight": (12001, 1280), "text_head.bias": (12001,)},
@@ -143,21 +172,24 @@ for dtype in (torch.bfloat16, torch.float32):
     for i, l in enumerate(eng.layers):
         for name, wkey in fit._WKEY.items():
             dense[l[wkey].data_ptr()] = sd[f"gpt.h.{i}.{name}.weight"].to(DEV, dtype).t().contiguous()
-    for rank in (4, 16):
+    for rank in ((4,) if BOTH else (4, 16)):
         for key in [k for k, v in dense.items() if v is None or getattr(v, "_of_fit", False)]:
             del dense[key]                                 # the transposed copies of the engine before: their addresses are free again
-        fe = fit.FitEngine(eng, sd, fit.FitConfig(rank=rank, alpha=2.0 * rank, dropout=0.0, lr=1e-4))
-        for row in fe.targets:
-            for tg in row.values():
-                dense[tg.wt.data_ptr()] = dense[tg.w.data_ptr()].t().contiguous()
-                dense[tg.wt.data_ptr()]._of_fit = True
+        fes = {a: fit.FitEngine(eng, sd, fit.FitConfig(rank=rank, alpha=2.0 * rank, dropout=0.0, lr=1e-4, attention=a))
+               for a in (ARMS if BOTH else (args.attention,))}
+        for fe in fes.values():
+            for row in fe.targets:
+                for tg in row.values():
+                    dense[tg.wt.data_ptr()] = dense[tg.w.data_ptr()].t().contiguous()
+                    dense[tg.wt.data_ptr()]._of_fit = True
         b = fe.batch(conds, texts, codes)
         real = sum(32 + t.numel() + 2 + c.numel() + 2 for t, c in zip(texts, codes))
         rect = 8 * max(32 + t.numel() + 2 + c.numel() + 2 for t, c in zip(texts, codes))
-        times, parts, peak = {"fit": [], "linear": []}, [], 0
+        times, parts, peak = {a: [] for a in ARMS}, {a: [] for a in ARMS}, {a: 0 for a in ARMS}
         for rnd in range(WARM + REPS):
-            for arm in ("fit", "linear"):
-                use_linear, clock.on = arm == "linear", arm == "fit" and rnd >= WARM
+            for arm in ARMS:
+                fe = fes[arm] if BOTH else fes[args.attention]
+                use_linear, clock.on = arm == "linear", arm != "linear" and rnd >= WARM
                 torch.cuda.synchronize()
                 torch.cuda.reset_peak_memory_stats()
                 base = torch.cuda.memory_allocated()
@@ -168,9 +200,9 @@ for dtype in (torch.bfloat16, torch.float32):
                 torch.cuda.synchronize()
                 if rnd >= WARM:
                     times[arm].append(e0.elapsed_time(e1))
-                    if arm == "fit":
-                        parts.append(clock.totals())
-                        peak = max(peak, torch.cuda.max_memory_allocated() - base)
+                    if arm != "linear":
+                        parts[arm].append(clock.totals())
+                        peak[arm] = max(peak[arm], torch.cuda.max_memory_allocated() - base)
         clock.on = False
         # the two heads with their cross-entropy, forward and backward, on their own over the step's head rows
         n_t, n_m = sum(t.numel() + 2 for t in texts), sum(c.numel() + 2 for c in codes)
@@ -192,19 +224,33 @@ for dtype in (torch.bfloat16, torch.float32):
         heads = heads[WARM:]
         name = {torch.bfloat16: "bf16", torch.float32: "fp32"}[dtype]
         say(f"--- {name}, r = {rank}: {real} real rows in a rectangle of {rect} ({rect - real} padding rows computed); "
-            f"loss_mel {rep['loss_mel']:.4f}; peak bytes of a step {peak / 2 ** 20:.0f} MiB")
-        say(f"  step, arm (fit)                       {med(times['fit'])}")
-        say(f"  step, arm (linear: F.linear frozen)   {med(times['linear'])}")
-        tot = statistics.median(times["fit"])
-        left = tot
-        for cat in ("frozen GEMMs forward", "frozen GEMMs backward", "LoRA products", "ittf_lora_wgrad", "optimizer"):
-            v = [p.get(cat, 0.0) for p in parts]
-            left -= statistics.median(v)
-            say(f"  {cat:<38s}{med(v)}   {100 * statistics.median(v) / tot:5.1f} %")
-        left -= statistics.median(heads)
-        say(f"  {'heads + cross-entropy (on their own)':<38s}{med(heads)}   {100 * statistics.median(heads) / tot:5.1f} %")
-        say(f"  {'plumbing (the rest of the step)':<38s}{left:8.2f}                      {100 * left / tot:5.1f} %")
-        del fe
+            f"loss_mel {rep['loss_mel']:.4f}")
+        for arm in ARMS:
+            if arm == "linear":
+                say(f"  step, arm (linear: F.linear frozen)   {med(times['linear'])}")
+                continue
+            label = f'attention="{arm}"' if BOTH else f'fit, attention="{args.attention}"'
+            say(f"  step, arm ({label}){'':<{max(0, 26 - len(label))}}{med(times[arm])}   peak bytes of a step {peak[arm] / 2 ** 20:.0f} MiB")
+            tot = statistics.median(times[arm])
+            left = tot
+            for cat in ("frozen GEMMs forward", "frozen GEMMs backward", "LoRA products", "ittf_lora_wgrad", "optimizer", "attention forward",
+                        "attention backward"):
+                v = [p.get(cat, 0.0) for p in parts[arm]]
+                left -= statistics.median(v)
+                say(f"    {cat:<36s}{med(v)}   {100 * statistics.median(v) / tot:5.1f} %")
+            left -= statistics.median(heads)
+            say(f"    {'heads + cross-entropy (on their own)':<36s}{med(heads)}   {100 * statistics.median(heads) / tot:5.1f} %")
+            say(f"    {'plumbing (the rest of the step)':<36s}{left:8.2f}                      {100 * left / tot:5.1f} %")
+        if BOTH:
+            t, h = times["torch"], times["hip"]
+            spread, gain = max(t) - min(t), statistics.median(t) - statistics.median(h)
+            lens = [32 + x.numel() + 2 + c.numel() + 2 for x, c in zip(texts, codes)]
+            saved = (4 * 20 * sum(n * n for n in lens) - 4 * 20 * rect) * args.layers     # (the hip arm keeps lse, not out)
+            say(f"  median(torch) - median(hip) = {gain:.2f} ms against the torch arm's spread (max - min) of {spread:.2f} ms: "
+                f"{'faster' if gain > spread else 'NOT faster by the rule'}")
+            say(f"  peak bytes torch - hip = {(peak['torch'] - peak['hip']) / 2 ** 20:.0f} MiB; the saved tensors differ by "
+                f"4 H sum n^2 L - 4 H M L = {saved / 2 ** 20:.0f} MiB: peak memory is {'lower' if peak['hip'] < peak['torch'] else 'NOT lower'} under hip")
+        del fe, fes
     del eng
     torch.cuda.empty_cache()
 with open(args.out, "w") as f:
